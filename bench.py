@@ -9,10 +9,15 @@ N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RC
 quoted "on 50M-event stream @1/2/4/8 GPU": the headline is STRONG scaling — the ONE 50 M-event stream
 cut into N contiguous time ranges of whole windows, one per rank, no data-path collective (SURVEY
 §8e; the reference cuts the same stream into pieces, eventCameraCalib.cpp:172-179); the only
-collectives are the timing barrier and a MAX over ranks.  Weak scaling (one 50 M stream per GPU) is
-reported beside it.  A "step" = one full pass of the hot path over the stream, HBM-resident when the
-timed region starts (the upload is never part of `value`).  Prints ONE JSON line; a failure in a leg
-beside the headline is listed in `failed_legs` and makes the exit code 1.
+collectives are the timing barrier and a MAX over ranks.  A "step" = one full pass of the hot path over
+the stream, HBM-resident when the timed region starts (the upload is never part of `value`).  Prints ONE
+JSON line.
+
+A plain run sets up, warms up, times --steps passes, writes --dump-outputs DIR (the arrays of the last
+timed pass) and prints the line.  Everything beside the headline runs under --full only: the fixed
+cost of a pass, roofline and stage times, the CPU baselines, h2d, policy P2, weak scaling (one 50 M
+stream per GPU) and the sharded search under N > 1, the solver (M2), ingest, init calibration and
+end-to-end legs.  A failure in such a leg is listed in `failed_legs` and makes the exit code 1.
 """
 import argparse
 import json
@@ -65,6 +70,67 @@ class leg:
         return True
 
 
+def dump_outputs(pipe, S, out_dir, prefix, budget, torch, np):
+    """--dump-outputs: the arrays a caller of DetectPipeline receives from the last pass over S windows (include/ecal.h,
+    ecal_extract_batch_dev), as float64 .npy files under out_dir (integers up to 2^32 are exact in float64).  Window, candidate
+    and representative arrays are whole up to a cap, the per-point arrays a sample; every sample is drawn with a fixed seed,
+    so two builds fed the same stream write the same rows.  Caps scale with `budget` (bytes, 64e6 for one rank)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20240613)
+    scale = budget / 64e6
+    cap_win, cap_cand, cap_pts, cap_rep = (int(c * scale) for c in (65536, 1 << 20, 1 << 18, 1 << 19))
+
+    def pick(n, cap):
+        # sorted row numbers of a seeded sample of at most `cap` of n rows (all of them when n <= cap)
+        return np.arange(n) if n <= cap else np.unique(rng.integers(0, n, size=cap))
+
+    def host(t):
+        return t.cpu().numpy().astype(np.int64)
+
+    seg_off, seg_cnt = host(pipe.seg_off[:2 * S]), host(pipe.seg_cnt[:2 * S])
+    n_clusters, win_info = host(pipe.n_clusters[:2 * S]), host(pipe.win_info[:S])
+    win_lo, win_hi = host(pipe.win_lo[:S]), host(pipe.win_hi[:S])
+    cap_slots = pipe.labels.numel()
+    assert (seg_off + seg_cnt <= cap_slots).all(), "segment beyond the pipeline's point slots"
+
+    def device_rows(t, idx):
+        # rows idx of a device array (indices checked on the host first: no out-of-range gather on the GPU)
+        assert idx.size == 0 or (idx.min() >= 0 and idx.max() < t.shape[0])
+        return t[torch.as_tensor(idx, device=t.device)].cpu().numpy()
+
+    arrays = {}
+    w = pick(S, cap_win)
+    s2 = np.stack([2 * w, 2 * w + 1], 1).reshape(-1)
+    arrays.update(window_index=w, win_lo=win_lo[w], win_hi=win_hi[w], win_info=win_info[w], seg_off=seg_off[s2],
+                  seg_cnt=seg_cnt[s2], n_clusters=n_clusters[s2])
+    # circle candidates j < win_info[s, 0] of window s sit at seg_off[2s] + j (cand_pair: + / - cluster, cand_xyr: x, y, r)
+    ok = (win_info[:, 3] & 0xFF) == 0
+    n_cand = np.where(ok, win_info[:, 0], 0)
+    first = np.repeat(seg_off[0::2] - (np.cumsum(n_cand) - n_cand), n_cand)
+    slot = first + np.arange(int(n_cand.sum()))
+    slot = slot[pick(slot.size, cap_cand)]
+    arrays.update(cand_pair=device_rows(pipe.cand_pair, slot), cand_xyr=device_rows(pipe.cand_xyr, slot))
+    # representatives: kept cluster k of segment 2s + pol at rep[seg_off[2s + pol] + k], win_info[s, 1 + pol] of them
+    n_rep = np.where(np.repeat(ok, 2), win_info[:, 1:3].reshape(-1), 0)
+    slot = np.repeat(seg_off - (np.cumsum(n_rep) - n_rep), n_rep) + np.arange(int(n_rep.sum()))
+    slot = slot[pick(slot.size, cap_rep)]
+    arrays.update(rep=device_rows(pipe.rep, slot))
+    # the points (positiveEvents_ / negativeEvents_ of every window): a seeded sample of them, by rank among all points
+    r = pick(int(seg_cnt.sum()), cap_pts)
+    pipe._xy_stale = True           # (the staged passes leave the points packed: pipe.xy unpacks them)
+    ends = np.cumsum(seg_cnt)
+    seg = np.searchsorted(ends, r, side="right")
+    slot = seg_off[seg] + (r - (ends[seg] - seg_cnt[seg]))
+    arrays.update(point_slot=slot, xy=device_rows(pipe.xy, slot), labels=device_rows(pipe.labels, slot),
+                  kept_labels=device_rows(pipe.kept_labels, slot))
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    assert total <= budget, "outputs of %d bytes exceed the %d-byte budget" % (total, budget)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -101,7 +167,17 @@ def main():
     ap.add_argument("--e2e-events", type=int, default=50_000_000,
                     help="events of the end-to-end leg: one stream with tilted views through keyframe search -> init calibration -> "
                          "rectify -> splines -> ecal_associate_dev -> the spline solve fed by THAT association (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: fixed cost of a pass, the event -> point map and plain-extraction "
+                         "timings, roofline, CPU baselines, h2d, policy P2, weak scaling and the sharded search (N > 1), solver, "
+                         "ingest, init calibration and end-to-end legs (each still switched off by its own option).  Without it a run "
+                         "sets up, warms up, times --steps passes, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass computed (windows, DBSCAN counts, circle candidates, "
+                         "representatives, a seeded sample of the points' labels and coordinates) as DIR/<name>.npy, float64, "
+                         "at most 64 MB in all")
     args = ap.parse_args()
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start one rank per GPU as CHILD processes of this one (which has
@@ -134,7 +210,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world == 1 and args.e2e_events > 0 and not os.environ.get("ECAL_BENCH_NO_CPP_CHAIN"):
+    if full and world == 1 and args.e2e_events > 0 and not os.environ.get("ECAL_BENCH_NO_CPP_CHAIN"):
         # the C++ driver as a cold process on a GPU nobody else holds: before this process creates its HIP context
         global _CPP_CHAIN_IDLE
         try:
@@ -275,6 +351,10 @@ def main():
     else:
         covered_total = n_covered
 
+    if args.dump_outputs:
+        # what the last timed pass left in the pipeline's arrays, before any leg below reuses them
+        dump_outputs(pipe, S, args.dump_outputs, "" if world == 1 else "rank%d_" % rank, 64_000_000 // world, torch, np)
+
     ms_per_step_local = elapsed / max(args.steps, 1) * 1e3
     stage_ms = np.zeros(4)
     for k in range(args.steps):
@@ -286,7 +366,7 @@ def main():
     # bounds, per-kernel ramp-up): passes over the first S, S/2 and S/4 windows, straight line through the three times,
     # its value at zero windows.  At N = 8 a rank's pass is an eighth of the stream: this is what caps strong scaling.
     pass_ms_fixed = None
-    if rank == 0 and args.steps > 0 and S >= 64 and not args.no_fixed_cost:
+    if full and rank == 0 and args.steps > 0 and S >= 64 and not args.no_fixed_cost:
         sizes, times = [S, S // 2, S // 4], []
         reps = max(10, args.steps)
         for Sw in sizes:
@@ -309,7 +389,7 @@ def main():
     # the timed pass with the OTHER setting of the event -> point map (the library's DetectPipeline writes it by default, the
     # timed pass does not unless --event-point): both figures side by side, so that `value` can be compared like for like
     event_point_leg = None
-    if rank == 0 and args.steps > 0:
+    if full and rank == 0 and args.steps > 0:
         other = not args.event_point
         for _ in range(2):
             staged_pass(n_local, S, event_point=other)
@@ -330,7 +410,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     plain_extract_ms = None
-    if rank == 0 and args.steps > 0:
+    if full and rank == 0 and args.steps > 0:
         fe = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         # the plain extraction (smaller pid at tied medians: ecal_extract_batch_dev alone), for comparison
         def plain_extract():
@@ -357,7 +437,7 @@ def main():
 
     # ---- beside the headline under N > 1: the adaptive-window search of the same stream cut over the ranks, and WEAK scaling
     sharded_p2 = weak = None
-    if world > 1 and args.steps > 0:
+    if full and world > 1 and args.steps > 0:
         if args.p2_pieces != 0:
             # the reference driver's adaptive-window search (policy P2) over the same stream: rank r searches the pieces
             # [P r / N, P (r + 1) / N) — with the bounds they have in the whole run (ecal_adaptive_params.piece_first / piece_count) —
@@ -473,7 +553,7 @@ def main():
         out["policy_p2_sharded"] = sharded_p2
     if pass_ms_fixed is not None:
         out["pass_ms_fixed"] = pass_ms_fixed
-    if rank == 0:
+    if full and rank == 0:
         # the dominant KERNEL: the extraction stage is its first pass (which resolves the ties of small clusters itself since round 5)
         # + the launches of the listed path for what that leaves; the plain pass — timed alone below the stage — stands for it
         kernel_ms = [float(x) for x in stage_ms]
@@ -564,7 +644,7 @@ def main():
                     "host_cpus": os.cpu_count(),
                 }
     # ---- reported beside the contract number (rank 0, one GPU): PCIe upload and the reference's window policy ----
-    if rank == 0 and world == 1 and not args.no_h2d:
+    if full and rank == 0 and world == 1 and not args.no_h2d:
         with leg(out, "h2d"):
             host = torch.empty(events.numel(), dtype=torch.uint8, pin_memory=True)
             host.copy_(events)
@@ -584,7 +664,7 @@ def main():
                           "GBs": round(events.numel() / h2d_ms / 1e6, 2),
                           "Mevents_per_s_including_upload": round(n_events / ((h2d_ms + ms_per_step) * 1e-3) / 1e6, 1),
                           "note": "pinned host -> HBM copy of the packed stream, once per stream; never part of `value`"}
-    if rank == 0 and world == 1 and args.p2_pieces != 0:
+    if full and rank == 0 and world == 1 and args.p2_pieces != 0:
         with leg(out, "policy_p2_error"):
             # policy P2 of SURVEY 8d: the reference driver's adaptive success / slide / grow windows per piece
             # (eventCameraCalib.cpp:49-95) + keyframe gate, lock-step over all pieces; counted as the reference
@@ -660,22 +740,22 @@ def main():
             traceback.print_exc(file=sys.stderr)
             return {"error": "%s: %s" % (type(exc).__name__, str(exc)[:300])}
 
-    if args.solver_iters > 0:
+    if full and args.solver_iters > 0:
         del events
         pipe = None
         torch.cuda.empty_cache()
         out_solver = guarded(solver_leg, args, ctx, dev, world, rank, n_events, rate, t_start, dist, torch, np)
         if rank == 0:
             out["solver"] = out_solver
-    if args.ingest_events > 0:
+    if full and args.ingest_events > 0:
         out_ingest = guarded(ingest_leg, args, ctx, dev, world, rank, dist, torch, np, rate)
         if rank == 0:
             out["ingest"] = out_ingest
-    if args.calib_views > 0:
+    if full and args.calib_views > 0:
         out_calib = guarded(calib_leg, args, ctx, dev, world, rank, dist, torch, np)
         if rank == 0:
             out["init_calibration"] = out_calib
-    if args.e2e_events > 0 and rank == 0 and world == 1:
+    if full and args.e2e_events > 0 and rank == 0 and world == 1:
         out["end_to_end"] = guarded(e2e_leg, args, ctx, dev, torch, np)
     failed = []
     if rank == 0:

@@ -1,6 +1,8 @@
 """CPU suite: pin the oracle (own restatement vs the reference's compiled kdtree.cpp vs the closed
 form the HIP kernel implements vs scikit-learn) and the golden fixtures."""
 import glob
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -11,7 +13,52 @@ import oracle_lib as O
 import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-needs_ref = pytest.mark.skipif(not O.have_ref_kdtree(), reason="oracle/_ref/libkdtree_ref.so not built")
+# what the reference's compiled kdtree.cpp returns on the inputs of the three tests below, recorded where oracle/_ref was built
+# (tests/golden/make_kdtree_ref_golden.py): the tests compare with the library where it is built, and with these digests always
+REF_DIGESTS_FILE = os.path.join(GOLDEN, "kdtree_ref_digests.json")
+
+
+def _digest(*arrays):
+    h = hashlib.sha1()
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        h.update(np.int64(a.size).tobytes() + a.tobytes())
+    return h.hexdigest()
+
+
+def _dbscan_digest(rc, labels, n, clusters=None):
+    parts = [np.array([rc, n]), labels]
+    if clusters is not None:
+        parts += [np.array([len(c) for c in clusters])] + list(clusters)
+    return _digest(*parts)
+
+
+def _ref_digests(key):
+    with open(REF_DIGESTS_FILE) as f:
+        return json.load(f)[key]
+
+
+def range_query_cases(seed):
+    rng = np.random.default_rng(100 + seed)
+    for _ in range(25):
+        xy, off, lattice = synth.random_segments(rng, 1, max_n=500, with_empty=False)
+        eps = float(rng.choice([3, 4, 4.5, 5, 2.5, 1.7, 0.3]))
+        yield xy, eps
+
+
+def driver_cases(seed):
+    rng = np.random.default_rng(200 + seed)
+    for _ in range(20):
+        xy, off, lattice = synth.random_segments(rng, 1, max_n=600, with_empty=False)
+        eps = float(rng.choice([3, 4, 4.5, 5, 2.5, 1.7]))
+        minpts = int(rng.choice([1, 2, 5]))
+        yield xy, eps, minpts
+
+
+def arc_cases():
+    rng = np.random.default_rng(5)
+    for noise in (0.1, 0.5):
+        yield synth.one_arc_slice(rng, noise)
 
 
 def test_survey_three_point_demo():
@@ -32,43 +79,47 @@ def test_failed_inputs():
     assert rc == 1                      # dbscan.h:123
 
 
-@needs_ref
 @pytest.mark.parametrize("seed", range(6))
 def test_range_query_matches_reference_kdtree(seed):
-    """Own tree + walk == reference kd_insert/kd_nearest_range, hit for hit, in list order."""
-    rng = np.random.default_rng(100 + seed)
-    for _ in range(25):
-        xy, off, lattice = synth.random_segments(rng, 1, max_n=500, with_empty=False)
-        eps = float(rng.choice([3, 4, 4.5, 5, 2.5, 1.7, 0.3]))
+    """Own tree + walk == reference kd_insert/kd_nearest_range, hit for hit, in list order (the compiled reference where
+    oracle/_ref is built; its recorded results always)."""
+    want = _ref_digests("range_query")[str(seed)]
+    cases = list(range_query_cases(seed))
+    assert len(cases) == len(want)
+    for (xy, eps), d in zip(cases, want):
         o1, i1 = O.range_query_all(xy, eps)
-        o2, i2 = O.range_query_all(xy, eps, kdapi=True)
-        assert (o1 == o2).all() and (i1 == i2).all()
+        if O.have_ref_kdtree():
+            o2, i2 = O.range_query_all(xy, eps, kdapi=True)
+            assert (o1 == o2).all() and (i1 == i2).all()
+        assert _digest(o1, i1) == d
 
 
-@needs_ref
 @pytest.mark.parametrize("seed", range(4))
 def test_driver_on_reference_kdtree(seed):
     """Restated Run()/expandCluster() on top of the reference kd_* ABI == fully restated path,
-    including the element order inside every cluster."""
-    rng = np.random.default_rng(200 + seed)
-    for _ in range(20):
-        xy, off, lattice = synth.random_segments(rng, 1, max_n=600, with_empty=False)
-        eps = float(rng.choice([3, 4, 4.5, 5, 2.5, 1.7]))
-        minpts = int(rng.choice([1, 2, 5]))
+    including the element order inside every cluster (the reference's recorded results where oracle/_ref is not built)."""
+    want = _ref_digests("driver")[str(seed)]
+    cases = list(driver_cases(seed))
+    assert len(cases) == len(want)
+    for (xy, eps, minpts), d in zip(cases, want):
         rc1, l1, n1, c1 = O.dbscan(xy, eps, minpts, with_members=True)
-        rc2, l2, n2, c2 = O.dbscan(xy, eps, minpts, kdapi=True, with_members=True)
-        assert rc1 == rc2 == 0 and n1 == n2 and (l1 == l2).all()
-        assert all((a == b).all() for a, b in zip(c1, c2))
+        if O.have_ref_kdtree():
+            rc2, l2, n2, c2 = O.dbscan(xy, eps, minpts, kdapi=True, with_members=True)
+            assert rc1 == rc2 == 0 and n1 == n2 and (l1 == l2).all()
+            assert all((a == b).all() for a, b in zip(c1, c2))
+        assert rc1 == 0 and _dbscan_digest(rc1, l1, n1, c1) == d
 
 
-@needs_ref
 def test_arc_slices_on_reference_kdtree():
-    rng = np.random.default_rng(5)
-    for noise in (0.1, 0.5):
-        xy = synth.one_arc_slice(rng, noise)
+    want = _ref_digests("arc_slices")
+    cases = list(arc_cases())
+    assert len(cases) == len(want)
+    for xy, d in zip(cases, want):
         rc1, l1, n1 = O.dbscan(xy, 4.0, 2)
-        rc2, l2, n2 = O.dbscan(xy, 4.0, 2, kdapi=True)
-        assert n1 == n2 and (l1 == l2).all() and n1 >= 30
+        if O.have_ref_kdtree():
+            rc2, l2, n2 = O.dbscan(xy, 4.0, 2, kdapi=True)
+            assert n1 == n2 and (l1 == l2).all()
+        assert n1 >= 30 and _dbscan_digest(rc1, l1, n1) == d
 
 
 @pytest.mark.parametrize("seed", range(6))

@@ -8,6 +8,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS=${PMC_ARGS:-"--steps 4 --warmup 1 --cpu-sample 0 --solver-cpu-sample 0 --p2-pieces 0 --no-h2d --ingest-events 0 --calib-views 0 --solver-iters 0"}
+ARGS="--full $ARGS"     # the M1 passes beside the timed ones (fixed cost, event -> point map, plain extraction) counted too
 A="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU"
 B="SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_WAVES"
 rocprofv3 --pmc $A --output-format csv -d $OUT/pa -- python3 $ROOT/bench.py $ARGS > $OUT/bench_pa.log 2>&1
