@@ -38,6 +38,10 @@
 namespace {
 
 constexpr int AD_MAX_ROWS = 32;
+static_assert(AD_MAX_ROWS == ECAL_FRAME_MAX_ROWS, "the handed-over frame (ecal_keyframe_frame) is staged by the search's row bound");
+// the search's pinned block (ecal_ctx::pass_pinned): 16 counter words, the [8][4] report ring behind them, and from byte
+// AD_PIN_FRAME the handed-over frame on its way to the device (two words, the time stamp, [AD_MAX_ROWS][2] row directions)
+constexpr size_t AD_PIN_FRAME = 512, AD_PINNED_BYTES = AD_PIN_FRAME + 8 * (2 + 2 * (size_t) AD_MAX_ROWS);
 
 using ecal::row_direction;   // (row_direction.hpp: shared with the grid finder's epilogue)
 
@@ -974,17 +978,17 @@ extern "C" uint64_t ecal_detect_keyframes_cap_hint_dev(ecal_ctx *ctx, const uint
     if (!ctx || !ap || (n_events && !d_events)) return 0;
     if (n_events == 0) return ecal_detect_keyframes_cap_hint(ap, 0);
     if (hipSetDevice(ctx->device) != hipSuccess) return 0;
-    ecal_devbuf *B = ctx->host_pipe;
-    if (ecal_ensure(ctx, B[0], 2 * sizeof(double)) || ecal_ensure(ctx, B[2], 4) || ecal_ensure(ctx, B[3], 4) || ecal_ensure(ctx, B[4], 8)) return 0;
+    if (ecal_det_ensure_bounds(ctx, 1)) return 0;
+    const ecal_det_scratch &det = ctx->det;   // (one window: t0 and t1 back to back)
     const double t[2] = {ap->start_time, ap->end_time};
     uint32_t lo = 0, hi = 0;
     hipStream_t st = ctx->stream;
-    if (hipMemcpyAsync(B[0].ptr, t, sizeof(t), hipMemcpyHostToDevice, st) != hipSuccess) return 0;
-    if (ecal_window_bounds_dev(ctx, d_events, n_events, (const double *) B[0].ptr, (const double *) B[0].ptr + 1, 1, (uint32_t *) B[2].ptr,
-                               (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, st))
+    if (hipMemcpyAsync(det.t0(), t, sizeof(t), hipMemcpyHostToDevice, st) != hipSuccess) return 0;
+    if (ecal_window_bounds_dev(ctx, d_events, n_events, det.t0(), det.t1(), 1, det.win_lo.as<uint32_t>(), det.win_hi.as<uint32_t>(),
+                               det.win_base.as<uint32_t>(), st))
         return 0;
-    if (hipMemcpyAsync(&lo, B[2].ptr, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&hi, B[3].ptr, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    if (hipMemcpyAsync(&lo, det.win_lo.ptr, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&hi, det.win_hi.ptr, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return 0;
     const uint64_t hint = ecal_detect_keyframes_cap_hint(ap, hi > lo ? hi - lo : 0);
     return hint < 4096 ? 4096 : hint;
@@ -1071,15 +1075,9 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
     int rc;
     const uint32_t D = adaptive_slots_per_piece(P, ctx->sw.adaptive_depth), d_max = adaptive_depth_max(ctx->sw.adaptive_depth_max);
     const uint32_t S = D * P;   // window slots per pass, dealt out among the pieces still at work: the current window and the likely chain after it
-    const size_t cap = (size_t) cap_points + 16;
-    ecal_devbuf *B = ctx->host_pipe;  // roles as in ecal_detect_pass; 0 holds t0 and t1 back to back
+    const ecal_det_scratch &det = ctx->det;
     const auto t_scratch0 = std::chrono::steady_clock::now();
-    const size_t sizes[17] = {2ul * S * sizeof(double), 16, S * 4ul, S * 4ul, (S + 1) * 4ul, cap * 16, 2ul * S * 4, 2ul * S * 4, cap * 4,
-                              cap * 4, 2ul * S * 4, cap * 4, cap * 4, 4ul * S * 4, cap * 8, cap * 24, 16};
-    for (int i = 0; i < 17; i++)
-        if ((rc = ecal_ensure(ctx, B[i], sizes[i]))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_order, (size_t) S * M * sizeof(int32_t)))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_found, (size_t) S * sizeof(uint32_t)))) return rc;
+    if ((rc = ecal_det_ensure(ctx, S, cap_points, M))) return rc;
     // per piece: 7 doubles + (3 + AD_NREJ) x rows x 2 doubles of row directions + AD_NREJ doubles + 10 words
     const size_t state_bytes = (size_t) P * (8 * (7 + AD_NREJ + 2 * (size_t) rows * (3 + AD_NREJ)) + 4 * 12) + 128 + 8 * (2 + 2 * (size_t) AD_MAX_ROWS);
     if ((rc = ecal_ensure(ctx, ctx->adaptive_state, state_bytes))) return rc;
@@ -1089,13 +1087,7 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
     if (rec_cap > 0xFFFFFFF0ull) return ECAL_ERR_RANGE;
     const size_t key_stride = 8 + 16 + 8 + 24 * (size_t) M + 8;  // time, duration, events (padded), features, piece + run
     if ((rc = ecal_ensure(ctx, ctx->adaptive_keys, rec_cap * key_stride + 64))) return rc;
-    if (ctx->pass_pinned_cap < 64) {
-        if (ctx->pass_pinned) (void) hipHostFree(ctx->pass_pinned);
-        ctx->pass_pinned = nullptr;
-        ctx->pass_pinned_cap = 0;
-        ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &ctx->pass_pinned, 4096, hipHostMallocDefault));
-        ctx->pass_pinned_cap = 4096;
-    }
+    ECAL_HIP_TRY(ctx, ecal_ensure_pinned(ctx->pass_pinned, AD_PINNED_BYTES));
     if (ctx->sw.adaptive_trace)
         fprintf(stderr, "ecal_detect_keyframes: scratch buffers ready after %.4f s (cap_points %u)\n",
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_scratch0).count(), cap_points);
@@ -1144,12 +1136,12 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
     double *d_kt = (double *) ctx->adaptive_keys.ptr, *d_kd = d_kt + max_keys, *d_kf = d_kd + 2 * (size_t) max_keys;
     int32_t *d_ke = (int32_t *) (d_kf + 3 * (size_t) max_keys * M);
     uint32_t *d_kp = (uint32_t *) (d_ke + max_keys + (max_keys & 1u)), *d_kg = d_kp + max_keys;
-    double *d_t0 = (double *) B[0].ptr, *d_t1 = d_t0 + S;
+    double *d_t0 = det.t0(), *d_t1 = det.t1();
     hipLaunchKernelGGL(adaptive_init_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, rows, ap->motion_time_step, a);
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(B[16].ptr, 0, sizeof(int), st));
-    ctx->overflow_sticky = (const int *) B[16].ptr;   // (wiped here, once: the passes' slicing calls leave it alone)
+    ECAL_HIP_TRY(ctx, hipMemsetAsync(det.overflow.ptr, 0, sizeof(int), st));
+    ctx->overflow_sticky = det.overflow.as<const int>();   // (wiped here, once: the passes' slicing calls leave it alone)
     if (a.ext) ECAL_HIP_TRY(ctx, hipMemsetAsync((void *) a.ext, 0, 8 * (2 + 2 * (size_t) AD_MAX_ROWS), st));   // (the frame from before: not known yet)
-    uint32_t *h = reinterpret_cast<uint32_t *>(ctx->pass_pinned);  // [0..15] counters
+    uint32_t *h = ctx->pass_pinned.as<uint32_t>();  // [0..15] counters
     // The host runs `ahead` passes ahead of the device's counters: before it enqueues pass p it waits for the counters that pass
     // p - ahead left (a copy to pinned memory + an event behind every pass) — the device always has work queued, and at most
     // `ahead` passes run with nothing left to do.
@@ -1200,7 +1192,7 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
             return ECAL_ERR_INVALID;
         }
         if (r == 0) return ECAL_OK;
-        double *stage = reinterpret_cast<double *>(ctx->pass_pinned) + 64;   // (bytes 512 ..: behind the counters and the report ring)
+        double *stage = reinterpret_cast<double *>(ctx->pass_pinned.as<unsigned char>() + AD_PIN_FRAME);
         const uint32_t word[2] = {f.has ? 2u : 1u, 0u};
         memcpy(stage, word, sizeof(word));
         stage[1] = f.time;
@@ -1279,37 +1271,21 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
             AD_TRY(take_ext(0, seq));
             // (few pieces still at work — known two passes late —: the stages' latency forms, ecal_ctx::latency_pass)
             ctx->latency_pass = last_active <= AD_THIRD_IN_ONE_PIECES ? 2 : (last_active <= AD_STAGE_LATENCY_PIECES ? 1 : 0);
-            AD_TRY(ecal_window_bounds_dev(ctx, d_events, n_events, d_t0, d_t1, Sw, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr,
-                                          (uint32_t *) B[4].ptr, st));
-            AD_TRY(ecal_slice_events_dev(ctx, d_events, n_events, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, Sw, 0,
-                                         cap_points, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr,
-                                         (int32_t *) B[8].ptr, (int *) B[16].ptr, st));
-            AD_TRY(ecal_dbscan_batch_dev(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, 2 * Sw, cap_points, 0,
-                                         prm->dbscan_eps, prm->dbscan_min_samples, (int32_t *) B[9].ptr, (uint32_t *) B[10].ptr, st));
-            AD_TRY(ecal_extract_for_ctx(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, (int32_t *) B[9].ptr,
-                                        (uint32_t *) B[10].ptr, Sw, cap_points, prm->dbscan_eps, prm->cluster_min_sample, prm->need_clusters,
-                                        prm->circle_radius_threshold, prm->fit_circle, prm->knn_num, (uint32_t *) B[13].ptr,
-                                        (uint32_t *) B[14].ptr, (double *) B[15].ptr, (int32_t *) B[11].ptr, (uint32_t *) B[12].ptr, st));
             // (few pieces still at work — known two passes late —: the grid finder's latency form, a wave per start, ecal_grid.hip)
-            ctx->grid_hint_windows = last_active <= AD_GRID_LATENCY_PIECES ? 1u : Sw;
             // (the rows' line fits of the windows that hold a grid: by the grid finder's own workgroups, under the launch's slowest
             // failing window; patterns of more than 64 rows: by adaptive_dir_kernel behind it — same values)
             const bool dirs_in_grid = prm->rows <= 64;
-            rc = ecal_grid_order_dirs_dev(ctx, (uint32_t *) B[13].ptr, (uint32_t *) B[6].ptr, (double *) B[15].ptr, Sw, prm->rows, prm->cols,
-                                          (int32_t *) ctx->host_grid_order.ptr, (uint32_t *) ctx->host_grid_found.ptr,
-                                          dirs_in_grid ? (double *) ctx->adaptive_dirs.ptr : nullptr, st);
-            ctx->grid_hint_windows = 0;
-            AD_TRY(rc);
+            AD_TRY(ecal_det_chain(ctx, d_events, n_events, Sw, prm, cap_points, dirs_in_grid ? (double *) ctx->adaptive_dirs.ptr : nullptr,
+                                  last_active <= AD_GRID_LATENCY_PIECES ? 1u : Sw, st));
             if (!dirs_in_grid)
-                hipLaunchKernelGGL(adaptive_dir_kernel, dim3(Sw), dim3(64), 0, st, prm->rows, prm->cols, (const uint32_t *) B[13].ptr,
-                                   (const uint32_t *) B[6].ptr, (const double *) B[15].ptr, (const int32_t *) ctx->host_grid_order.ptr,
-                                   (const uint32_t *) ctx->host_grid_found.ptr, (double *) ctx->adaptive_dirs.ptr);
+                hipLaunchKernelGGL(adaptive_dir_kernel, dim3(Sw), dim3(64), 0, st, prm->rows, prm->cols, det.win_info.as<const uint32_t>(),
+                                   det.seg_off.as<const uint32_t>(), det.cand_xyr.as<const double>(), det.grid_order.as<const int32_t>(),
+                                   det.grid_found.as<const uint32_t>(), ctx->adaptive_dirs.as<double>());
             hipLaunchKernelGGL(adaptive_step_kernel, dim3(P), dim3(64), 0, st, P, prm->rows, prm->cols, max_levels,
-                               (const uint32_t *) B[13].ptr, (const uint32_t *) B[6].ptr, (const uint32_t *) B[7].ptr,
-                               (const double *) B[15].ptr, (const int32_t *) ctx->host_grid_order.ptr,
-                               (const uint32_t *) ctx->host_grid_found.ptr, a, ap->motion_time_step, ap->frame_event_num_threshold,
-                               max_keys, d_kt, d_kd, d_ke, d_kf, d_kp, d_kg, d_t0, d_t1, (const int *) B[16].ptr,
-                               (const double *) ctx->adaptive_dirs.ptr);
+                               det.win_info.as<const uint32_t>(), det.seg_off.as<const uint32_t>(), det.seg_cnt.as<const uint32_t>(),
+                               det.cand_xyr.as<const double>(), det.grid_order.as<const int32_t>(), det.grid_found.as<const uint32_t>(), a,
+                               ap->motion_time_step, ap->frame_event_num_threshold, max_keys, d_kt, d_kd, d_ke, d_kf, d_kp, d_kg, d_t0, d_t1,
+                               det.overflow.as<const int>(), ctx->adaptive_dirs.as<const double>());
             // shared-map gate: verification and restarts pass by pass
             // (... and the re-runs start inside the slot allocation's launch: restart_piece)
             if (shared)

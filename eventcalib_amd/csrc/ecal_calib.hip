@@ -968,9 +968,9 @@ extern "C" int ecal_calibrate_views(ecal_ctx *ctx, const double *obj, uint32_t n
     w.d_xi = base + o_xi;
     double *d_H = base + o_H, *d_err = base + o_err;
     uint32_t *d_ok = (uint32_t *) (base + o_ok);
-    if (!ctx->calib_pinned) ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &ctx->calib_pinned, (CB_RED_STRIDE + 48) * sizeof(double), hipHostMallocDefault));
-    w.h_red = ctx->calib_pinned;
-    w.h_intr[0] = ctx->calib_pinned + CB_RED_STRIDE;
+    ECAL_HIP_TRY(ctx, ecal_ensure_pinned(ctx->calib_pinned, (CB_RED_STRIDE + 48) * sizeof(double)));
+    w.h_red = ctx->calib_pinned.as<double>();
+    w.h_intr[0] = w.h_red + CB_RED_STRIDE;
     w.h_intr[1] = w.h_intr[0] + 16;
     w.h_xi = w.h_intr[1] + 16;
     ECAL_HIP_TRY(ctx, hipMemcpyAsync(w.d_obj, obj, 3 * (size_t) n_pts * sizeof(double), hipMemcpyHostToDevice, w.st));

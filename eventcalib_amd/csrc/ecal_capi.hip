@@ -104,19 +104,25 @@ uint32_t *ecal_zero_words(ecal_ctx *ctx, hipStream_t st, uint32_t n) {
     return p;
 }
 
-unsigned char *ecal_fetch_pinned(ecal_ctx *ctx, size_t bytes) {
-    if (ctx->fetch_pinned_cap >= bytes) return ctx->fetch_pinned;
-    if (ctx->fetch_pinned) (void) hipHostFree(ctx->fetch_pinned);
-    ctx->fetch_pinned = nullptr;
-    ctx->fetch_pinned_cap = 0;
+hipError_t ecal_ensure_pinned(ecal_pinned &b, size_t bytes) {
+    if (b.cap >= bytes) return hipSuccess;
+    if (b.ptr) (void) hipHostFree(b.ptr);
+    b.ptr = nullptr;
+    b.cap = 0;
     const size_t want = (bytes + bytes / 4 + 4095) & ~(size_t) 4095;
-    if (hipHostMalloc((void **) &ctx->fetch_pinned, want, hipHostMallocDefault) != hipSuccess) {
-        (void) hipGetLastError();
-        ctx->fetch_pinned = nullptr;
-        return nullptr;
+    const hipError_t e = hipHostMalloc(&b.ptr, want, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        b.ptr = nullptr;
+        return e;
     }
-    ctx->fetch_pinned_cap = want;
-    return ctx->fetch_pinned;
+    b.cap = want;
+    return hipSuccess;
+}
+
+unsigned char *ecal_fetch_pinned(ecal_ctx *ctx, size_t bytes) {
+    if (ecal_ensure_pinned(ctx->fetch_pinned, bytes) == hipSuccess) return ctx->fetch_pinned.as<unsigned char>();
+    (void) hipGetLastError();
+    return nullptr;
 }
 
 int ecal_ensure(ecal_ctx *ctx, ecal_devbuf &b, size_t bytes) {
@@ -196,12 +202,6 @@ extern "C" int ecal_init(int device, ecal_ctx **out) {
     return ECAL_OK;
 }
 
-static void release(ecal_devbuf &b) {
-    if (b.ptr) (void) hipFree(b.ptr);
-    b.ptr = nullptr;
-    b.cap = 0;
-}
-
 extern "C" void ecal_destroy(ecal_ctx *ctx) {
     if (!ctx) return;
     (void) hipSetDevice(ctx->device);
@@ -210,25 +210,21 @@ extern "C" void ecal_destroy(ecal_ctx *ctx) {
         (void) hipStreamDestroy(ctx->stream);
     }
     (void) ecal_comm_destroy(ctx);
-    if (ctx->calib_pinned) (void) hipHostFree(ctx->calib_pinned);
     if (ctx->tail_seen) (void) hipHostFree(ctx->tail_seen);
     if (ctx->copy_stream) (void) hipStreamDestroy(ctx->copy_stream);
     for (auto &c : ctx->zero_rings)
         if (c.ptr) (void) hipFree(c.ptr);
     for (auto &e : ctx->adaptive_ev)
         if (e) (void) hipEventDestroy(e);
-    if (ctx->pass_pinned) (void) hipHostFree(ctx->pass_pinned);
-    if (ctx->fetch_pinned) (void) hipHostFree(ctx->fetch_pinned);
     if (ctx->wb_done) (void) hipEventDestroy(ctx->wb_done);
     for (int k = 0; k < 2; k++) {
         if (ctx->ev_uploaded[k]) (void) hipEventDestroy(ctx->ev_uploaded[k]);
         if (ctx->ev_consumed[k]) (void) hipEventDestroy(ctx->ev_consumed[k]);
     }
-    for (ecal_devbuf *b : ctx->all_bufs()) release(*b);
     ctx->roctx_push = nullptr;
     ctx->roctx_pop = nullptr;
     if (ctx->roctx_lib) (void) dlclose(ctx->roctx_lib);
-    delete ctx;
+    delete ctx;   // (the scratch buffers, device and pinned, free themselves)
 }
 
 extern "C" int ecal_set_profile_ranges(ecal_ctx *ctx, int on) {

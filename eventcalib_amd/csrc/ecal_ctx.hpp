@@ -12,9 +12,45 @@
 
 #include "../../include/ecal.h"
 
+// grow-only device scratch (ecal_ensure): never shrinks, freed with its owner
 struct ecal_devbuf {
     void *ptr = nullptr;
     size_t cap = 0;
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+    ecal_devbuf() = default;
+    ecal_devbuf(const ecal_devbuf &) = delete;
+    ecal_devbuf &operator=(const ecal_devbuf &) = delete;
+    ~ecal_devbuf() {
+        if (ptr) (void) hipFree(ptr);
+    }
+};
+// grow-only pinned host staging (ecal_ensure_pinned): never shrinks, freed with its owner
+struct ecal_pinned {
+    void *ptr = nullptr;
+    size_t cap = 0;
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+    ecal_pinned() = default;
+    ecal_pinned(const ecal_pinned &) = delete;
+    ecal_pinned &operator=(const ecal_pinned &) = delete;
+    ~ecal_pinned() {
+        if (ptr) (void) hipHostFree(ptr);
+    }
+};
+
+// The scratch of the detection chain (ecal_det_slice + ecal_det_finish) for `slots` windows, sized by ecal_det_ensure (the
+// whole chain) or ecal_det_ensure_bounds (the window bounds alone).  cap = cap_points + 16 points.
+struct ecal_det_scratch {
+    uint32_t slots = 0;                               // the windows of the last sizing call: the layout of `times`
+    ecal_devbuf times;                                // [2][slots] double: every window's t0, then every window's t1
+    ecal_devbuf win_lo, win_hi, win_base;             // u32 [S], [S], [S + 1]: the windows' event ranges, their points' offsets
+    ecal_devbuf xy, seg_off, seg_cnt, event_point;    // the sliced points: double [cap][2], u32 [2S], u32 [2S], i32 [cap]
+    ecal_devbuf labels, n_clusters, kept, rep;        // DBSCAN and the extraction: i32 [cap], u32 [2S], i32 [cap], u32 [cap]
+    ecal_devbuf win_info, cand_pair, cand_xyr;        // u32 [S][4], u32 [cap][2], double [cap][3]
+    ecal_devbuf overflow;                             // int: the slicer's overflow flag
+    ecal_devbuf grid_order, grid_found;               // i32 [S][M], u32 [S]
+    ecal_devbuf out;                                  // the entry point's result before its download (ecal_detect_pass, the tiled ingest)
+    double *t0() const { return times.as<double>(); }
+    double *t1() const { return times.as<double>() + slots; }
 };
 
 // Debug / test switches (ECAL_FORCE, ECAL_TRACE, ECAL_ADAPTIVE_SHAPE, …: ecal_capi.hip), read from the environment ONCE per context (ecal_init) — not per call: getenv is not safe against a
@@ -76,20 +112,17 @@ struct ecal_ctx {
     ecal_devbuf bfs_big;    // ecal_cluster_order_dev: workspace + hit-list arena of the global-scratch launch
     ecal_devbuf as_cnt, as_off;  // association: per-block counts / offsets
     ecal_devbuf as_host;         // staging of ecal_associate
-    ecal_devbuf ingest_ev[2], ingest_feat;  // ecal_detect_stream_tiled: ping-pong event chunks, gathered features
-    hipStream_t copy_stream = nullptr;      // uploads of the double-buffered ingest
-    double *pass_pinned = nullptr;          // ecal_detect_pass: pinned window bounds in, packed verdicts out
-    size_t pass_pinned_cap = 0;
-    unsigned char *fetch_pinned = nullptr;  // ecal_fetch_pinned: pinned staging of the larger result downloads (a hipMemcpy into pageable memory the runtime has not seen before runs at ~0.3 GB/s: 25 - 30 ms for the keyframe search's 8 MB in the first calls of a process)
-    size_t fetch_pinned_cap = 0;
+    ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks
+    hipStream_t copy_stream = nullptr;  // uploads of the double-buffered ingest
+    ecal_pinned pass_pinned;            // ecal_detect_pass: window times in, packed verdicts out; the keyframe search: counters, report ring, handed-over frame
+    ecal_pinned fetch_pinned;           // ecal_fetch_pinned: pinned staging of the larger result downloads (a hipMemcpy into pageable memory the runtime has not seen before runs at ~0.3 GB/s: 25 - 30 ms for the keyframe search's 8 MB in the first calls of a process)
     hipEvent_t ev_uploaded[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
-    ecal_devbuf host_pipe[17];  // staging of ecal_detect_batch
-    ecal_devbuf host_grid_order, host_grid_found;
+    ecal_det_scratch det;       // the detection chain's scratch: ecal_detect_batch / _pass / _stream_tiled, the keyframe search
     ecal_devbuf host_rect[11];  // staging of ecal_rectify_batch
     ecal_devbuf calib_scratch;  // ecal_calibrate_views: views, blocks, reduced records
     ecal_devbuf adaptive_state, adaptive_keys, adaptive_dirs;  // ecal_detect_keyframes: per-piece window state, keyframe records, row directions per window
     hipEvent_t adaptive_ev[8] = {};             // ecal_detect_keyframes: one behind every pass in flight
-    double *calib_pinned = nullptr;  // pinned host landing zone of the reduced record
+    ecal_pinned calib_pinned;  // pinned host landing zone of the reduced record
     void *comm = nullptr;   // ncclComm_t (ecal_comm.hip); null = single rank
     int comm_rank = 0, comm_size = 1;
     // Words of device memory that are zero when handed out (ecal_zero_words): the to-do counters of the stage calls.  A ring
@@ -118,17 +151,6 @@ struct ecal_ctx {
     void *roctx_lib = nullptr;
     uint32_t n_cu = 256;  // compute units of the device (grid size of the persistent kernels)
     bool attrs_set = false, slice_attrs_set = false, det_attr_set = false, bfs_attr_set = false;
-    std::vector<ecal_devbuf *> all_bufs() {
-        return {&in_xy, &in_off, &in_cnt, &out_labels, &out_ncl, &px_todo, &pxs_todo, &wb_status, &px_tree, &px_tree_flag, &big_slot, &big_anc, &big_cur, &big_inv, &big_cs, &big_flags,
-                &sl_pts, &sl_pol, &sl_bend, &sl_sorted, &sl_rep, &sl_pos, &sl_order, &sl_order_big, &bucket_tab, &sort_scratch,
-                &det_members, &det_koff, &det_ksize, &det_sorted, &det_norms, &det_todo, &bfs_lists, &bfs_defer, &bfs_big, &bfs_host, &tie_list, &tie_order, &as_cnt, &as_off,
-                &host_rect[0], &host_rect[1], &host_rect[2], &host_rect[3], &host_rect[4], &host_rect[5], &host_rect[6],
-                &host_rect[7], &host_rect[8], &host_rect[9], &host_rect[10],
-                &host_pipe[0], &host_pipe[1], &host_pipe[2], &host_pipe[3], &host_pipe[4], &host_pipe[5],
-                &host_pipe[6], &host_pipe[7], &host_pipe[8], &host_pipe[9], &host_pipe[10], &host_pipe[11],
-                &host_pipe[12], &host_pipe[13], &host_pipe[14], &host_pipe[15], &host_pipe[16],
-                &host_grid_order, &host_grid_found, &calib_scratch, &adaptive_state, &adaptive_keys, &adaptive_dirs, &as_host, &ingest_ev[0], &ingest_ev[1], &ingest_feat};
-    }
 };
 
 #define ECAL_HIP_TRY(ctx, call)                                                                       \
@@ -204,3 +226,21 @@ uint32_t *ecal_zero_words(ecal_ctx *ctx, hipStream_t st, uint32_t n);
 unsigned char *ecal_fetch_pinned(ecal_ctx *ctx, size_t bytes);
 // ensure a scratch buffer of at least `bytes` (contents are NOT preserved)
 int ecal_ensure(ecal_ctx *ctx, ecal_devbuf &b, size_t bytes);
+// the same for pinned host staging: hipSuccess, or the allocation's error with the buffer left empty
+hipError_t ecal_ensure_pinned(ecal_pinned &b, size_t bytes);
+// ctx->det for S windows of up to cap_points points and M = rows x cols grid points (0: no grid stage), or for the window
+// bounds alone; either sets the layout of det.times
+int ecal_det_ensure(ecal_ctx *ctx, uint32_t S, uint32_t cap_points, uint32_t M);
+int ecal_det_ensure_bounds(ecal_ctx *ctx, uint32_t S);
+// The detection chain on ctx->det for the S windows whose times stand in det.t0() / det.t1(), over d_events[0, n_events) (ecal_host.hip).
+// ecal_det_slice: window bounds, slicing.  ecal_det_finish: DBSCAN, extraction and, when prm->rows x cols > 0, the grid finder,
+// with the found grids' row directions into d_dirs[S][rows][2] (null: none) and grid_hint as ecal_ctx::grid_hint_windows for
+// its call.  (Two calls: the double-buffered ingest frees its event chunk between them.)
+int ecal_det_slice(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, uint32_t S, uint32_t cap_points, hipStream_t st);
+int ecal_det_finish(ecal_ctx *ctx, uint32_t S, const ecal_detect_params *prm, uint32_t cap_points, double *d_dirs, uint32_t grid_hint,
+                    hipStream_t st);
+inline int ecal_det_chain(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, uint32_t S, const ecal_detect_params *prm,
+                          uint32_t cap_points, double *d_dirs, uint32_t grid_hint, hipStream_t st) {
+    const int rc = ecal_det_slice(ctx, d_events, n_events, S, cap_points, st);
+    return rc ? rc : ecal_det_finish(ctx, S, prm, cap_points, d_dirs, grid_hint, st);
+}

@@ -955,22 +955,22 @@ extern "C" int ecal_grid_order(ecal_ctx *ctx, const double *cand_xyr, uint32_t n
     if (n < M || n > GR_MAXC) return ECAL_OK;      // (the kernel's own rule: fewer candidates than pattern points, or more than it handles)
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    ecal_devbuf *B = ctx->host_pipe;   // roles as in ecal_detect_pass: 13 win_info, 6 seg_off, 15 candidates
+    ecal_det_scratch &det = ctx->det;   // (one window of n candidates)
     int rc;
-    if ((rc = ecal_ensure(ctx, B[13], 4 * sizeof(uint32_t))) || (rc = ecal_ensure(ctx, B[6], 2 * sizeof(uint32_t))) ||
-        (rc = ecal_ensure(ctx, B[15], (size_t) n * 3 * sizeof(double))) || (rc = ecal_ensure(ctx, ctx->host_grid_order, M * sizeof(int32_t))) ||
-        (rc = ecal_ensure(ctx, ctx->host_grid_found, sizeof(uint32_t))))
+    if ((rc = ecal_ensure(ctx, det.win_info, 4 * sizeof(uint32_t))) || (rc = ecal_ensure(ctx, det.seg_off, 2 * sizeof(uint32_t))) ||
+        (rc = ecal_ensure(ctx, det.cand_xyr, (size_t) n * 3 * sizeof(double))) || (rc = ecal_ensure(ctx, det.grid_order, M * sizeof(int32_t))) ||
+        (rc = ecal_ensure(ctx, det.grid_found, sizeof(uint32_t))))
         return rc;
     const uint32_t info[4] = {n, 0, 0, 0}, off[2] = {0, 0};
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[13].ptr, info, sizeof(info), hipMemcpyHostToDevice, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[6].ptr, off, sizeof(off), hipMemcpyHostToDevice, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[15].ptr, cand_xyr, (size_t) n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.win_info.ptr, info, sizeof(info), hipMemcpyHostToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.seg_off.ptr, off, sizeof(off), hipMemcpyHostToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.cand_xyr.ptr, cand_xyr, (size_t) n * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (the sources are the caller's pageable memory and this frame's locals)
-    if ((rc = ecal_grid_order_dev(ctx, (const uint32_t *) B[13].ptr, (const uint32_t *) B[6].ptr, (const double *) B[15].ptr, 1, rows, cols,
-                                  (int32_t *) ctx->host_grid_order.ptr, (uint32_t *) ctx->host_grid_found.ptr, st)))
+    if ((rc = ecal_grid_order_dev(ctx, det.win_info.as<uint32_t>(), det.seg_off.as<uint32_t>(), det.cand_xyr.as<double>(), 1, rows, cols,
+                                  det.grid_order.as<int32_t>(), det.grid_found.as<uint32_t>(), st)))
         return rc;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(order, ctx->host_grid_order.ptr, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(found, ctx->host_grid_found.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(order, det.grid_order.ptr, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(found, det.grid_found.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
     return ECAL_OK;
 }

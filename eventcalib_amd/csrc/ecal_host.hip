@@ -287,6 +287,64 @@ struct Out {
 };
 }  // namespace
 
+int ecal_det_ensure_bounds(ecal_ctx *ctx, uint32_t S) {
+    ecal_det_scratch &det = ctx->det;
+    int rc;
+    if ((rc = ecal_ensure(ctx, det.times, 2ul * S * sizeof(double))) || (rc = ecal_ensure(ctx, det.win_lo, S * 4ul)) ||
+        (rc = ecal_ensure(ctx, det.win_hi, S * 4ul)) || (rc = ecal_ensure(ctx, det.win_base, (S + 1) * 4ul)))
+        return rc;
+    det.slots = S;
+    return ECAL_OK;
+}
+
+int ecal_det_ensure(ecal_ctx *ctx, uint32_t S, uint32_t cap_points, uint32_t M) {
+    int rc;
+    if ((rc = ecal_det_ensure_bounds(ctx, S))) return rc;
+    ecal_det_scratch &det = ctx->det;
+    const size_t cap = (size_t) cap_points + 16;
+    const struct {
+        ecal_devbuf &buf;
+        size_t bytes;
+    } need[] = {{det.xy, cap * 16},         {det.seg_off, 2ul * S * 4},          {det.seg_cnt, 2ul * S * 4}, {det.event_point, cap * 4},
+                {det.labels, cap * 4},      {det.n_clusters, 2ul * S * 4},       {det.kept, cap * 4},        {det.rep, cap * 4},
+                {det.win_info, 4ul * S * 4}, {det.cand_pair, cap * 8},           {det.cand_xyr, cap * 24},   {det.overflow, 16},
+                {det.grid_order, (size_t) S * M * 4}, {det.grid_found, S * 4ul}};
+    for (const auto &n : need)
+        if ((rc = ecal_ensure(ctx, n.buf, n.bytes))) return rc;
+    return ECAL_OK;
+}
+
+int ecal_det_slice(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, uint32_t S, uint32_t cap_points, hipStream_t st) {
+    ecal_det_scratch &det = ctx->det;
+    int rc;
+    if ((rc = ecal_window_bounds_dev(ctx, d_events, n_events, det.t0(), det.t1(), S, det.win_lo.as<uint32_t>(), det.win_hi.as<uint32_t>(),
+                                     det.win_base.as<uint32_t>(), st)))
+        return rc;
+    return ecal_slice_events_dev(ctx, d_events, n_events, det.win_lo.as<uint32_t>(), det.win_hi.as<uint32_t>(), det.win_base.as<uint32_t>(), S, 0,
+                                 cap_points, det.xy.as<double>(), det.seg_off.as<uint32_t>(), det.seg_cnt.as<uint32_t>(),
+                                 det.event_point.as<int32_t>(), det.overflow.as<int>(), st);
+}
+
+int ecal_det_finish(ecal_ctx *ctx, uint32_t S, const ecal_detect_params *prm, uint32_t cap_points, double *d_dirs, uint32_t grid_hint,
+                    hipStream_t st) {
+    ecal_det_scratch &det = ctx->det;
+    int rc;
+    if ((rc = ecal_dbscan_batch_dev(ctx, det.xy.as<double>(), det.seg_off.as<uint32_t>(), det.seg_cnt.as<uint32_t>(), 2 * S, cap_points, 0,
+                                    prm->dbscan_eps, prm->dbscan_min_samples, det.labels.as<int32_t>(), det.n_clusters.as<uint32_t>(), st)))
+        return rc;
+    if ((rc = ecal_extract_for_ctx(ctx, det.xy.as<double>(), det.seg_off.as<uint32_t>(), det.seg_cnt.as<uint32_t>(), det.labels.as<int32_t>(),
+                                   det.n_clusters.as<uint32_t>(), S, cap_points, prm->dbscan_eps, prm->cluster_min_sample, prm->need_clusters,
+                                   prm->circle_radius_threshold, prm->fit_circle, prm->knn_num, det.win_info.as<uint32_t>(),
+                                   det.cand_pair.as<uint32_t>(), det.cand_xyr.as<double>(), det.kept.as<int32_t>(), det.rep.as<uint32_t>(), st)))
+        return rc;
+    if (prm->rows * prm->cols == 0) return ECAL_OK;
+    ctx->grid_hint_windows = grid_hint;
+    rc = ecal_grid_order_dirs_dev(ctx, det.win_info.as<uint32_t>(), det.seg_off.as<uint32_t>(), det.cand_xyr.as<double>(), S, prm->rows, prm->cols,
+                                  det.grid_order.as<int32_t>(), det.grid_found.as<uint32_t>(), d_dirs, st);
+    ctx->grid_hint_windows = 0;
+    return rc;
+}
+
 extern "C" int ecal_detect_batch(ecal_ctx *ctx, const ecal_stream *es, const double *t0, const double *t1, uint32_t S,
                                  const ecal_detect_params *prm, uint32_t cap_points, ecal_detect_result *res) {
     if (!ctx || !es || !prm || !res || (S && (!t0 || !t1))) return ECAL_ERR_INVALID;
@@ -297,64 +355,31 @@ extern "C" int ecal_detect_batch(ecal_ctx *ctx, const ecal_stream *es, const dou
     if (S == 0) return ECAL_OK;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    int rc;
-    const size_t cap = (size_t) cap_points + 16;
-    ecal_devbuf &b = ctx->host_pipe[0];
-    (void) b;
-    ecal_devbuf *B = ctx->host_pipe;  // 0 t0, 1 t1, 2 lo, 3 hi, 4 base, 5 xy, 6 seg_off, 7 seg_cnt, 8 event_point,
-                                      // 9 labels, 10 ncl, 11 kept, 12 rep, 13 info, 14 pair, 15 xyr, 16 flag
-    const size_t sizes[17] = {S * sizeof(double), S * sizeof(double), S * 4ul, S * 4ul, (S + 1) * 4ul,
-                              cap * 16, 2ul * S * 4, 2ul * S * 4, cap * 4, cap * 4, 2ul * S * 4, cap * 4, cap * 4,
-                              4ul * S * 4, cap * 8, cap * 24, 16};
-    for (int i = 0; i < 17; i++)
-        if ((rc = ecal_ensure(ctx, B[i], sizes[i]))) return rc;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[0].ptr, t0, S * sizeof(double), hipMemcpyHostToDevice, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[1].ptr, t1, S * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = ecal_window_bounds_dev(ctx, es->d_events, es->n_events, (double *) B[0].ptr, (double *) B[1].ptr, S,
-                                     (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, st)))
-        return rc;
-    if ((rc = ecal_slice_events_dev(ctx, es->d_events, es->n_events, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr,
-                                    (uint32_t *) B[4].ptr, S, 0, cap_points, (double *) B[5].ptr,
-                                    (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, (int32_t *) B[8].ptr,
-                                    (int *) B[16].ptr, st)))
-        return rc;
-    if ((rc = ecal_dbscan_batch_dev(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, 2 * S,
-                                    cap_points, 0, prm->dbscan_eps, prm->dbscan_min_samples, (int32_t *) B[9].ptr,
-                                    (uint32_t *) B[10].ptr, st)))
-        return rc;
-    if ((rc = ecal_extract_for_ctx(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr,
-                                     (int32_t *) B[9].ptr, (uint32_t *) B[10].ptr, S, cap_points, prm->dbscan_eps, prm->cluster_min_sample,
-                                     prm->need_clusters, prm->circle_radius_threshold, prm->fit_circle, prm->knn_num,
-                                     (uint32_t *) B[13].ptr,
-                                     (uint32_t *) B[14].ptr, (double *) B[15].ptr, (int32_t *) B[11].ptr,
-                                     (uint32_t *) B[12].ptr, st)))
-        return rc;
     const uint32_t M = prm->rows * prm->cols;
-    if (M > 0) {
-        if ((rc = ecal_ensure(ctx, ctx->host_grid_order, (size_t) S * M * sizeof(int32_t)))) return rc;
-        if ((rc = ecal_ensure(ctx, ctx->host_grid_found, (size_t) S * sizeof(uint32_t)))) return rc;
-        if ((rc = ecal_grid_order_dev(ctx, (uint32_t *) B[13].ptr, (uint32_t *) B[6].ptr, (double *) B[15].ptr, S,
-                                      prm->rows, prm->cols, (int32_t *) ctx->host_grid_order.ptr,
-                                      (uint32_t *) ctx->host_grid_found.ptr, st)))
-            return rc;
-        if (res->grid_order)
-            ECAL_HIP_TRY(ctx, hipMemcpyAsync(res->grid_order, ctx->host_grid_order.ptr, (size_t) S * M * sizeof(int32_t),
-                                             hipMemcpyDeviceToHost, st));
-        if (res->grid_found)
-            ECAL_HIP_TRY(ctx, hipMemcpyAsync(res->grid_found, ctx->host_grid_found.ptr, (size_t) S * sizeof(uint32_t),
-                                             hipMemcpyDeviceToHost, st));
-    }
+    ecal_det_scratch &det = ctx->det;
+    int rc;
+    if ((rc = ecal_det_ensure(ctx, S, cap_points, M))) return rc;
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t0(), t0, S * sizeof(double), hipMemcpyHostToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t1(), t1, S * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = ecal_det_chain(ctx, es->d_events, es->n_events, S, prm, cap_points, nullptr, 0, st))) return rc;
     int overflow = 0;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&overflow, B[16].ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-    const Out outs[] = {{res->win_lo, &B[2], S * 4ul},        {res->win_hi, &B[3], S * 4ul},
-                        {res->win_base, &B[4], (S + 1) * 4ul}, {res->xy, &B[5], (size_t) cap_points * 16},
-                        {res->seg_off, &B[6], 2ul * S * 4},    {res->seg_cnt, &B[7], 2ul * S * 4},
-                        {res->event_point, &B[8], (size_t) cap_points * 4},
-                        {res->labels, &B[9], (size_t) cap_points * 4},
-                        {res->n_clusters, &B[10], 2ul * S * 4}, {res->kept_labels, &B[11], (size_t) cap_points * 4},
-                        {res->rep, &B[12], (size_t) cap_points * 4}, {res->win_info, &B[13], 4ul * S * 4},
-                        {res->cand_pair, &B[14], (size_t) cap_points * 8},
-                        {res->cand_xyr, &B[15], (size_t) cap_points * 24}};
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&overflow, det.overflow.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    const Out outs[] = {{res->win_lo, &det.win_lo, S * 4ul},
+                        {res->win_hi, &det.win_hi, S * 4ul},
+                        {res->win_base, &det.win_base, (S + 1) * 4ul},
+                        {res->xy, &det.xy, (size_t) cap_points * 16},
+                        {res->seg_off, &det.seg_off, 2ul * S * 4},
+                        {res->seg_cnt, &det.seg_cnt, 2ul * S * 4},
+                        {res->event_point, &det.event_point, (size_t) cap_points * 4},
+                        {res->labels, &det.labels, (size_t) cap_points * 4},
+                        {res->n_clusters, &det.n_clusters, 2ul * S * 4},
+                        {res->kept_labels, &det.kept, (size_t) cap_points * 4},
+                        {res->rep, &det.rep, (size_t) cap_points * 4},
+                        {res->win_info, &det.win_info, 4ul * S * 4},
+                        {res->cand_pair, &det.cand_pair, (size_t) cap_points * 8},
+                        {res->cand_xyr, &det.cand_xyr, (size_t) cap_points * 24},
+                        {res->grid_order, &det.grid_order, (size_t) S * M * sizeof(int32_t)},   // (M = 0: no grid stage ran)
+                        {res->grid_found, &det.grid_found, M ? (size_t) S * sizeof(uint32_t) : 0}};
     for (const Out &o : outs)
         if (o.host && o.bytes) ECAL_HIP_TRY(ctx, hipMemcpyAsync(o.host, o.dev->ptr, o.bytes, hipMemcpyDeviceToHost, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -387,17 +412,15 @@ extern "C" int ecal_rectify_keyframes(ecal_ctx *ctx, const ecal_stream *es, cons
         t1[f] = durations[2 * f + 1];
     }
     // slots = the events the windows cover: one bounds pass tells
-    ecal_devbuf *B = ctx->host_pipe;
-    const size_t pre[5] = {F * sizeof(double), F * sizeof(double), F * 4ul, F * 4ul, (F + 1) * 4ul};
-    for (int i = 0; i < 5; i++)
-        if ((rc = ecal_ensure(ctx, B[i], pre[i]))) return rc;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[0].ptr, t0.data(), F * sizeof(double), hipMemcpyHostToDevice, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[1].ptr, t1.data(), F * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = ecal_window_bounds_dev(ctx, es->d_events, es->n_events, (double *) B[0].ptr, (double *) B[1].ptr, F, (uint32_t *) B[2].ptr,
-                                     (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, st)))
+    const ecal_det_scratch &det = ctx->det;
+    if ((rc = ecal_det_ensure_bounds(ctx, F))) return rc;
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t0(), t0.data(), F * sizeof(double), hipMemcpyHostToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t1(), t1.data(), F * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = ecal_window_bounds_dev(ctx, es->d_events, es->n_events, det.t0(), det.t1(), F, det.win_lo.as<uint32_t>(), det.win_hi.as<uint32_t>(),
+                                     det.win_base.as<uint32_t>(), st)))
         return rc;
     uint32_t total = 0;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&total, (uint32_t *) B[4].ptr + F, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&total, det.win_base.as<uint32_t>() + F, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
     ecal_detect_params dp = *dprm;
     dp.rows = dp.cols = 0;   // (no grid ordering: rectifyFeatures works on the clusters)
@@ -422,8 +445,8 @@ extern "C" int ecal_rectify_keyframes(ecal_ctx *ctx, const ecal_stream *es, cons
     ECAL_HIP_TRY(ctx, hipMemcpyAsync(R[1].ptr, landmarks, rs[1], hipMemcpyHostToDevice, st));
     ECAL_HIP_TRY(ctx, hipMemcpyAsync(R[2].ptr, ident.data(), rs[2], hipMemcpyHostToDevice, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (pageable sources: consumed)
-    if ((rc = ecal_rectify_batch_dev(ctx, (const double *) B[5].ptr, (const uint32_t *) B[6].ptr, (const uint32_t *) B[7].ptr,
-                                     (const int32_t *) B[11].ptr, (const uint32_t *) B[13].ptr, (const uint32_t *) R[2].ptr,
+    if ((rc = ecal_rectify_batch_dev(ctx, det.xy.as<double>(), det.seg_off.as<uint32_t>(), det.seg_cnt.as<uint32_t>(), det.kept.as<int32_t>(),
+                                     det.win_info.as<uint32_t>(), (const uint32_t *) R[2].ptr,
                                      (const double *) R[0].ptr, F, (const double *) R[1].ptr, rprm, (double *) R[3].ptr, (uint32_t *) R[4].ptr,
                                      (uint32_t *) R[5].ptr, st)))
         return rc;
@@ -516,54 +539,23 @@ extern "C" int ecal_detect_pass(ecal_ctx *ctx, const uint8_t *d_events, uint64_t
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     int rc;
-    const size_t cap = (size_t) cap_points + 16, W = 3 + 3 * (size_t) M;
-    ecal_devbuf *B = ctx->host_pipe;  // roles as in ecal_detect_batch; 0 holds t0 and t1 back to back
-    const size_t sizes[17] = {2ul * S * sizeof(double), 16, S * 4ul, S * 4ul, (S + 1) * 4ul, cap * 16, 2ul * S * 4, 2ul * S * 4, cap * 4,
-                              cap * 4, 2ul * S * 4, cap * 4, cap * 4, 4ul * S * 4, cap * 8, cap * 24, 16};
-    for (int i = 0; i < 17; i++)
-        if ((rc = ecal_ensure(ctx, B[i], sizes[i]))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_order, (size_t) S * M * sizeof(int32_t)))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_found, (size_t) S * sizeof(uint32_t)))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->ingest_feat, (size_t) S * W * sizeof(double)))) return rc;
-    const size_t pin_need = 2ul * S * sizeof(double) + (size_t) S * W * sizeof(double) + 16;
-    if (ctx->pass_pinned_cap < pin_need) {
-        if (ctx->pass_pinned) (void) hipHostFree(ctx->pass_pinned);
-        ctx->pass_pinned = nullptr;
-        ctx->pass_pinned_cap = 0;
-        ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &ctx->pass_pinned, pin_need + pin_need / 2, hipHostMallocDefault));
-        ctx->pass_pinned_cap = pin_need + pin_need / 2;
-    }
-    double *h_t = ctx->pass_pinned, *h_out = ctx->pass_pinned + 2 * (size_t) S;
+    const size_t W = 3 + 3 * (size_t) M;
+    ecal_det_scratch &det = ctx->det;
+    if ((rc = ecal_det_ensure(ctx, S, cap_points, M)) || (rc = ecal_ensure(ctx, det.out, (size_t) S * W * sizeof(double)))) return rc;
+    ECAL_HIP_TRY(ctx, ecal_ensure_pinned(ctx->pass_pinned, 2ul * S * sizeof(double) + (size_t) S * W * sizeof(double) + 16));
+    double *h_t = ctx->pass_pinned.as<double>(), *h_out = h_t + 2 * (size_t) S;
     memcpy(h_t, t0, S * sizeof(double));
     memcpy(h_t + S, t1, S * sizeof(double));
-    double *d_t0 = (double *) B[0].ptr, *d_t1 = d_t0 + S;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_t0, h_t, 2ul * S * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = ecal_window_bounds_dev(ctx, d_events, n_events, d_t0, d_t1, S, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr,
-                                     (uint32_t *) B[4].ptr, st)))
-        return rc;
-    if ((rc = ecal_slice_events_dev(ctx, d_events, n_events, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, S, 0,
-                                    cap_points, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, (int32_t *) B[8].ptr,
-                                    (int *) B[16].ptr, st)))
-        return rc;
-    if ((rc = ecal_dbscan_batch_dev(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, 2 * S, cap_points, 0,
-                                    prm->dbscan_eps, prm->dbscan_min_samples, (int32_t *) B[9].ptr, (uint32_t *) B[10].ptr, st)))
-        return rc;
-    if ((rc = ecal_extract_for_ctx(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, (int32_t *) B[9].ptr,
-                                     (uint32_t *) B[10].ptr, S, cap_points, prm->dbscan_eps, prm->cluster_min_sample, prm->need_clusters,
-                                     prm->circle_radius_threshold, prm->fit_circle, prm->knn_num, (uint32_t *) B[13].ptr,
-                                     (uint32_t *) B[14].ptr, (double *) B[15].ptr, (int32_t *) B[11].ptr, (uint32_t *) B[12].ptr, st)))
-        return rc;
-    if ((rc = ecal_grid_order_dev(ctx, (uint32_t *) B[13].ptr, (uint32_t *) B[6].ptr, (double *) B[15].ptr, S, prm->rows, prm->cols,
-                                  (int32_t *) ctx->host_grid_order.ptr, (uint32_t *) ctx->host_grid_found.ptr, st)))
-        return rc;
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t0(), h_t, 2ul * S * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = ecal_det_chain(ctx, d_events, n_events, S, prm, cap_points, nullptr, 0, st))) return rc;
     const uint32_t tot = S * (M + 1);
-    hipLaunchKernelGGL(pack_pass_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, (const uint32_t *) B[13].ptr, (const uint32_t *) B[6].ptr,
-                       (const uint32_t *) B[7].ptr, (const double *) B[15].ptr, (const int32_t *) ctx->host_grid_order.ptr,
-                       (const uint32_t *) ctx->host_grid_found.ptr, S, M, (double *) ctx->ingest_feat.ptr);
+    hipLaunchKernelGGL(pack_pass_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, det.win_info.as<const uint32_t>(),
+                       det.seg_off.as<const uint32_t>(), det.seg_cnt.as<const uint32_t>(), det.cand_xyr.as<const double>(),
+                       det.grid_order.as<const int32_t>(), det.grid_found.as<const uint32_t>(), S, M, det.out.as<double>());
     // the overflow flag lands in the pinned block too: a copy into pageable memory would take the runtime's synchronous path
     int *h_flag = reinterpret_cast<int *>(h_out + (size_t) S * W);
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(h_out, ctx->ingest_feat.ptr, (size_t) S * W * sizeof(double), hipMemcpyDeviceToHost, st));
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(h_flag, B[16].ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(h_out, det.out.ptr, (size_t) S * W * sizeof(double), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(h_flag, det.overflow.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
     const int overflow = *h_flag;
     if (overflow) {
@@ -634,15 +626,8 @@ extern "C" int ecal_detect_stream_tiled(ecal_ctx *ctx, const uint8_t *events, ui
     for (int k = 0; k < 2; k++)
         if ((rc = ecal_ensure(ctx, ctx->ingest_ev[k], max_ev * 25 + 32))) return rc;
     const uint32_t Wc = windows_per_chunk;
-    const size_t cap = (size_t) max_ev + 16;
-    ecal_devbuf *B = ctx->host_pipe;  // same roles as in ecal_detect_batch
-    const size_t sizes[17] = {Wc * sizeof(double), Wc * sizeof(double), Wc * 4ul, Wc * 4ul, (Wc + 1) * 4ul, cap * 16, 2ul * Wc * 4,
-                              2ul * Wc * 4, cap * 4, cap * 4, 2ul * Wc * 4, cap * 4, cap * 4, 4ul * Wc * 4, cap * 8, cap * 24, 16};
-    for (int i = 0; i < 17; i++)
-        if ((rc = ecal_ensure(ctx, B[i], sizes[i]))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_order, (size_t) Wc * (M ? M : 1) * sizeof(int32_t)))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->host_grid_found, (size_t) Wc * sizeof(uint32_t)))) return rc;
-    if ((rc = ecal_ensure(ctx, ctx->ingest_feat, (size_t) Wc * (M ? M : 1) * 24))) return rc;
+    ecal_det_scratch &det = ctx->det;
+    if ((rc = ecal_det_ensure(ctx, Wc, (uint32_t) max_ev, M)) || (rc = ecal_ensure(ctx, det.out, (size_t) Wc * (M ? M : 1) * 24))) return rc;
     std::vector<double> t0(Wc), t1(Wc);
     auto upload = [&](uint32_t c) -> int {
         const int k = c & 1;
@@ -664,47 +649,27 @@ extern "C" int ecal_detect_stream_tiled(ecal_ctx *ctx, const uint8_t *events, ui
             t1[w] = nextafter(t_start + window_len * (double) (w0 + w + 1), -INFINITY);
         }
         // the host vectors are reused per chunk: wait until the previous chunk's copies of them were taken
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[0].ptr, t0.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(B[1].ptr, t1.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
+        ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t0(), t0.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
+        ECAL_HIP_TRY(ctx, hipMemcpyAsync(det.t1(), t1.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
         ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));  // also bounds the host's run-ahead to one chunk
         ECAL_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_uploaded[k], 0));
-        if ((rc = ecal_window_bounds_dev(ctx, d_ev, ne, (double *) B[0].ptr, (double *) B[1].ptr, nw, (uint32_t *) B[2].ptr,
-                                         (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, st)))
-            return rc;
-        if ((rc = ecal_slice_events_dev(ctx, d_ev, ne, (uint32_t *) B[2].ptr, (uint32_t *) B[3].ptr, (uint32_t *) B[4].ptr, nw, 0,
-                                        (uint32_t) max_ev, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr,
-                                        (int32_t *) B[8].ptr, (int *) B[16].ptr, st)))
-            return rc;
+        if ((rc = ecal_det_slice(ctx, d_ev, ne, nw, (uint32_t) max_ev, st))) return rc;
         ECAL_HIP_TRY(ctx, hipEventRecord(ctx->ev_consumed[k], st));  // the packed records are not read after slicing
-        if ((rc = ecal_dbscan_batch_dev(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, 2 * nw,
-                                        (uint32_t) max_ev, 0, prm->dbscan_eps, prm->dbscan_min_samples, (int32_t *) B[9].ptr,
-                                        (uint32_t *) B[10].ptr, st)))
-            return rc;
-        if ((rc = ecal_extract_for_ctx(ctx, (double *) B[5].ptr, (uint32_t *) B[6].ptr, (uint32_t *) B[7].ptr, (int32_t *) B[9].ptr,
-                                         (uint32_t *) B[10].ptr, nw, (uint32_t) max_ev, prm->dbscan_eps, prm->cluster_min_sample, prm->need_clusters,
-                                         prm->circle_radius_threshold, prm->fit_circle, prm->knn_num, (uint32_t *) B[13].ptr,
-                                         (uint32_t *) B[14].ptr, (double *) B[15].ptr, (int32_t *) B[11].ptr, (uint32_t *) B[12].ptr,
-                                         st)))
-            return rc;
-        if (win_info) ECAL_HIP_TRY(ctx, hipMemcpyAsync(win_info + 4 * (size_t) w0, B[13].ptr, 4ul * nw * 4, hipMemcpyDeviceToHost, st));
+        if ((rc = ecal_det_finish(ctx, nw, prm, (uint32_t) max_ev, nullptr, 0, st))) return rc;
+        if (win_info) ECAL_HIP_TRY(ctx, hipMemcpyAsync(win_info + 4 * (size_t) w0, det.win_info.ptr, 4ul * nw * 4, hipMemcpyDeviceToHost, st));
         if (M > 0) {
-            if ((rc = ecal_grid_order_dev(ctx, (uint32_t *) B[13].ptr, (uint32_t *) B[6].ptr, (double *) B[15].ptr, nw, prm->rows,
-                                          prm->cols, (int32_t *) ctx->host_grid_order.ptr, (uint32_t *) ctx->host_grid_found.ptr, st)))
-                return rc;
-            if (grid_found)
-                ECAL_HIP_TRY(ctx, hipMemcpyAsync(grid_found + w0, ctx->host_grid_found.ptr, nw * 4ul, hipMemcpyDeviceToHost, st));
+            if (grid_found) ECAL_HIP_TRY(ctx, hipMemcpyAsync(grid_found + w0, det.grid_found.ptr, nw * 4ul, hipMemcpyDeviceToHost, st));
             if (features) {
                 const uint32_t tot = nw * M;
-                hipLaunchKernelGGL(gather_features_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, (const uint32_t *) B[13].ptr,
-                                   (const uint32_t *) B[6].ptr, (const double *) B[15].ptr, (const int32_t *) ctx->host_grid_order.ptr,
-                                   (const uint32_t *) ctx->host_grid_found.ptr, nw, M, (double *) ctx->ingest_feat.ptr);
-                ECAL_HIP_TRY(ctx, hipMemcpyAsync(features + 3 * (size_t) w0 * M, ctx->ingest_feat.ptr, (size_t) tot * 24,
-                                                 hipMemcpyDeviceToHost, st));
+                hipLaunchKernelGGL(gather_features_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, det.win_info.as<const uint32_t>(),
+                                   det.seg_off.as<const uint32_t>(), det.cand_xyr.as<const double>(), det.grid_order.as<const int32_t>(),
+                                   det.grid_found.as<const uint32_t>(), nw, M, det.out.as<double>());
+                ECAL_HIP_TRY(ctx, hipMemcpyAsync(features + 3 * (size_t) w0 * M, det.out.ptr, (size_t) tot * 24, hipMemcpyDeviceToHost, st));
             }
         }
     }
     int overflow = 0;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&overflow, B[16].ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&overflow, det.overflow.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
     ECAL_HIP_TRY(ctx, hipStreamSynchronize(cs));
     *n_windows = S;
