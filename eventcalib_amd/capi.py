@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "ecal_solver_solve", "ecal_inverse_radial_distortion", "ecal_solver_create_dev", "ecal_solver_num_residuals",
     "ecal_associate_ranges_dev", "ecal_ref_nth_element_f64", "ecal_solver_create_from_stream", "ecal_rectify_keyframes", "ecal_solver_time_shard_cuts",
     "ecal_slice_events_packed_dev", "ecal_dbscan_batch_packed_dev", "ecal_extract_batch_packed_dev", "ecal_unpack_points_dev",
+    "ecal_report_default_options", "ecal_solver_report_dev", "ecal_solver_report", "ecal_solver_num_landmarks",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -497,8 +498,28 @@ class LmSummary(ctypes.Structure):
                 ("seconds_linear_solve", ctypes.c_double)]
 
 
+class ReportOptions(ctypes.Structure):
+    """ecal_report_options (include/ecal.h)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("cell_px", ctypes.c_uint32), ("hist_bins", ctypes.c_uint32),
+                ("hist_range", ctypes.c_double), ("outlier_thresh", ctypes.c_double)]
+
+
+# ecal_bin_stats / ecal_report_totals as numpy records
+BIN_STATS = np.dtype([("n", np.uint64), ("n_out", np.uint64), ("sum_r", np.float64), ("sum_r2", np.float64), ("sum_abs", np.float64),
+                      ("max_abs", np.float64)])
+REPORT_TOTALS = np.dtype([("all", BIN_STATS), ("cost", np.float64)])
+
+
 def _declare_solver(L):
     vp, i32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    L.ecal_report_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
+    L.ecal_report_default_options.restype = None
+    L.ecal_solver_report_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.ecal_solver_report_dev.restype = i32
+    L.ecal_solver_report.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp]
+    L.ecal_solver_report.restype = i32
+    L.ecal_solver_num_landmarks.argtypes = [vp]
+    L.ecal_solver_num_landmarks.restype = ctypes.c_uint32
     L.ecal_solver_create.argtypes = [vp, ctypes.POINTER(_SplineProblem), ctypes.POINTER(vp)]
     L.ecal_solver_create.restype = i32
     L.ecal_solver_create_dev.argtypes = [vp, ctypes.POINTER(_SplineProblem), vp, vp, ctypes.POINTER(vp)]
@@ -607,6 +628,7 @@ class Solver:
         P.n_landmarks = keep["landmarks"].reshape(-1, 3).shape[0]
         P.circle_radius = float(problem["circle_radius"])
         P.huber_a = float(problem["huber_a"])
+        self.huber_a = P.huber_a
         P.use_so3 = int(bool(problem.get("use_so3", False)))
         P.camera_model = CAMERA_FISHEYE if problem.get("fisheye", False) else CAMERA_RADIAL
         h = ctypes.c_void_p()
@@ -620,6 +642,7 @@ class Solver:
         self.n_cp = (self.n_params - 9) // 7
         self.n_chunks = int(L.ecal_solver_num_chunks(h))
         self.n_res = int(L.ecal_solver_num_residuals(h))
+        self.n_landmarks = int(L.ecal_solver_num_landmarks(h))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -655,6 +678,77 @@ class Solver:
 
     def evaluate_dev(self, d_params, with_jacobian, d_accum, stream=0):
         self.ctx._check(self.ctx._L.ecal_solver_evaluate_dev(self._h, d_params, int(with_jacobian), d_accum, stream))
+
+    def report_options(self, **options):
+        """ecal_report_default_options with the given members (width, height, cell_px, hist_bins, hist_range, outlier_thresh) set."""
+        o = ReportOptions()
+        self.ctx._L.ecal_report_default_options(ctypes.byref(o))
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise TypeError("no report option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def report_dev(self, d_params, d_kf_time, n_keyframes, options, d_total, d_kf=None, d_lm=None, d_cell_n=None, d_cell_sum_r2=None,
+                   d_hist=None, stream=0):
+        """ecal_solver_report_dev: raw device pointers (None: that family is skipped), records laid out as BIN_STATS /
+        REPORT_TOTALS; no host synchronisation."""
+        self.ctx._check(self.ctx._L.ecal_solver_report_dev(self._h, d_params, d_kf_time, int(n_keyframes),
+                                                           ctypes.byref(options) if options is not None else None, d_total, d_kf, d_lm,
+                                                           d_cell_n, d_cell_sum_r2, d_hist, stream))
+
+    def report(self, params, kf_time=None, families=("kf", "lm", "cells", "hist"), **options):
+        """ecal_solver_report: the raw residuals at `params` binned on the GPU, in board units (the unit of circle_radius).
+        kf_time: ascending keyframe times (all segments); options: ReportOptions members.  Returns a dict: `totals` (one
+        REPORT_TOTALS record), `kf` [K] / `lm` [n_landmarks] (BIN_STATS), `cell_n` / `cell_sum_r2` [cells_y, cells_x], `hist`
+        [hist_bins] with `hist_edges`, and per family `<family>_rms`, `_mean`, `_outlier_frac` (NaN where a bin is empty);
+        `rms`, `mean`, `outlier_frac` of the totals, `cost` (= evaluate(params, False)[0]) and `empty_cell_frac`."""
+        p = np.ascontiguousarray(params, np.float64)
+        assert p.shape[0] == self.n_params
+        o = self.report_options(**options)
+        want = set(families)
+        if kf_time is None:
+            want.discard("kf")
+        kt = np.ascontiguousarray(kf_time, np.float64) if "kf" in want else None
+        total = np.zeros(1, REPORT_TOTALS)
+        kf = np.zeros(kt.shape[0], BIN_STATS) if "kf" in want else None
+        lm = np.zeros(self.n_landmarks, BIN_STATS) if "lm" in want else None
+        cn = cs = hist = None
+        if "cells" in want and o.cell_px:
+            cy, cx = -(-o.height // o.cell_px), -(-o.width // o.cell_px)
+            cn, cs = np.zeros((cy, cx), np.uint64), np.zeros((cy, cx))
+        elif "cells" in want:
+            cn, cs = np.zeros((1, 1), np.uint64), np.zeros((1, 1))    # (the call refuses cell_px == 0)
+        if "hist" in want:
+            hist = np.zeros(max(int(o.hist_bins), 1), np.uint64)
+
+        def ptr(a):
+            return _ptr(a) if a is not None else None
+        self.ctx._check(self.ctx._L.ecal_solver_report(self._h, _ptr(p), ptr(kt), 0 if kt is None else kt.shape[0], ctypes.byref(o),
+                                                       _ptr(total), ptr(kf), ptr(lm), ptr(cn), ptr(cs), ptr(hist)))
+
+        def derived(out, name, b):
+            n = b["n"].astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[name + "rms"] = np.sqrt(b["sum_r2"] / n)
+                out[name + "mean"] = b["sum_r"] / n
+                out[name + "outlier_frac"] = b["n_out"] / n
+        out = {"totals": total[0], "cost": float(total[0]["cost"]), "options": o}
+        derived(out, "", total["all"][0])
+        if kf is not None:
+            out["kf"] = kf
+            derived(out, "kf_", kf)
+        if lm is not None:
+            out["lm"] = lm
+            derived(out, "lm_", lm)
+        if cn is not None:
+            out["cell_n"], out["cell_sum_r2"] = cn, cs
+            out["empty_cell_frac"] = float((cn == 0).mean())
+        if hist is not None:
+            out["hist"] = hist
+            rng = o.hist_range if o.hist_range > 0 else 4.0 * self.huber_a
+            out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
+        return out
 
     def default_options(self):
         o = LmOptions()

@@ -8,6 +8,7 @@
 // landmark of that circle).  Output order = event (time) order, as relationContainer_ (:181-183).
 // Ties (equidistant keyframes / centres) go to the smaller index; nanoflann's choice is unpinned.
 #include "ecal_ctx.hpp"
+#include "block_utils.hpp"
 
 #pragma clang fp contract(off)
 
@@ -100,27 +101,7 @@ __device__ __forceinline__ int associate_one_staged(double t, double x, double y
     return (fabs(dis - c[3 * bi + 2]) < edge_tol) ? bi : -1;
 }
 
-// first index in [0, K] whose kf_time is not below t, by one wave: 64 probes a round (three rounds for thousands of keyframes
-// where a thread's bisection takes thirteen dependent loads)
-__device__ __forceinline__ uint32_t wave_lower_bound(const double *kf_time, uint32_t K, double t) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t lo = 0, hi = K;   // every index below lo is < t, every index from hi on is >= t
-    while (lo < hi) {
-        const uint32_t span = hi - lo, step = (span + 63u) / 64u;
-        const uint32_t idx = lo + lane * step;
-        const bool less = idx < hi && kf_time[idx] < t;
-        const uint32_t c = (uint32_t) __popcll(__ballot(less));   // ascending times: the probes below t come first
-        if (c == 0) {
-            hi = lo;
-        } else {
-            const uint32_t nhi = lo + c * step < hi ? lo + c * step : hi;
-            lo = lo + (c - 1u) * step + 1u;
-            hi = nhi;
-        }
-    }
-    return lo;
-}
-
+// (wave_lower_bound: block_utils.hpp)
 constexpr uint32_t AS_KF_LDS = 6, AS_CIRC_LDS = 64, AS_RNG_LDS = 32;   // keyframes / circles per keyframe / time ranges a block stages
 
 template <bool WRITE>

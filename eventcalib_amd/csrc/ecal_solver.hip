@@ -22,9 +22,8 @@
 #include <thread>
 #include <limits>
 #include <sched.h>
-#include "ecal_ctx.hpp"
+#include "ecal_solver_state.hpp"
 #include "spline_residual.hpp"
-#include "arrow_layout.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -33,19 +32,11 @@
 
 namespace ecal {
 
-struct ResRecord {  // 32 bytes per residual: the algorithmic traffic unit of SURVEY §8(d)
-    double u, v, t;
-    uint32_t lm, seg;
-};
-struct Chunk {
-    uint32_t start, count, seg, span;
-};
+// (ResRecord, Chunk, NE_T, NE_CHUNK, NeProgress, struct ecal_solver: ecal_solver_state.hpp)
 
-constexpr int NE_T = 256;   // threads per workgroup = rows per batch
 constexpr int NE_LD = 36;   // padded row: 33 Jacobian entries, the residual, 2 zeros
 // Gram accumulation: 4-column tiles of the padded row (v_mfma_f64_4x4x4_4b_f64 multiplies four 4x4 blocks per instruction)
 constexpr int NE_TW = 4, NE_TG = NE_LD / NE_TW, NE_TILES = NE_TG * (NE_TG + 1) / 2, NE_WAVES = NE_T / 64;
-constexpr uint32_t NE_CHUNK = 16384;  // residuals per workgroup (one span): few, long chunks keep the FP64 atomics rare
 constexpr uint32_t NE_REPL = 64;      // replicas of the shared head (cost, intrinsics block) that the chunks add into
 
 // (accumulation buffer layout: ACC_HEAD, ACC_PER_CP — arrow_layout.hpp)
@@ -71,23 +62,7 @@ __device__ __forceinline__ void local_to_unknown(int li, uint32_t c0, bool &is_i
 // Row index swizzle of the wave's column-major slab (see normal_eq_kernel)
 __host__ __device__ constexpr int ne_swz(int c) { return 16 * (c & 1) ^ 2 * ((c >> 1) & 1); }
 
-// A streamed evaluation (ecal_solver_solve, one rank, a long spline): the host factorises the interiors of its partition of the
-// control points (arrow_host_parts.hpp) WHILE the kernel is still accumulating the later ones.  The chunks are ordered by knot
-// span, i.e. by control point; group g = the chunks whose span's last control point lies in [cut[g], cut[g + 1]).  A chunk
-// with last control point s adds to the records s - 3 .. s, so the records of interior g ([cut[g], cut[g + 1] - 3)) are touched
-// by group g alone and the three records of the separator behind it by groups g and g + 1.  The workgroup that finishes a group
-// (a counter per group) copies the interior's records into the host's pinned buffer and raises the group's flag there; the
-// second of the two groups beside a separator to finish does the same for the separator's records.  The counters are restored
-// by the workgroup that zeroes them: nothing to prepare per launch.
-// (NE_MAX_GROUPS: arrow_layout.hpp)
-struct NeProgress {
-    uint32_t n_groups, n_cp;
-    uint32_t cut[NE_MAX_GROUPS + 1];      // cut[n_groups] = n_cp
-    uint32_t init[2 * NE_MAX_GROUPS];     // [g]: chunks of group g; [NE_MAX_GROUPS + b]: groups with chunks beside separator b
-    uint32_t *left;                       // the running counters, same layout (device memory)
-    double *host_acc;                     // the pinned accumulation buffer as the device sees it
-    uint32_t *host_flag;                  // pinned; [g] / [NE_MAX_GROUPS + b] = number of the evaluation that delivered them
-};
+// (the streamed evaluation's progress block, NeProgress: ecal_solver_state.hpp)
 
 // records [r_lo, r_hi) of the accumulation buffer to the host's copy; the values were added by other workgroups' atomics on
 // any of the eight XCDs: agent-scope loads (a plain load could be served from this XCD's L2)
@@ -419,33 +394,6 @@ __global__ void reduce_heads_kernel(const double *__restrict__ heads, double *__
 
 using namespace ecal;
 
-struct ecal_solver {
-    ecal_ctx *ctx = nullptr;
-    uint64_t n_res = 0;
-    uint32_t n_cp = 0, n_seg = 0, n_chunks = 0;
-    double radius = 0, huber_a = 0;
-    bool use_so3 = false;  // cumulative SO3 spline + LocalParameterizationSO3 instead of the quaternion spline
-    bool fisheye = false;  // camera_model == ECAL_CAMERA_FISHEYE
-    std::vector<uint32_t> cp_off, knot_off;
-    std::vector<double> knots;
-    ResRecord *d_rec = nullptr;
-    Chunk *d_chunks = nullptr;
-    double *d_knots = nullptr, *d_landmarks = nullptr, *d_params = nullptr, *d_accum = nullptr, *d_heads = nullptr;
-    uint32_t *d_knot_off = nullptr, *d_cp_off = nullptr;
-    // ecal_solver_solve's pinned staging (kept: pinning 3 MB per solve costs more than an LM iteration) and the streamed
-    // evaluation's progress block (NeProgress)
-    double *h_acc = nullptr, *h_x = nullptr;
-    uint32_t *h_flag = nullptr, *d_left = nullptr;
-    NeProgress *d_prog = nullptr;
-    NeProgress prog{};             // the host's copy (prog.n_groups = 0: not set up)
-    std::shared_ptr<void> host_pool;   // ecal_solver_solve's worker threads (HostPool), parked between solves
-    int host_pool_workers = -1;
-    uint32_t stream_epoch = 0;
-    uint32_t last_solve[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ecal_debug_solver_last_solve: how the last ecal_solver_solve ran
-    size_t n_params() const { return 9 + 7 * (size_t) n_cp; }
-    size_t n_accum() const { return ACC_HEAD + ACC_PER_CP * (size_t) n_cp; }
-};
-
 extern "C" void ecal_solver_destroy(ecal_solver *s) {
     if (!s) return;
     (void) hipSetDevice(s->ctx->device);
@@ -476,6 +424,7 @@ extern "C" int ecal_solver_create(ecal_ctx *ctx, const ecal_spline_problem *p, e
     s->ctx = ctx;
     s->n_res = p->n_res;
     s->n_seg = p->n_segments;
+    s->n_lm = p->n_landmarks;
     s->radius = p->circle_radius;
     s->huber_a = p->huber_a;
     s->use_so3 = p->use_so3 != 0;
@@ -714,6 +663,7 @@ extern "C" int ecal_solver_create_dev(ecal_ctx *ctx, const ecal_spline_problem *
     if (!s) return ECAL_ERR_NOMEM;
     s->ctx = ctx;
     s->n_seg = p->n_segments;
+    s->n_lm = p->n_landmarks;
     s->radius = p->circle_radius;
     s->huber_a = p->huber_a;
     s->use_so3 = p->use_so3 != 0;

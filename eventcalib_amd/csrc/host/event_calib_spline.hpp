@@ -30,6 +30,26 @@ public:
         int iterations = 0;
         double initial_cost = 0, final_cost = 0;
     };
+    // The calibration quality report (ecal_solver_report) at the solution: the raw residuals, in board units (the unit of
+    // Circles_Radius), binned per keyframe of frames(), per circle of the board in grid order, per cell of the sensor and into
+    // a histogram.  Filled when the constructor is given report options; valid = false otherwise.
+    struct Report {
+        bool valid = false;
+        ecal_report_options options{};
+        ecal_report_totals totals{};
+        std::vector<ecal_bin_stats> keyframes, landmarks;
+        uint32_t cells_x = 0, cells_y = 0;
+        std::vector<uint64_t> cell_n, hist;   // cell_n [cells_y][cells_x]
+        std::vector<double> cell_sum_r2;
+        double hist_range = 0;                 // the histogram covers [-hist_range, hist_range), its end bins the tails
+        static double rms(const ecal_bin_stats &b) { return b.n ? std::sqrt(b.sum_r2 / (double) b.n) : 0.0; }
+        double outlierFraction() const { return totals.all.n ? (double) totals.all.n_out / (double) totals.all.n : 0.0; }
+        double emptyCellFraction() const {
+            size_t empty = 0;
+            for (uint64_t n : cell_n) empty += n == 0;
+            return cell_n.empty() ? 0.0 : (double) empty / (double) cell_n.size();
+        }
+    };
 
     // rotation matrix (row-major) -> quaternion xyzw, Eigen::Quaterniond(Matrix3d)'s branch structure
     static void quaternionFromMatrix(const double *m, double *q) {
@@ -76,9 +96,13 @@ public:
 
     EventCalibSpline(std::vector<Frame> frames, EventContainer::Ptr eventContainer, CirclePatternParameters::Ptr pattern, bool useSO3,
                      double motionTimeStep, const double K[4], const double distCoeffs[5], int maxIterations = 50,
-                     bool fisheye = false)
+                     bool fisheye = false, const ecal_report_options *reportOptions = nullptr)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
           fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations) {
+        if (reportOptions) {
+            report_.options = *reportOptions;
+            wantReport_ = true;
+        }
         if (frames_.size() <= 10) throw std::logic_error("too few frames in the map.");  // :26-28
         std::sort(frames_.begin(), frames_.end(), [](const Frame &a, const Frame &b) { return a.timeStamp < b.timeStamp; });
         reduceMap();
@@ -131,6 +155,7 @@ public:
     const double *intrinsics() const { return intrinsics_; }  // fx fy cx cy k1..k5 (inverse radial polynomial)
     const std::vector<Frame> &frames() const { return frames_; }
     const Summary &summary() const { return summary_; }
+    const Report &report() const { return report_; }
     size_t splineNum() const { return segments_.size(); }
 
     int time2splineIdx(double t) const {
@@ -231,6 +256,25 @@ private:
         opt.max_num_iterations = maxIterations_;
         ecal_lm_summary sm;
         rc = ecal_solver_solve(solver, x.data(), &opt, &sm);
+        if (rc == ECAL_OK && wantReport_) {   // at the solution, on the records the solve ran on
+            Report &r = report_;
+            const ecal_report_options &o = r.options;
+            r.cells_x = o.cell_px ? (o.width + o.cell_px - 1) / o.cell_px : 0;
+            r.cells_y = o.cell_px ? (o.height + o.cell_px - 1) / o.cell_px : 0;
+            r.keyframes.assign(F, ecal_bin_stats{});
+            r.landmarks.assign(n_circ, ecal_bin_stats{});
+            r.cell_n.assign((size_t) r.cells_x * r.cells_y, 0);
+            r.cell_sum_r2.assign(r.cell_n.size(), 0.0);
+            r.hist.assign(o.hist_bins, 0);
+            r.hist_range = o.hist_range > 0 ? o.hist_range : 4.0 * prob.huber_a;
+            rc = ecal_solver_report(solver, x.data(), kf_time.data(), F, &o, &r.totals, r.keyframes.data(), r.landmarks.data(),
+                                    r.cell_n.data(), r.cell_sum_r2.data(), r.hist.data());
+            r.valid = rc == ECAL_OK;
+            if (rc != ECAL_OK) {
+                ecal_solver_destroy(solver);
+                throw std::runtime_error(std::string("ecal_solver_report: ") + ecal_last_error(ctx));
+            }
+        }
         ecal_solver_destroy(solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_solve: ") + ecal_last_error(ctx));
         std::copy(x.begin(), x.begin() + 9, intrinsics_);
@@ -271,6 +315,8 @@ private:
     std::vector<double> knots_, cpQ_, cpT_;
     double intrinsics_[9];
     Summary summary_;
+    Report report_;
+    bool wantReport_ = false;
 };
 
 }  // namespace opengv2

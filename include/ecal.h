@@ -703,6 +703,46 @@ int ecal_solver_evaluate(ecal_solver *s, const double *params, int with_jacobian
 int ecal_residuals_dev(ecal_solver *s, const double *d_params, double *d_r /*[n_res]*/, double *d_J /*[n_res][33] or NULL*/,
                        uint32_t *d_cp0 /*[n_res] or NULL*/, void *stream);
 int ecal_residuals(ecal_solver *s, const double *params, double *r, double *J, uint32_t *cp0);
+/* Calibration quality report: the raw residuals of the problem at `params` (the r of ecal_residuals, no loss function) binned on
+ * the GPU in one pass over the solver's records — which keyframes fit badly, which circles of the board, which parts of the
+ * sensor were never covered — a few kilobytes out instead of one double per residual.  Residuals are in BOARD UNITS, the unit of
+ * ecal_spline_problem.circle_radius (a distance on the board plane), not pixels.
+ *   totals    all residuals; cost = sum rho(r^2) / 2 with the solver's Huber loss = [0] of ecal_solver_evaluate(with_jacobian = 0)
+ *   kf        [n_keyframes]: a residual counts for the keyframe nearest in time in the ascending table kf_time [n_keyframes]
+ *             (all segments in one table), by the association's rule: the first index with kf_time >= t against its predecessor,
+ *             the predecessor when d0 * d0 <= d1 * d1; no max_dt gate: every residual lands in exactly one keyframe
+ *   lm        [n_landmarks], indexed by lm_id (at most 1024 landmarks: ECAL_ERR_RANGE)
+ *   cell_n / cell_sum_r2 [cells_y][cells_x], cells_x = ceil(width / cell_px), cells_y = ceil(height / cell_px): the sensor in
+ *             square cells, cell_x = min((uint32) max(u, 0) / cell_px, cells_x - 1), the same for y; cell_px == 0 or more than
+ *             8192 cells is ECAL_ERR_INVALID
+ *   hist      [hist_bins], 1 <= hist_bins <= 256: bin = clamp((int) floor((r + hist_range) * hist_bins / (2 hist_range)), 0,
+ *             hist_bins - 1): the first and the last bin catch the tails
+ * n_out counts the residuals with |r| > outlier_thresh.  Any output but the totals may be NULL: that family is skipped (and its
+ * options are not looked at).  n_keyframes == 0 with a kf output is ECAL_ERR_INVALID; a solver without residuals gives zeros.
+ * The call zeroes its outputs itself on `stream`; the _dev form takes device pointers and does not synchronise with the host.
+ * FP64 sums are accumulated with atomics: they depend on the order of arrival in the last bits, the counts do not. */
+typedef struct ecal_report_options {
+    uint32_t width, height, cell_px; /* sensor size and the cell's side, pixels */
+    uint32_t hist_bins;
+    double hist_range;               /* the histogram covers [-hist_range, hist_range); <= 0: 4 * huber_a */
+    double outlier_thresh;           /* <= 0: the solver's huber_a */
+} ecal_report_options;
+typedef struct ecal_bin_stats {
+    uint64_t n, n_out;
+    double sum_r, sum_r2, sum_abs, max_abs;
+} ecal_bin_stats;
+typedef struct ecal_report_totals {
+    ecal_bin_stats all;
+    double cost;
+} ecal_report_totals;
+void ecal_report_default_options(ecal_report_options *opt); /* 346 x 260, 16 px cells, 64 bins, range and threshold from huber_a */
+int ecal_solver_report_dev(ecal_solver *s, const double *d_params, const double *d_kf_time, uint32_t n_keyframes,
+                           const ecal_report_options *opt /*NULL: the defaults*/, ecal_report_totals *d_total, ecal_bin_stats *d_kf,
+                           ecal_bin_stats *d_lm, uint64_t *d_cell_n, double *d_cell_sum_r2, uint64_t *d_hist, void *stream);
+int ecal_solver_report(ecal_solver *s, const double *params, const double *kf_time, uint32_t n_keyframes,
+                       const ecal_report_options *opt, ecal_report_totals *total, ecal_bin_stats *kf, ecal_bin_stats *lm,
+                       uint64_t *cell_n, double *cell_sum_r2, uint64_t *hist);
+uint32_t ecal_solver_num_landmarks(const ecal_solver *s);
 void ecal_lm_default_options(ecal_lm_options *opt);
 int ecal_solver_solve(ecal_solver *s, double *params /*in: start, out: solution*/, const ecal_lm_options *opt,
                       ecal_lm_summary *summary);
