@@ -1,4 +1,4 @@
-// DBSCAN of one segment of event PIXELS (integer coordinates) by one workgroup, in 22 KB of LDS (seven per CU).
+// DBSCAN of one segment of event PIXELS (integer coordinates) by one workgroup, in 20 480 B of LDS (eight per CU).
 //
 // Same contract as dbscan_device.hpp (labels identical to dbscan/include/dbscan.h:115-265 on top of
 // dbscan/src/kdtree.cpp:106-179, including the range query's pruning quirk); this is the form the hot path
@@ -10,7 +10,16 @@
 // dependent LDS operations and barriers, and kernel time is ~ 1 / (workgroups per CU) from 1 to 6
 // (tools/occupancy_probe.sh, profiles/r01_notes.md) — so throughput is proportional to the workgroups a CU can
 // hold, i.e. to 160 KB / LDS per workgroup (capacity 768 points instead of 1024: 22.1 KB, 7 instead of 6 workgroups,
-// 1.157 -> 1.033 ms on the benchmark stream whose segments hold <= 666 points).  For integer pixels the
+// 1.157 -> 1.033 ms on the benchmark stream whose segments hold <= 666 points; a rank table of 2 KB instead of 4.2 KB:
+// 20 480 B, 8 workgroups = the CU's 32 wave slots, 1.035 -> 0.999 ms — the table's extra instructions alone cost
+// 0.033 ms, the eighth workgroup buys 0.069 ms, profiles/dbscan_rank_table_eight_workgroups.md).
+// The rank table: one u16 per row and group of PX_G = 4 bitmap words = the points in front of the group in raster
+// order; a point's rank is its group's entry + the popcounts of the <= 3 words of the group in front of its own
+// (read unconditionally, counted by position) + the bits below it in its own word.  Capacity PX_GROUPS = 1032 entries:
+// a segment whose padded box has rows x ceil(words per row / 4) > 1032 is left to the to-do list — of the boxes the
+// 3232-word bitmap admits only those of 9 words x 345 .. 359 rows (a 346x260 sensor's: at most 268 x 3 = 804).  G = 3
+// would need 1072 entries for the sensor (80 bytes too many), a u16 per pair of words is the 3232 bytes that were shed.
+// For integer pixels the
 // closed form of the pruning quirk (design/03_dbscan.md) collapses to two bits per point,
 //     f_d(j) = "an ancestor of j in the insertion-order kd-tree splits on d at j's own d-coordinate",
 // and  i -> j is pruned  <=>  j = i + eps * e_d exactly  and  f_d(j)   (integral eps only),
@@ -19,7 +28,7 @@
 //
 // Phases: A load/pack + bounding box; B kd replay -> f bits (wave 0 builds the first 64 nodes, the rest walk
 // that top tree read-only, then level-synchronous bidding with one barrier per level); bitmap of the points;
-// raster ranks (row starts + per-word prefix counts); D core test = popcount of the disc's row windows;
+// raster ranks (starts per row and group of four words); D core test = popcount of the disc's row windows;
 // E union-find over the set bits of the half disc (each pair once), one-way edges to a list + fix-point;
 // F seeds ranked in pid order = the reference's cluster ids.
 #pragma once
@@ -35,7 +44,9 @@ constexpr int PX_T = ECAL_PX_T;
 constexpr int PX_CAP = 768;    // points per segment of the first pass (three per thread)
 constexpr int PX_CAP2 = 2048;  // second pass over the segments the first one left: eight per thread, 10-bit bitmap coordinates
 constexpr uint32_t PX_WORDS = 3232;    // bitmap words: 346x260 padded by 2*4 = 354x268 bits = 268 rows x 12 words = 3216
-constexpr uint32_t PX_ROWS = 472;      // rowstart[PX_ROWS + 1]: 512 u16
+constexpr uint32_t PX_ROWS = 472;      // bitmap rows (the row counts of the rank phase: u16[PX_ROWS] in parent[], not yet in use)
+constexpr uint32_t PX_G = 4;           // bitmap words per entry of the rank table
+constexpr uint32_t PX_GROUPS = 1032;   // entries of the rank table: rows x ceil(words per row / PX_G) of a segment's box must fit
 constexpr uint32_t PX_EDGE_CAP = 64;   // one-way edges kept (more: left to the general kernel)
 constexpr int PX_RMAX = 15;
 
@@ -126,11 +137,13 @@ struct PixelLayout {
     static_assert(4 * PX_WORDS + 16 + 4 * CAP >= 8 * CAP + 4, "child slots must fit bitmap + parent");
     static_assert(slot_off % 16 == 0 && PX_WORDS % 4 == 0, "the bitmap is cleared with 16-byte stores");
     static_assert(PX_WORDS >= (uint32_t) CAP, "component labels (E.3) must fit the bitmap region");
-    static constexpr size_t rowstart_off = parent_off + 4 * CAP;            // u16[512]
-    static constexpr size_t wpre_off = rowstart_off + 1024;                 // u8[PX_WORDS]
-    static constexpr size_t red_off = wpre_off + PX_WORDS;                  // u32[48]
+    static_assert(4 * CAP >= 2 * PX_ROWS, "the row counts of the rank phase borrow parent[]");
+    static constexpr size_t gstart_off = parent_off + 4 * CAP;              // u16[PX_GROUPS]
+    static constexpr size_t red_off = gstart_off + 2 * PX_GROUPS;           // u32[48]
+    static_assert(red_off % 4 == 0, "red[] holds 32-bit words");
     static constexpr size_t bytes = red_off + 4 * 48;
 };
+static_assert(PixelLayout<PX_CAP>::bytes <= 20480, "eight workgroups of the first pass per CU: 8 x 20 480 B = 160 KiB, all the LDS a CU has");
 
 // Word formats by capacity.  Child-slot word: pid << 2 CB | x' << CB | y' (x', y' = bitmap coordinates < 2^CB - 1):
 // ds_min_u32 orders the bids by pid, and the winner's coordinates come back with its id — one dependent LDS read per
@@ -213,8 +226,8 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
     uint32_t *const slot = reinterpret_cast<uint32_t *>(px_smem + L::slot_off);
     uint32_t *const bm = reinterpret_cast<uint32_t *>(px_smem + L::bm_off);
     uint32_t *const parent = reinterpret_cast<uint32_t *>(px_smem + L::parent_off);
-    uint16_t *const rowstart = reinterpret_cast<uint16_t *>(px_smem + L::rowstart_off);
-    uint8_t *const wpre = reinterpret_cast<uint8_t *>(px_smem + L::wpre_off);
+    uint16_t *const gstart = reinterpret_cast<uint16_t *>(px_smem + L::gstart_off);
+    uint16_t *const rowcnt = reinterpret_cast<uint16_t *>(px_smem + L::parent_off);  // rank phase only: phase D is the first to use parent[]
     uint32_t *const red = reinterpret_cast<uint32_t *>(px_smem + L::red_off);
     uint32_t *const n_edges = red + 36;
     uint32_t *const rootw = red + 37;
@@ -334,7 +347,9 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
     // 64-bit window fetches may read the first word of the next row (or the spare word after the last row):
     // those bits are always masked off
     const uint32_t RW = (W + 31u) >> 5;
+    const uint32_t NG = (RW + PX_G - 1u) / PX_G;  // rank-table entries per row
     if (H > PX_ROWS || (uint64_t) H * RW > PX_WORDS || W > F::CMASK || H > F::CMASK) PX_BAIL();
+    if (H * NG > PX_GROUPS) PX_BAIL();   // (only a box of 9 words x 345 .. 359 rows; a 346x260 sensor's is at most 268 rows x 3 entries = 804)
     uint32_t mcx[PPT], myy[PPT], me[PPT];
 #pragma unroll
     for (int u = 0; u < PPT; u++) {
@@ -473,34 +488,48 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
     }
     __syncthreads();
     ECAL_PHASE_MARK(1);
-    // raster ranks: per-word prefix inside each row (u8: a row holds at most 255 points here), then row starts
+    // raster ranks: the points before each group of PX_G words of a row (first inside the row, then the row starts on top)
     for (uint32_t r = tid; r < H; r += T) {
         uint32_t acc = 0;
         for (uint32_t w = 0; w < RW; w++) {
-            wpre[r * RW + w] = (uint8_t) acc;
+            if ((w & (PX_G - 1u)) == 0u) gstart[r * NG + w / PX_G] = (uint16_t) acc;
             acc += (uint32_t) __popc(bm[r * RW + w]);
         }
-        if (acc > 255u) bad = true;
-        rowstart[r] = (uint16_t) acc;  // row count for now
+        rowcnt[r] = (uint16_t) acc;
     }
     if (block_any(bad, anyf, any_round)) PX_BAIL();
     {
         const uint32_t per = (H + T - 1) / T, r0 = tid * per;
         uint32_t sum = 0;
-        for (uint32_t r = r0; r < r0 + per && r < H; r++) sum += rowstart[r];
+        for (uint32_t r = r0; r < r0 + per && r < H; r++) sum += rowcnt[r];
         uint32_t total;
         uint32_t run = block_exscan<T>(sum, red, &total);
         for (uint32_t r = r0; r < r0 + per && r < H; r++) {
-            const uint32_t c = rowstart[r];
-            rowstart[r] = (uint16_t) run;
+            const uint32_t c = rowcnt[r];
+            for (uint32_t g = 0; g < NG; g++) gstart[r * NG + g] += (uint16_t) run;
             run += c;
         }
     }
     __syncthreads();
-    auto rank_of = [&](uint32_t cx, uint32_t yy) -> uint32_t {
-        const uint32_t w = yy * RW + (cx >> 5);
-        return (uint32_t) rowstart[yy] + (uint32_t) wpre[w] + (uint32_t) __popc(__builtin_amdgcn_ubfe(bm[w], 0u, cx & 31u));
+    // rank of the point at column cx of the row whose first word is rw = row * RW and whose first table entry is rg = row * NG:
+    // the entry of its group + the whole words of the group before its own + the bits below it.  The (up to) three words
+    // before are read whatever the position in the group and counted by it (no loop, no branch); the ones not counted may
+    // belong to the row before or, for the first words of the bitmap, to the bytes in front of it: LDS of this workgroup either way.
+    auto rank_at = [&](uint32_t cx, uint32_t rw, uint32_t rg) -> uint32_t {
+        const uint32_t wi = cx >> 5, j = wi & (PX_G - 1u);
+        static_assert(PX_G == 4 && L::bm_off >= 4 * (PX_G - 1), "three words in front of the own one");
+        int qi = (int) (rw + wi) - 3;
+        asm("" : "+v"(qi));   // (one address for the four words; left alone, the compiler forms two)
+        const uint32_t *const q = bm + qi;
+        const uint32_t w3 = q[0], w2 = q[1], w1 = q[2], w0 = q[3];  // (loaded first: a load inside the selects would become a branch around it)
+        uint32_t r = (uint32_t) gstart[rg + wi / PX_G] + (uint32_t) __popc(__builtin_amdgcn_ubfe(w0, 0u, cx & 31u));
+        r += (uint32_t) __popc(j >= 1u ? w1 : 0u);
+        r += (uint32_t) __popc(j >= 2u ? w2 : 0u);
+        r += (uint32_t) __popc(j >= 3u ? w3 : 0u);
+        asm("" : "+v"(r));    // (the sum as it stands: the callers' scaling to a byte offset is not spread over its five terms)
+        return r;
     };
+    auto rank_of = [&](uint32_t cx, uint32_t yy) -> uint32_t { return rank_at(cx, __umul24(yy, RW), __umul24(yy, NG)); };   // (rows < 2^11, words per row <= 101)
     // the 2 Rd + 1 columns from c0 of one bitmap row (word index a = row * RW + (c0 >> 5), sh5 = c0 & 31)
     auto window = [&](uint32_t a, uint32_t sh5) -> uint32_t { return __builtin_amdgcn_alignbit(bm[a + 1], bm[a], sh5); };
     auto mask_of = [&](int k) -> uint32_t { return E2I > 0 ? px_disc_mask(E2I, px_isqrt(E2I), k) : dm[k]; };
@@ -578,6 +607,7 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
         if (!(wbase + u * T < n) || !core[u]) continue;
         const uint32_t cx = mcx[u], yy = myy[u], c0 = cx - (uint32_t) Rd, sh5 = c0 & 31u;
         const uint32_t a0 = (yy - (uint32_t) Rd) * RW + (c0 >> 5);
+        const uint32_t rw0 = (yy - (uint32_t) Rd) * RW, rg0 = (yy - (uint32_t) Rd) * NG;  // first row of the disc in the bitmap and in the rank table
         const uint32_t fi = f[u];
         uint32_t ri = i;  // current root of i's component
         // Anchors = neighbours already joined with i (as k, b).  A neighbour j within a two-way edge of an anchor a
@@ -591,8 +621,7 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
                 const int ex0 = (int) b - (int) ab0, ey0 = (int) k - (int) ak0, ex1 = (int) b - (int) ab1, ey1 = (int) k - (int) ak1;
                 if (__mul24(ex0, ex0) + __mul24(ey0, ey0) <= tlim || __mul24(ex1, ex1) + __mul24(ey1, ey1) <= tlim) return false;
             }
-            const uint32_t nx = c0 + b, ny = yy - (uint32_t) Rd + k;
-            const uint32_t pfj = pf[rank_of(nx, ny)];
+            const uint32_t pfj = pf[rank_at(c0 + b, rw0 + __umul24(k, RW), rg0 + __umul24(k, NG))];
             if (!(pfj & F::PF_CORE)) return false;
             const uint32_t pj = pfj & F::PF_PID;
             // j = i - eps e_d: the query from j misses i exactly when i carries bit d; the query from i always
@@ -766,8 +795,9 @@ __device__ __forceinline__ int px_segment(unsigned char *px_smem, const uint32_t
 }
 
 // first pass: workgroup b handles segment b; what it cannot take goes to todo / todo_count
+// (eight workgroups per CU are eight waves per SIMD: the second launch bound keeps the registers, the scalar ones included, inside that)
 template <int E2I, int CAP>
-__global__ __launch_bounds__(PX_T) void dbscan_pixel_kernel(const double *__restrict__ xy,
+__global__ __launch_bounds__(PX_T, 8) void dbscan_pixel_kernel(const double *__restrict__ xy,
                                                             const uint32_t *__restrict__ seg_off,
                                                             const uint32_t *__restrict__ seg_cnt, const PxGeom geom,
                                                             uint32_t minpts, int32_t *__restrict__ labels,
