@@ -580,7 +580,12 @@ __global__ void bucket_table_kernel(uint2 *__restrict__ tab) {
 
 // first pass: workgroup b handles window b; what it cannot take goes to todo / todo_count
 #ifndef ECAL_RO_WAVES
-#define ECAL_RO_WAVES 5   // waves per SIMD the reference-order kernel is compiled for (0: the compiler's choice = 4; measured 50 M events: 4 -> 1.15 ms, 5 -> 1.03 ms, 6 (104 B of scratch per lane) -> 1.13 ms)
+// waves per SIMD the reference-order kernel is compiled for (0: the compiler's choice = 4).  Eight slots per thread for every
+// window, measured on 50 M events: 4 -> 1.15 ms, 5 -> 1.03 ms, 6 (60 - 104 B of scratch per lane) -> 1.06 - 1.13 ms.  With the
+// six-slot form for windows of <= 1535 events (slice_hash.hpp) the kernel needs 96 VGPRs at 5 and no scratch; at 6 (80 VGPRs) the
+// six-slot form still runs without scratch and PixHash<11>::obytes allows the sixth workgroup per CU, but the eight-slot form
+// spills 52 B per lane: on 50 M events in 1500-event windows 5 -> 0.940 ms, 6 -> 0.833 ms (parent 0.916); on 1875-event windows (eight-slot form) 6 -> 0.1210 ms against the parent's 0.1209 (profiles/slice_six_slots.md).
+#define ECAL_RO_WAVES 6
 #endif
 #if ECAL_RO_WAVES
 #define ECAL_RO_ATTR __attribute__((amdgpu_waves_per_eu(ECAL_RO_WAVES, ECAL_RO_WAVES)))

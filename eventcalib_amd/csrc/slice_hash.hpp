@@ -46,7 +46,9 @@ static __device__ unsigned long long g_ro_cycles[16];
 // barrier looks its pixel up in the OTHER polarity's table (present: the pixel is erased, EventFrame.cpp:24-32).  Load
 // factor ~0.3: 1.2 probes on average.  An event's pixel, polarity and representative stay in the registers of its thread
 // from decode to output: the tables are all the LDS there is (16 KB).
-// LOGC = 11: the first pass (<= 2047 events, x <= 2047, y <= 1023; 24 KB of LDS, six windows per CU);
+// LOGC = 11: the first pass (<= 2047 events, x <= 2047, y <= 1023; 24 KB of LDS, six windows per CU — in the reference order
+// 25.7 KB and 80 VGPRs: six per CU as well, six waves per SIMD; windows of <= 1535 events with six event slots per thread,
+// longer ones with eight: slice_hash_window at the end of this file);
 // LOGC = 12: the second pass over the windows the first one lists (<= 4095 events, x, y <= 1023; 49 KB, three per CU).
 // LOGC = 13 (round 6): the third pass, reference order only (<= 5119 events, x <= 511, y <= 1023; 66 KB, two per CU) — the
 // keyframe search grows its windows to nine and ten steps (eventCameraCalib.cpp:57-95), 4500 - 5000 events on the benchmark
@@ -73,7 +75,9 @@ struct PixHash {
     //   W u32[2 NOFF]       per sequence position: members of the bucket first seen there, then  run start << 10 | members
     //   region u16[2 NOFF]  the runs of the buckets of three and more; before the epochs the keys' epoch-7 buckets (second
     //                       pass); at the very end pos u16[SLOTS] by event index
-    //   cur u16[2 NOFF]     list position of key uid after the early epochs, final index at the end
+    //   cur u16[2 NOFF]     final index of key uid — written after the last epoch, when W is dead: it takes W's first half.
+    //                       (The list positions the early epochs leave, <= 127 per set, wait in the set's part of W behind
+    //                       the 128 entries those epochs use as scratch: ecur_off.)
     //   fa u32[FA_CAP]      first sequence position per bucket, the + table then the - table; before the epochs the keys'
     //                       early bucket words
     //   keep u32[16 NI]     kept keys by list position (bitmaps of both sets) and the running counts of their words
@@ -98,13 +102,22 @@ struct PixHash {
     static constexpr uint32_t FA_CAP = LOGC == 11 ? (uint32_t) ECAL_RO_FA : 4800u;    // B(+) + B(-): 1109 + 1109 / 2357 + 2357 (+ slack)
     static constexpr size_t w_off = 0;
     static constexpr size_t region_off = w_off + 4 * PSL;
-    static constexpr size_t cur_off = region_off + 2 * (PSL > SLOTS ? PSL : SLOTS);
-    static constexpr size_t fa_off = cur_off + 2 * PSL;
+    static constexpr size_t cur_off = w_off;
+    static constexpr size_t ecur_off = 4 * 128;                       // bytes into a set's part of W: u16[128]
+    static_assert(ecur_off + 2 * 128 <= 4 * NOFF, "the early epochs' positions lie inside the set's part of W");
+    static_assert(cur_off + 2 * PSL <= region_off, "cur lies inside W (every LOGC): nothing sits between region and fa any more");
+    static constexpr size_t fa_off = region_off + 2 * (PSL > SLOTS ? PSL : SLOTS);
     static constexpr size_t keep_off = fa_off + 4 * FA_CAP;
     static constexpr size_t bcnt_off = keep_off + 4 * 16 * NI;        // u32[PER * 4 + 1]: batch counts of the rank scan
     static constexpr size_t ored_off = bcnt_off + 4 * (SLOTS / 64 + 4);
-    static constexpr size_t obytes = ored_off + 16 * 8 + 16;
+    // first pass: the event words (meta) of the slots 4 and 5 wait here while the epochs run, each thread's own at [slot - 4][tid]:
+    // the two registers that let the six-slot form run at six waves per SIMD without scratch
+    static constexpr int NSTASH = LOGC == 11 ? 2 : 0, STASH0 = 4;
+    static constexpr size_t stash_off = ored_off + 16 * 8 + 16;       // u32[NSTASH][PXH_T]
+    static constexpr size_t obytes = stash_off + 4 * NSTASH * PXH_T;
 };
+// six workgroups of the first pass per CU: a sixth of the 160 KB of LDS, in the 512 B the allocation counts in
+static_assert(6 * PixHash<11>::obytes <= 163840 && PixHash<11>::obytes <= 27136, "first pass: six workgroups per CU");
 
 // std::hash<double> of the integers 0 .. 2047 (the pixel kernels' coordinates), built at compile time
 struct HashIntTable {
@@ -247,15 +260,16 @@ __device__ __forceinline__ void early_epochs_packed(uint32_t m, uint32_t *fa, ui
 
 // Returns false when the window is not this pass's (too many events or keys, a non-pixel coordinate): it is then put on `todo`, or —
 // todo == nullptr — left to the caller (nothing has been written for it yet except, with seg_fmt, its "doubles" mark).
-template <int LOGC, bool REFORDER>
-__device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uint32_t s, const uint8_t *__restrict__ rec,
-                                                  const uint32_t *__restrict__ win_lo, const uint32_t *__restrict__ win_hi,
-                                                  const uint32_t *__restrict__ win_base, uint32_t cap_points,
-                                                  double *__restrict__ xy_out, uint32_t *__restrict__ seg_off,
-                                                  uint32_t *__restrict__ seg_cnt, int32_t *__restrict__ event_point,
-                                                  int *overflow, uint32_t *__restrict__ todo,
-                                                  uint32_t *__restrict__ todo_count, const uint2 *__restrict__ bucket_tab = nullptr,
-                                                  uint32_t *__restrict__ xy16 = nullptr, uint32_t *__restrict__ seg_fmt = nullptr) {
+// PER = event slots per thread (event k = tid + 256 j, j < PER): the caller's window has at most 256 PER - 1 events.
+template <int LOGC, bool REFORDER, int PER>
+__device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, const uint32_t s, const uint8_t *__restrict__ rec,
+                                                        const uint32_t *__restrict__ win_lo, const uint32_t *__restrict__ win_hi,
+                                                        const uint32_t *__restrict__ win_base, uint32_t cap_points,
+                                                        double *__restrict__ xy_out, uint32_t *__restrict__ seg_off,
+                                                        uint32_t *__restrict__ seg_cnt, int32_t *__restrict__ event_point,
+                                                        int *overflow, uint32_t *__restrict__ todo,
+                                                        uint32_t *__restrict__ todo_count, const uint2 *__restrict__ bucket_tab,
+                                                        uint32_t *__restrict__ xy16, uint32_t *__restrict__ seg_fmt) {
     // xy16 / seg_fmt (ecal_packed_points): the window's points go out as x | y << 16 (4 bytes a point instead of 16: these ARE
     // sensor pixels) and its two segments are marked 1 = "packed only"; the doubles are made on request (ecal_unpack_points_dev)
     using L = PixHash<LOGC>;
@@ -267,7 +281,8 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
     // the per-event word of the reference-order block: first occurrence (MB bits) | erased | polarity | key | rank << 16
     constexpr uint32_t MB = LOGC <= 12 ? 12u : 13u, M_IDX = (1u << MB) - 1u, M_ER = 1u << MB, M_POL = 2u << MB, M_KEY = 4u << MB;
     static_assert(MB + 3u <= 16u && L::CAP <= M_IDX, "the word's fields");
-    constexpr int PXH_PER = L::PER;
+    static_assert(PER >= 1 && PER <= L::PER, "a short form of the pass: fewer slots, the same tables and limits");
+    constexpr int PXH_PER = PER;
     constexpr uint32_t NONE = L::CAP, EMPTY = 0xFFFFFFFFu;
     const uint32_t tid = threadIdx.x;
     const uint32_t lo = win_lo[s], n = win_hi[s] - lo, base = win_base[s];
@@ -322,6 +337,12 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         uint4 *t4 = reinterpret_cast<uint4 *>(tab);
         for (uint32_t q = tid; q < 2 * PXH_SLOTS / 4; q += T) t4[q] = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
     }
+    // pix[j]: the pixel, x << 10 | y (PIXB <= 21 bits), and the polarity in bit 31 (POLB) — one register per event from decode to
+    // output; PIX_OF() / POL_OF() take the word apart, pix << LOGC drops the polarity by itself
+    constexpr uint32_t POLB = 0x80000000u, PIXM = (1u << PIXB) - 1u;
+    static_assert(PIXB < 31u, "bit 31 of the pixel word is free");
+#define PIX_OF(w) ((w) & PIXM)
+#define POL_OF(w) (((w) & POLB) != 0u)
     bool bad = false;
     uint32_t pix[PXH_PER];
 #pragma unroll
@@ -333,7 +354,7 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         const bool okc = x == floor(x) && y == floor(y) && x <= L::XMAX && y <= L::YMAX && __double_as_longlong(x) >= 0 &&
                          __double_as_longlong(y) >= 0;
         bad = bad || (k < n && !okc);
-        pix[j] = (((uint32_t) (int) x << 10) | ((uint32_t) (int) y & 0x3FFu)) & ((1u << PIXB) - 1u);
+        pix[j] = ((((uint32_t) (int) x << 10) | ((uint32_t) (int) y & 0x3FFu)) & PIXM) | (vp[j] ? POLB : 0u);
     }
     const bool wave_bad = __any(bad);
     if ((tid & 63) == 0) badf[tid >> 6] = wave_bad ? 1u : 0u;   // one flag word per wave
@@ -352,7 +373,7 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
     uint2 bw[EARLY_GATHER ? PXH_PER : 1];
     if constexpr (EARLY_GATHER) {
 #pragma unroll
-        for (int j = 0; j < PXH_PER; j++) bw[j] = (tid + j * T < n) ? bucket_tab[pix[j]] : make_uint2(0u, 0u);
+        for (int j = 0; j < PXH_PER; j++) bw[j] = (tid + j * T < n) ? bucket_tab[PIX_OF(pix[j])] : make_uint2(0u, 0u);
     }
     // b. every event into its polarity's table: the slot of its pixel ends up holding the smallest event index
     // (The first probe of all of a thread's events is read before any is looked at: the probes of different events are
@@ -363,20 +384,20 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         uint32_t w0[PXH_PER];
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
-            hs[j] = L::slot(pix[j]);
-            w0[j] = tab[(vp[j] ? PXH_SLOTS : 0u) + hs[j]];
+            hs[j] = L::slot(PIX_OF(pix[j]));
+            w0[j] = tab[(POL_OF(pix[j]) ? PXH_SLOTS : 0u) + hs[j]];
         }
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
             if (k < n) {
-                uint32_t *const t = tab + (vp[j] ? PXH_SLOTS : 0u);
-                const uint32_t mine = (pix[j] << LOGC) | k;
+                uint32_t *const t = tab + (POL_OF(pix[j]) ? PXH_SLOTS : 0u);
+                const uint32_t mine = (pix[j] << LOGC) | k;   // (PIXB + LOGC = 32: the polarity bit falls off)
                 uint32_t h = hs[j], w = w0[j];
                 for (;;) {
                     if (w == EMPTY) w = atomicCAS(&t[h], EMPTY, mine);   // EMPTY back: the slot is mine
                     if (w == EMPTY) break;
-                    if ((w >> LOGC) == pix[j]) {
+                    if ((w >> LOGC) == PIX_OF(pix[j])) {
                         atomicMin(&t[h], mine);
                         break;
                     }
@@ -396,20 +417,20 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         uint32_t fw[PXH_PER], ow[PXH_PER];
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {   // own slot and first probe of the other table: all reads first
-            fw[j] = tab[(vp[j] ? PXH_SLOTS : 0u) + hs[j]];
-            ow[j] = tab[(vp[j] ? 0u : PXH_SLOTS) + L::slot(pix[j])];
+            fw[j] = tab[(POL_OF(pix[j]) ? PXH_SLOTS : 0u) + hs[j]];
+            ow[j] = tab[(POL_OF(pix[j]) ? 0u : PXH_SLOTS) + L::slot(PIX_OF(pix[j]))];
         }
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
             if (k < n) {
                 const uint32_t first = fw[j] & IDXM;
-                const uint32_t *const o = tab + (vp[j] ? 0u : PXH_SLOTS);
-                uint32_t h = L::slot(pix[j]), w = ow[j];
+                const uint32_t *const o = tab + (POL_OF(pix[j]) ? 0u : PXH_SLOTS);
+                uint32_t h = L::slot(PIX_OF(pix[j])), w = ow[j];
                 bool both = false;
                 for (;;) {
                     if (w == EMPTY) break;
-                    if ((w >> LOGC) == pix[j]) {
+                    if ((w >> LOGC) == PIX_OF(pix[j])) {
                         both = true;
                         break;
                     }
@@ -449,11 +470,12 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
             const bool isu = k < n && (firstk[j] & 0x7FFFu) == k;
-            const unsigned long long mP = __ballot(isu && vp[j] != 0), mN = __ballot(isu && vp[j] == 0);
+            const bool pol_ = POL_OF(pix[j]);
+            const unsigned long long mP = __ballot(isu && pol_), mN = __ballot(isu && !pol_);
             const unsigned long long lower = (1ull << lane) - 1ull;
-            const uint32_t below = (uint32_t) __popcll((vp[j] ? mP : mN) & lower);
+            const uint32_t below = (uint32_t) __popcll((pol_ ? mP : mN) & lower);
             if (lane == 0) bcnt[j * (T / 64) + wave] = (uint32_t) __popcll(mP) | ((uint32_t) __popcll(mN) << 16);
-            meta[j] = k < n ? ((firstk[j] & M_IDX) | ((firstk[j] & 0x8000u) ? M_ER : 0u) | (vp[j] ? M_POL : 0u) |
+            meta[j] = k < n ? ((firstk[j] & M_IDX) | ((firstk[j] & 0x8000u) ? M_ER : 0u) | (pol_ ? M_POL : 0u) |
                                (isu ? M_KEY : 0u) | (below << 16))
                             : M_ER;   // (no event: "erased", not a key)
         }
@@ -515,10 +537,13 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
                         if (rank < N_EARLY) fa[(pos_ ? 0u : faN) + rank] = bw[j].y;
                         if (L::MAX_EPOCHS > 7 && (pos_ ? EP : EN) > 7)   // (second pass, a set of more than 1109 keys)
                             region[(pos_ ? 0u : L::NOFF) + rank] =
-                                (uint16_t) mod_hash(ref_hash_combine2(HASH_INT.v[pix[j] >> 10], HASH_INT.v[pix[j] & 0x3FFu]), mod_for_epoch(7));
+                                (uint16_t) mod_hash(ref_hash_combine2(HASH_INT.v[PIX_OF(pix[j]) >> 10], HASH_INT.v[pix[j] & 0x3FFu]), mod_for_epoch(7));
                     }
                 }
             }
+            uint32_t *const stash = reinterpret_cast<uint32_t *>(smem + L::stash_off);
+#pragma unroll
+            for (int j = L::STASH0; j < L::STASH0 + L::NSTASH && j < PXH_PER; j++) stash[(j - L::STASH0) * T + tid] = meta[j];
             if (ECAL_RO_STOP == 2) return true;
             // Wave pair 0 (waves 0, 1) takes the + set, pair 1 the - set; thread l128 = 0 .. 127 of a pair owns the keys
             // u = l128 + 128 i: packed bucket numbers and list position stay in its registers from here on.
@@ -529,6 +554,9 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
             const uint32_t uoff = pol == 0u ? 0u : L::NOFF;
             uint32_t *const Wp = W + uoff, *const fap = fa + (pol == 0u ? 0u : faN);
             uint16_t *const regp = region + uoff, *const curp = cur + uoff;
+            // (the early epochs' list positions: in the set's own part of W, past those epochs' scratch; read back into cu[0]
+            // before the barrier in front of the first later epoch, which clears W)
+            uint16_t *const ecurp = reinterpret_cast<uint16_t *>(reinterpret_cast<unsigned char *>(Wp) + L::ecur_off);
             constexpr uint32_t KW = 4u * NI;   // bitmap words per polarity (128 NI list positions)
             uint32_t *const kW = keepW + pol * KW, *const kPre = keepW + 2u * KW + pol * KW;   // bitmaps, their running counts
             if (tid == 0) ored[10] = 0u;
@@ -544,11 +572,11 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
             if (l128 < KW) kW[l128] = 0u;
             __syncthreads();
     RO_MARK(5);
-            if (sub == 0u && m) early_epochs_packed(m, fap, Wp, regp, curp);
+            if (sub == 0u && m) early_epochs_packed(m, fap, Wp, regp, ecurp);
             __syncthreads();
     RO_MARK(6);
             if (ECAL_RO_STOP == 3) return true;
-            if (l128 < (m < 127u ? m : 127u)) cu[0] = (cu[0] & 0xFFFF0000u) | (uint32_t) curp[l128];
+            if (l128 < (m < 127u ? m : 127u)) cu[0] = (cu[0] & 0xFFFF0000u) | (uint32_t) ecurp[l128];
             const int EMAX = EP > EN ? EP : EN;
             if (E > 4) {
                 for (uint32_t b = l128; b < 257u; b += 128u) fap[b] = 0xFFFFFFFFu;
@@ -652,6 +680,8 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         }
                 return false;
             }
+#pragma unroll
+            for (int j = L::STASH0; j < L::STASH0 + L::NSTASH && j < PXH_PER; j++) meta[j] = stash[(j - L::STASH0) * T + tid];
             // the erased keys drop out (EventFrame.cpp:24-32): index of a kept key = kept keys in front of it in the list
 #pragma unroll
             for (int i = 0; i < NI; i++) {
@@ -708,10 +738,10 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
                         if (meta[j] & M_KEY) {
                             const uint32_t slot = (meta[j] & M_POL) ? at : nP + at;
                             if (xy16) {
-                                xy16[base + slot] = (pix[j] >> 10) | ((pix[j] & 0x3FFu) << 16);
+                                xy16[base + slot] = (PIX_OF(pix[j]) >> 10) | ((pix[j] & 0x3FFu) << 16);
                             } else {
                                 double2 v;
-                                v.x = (double) (pix[j] >> 10);
+                                v.x = (double) (PIX_OF(pix[j]) >> 10);
                                 v.y = (double) (pix[j] & 0x3FFu);
                                 out2[slot] = v;
                             }
@@ -743,9 +773,10 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
     for (int j = 0; j < PXH_PER; j++) {
         const uint32_t k = tid + j * T;
         const bool isrep = k < n && repk[j] == k;
-        const unsigned long long mP = __ballot(isrep && vp[j] != 0), mN = __ballot(isrep && vp[j] == 0);
+        const bool pol_ = POL_OF(pix[j]);
+        const unsigned long long mP = __ballot(isrep && pol_), mN = __ballot(isrep && !pol_);
         const unsigned long long lower = (1ull << lane) - 1ull;
-        below[j] = (uint32_t) __popcll((vp[j] ? mP : mN) & lower);
+        below[j] = (uint32_t) __popcll((pol_ ? mP : mN) & lower);
         if (lane == 0) bcnt[j * (T / 64) + wave] = (uint32_t) __popcll(mP) | ((uint32_t) __popcll(mN) << 16);
     }
     __syncthreads();
@@ -767,7 +798,7 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         const uint32_t k = tid + j * T;
         if (k < n && repk[j] == k) {
             const uint32_t ex = bcnt[j * (T / 64) + wave];
-            pos[k] = (uint16_t) ((vp[j] ? (ex & 0xFFFFu) : (ex >> 16)) + below[j]);
+            pos[k] = (uint16_t) ((POL_OF(pix[j]) ? (ex & 0xFFFFu) : (ex >> 16)) + below[j]);
         }
     }
     __syncthreads();
@@ -786,12 +817,12 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
                 const uint32_t at = pos[r];
                 if (ep) ep[k] = (int32_t) at;
                 if (r == k) {
-                    const uint32_t slot = vp[j] ? at : nP + at;
+                    const uint32_t slot = POL_OF(pix[j]) ? at : nP + at;
                     if (xy16) {
-                        xy16[base + slot] = (pix[j] >> 10) | ((pix[j] & 0x3FFu) << 16);
+                        xy16[base + slot] = (PIX_OF(pix[j]) >> 10) | ((pix[j] & 0x3FFu) << 16);
                     } else {
                         double2 v;
-                        v.x = (double) (pix[j] >> 10);
+                        v.x = (double) (PIX_OF(pix[j]) >> 10);
                         v.y = (double) (pix[j] & 0x3FFu);
                         out2[slot] = v;
                     }
@@ -807,5 +838,33 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
         if (seg_fmt) seg_fmt[2 * s] = seg_fmt[2 * s + 1] = xy16 ? 1u : 0u;
     }
     return true;
+#undef PIX_OF
+#undef POL_OF
+}
+
+// The pass's entry.  First pass (LOGC = 11): a window of at most 1535 events — the shipped 1.5 ms windows at 1 Mev/s hold 1500 —
+// goes through the six-slot form, one of 1536 .. 2047 through the eight-slot form: the slots j = 6, 7 of the eight-slot code
+// are empty in every lane of such a window, yet its pixel tests, first probes, ballots and packing still run for them.  The
+// choice is uniform over the workgroup; tables, limits (CAP = 2047) and results are the same.
+constexpr int PXH_SHORT_PER = 6;
+template <int LOGC, bool REFORDER>
+__device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uint32_t s, const uint8_t *__restrict__ rec,
+                                                  const uint32_t *__restrict__ win_lo, const uint32_t *__restrict__ win_hi,
+                                                  const uint32_t *__restrict__ win_base, uint32_t cap_points,
+                                                  double *__restrict__ xy_out, uint32_t *__restrict__ seg_off,
+                                                  uint32_t *__restrict__ seg_cnt, int32_t *__restrict__ event_point,
+                                                  int *overflow, uint32_t *__restrict__ todo,
+                                                  uint32_t *__restrict__ todo_count, const uint2 *__restrict__ bucket_tab = nullptr,
+                                                  uint32_t *__restrict__ xy16 = nullptr, uint32_t *__restrict__ seg_fmt = nullptr) {
+    if constexpr (LOGC == 11) {
+        static_assert(PXH_SHORT_PER < PixHash<11>::PER, "the short form");
+        if (win_hi[s] - win_lo[s] < (uint32_t) PXH_SHORT_PER * PXH_T)
+            return slice_hash_window_slots<11, REFORDER, PXH_SHORT_PER>(smem, s, rec, win_lo, win_hi, win_base, cap_points, xy_out, seg_off,
+                                                                        seg_cnt, event_point, overflow, todo, todo_count, bucket_tab, xy16,
+                                                                        seg_fmt);
+    }
+    return slice_hash_window_slots<LOGC, REFORDER, PixHash<LOGC>::PER>(smem, s, rec, win_lo, win_hi, win_base, cap_points, xy_out, seg_off,
+                                                                       seg_cnt, event_point, overflow, todo, todo_count, bucket_tab, xy16,
+                                                                       seg_fmt);
 }
 }  // namespace ecal
