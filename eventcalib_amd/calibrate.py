@@ -94,7 +94,7 @@ def check_pose(R_ref, twb_ref, t_ref, R_cur, twb_cur, t_cur, step):
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
-                     gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False):
+                     gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     gate_mode: capi.GATE_SHARED_MAP (default: the reference's keyframe gate as its single-worker run computes it — one keyframe
@@ -109,7 +109,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     tables: also return the per-stage tables (keyframe records, PnP poses and verdicts, rectified circles, accepted frames, the
     spline's start) that tests/test_gpu_oracle_chain.py compares with the CPU oracle chain.
     report: also bin the residuals at the solution on the GPU (capi.Solver.report: per keyframe of the splines, per circle of
-    the board, per 16-pixel cell of the sensor, histogram; board units) into out["report"] — a stage of its own, `report`."""
+    the board, per 16-pixel cell of the sensor, histogram; board units) into out["report"] — a stage of its own, `report`.
+    board_image: also carry EVERY event of the stream through the solution onto the board (capi.Solver.board_image: the
+    motion-compensated image per polarity and the ring profile of every circle) into out["board_image"] — a stage of its own,
+    `board_image`."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -299,6 +302,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
         mark("lm_solve")
         out["report"] = solver.report(x, kf["time"][kf_idx], width=int(width), height=int(height))
         mark("report")
+    if board_image:
+        mark("lm_solve")
+        out["board_image"] = solver.board_image(x, events)
+        mark("board_image")
     solver.close()
     mark("lm_solve")
     out["spline"] = {"splines": len(segs), "control_points": int(seg_cp_off[-1]), "residuals": int(n_res),

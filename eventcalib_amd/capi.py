@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "ecal_associate_ranges_dev", "ecal_ref_nth_element_f64", "ecal_solver_create_from_stream", "ecal_rectify_keyframes", "ecal_solver_time_shard_cuts",
     "ecal_slice_events_packed_dev", "ecal_dbscan_batch_packed_dev", "ecal_extract_batch_packed_dev", "ecal_unpack_points_dev",
     "ecal_report_default_options", "ecal_solver_report_dev", "ecal_solver_report", "ecal_solver_num_landmarks",
+    "ecal_board_image_default_options", "ecal_solver_board_image_dev", "ecal_solver_board_image", "ecal_solver_board_points_dev", "ecal_solver_board_points",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -510,8 +511,31 @@ BIN_STATS = np.dtype([("n", np.uint64), ("n_out", np.uint64), ("sum_r", np.float
 REPORT_TOTALS = np.dtype([("all", BIN_STATS), ("cost", np.float64)])
 
 
+class BoardImageOptions(ctypes.Structure):
+    """ecal_board_image_options (include/ecal.h)."""
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("bin", ctypes.c_double), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("ring_bins", ctypes.c_uint32), ("ring_range", ctypes.c_double)]
+
+
+# ecal_board_image_totals / ecal_ring_stats as numpy records; the kernel's block and staging sizes (ECAL_BOARD_IMAGE_*)
+BOARD_IMAGE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
+                               ("n_outside_image", np.uint64), ("n_image", np.uint64, (2,)), ("n_ring", np.uint64)])
+RING_STATS = np.dtype([("n", np.uint64), ("sum_d", np.float64), ("sum_d2", np.float64)])
+BOARD_IMAGE_BLOCK, BOARD_IMAGE_CP_LDS = 4096, 16
+
+
 def _declare_solver(L):
     vp, i32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    L.ecal_board_image_default_options.argtypes = [vp, ctypes.POINTER(BoardImageOptions)]
+    L.ecal_board_image_default_options.restype = i32
+    L.ecal_solver_board_image_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(BoardImageOptions), vp, vp, vp, vp, vp]
+    L.ecal_solver_board_image_dev.restype = i32
+    L.ecal_solver_board_image.argtypes = [vp, vp, vp, ctypes.POINTER(BoardImageOptions), vp, vp, vp, vp]
+    L.ecal_solver_board_image.restype = i32
+    L.ecal_solver_board_points_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp]
+    L.ecal_solver_board_points_dev.restype = i32
+    L.ecal_solver_board_points.argtypes = [vp, vp, vp, vp, vp]
+    L.ecal_solver_board_points.restype = i32
     L.ecal_report_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
     L.ecal_report_default_options.restype = None
     L.ecal_solver_report_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
@@ -749,6 +773,144 @@ class Solver:
             rng = o.hist_range if o.hist_range > 0 else 4.0 * self.huber_a
             out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
         return out
+
+    def board_image_options(self, **options):
+        """ecal_board_image_default_options (the landmarks' bounding box padded by 3 radii, bin = radius / 8, 64 ring bins over
+        +- radius) with the given members (x0, y0, bin, width, height, ring_bins, ring_range) set."""
+        o = BoardImageOptions()
+        self.ctx._check(self.ctx._L.ecal_board_image_default_options(self._h, ctypes.byref(o)))
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise TypeError("no board image option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def _events_arg(self, events):
+        """events of the board-image calls -> (device pointer, count, object to keep alive): an EventStream-like object with an
+        ecal_stream handle is not taken here; a torch uint8 tensor on the GPU (packed 25-byte records, time-sorted) or a host
+        array / bytes of such records, which is uploaded."""
+        import torch
+        if isinstance(events, torch.Tensor):
+            t = events if events.is_cuda else events.cuda()
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray))
+                                                      else np.asarray(events, np.uint8).ravel())).cuda()
+        t = t.contiguous().view(torch.uint8).reshape(-1)
+        assert t.numel() % 25 == 0, "packed 25-byte event records"
+        return t.data_ptr() if t.numel() else None, t.numel() // 25, t
+
+    def board_image_dev(self, d_params, d_events, n_events, options, d_img, d_totals, d_ring_stats=None, d_ring_hist=None, stream=0):
+        """ecal_solver_board_image_dev: raw device pointers (None: that output is skipped), records laid out as
+        BOARD_IMAGE_TOTALS / RING_STATS; no host synchronisation."""
+        self.ctx._check(self.ctx._L.ecal_solver_board_image_dev(self._h, d_params, d_events, int(n_events),
+                                                                ctypes.byref(options) if options is not None else None, d_img, d_totals,
+                                                                d_ring_stats, d_ring_hist, stream))
+
+    def board_points_dev(self, d_params, d_events, n_events, d_xw, d_flag, stream=0):
+        """ecal_solver_board_points_dev: d_xw [n, 2] f64, d_flag [n] u8 (0 ok, 1 outside time, 2 behind)."""
+        self.ctx._check(self.ctx._L.ecal_solver_board_points_dev(self._h, d_params, d_events, int(n_events), d_xw, d_flag, stream))
+
+    def board_points(self, x, events):
+        """The board point of every event at the parameters x: (xw [n, 2] float64, flag [n] uint8: 0 ok, 1 outside every
+        segment's time range, 2 behind the camera; xw is zero where the flag is not 0)."""
+        import torch
+        p = torch.as_tensor(np.ascontiguousarray(x, np.float64), device="cuda")
+        assert p.shape[0] == self.n_params
+        d_ev, n, keep = self._events_arg(events)
+        xw = torch.zeros((n, 2), dtype=torch.float64, device="cuda")
+        flag = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        self.board_points_dev(p.data_ptr(), d_ev, n, xw.data_ptr(), flag.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        del keep
+        return xw.cpu().numpy(), flag.cpu().numpy()
+
+    def board_image(self, x, events, outputs=("image", "ring_stats", "ring_hist"), **options):
+        """ecal_solver_board_image_dev: every event of the packed, time-sorted stream `events` carried through the intrinsics
+        and the spline pose of the parameters x onto the board plane (board units, the unit of circle_radius).  Returns a dict:
+        `image` [2, H, W] uint32 (0: negative, 1: positive events), `totals` (one BOARD_IMAGE_TOTALS record), `ring_stats`
+        [n_landmarks, 2] (RING_STATS per landmark and polarity), `ring_n` / `ring_mean` / `ring_std` [n_landmarks] of d = |Xw -
+        lm| - radius over both polarities (NaN where a circle drew no event), `ring_hist` [n_landmarks, ring_bins] with
+        `ring_edges`, `options` and `extent` = (x0, x0 + W bin, y0, y0 + H bin), the image's frame in board units."""
+        import torch
+        p = torch.as_tensor(np.ascontiguousarray(x, np.float64), device="cuda")
+        assert p.shape[0] == self.n_params
+        o = self.board_image_options(**options)
+        d_ev, n, keep = self._events_arg(events)
+        H, W, B, L = int(o.height), int(o.width), int(o.ring_bins), self.n_landmarks
+        want = set(outputs)
+        # (sizes that the call itself refuses must not be allocated first)
+        big = H * W > (1 << 24) or B > 256
+        img = torch.zeros((2, H, W), dtype=torch.int32, device="cuda") if "image" in want and not big else None
+        tot = torch.zeros(7, dtype=torch.int64, device="cuda")
+        rs = torch.zeros((L, 2, 3), dtype=torch.float64, device="cuda") if "ring_stats" in want and B else None
+        rh = torch.zeros((L, max(B, 1)), dtype=torch.int64, device="cuda") if "ring_hist" in want and B and not big else None
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        self.board_image_dev(p.data_ptr(), d_ev, n, o, ptr(img), tot.data_ptr(), ptr(rs), ptr(rh), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        del keep
+        out = {"totals": tot.cpu().numpy().view(BOARD_IMAGE_TOTALS)[0], "options": o,
+               "extent": (o.x0, o.x0 + W * o.bin, o.y0, o.y0 + H * o.bin)}
+        if img is not None:
+            out["image"] = img.cpu().numpy().view(np.uint32)
+        if rs is not None:
+            st = rs.cpu().numpy().reshape(L, 2 * 3).view(RING_STATS).reshape(L, 2)
+            out["ring_stats"] = st
+            nn = st["n"].sum(axis=1).astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                mean = st["sum_d"].sum(axis=1) / nn
+                out["ring_n"], out["ring_mean"] = st["n"].sum(axis=1), mean
+                out["ring_std"] = np.sqrt(np.maximum(st["sum_d2"].sum(axis=1) / nn - mean * mean, 0.0))
+        if rh is not None:
+            out["ring_hist"] = rh.cpu().numpy().view(np.uint64)
+            out["ring_edges"] = np.linspace(-o.ring_range, o.ring_range, B + 1)
+        return out
+
+    def _with_stream(self, events, call):
+        """call(ecal_stream handle) on an ecal_stream made of the host records `events` (any order: the stream sorts)"""
+        L = self.ctx._L
+        L.ecal_stream_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
+        L.ecal_stream_create.restype = ctypes.c_int
+        L.ecal_stream_destroy.argtypes = [ctypes.c_void_p]
+        L.ecal_stream_destroy.restype = None
+        ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
+        assert ev.size % 25 == 0, "packed 25-byte event records"
+        h = ctypes.c_void_p()
+        self.ctx._check(L.ecal_stream_create(self.ctx._h, _ptr(ev) if ev.size else None, ev.size // 25, ctypes.byref(h)))
+        try:
+            return call(h, ev.size // 25)
+        finally:
+            L.ecal_stream_destroy(h)
+
+    def board_image_host(self, x, events, outputs=("image", "ring_stats", "ring_hist"), **options):
+        """ecal_solver_board_image, the host-buffer form over an ecal_stream made of the host records `events`: (image [2, H, W]
+        or None, totals record, ring_stats [n_landmarks, 2] or None, ring_hist [n_landmarks, ring_bins] or None)."""
+        p = np.ascontiguousarray(x, np.float64)
+        assert p.shape[0] == self.n_params
+        o = self.board_image_options(**options)
+        H, W, B, L = int(o.height), int(o.width), int(o.ring_bins), self.n_landmarks
+        ok = H * W <= (1 << 24) and B <= 256
+        img = np.zeros((2, H, W), np.uint32) if "image" in outputs and ok else None
+        tot = np.zeros(1, BOARD_IMAGE_TOTALS)
+        rs = np.zeros((L, 2), RING_STATS) if "ring_stats" in outputs and B else None
+        rh = np.zeros((L, B), np.uint64) if "ring_hist" in outputs and B and ok else None
+
+        def ptr(a):
+            return _ptr(a) if a is not None and a.size else None
+        self._with_stream(events, lambda h, n: self.ctx._check(self.ctx._L.ecal_solver_board_image(
+            self._h, _ptr(p), h, ctypes.byref(o), ptr(img), _ptr(tot), ptr(rs), ptr(rh))))
+        return img, tot[0], rs, rh
+
+    def board_points_host(self, x, events):
+        """ecal_solver_board_points, the host-buffer form: (xw [n, 2], flag [n])."""
+        p = np.ascontiguousarray(x, np.float64)
+        assert p.shape[0] == self.n_params
+        n = np.asarray(events, np.uint8).size // 25
+        xw, flag = np.zeros((n, 2)), np.zeros(n, np.uint8)
+        self._with_stream(events, lambda h, m: self.ctx._check(self.ctx._L.ecal_solver_board_points(
+            self._h, _ptr(p), h, _ptr(xw) if n else None, _ptr(flag) if n else None)))
+        return xw, flag
 
     def default_options(self):
         o = LmOptions()

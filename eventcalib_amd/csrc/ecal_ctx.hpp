@@ -113,6 +113,7 @@ struct ecal_ctx {
     ecal_devbuf as_cnt, as_off;  // association: per-block counts / offsets
     ecal_devbuf as_host;         // staging of ecal_associate
     ecal_devbuf report_scratch;  // ecal_solver_report: the outputs' device images and the keyframe table
+    ecal_devbuf board_scratch;   // ecal_solver_board_image / _board_points: the outputs' device images
     ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks
     hipStream_t copy_stream = nullptr;  // uploads of the double-buffered ingest
     ecal_pinned pass_pinned;            // ecal_detect_pass: window times in, packed verdicts out; the keyframe search: counters, report ring, handed-over frame

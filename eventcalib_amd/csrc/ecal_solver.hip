@@ -398,7 +398,7 @@ extern "C" void ecal_solver_destroy(ecal_solver *s) {
     if (!s) return;
     (void) hipSetDevice(s->ctx->device);
     void *ptrs[] = {s->d_rec, s->d_chunks, s->d_knots, s->d_landmarks, s->d_params, s->d_accum, s->d_heads, s->d_knot_off, s->d_cp_off,
-                    s->d_left, s->d_prog};
+                    s->d_left, s->d_prog, s->d_seg_range};
     for (void *p : ptrs)
         if (p) (void) hipFree(p);
     void *pinned[] = {s->h_acc, s->h_x, s->h_flag};
@@ -507,6 +507,9 @@ extern "C" int ecal_solver_create(ecal_ctx *ctx, const ecal_spline_problem *p, e
     up((void **) &s->d_landmarks, p->landmarks, 3 * (size_t) p->n_landmarks * sizeof(double));
     up((void **) &s->d_knot_off, s->knot_off.data(), s->knot_off.size() * sizeof(uint32_t));
     up((void **) &s->d_cp_off, s->cp_off.data(), s->cp_off.size() * sizeof(uint32_t));
+    s->landmarks.assign(p->landmarks, p->landmarks + 3 * (size_t) p->n_landmarks);
+    const std::vector<double> seg_range = segment_time_ranges(s->knots, s->knot_off, s->cp_off);
+    up((void **) &s->d_seg_range, seg_range.data(), seg_range.size() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_params, s->n_params() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_accum, s->n_accum() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_heads, NE_REPL * ACC_HEAD * sizeof(double));
@@ -701,6 +704,9 @@ extern "C" int ecal_solver_create_dev(ecal_ctx *ctx, const ecal_spline_problem *
     up((void **) &s->d_landmarks, p->landmarks, 3 * (size_t) p->n_landmarks * sizeof(double));
     up((void **) &s->d_knot_off, s->knot_off.data(), s->knot_off.size() * sizeof(uint32_t));
     up((void **) &s->d_cp_off, s->cp_off.data(), s->cp_off.size() * sizeof(uint32_t));
+    s->landmarks.assign(p->landmarks, p->landmarks + 3 * (size_t) p->n_landmarks);
+    const std::vector<double> seg_range = segment_time_ranges(s->knots, s->knot_off, s->cp_off);
+    up((void **) &s->d_seg_range, seg_range.data(), seg_range.size() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_params, s->n_params() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_accum, s->n_accum() * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **) &s->d_heads, NE_REPL * ACC_HEAD * sizeof(double));

@@ -1,5 +1,5 @@
 // The solver object and its device records, shared by the translation units that launch kernels over them: ecal_solver.hip
-// (normal equations, Levenberg-Marquardt) and ecal_report.hip (the calibration quality report).  Not part of the public ABI.
+// (normal equations, Levenberg-Marquardt), ecal_report.hip (the calibration quality report) and ecal_board_image.hip.  Not part of the public ABI.
 #pragma once
 #include <memory>
 #include <vector>
@@ -39,6 +39,19 @@ struct NeProgress {
 
 }  // namespace ecal
 
+namespace ecal {
+// the segments' time ranges from the solver's knots: [n_seg][2] = (knots_g[3], knots_g[n_cp_g])
+inline std::vector<double> segment_time_ranges(const std::vector<double> &knots, const std::vector<uint32_t> &knot_off,
+                                               const std::vector<uint32_t> &cp_off) {
+    std::vector<double> r;
+    for (size_t g = 0; g + 1 < cp_off.size(); g++) {
+        r.push_back(knots[knot_off[g] + 3]);
+        r.push_back(knots[knot_off[g] + (cp_off[g + 1] - cp_off[g])]);
+    }
+    return r;
+}
+}  // namespace ecal
+
 struct ecal_solver {
     ecal_ctx *ctx = nullptr;
     uint64_t n_res = 0;
@@ -48,10 +61,12 @@ struct ecal_solver {
     bool fisheye = false;  // camera_model == ECAL_CAMERA_FISHEYE
     std::vector<uint32_t> cp_off, knot_off;
     std::vector<double> knots;
+    std::vector<double> landmarks;   // host copy [n_lm][3] (ecal_board_image_default_options)
     ecal::ResRecord *d_rec = nullptr;
     ecal::Chunk *d_chunks = nullptr;
     double *d_knots = nullptr, *d_landmarks = nullptr, *d_params = nullptr, *d_accum = nullptr, *d_heads = nullptr;
     uint32_t *d_knot_off = nullptr, *d_cp_off = nullptr;
+    double *d_seg_range = nullptr;   // [n_seg][2]: (knots_g[3], knots_g[n_cp_g]), the time range of every segment (ecal_board_image.hip)
     // ecal_solver_solve's pinned staging (kept: pinning 3 MB per solve costs more than an LM iteration) and the streamed
     // evaluation's progress block (NeProgress)
     double *h_acc = nullptr, *h_x = nullptr;
@@ -63,6 +78,7 @@ struct ecal_solver {
     uint32_t stream_epoch = 0;
     uint32_t last_solve[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ecal_debug_solver_last_solve: how the last ecal_solver_solve ran
     size_t report_lds = 0;   // ecal_solver_report_dev: the dynamic LDS its kernel has been allowed so far
+    size_t board_lds = 0;    // ecal_solver_board_image_dev: the same
     size_t n_params() const { return 9 + 7 * (size_t) n_cp; }
     size_t n_accum() const { return ecal::ACC_HEAD + ecal::ACC_PER_CP * (size_t) n_cp; }
 };

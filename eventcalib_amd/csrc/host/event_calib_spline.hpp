@@ -51,6 +51,25 @@ public:
         }
     };
 
+    // The board-frame event image (ecal_solver_board_image) at the solution: every event of the stream carried through the
+    // refined camera and the spline pose at its own time stamp onto the board, with the call's default options (the landmarks'
+    // bounding box padded by 3 radii, bin = radius / 8, 64 ring bins over +- radius).  Filled when the constructor is asked for
+    // it; valid = false otherwise.
+    struct BoardImage {
+        bool valid = false;
+        ecal_board_image_options options{};
+        ecal_board_image_totals totals{};
+        std::vector<uint32_t> image;              // [2][height][width]: 0 negative, 1 positive events
+        std::vector<ecal_ring_stats> ring_stats;  // [circle][polarity]
+        std::vector<uint64_t> ring_hist;          // [circle][ring_bins]
+        static double mean(const ecal_ring_stats &r) { return r.n ? r.sum_d / (double) r.n : 0.0; }
+        static double stddev(const ecal_ring_stats &r) {
+            if (!r.n) return 0.0;
+            const double m = mean(r), v = r.sum_d2 / (double) r.n - m * m;
+            return v > 0 ? std::sqrt(v) : 0.0;
+        }
+    };
+
     // rotation matrix (row-major) -> quaternion xyzw, Eigen::Quaterniond(Matrix3d)'s branch structure
     static void quaternionFromMatrix(const double *m, double *q) {
         double t = m[0] + m[4] + m[8];
@@ -96,9 +115,10 @@ public:
 
     EventCalibSpline(std::vector<Frame> frames, EventContainer::Ptr eventContainer, CirclePatternParameters::Ptr pattern, bool useSO3,
                      double motionTimeStep, const double K[4], const double distCoeffs[5], int maxIterations = 50,
-                     bool fisheye = false, const ecal_report_options *reportOptions = nullptr)
+                     bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
-          fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations) {
+          fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations),
+          wantBoardImage_(wantBoardImage) {
         if (reportOptions) {
             report_.options = *reportOptions;
             wantReport_ = true;
@@ -156,6 +176,7 @@ public:
     const std::vector<Frame> &frames() const { return frames_; }
     const Summary &summary() const { return summary_; }
     const Report &report() const { return report_; }
+    const BoardImage &boardImage() const { return boardImage_; }
     size_t splineNum() const { return segments_.size(); }
 
     int time2splineIdx(double t) const {
@@ -241,10 +262,11 @@ private:
                                                 5 * motionTimeStep_, 5.0, &prob, &solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_create_from_stream: ") + ecal_last_error(ctx));
         (void) n_events;
-        eventContainer_->release();  // eventContainer_->container.clear() (:194)
+        if (!wantBoardImage_) eventContainer_->release();  // eventContainer_->container.clear() (:194); the board image reads the stream once more
         summary_.residuals = ecal_solver_num_residuals(solver);
         if (summary_.residuals == 0) {
             ecal_solver_destroy(solver);
+            if (wantBoardImage_) eventContainer_->release();
             return false;
         }
         std::vector<double> x(ecal_solver_param_size(solver));
@@ -272,9 +294,25 @@ private:
             r.valid = rc == ECAL_OK;
             if (rc != ECAL_OK) {
                 ecal_solver_destroy(solver);
+                if (wantBoardImage_) eventContainer_->release();
                 throw std::runtime_error(std::string("ecal_solver_report: ") + ecal_last_error(ctx));
             }
         }
+        if (rc == ECAL_OK && wantBoardImage_) {   // every event of the stream through the solution
+            BoardImage &b = boardImage_;
+            (void) ecal_board_image_default_options(solver, &b.options);
+            b.image.assign(2 * (size_t) b.options.width * b.options.height, 0u);
+            b.ring_stats.assign(2 * (size_t) n_circ, ecal_ring_stats{});
+            b.ring_hist.assign((size_t) n_circ * b.options.ring_bins, 0);
+            rc = ecal_solver_board_image(solver, x.data(), es, &b.options, b.image.data(), &b.totals, b.ring_stats.data(), b.ring_hist.data());
+            b.valid = rc == ECAL_OK;
+            if (rc != ECAL_OK) {
+                ecal_solver_destroy(solver);
+                eventContainer_->release();
+                throw std::runtime_error(std::string("ecal_solver_board_image: ") + ecal_last_error(ctx));
+            }
+        }
+        if (wantBoardImage_) eventContainer_->release();
         ecal_solver_destroy(solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_solve: ") + ecal_last_error(ctx));
         std::copy(x.begin(), x.begin() + 9, intrinsics_);
@@ -317,6 +355,8 @@ private:
     Summary summary_;
     Report report_;
     bool wantReport_ = false;
+    BoardImage boardImage_;
+    bool wantBoardImage_ = false;
 };
 
 }  // namespace opengv2

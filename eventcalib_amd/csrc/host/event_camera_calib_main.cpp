@@ -172,7 +172,12 @@ int main(int argc, char **argv) {
     ecal_report_default_options(&reportOptions);
     reportOptions.width = (uint32_t) width;
     reportOptions.height = (uint32_t) height;
-    EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr);
+    // BoardImage (a key of this build, optional): 1 = every event of the stream carried through the solution onto the board
+    // (ecal_solver_board_image), written to saveDir/board_image.png and saveDir/BoardImage.txt; absent or 0: nothing changes
+    int wantBoardImage = 0;
+    fsSettings["BoardImage"] >> wantBoardImage;
+    EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
+                            wantBoardImage != 0);
     const double *x = spline.intrinsics();
     std::printf("refined %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g residuals %zu iterations %d splines %zu\n", x[0], x[1], x[2], x[3],
                 x[4], x[5], x[6], x[7], x[8], spline.summary().residuals, spline.summary().iterations, spline.splineNum());
@@ -235,6 +240,56 @@ int main(int argc, char **argv) {
         std::fprintf(f, "\n");
         std::fclose(f);
         std::printf("report rms %.9g outliers %.6f empty_cells %.6f\n", Rp::rms(a), rp.outlierFraction(), rp.emptyCellFraction());
+    }
+    if (wantBoardImage && spline.boardImage().valid) {
+        const EventCalibSpline::BoardImage &bi = spline.boardImage();
+        using Bi = EventCalibSpline::BoardImage;
+        const ecal_board_image_options &o = bi.options;
+        const size_t plane = (size_t) o.width * o.height;
+        // positive events in red and negative in green (the colours of EventFrame::undistortedImage, EventFrame.cpp:38-60), each
+        // channel min(255, round(255 * count / p99)), p99 = the 99th percentile (nearest rank) of the non-zero counts of both planes
+        std::vector<uint32_t> nz;
+        for (uint32_t c : bi.image)
+            if (c) nz.push_back(c);
+        std::sort(nz.begin(), nz.end());
+        const double p99 = nz.empty() ? 1.0 : (double) nz[(size_t) std::ceil(0.99 * (double) nz.size()) - 1];
+        std::vector<uint8_t> rgb(3 * plane, 0);
+        for (size_t i = 0; i < plane; i++) {
+            rgb[3 * i] = (uint8_t) std::min(255.0, std::round(255.0 * bi.image[plane + i] / p99));
+            rgb[3 * i + 1] = (uint8_t) std::min(255.0, std::round(255.0 * bi.image[i] / p99));
+        }
+        if (!ecal_host::write_png_rgb(std::string(argv[3]) + "/board_image.png", (int) o.width, (int) o.height, rgb)) {
+            std::fprintf(stderr, "cannot write %s/board_image.png\n", argv[3]);
+            return 3;
+        }
+        std::FILE *f = std::fopen((std::string(argv[3]) + "/BoardImage.txt").c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "cannot write %s/BoardImage.txt\n", argv[3]);
+            return 3;
+        }
+        const ecal_board_image_totals &t = bi.totals;
+        std::fprintf(f, "# board units (the unit of Circles_Radius); d = distance to the nearest circle's centre - radius, |d| < %.9g\n", o.ring_range);
+        std::fprintf(f, "totals n_events %llu n_outside_time %llu n_behind %llu n_outside_image %llu n_image_neg %llu n_image_pos %llu n_ring %llu\n",
+                     (unsigned long long) t.n_events, (unsigned long long) t.n_outside_time, (unsigned long long) t.n_behind,
+                     (unsigned long long) t.n_outside_image, (unsigned long long) t.n_image[0], (unsigned long long) t.n_image[1],
+                     (unsigned long long) t.n_ring);
+        std::fprintf(f, "image width %u height %u x0 %.17g y0 %.17g bin %.17g p99 %.9g\n", o.width, o.height, o.x0, o.y0, o.bin, p99);
+        const size_t n_circ = bi.ring_stats.size() / 2;
+        std::fprintf(f, "circles %zu\n", n_circ);
+        ecal_ring_stats all{};
+        for (size_t k = 0; k < n_circ; k++) {
+            const ecal_ring_stats &ng = bi.ring_stats[2 * k], &ps = bi.ring_stats[2 * k + 1];
+            std::fprintf(f, "circle %zu neg_n %llu neg_ring_mean %.9g neg_ring_std %.9g pos_n %llu pos_ring_mean %.9g pos_ring_std %.9g\n", k,
+                         (unsigned long long) ng.n, Bi::mean(ng), Bi::stddev(ng), (unsigned long long) ps.n, Bi::mean(ps), Bi::stddev(ps));
+            for (const ecal_ring_stats *r : {&ng, &ps}) {
+                all.n += r->n;
+                all.sum_d += r->sum_d;
+                all.sum_d2 += r->sum_d2;
+            }
+        }
+        std::fclose(f);
+        std::printf("board_image events %llu in_image %llu ring %llu ring_mean %.9g ring_std %.9g\n", (unsigned long long) t.n_events,
+                    (unsigned long long) (t.n_image[0] + t.n_image[1]), (unsigned long long) t.n_ring, Bi::mean(all), Bi::stddev(all));
     }
     return 0;
 }

@@ -434,4 +434,74 @@ ECAL_HD void quaternion_plus(const double q[4], const double d[3], double out[4]
     out[3] = dq[3] * q[3] - dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2];
 }
 
+// ---- the board point of a pixel (the board-frame event image, ecal_board_image.hip) ------------------------------------------
+// The first half of the residual on its own: pixel -> inverse camera model -> rotation by the pose -> intersection with the
+// plane z = 0.  The three functions below DUPLICATE lines of residual_core, spline_residual and spline_residual_so3 on purpose,
+// the same operations in the same order: the residual functions are not rewritten on top of them, because the code generation
+// of normal_eq_kernel (227 VGPRs) must not move.  tests/cpp/check_board_point.cpp holds the copies to the originals bit for bit.
+
+// residual_core up to Xw.  ifx / ify = 1 / fx, 1 / fy (0: computed here).  false: the ray does not meet the plane in front of
+// the camera — the depth s = -T_z / Y_z is not finite or not positive; Xw is then not meaningful.
+template <bool FISHEYE = false>
+ECAL_HD bool spline_board_point(double u, double v, const double *intr, double ifx_in, double ify_in, double ux, double uy, double uz,
+                                double w, const double T[3], double Xw[2]) {
+    const double cx = intr[2], cy = intr[3];
+    const double ifx = ifx_in != 0.0 ? ifx_in : 1.0 / intr[0], ify = ify_in != 0.0 ? ify_in : 1.0 / intr[1];
+    const double x = (u - cx) * ifx, y = (v - cy) * ify;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2, r8 = r6 * r2, r10 = r8 * r2;
+    const double poly = 1.0 + intr[4] * r2 + intr[5] * r4 + intr[6] * r6 + intr[7] * r8 + intr[8] * r10;
+    double c = poly;
+    if (FISHEYE) {
+        if (r2 > 1e-16) {
+            const double r = sqrt(r2), tn = tan(r * poly);
+            c = tn / r;
+        }
+    }
+    const double px = x * c, py = y * c, pz = 1.0;
+    const double cxp0 = uy * pz - uz * py, cxp1 = uz * px - ux * pz, cxp2 = ux * py - uy * px;
+    const double udp = ux * px + uy * py + uz * pz, udu = ux * ux + uy * uy + uz * uz;
+    const double Y0 = px + 2 * w * cxp0 + 2 * (ux * udp - px * udu);
+    const double Y1 = py + 2 * w * cxp1 + 2 * (uy * udp - py * udu);
+    const double Y2 = pz + 2 * w * cxp2 + 2 * (uz * udp - pz * udu);
+    const double iY2 = 1.0 / Y2;
+    const double s = -T[2] * iY2;
+    Xw[0] = T[0] + s * Y0;
+    Xw[1] = T[1] + s * Y1;
+    return s > 0.0 && s <= 1.79769313486231570e308;   // (NaN fails both)
+}
+
+// the pose of the quaternion spline at basis values b: spline_residual's blend and normalisation
+ECAL_HD void spline_pose_quat(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
+    double vq[4] = {0, 0, 0, 0};
+    T[0] = T[1] = T[2] = 0;
+    for (int j = 0; j < 4; j++) {
+        for (int k = 0; k < 4; k++) vq[k] += b[j] * q[j][k];
+        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
+    }
+    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
+    for (int k = 0; k < 4; k++) Q[k] = vq[k] * ivn;
+}
+
+// the pose of the cumulative SO3 spline: spline_residual_so3's product of the three factors
+ECAL_HD void spline_pose_so3(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
+    double beta[3];
+    beta[2] = b[3];
+    beta[1] = beta[2] + b[2];
+    beta[0] = beta[1] + b[1];
+    for (int k = 0; k < 4; k++) Q[k] = q[0][k];
+    T[0] = T[1] = T[2] = 0;
+    for (int j = 1; j <= 3; j++) {
+        const double inv[4] = {-q[j - 1][0], -q[j - 1][1], -q[j - 1][2], q[j - 1][3]};
+        double rel[4], d[3], bd[3], e[4], nq[4];
+        quat_mul(inv, q[j], rel);
+        so3_log(rel, d);
+        for (int k = 0; k < 3; k++) bd[k] = beta[j - 1] * d[k];
+        so3_exp(bd, e);
+        quat_mul(Q, e, nq);
+        for (int k = 0; k < 4; k++) Q[k] = nq[k];
+    }
+    for (int j = 0; j < 4; j++)
+        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
+}
+
 }  // namespace ecal

@@ -743,6 +743,55 @@ int ecal_solver_report(ecal_solver *s, const double *params, const double *kf_ti
                        const ecal_report_options *opt, ecal_report_totals *total, ecal_bin_stats *kf, ecal_bin_stats *lm,
                        uint64_t *cell_n, double *cell_sum_r2, uint64_t *hist);
 uint32_t ecal_solver_num_landmarks(const ecal_solver *s);
+/* Board-frame event image (the motion-compensated image of the calibration): EVERY event of a stream — not only the ones the
+ * association kept — carried through the intrinsics of `params` and the pose of the solver's spline at its own time stamp onto
+ * the board plane z = 0 (the first half of the residual: inverse camera model, rotation, ray / plane intersection).  With a good
+ * calibration the events collapse into sharp rings of radius circle_radius around the landmarks; with a bad one they smear.
+ * One pass over the packed, time-sorted 25-byte records; blocks of ECAL_BOARD_IMAGE_BLOCK events per workgroup.  Per event:
+ *   segment    the spline segment g with knots_g[3] <= t <= knots_g[n_cp_g] (both ends inclusive); none: n_outside_time
+ *              (the segments' time ranges are ascending and disjoint; a time at which two of them touch belongs to the earlier)
+ *   board point (Xw0, Xw1) in board units; a ray that does not meet the plane in front of the camera (depth not finite or
+ *              <= 0): n_behind
+ *   image      ix = floor((Xw0 - x0) / bin), iy = floor((Xw1 - y0) / bin); inside [0, width) x [0, height): img[p][iy][ix]++ with
+ *              p = 1 for a positive event (polarity byte != 0), 0 for a negative one, and n_image[p]++; else n_outside_image
+ *   ring profile (ring_bins > 0; at most 128 landmarks: ECAL_ERR_RANGE): the landmark nearest in the plane (squared distance,
+ *              ties to the lower index), d = |Xw - lm| - circle_radius; when |d| < ring_range: n_ring++,
+ *              ring_hist[lm][floor((d + ring_range) * ring_bins / (2 ring_range))]++ and ring_stats[lm][p] += {1, d, d * d}
+ * n_events = n_outside_time + n_behind + n_outside_image + n_image[0] + n_image[1].  Every count is an integer atomic and does
+ * not depend on the order of arrival; sum_d / sum_d2 do in their last bits.  bin > 0, width * height <= 2^24, ring_bins <= 256,
+ * ring_range > 0 when ring_bins > 0 (ECAL_ERR_INVALID otherwise).  Any of d_img / d_ring_stats / d_ring_hist may be NULL (the
+ * totals are the same); the call zeroes its outputs itself on `stream`; n_events == 0 is valid.  d_params: the solver's
+ * parameter vector (ecal_solver_param_size doubles). */
+#define ECAL_BOARD_IMAGE_BLOCK 4096u  /* events per workgroup */
+#define ECAL_BOARD_IMAGE_CP_LDS 16u   /* control points a workgroup stages on chip; a block that needs more (a very fine knot
+                                         vector) or meets more than one segment reads them from global memory: same results */
+typedef struct ecal_board_image_options {
+    double x0, y0, bin;     /* board coordinates of the image's corner, side of a pixel (board units) */
+    uint32_t width, height; /* pixels */
+    uint32_t ring_bins;     /* 0: no ring profile */
+    double ring_range;      /* the ring histogram covers d in (-ring_range, ring_range) */
+} ecal_board_image_options;
+typedef struct ecal_board_image_totals {
+    uint64_t n_events, n_outside_time, n_behind, n_outside_image, n_image[2], n_ring;
+} ecal_board_image_totals;
+typedef struct ecal_ring_stats {
+    uint64_t n;
+    double sum_d, sum_d2;
+} ecal_ring_stats;
+/* the landmarks' bounding box padded by 3 radii, bin = radius / 8, ring_bins = 64, ring_range = radius */
+int ecal_board_image_default_options(const ecal_solver *s, ecal_board_image_options *opt);
+int ecal_solver_board_image_dev(ecal_solver *s, const double *d_params, const uint8_t *d_events, uint64_t n_events,
+                                const ecal_board_image_options *opt /*NULL: the defaults*/, uint32_t *d_img /*[2][height][width]*/,
+                                ecal_board_image_totals *d_totals, ecal_ring_stats *d_ring_stats /*[n_landmarks][2]*/,
+                                uint64_t *d_ring_hist /*[n_landmarks][ring_bins]*/, void *stream);
+/* the per-event form (scatter plots; the seam the tests pin the arithmetic through): d_xw [n_events][2] board points (zeros
+ * where the flag is not 0), d_flag [n_events]: 0 ok, 1 outside every segment's time range, 2 behind the camera */
+int ecal_solver_board_points_dev(ecal_solver *s, const double *d_params, const uint8_t *d_events, uint64_t n_events,
+                                 double *d_xw, uint8_t *d_flag, void *stream);
+/* host-buffer forms over a resident ecal_stream: params and outputs in host memory, synchronous */
+int ecal_solver_board_image(ecal_solver *s, const double *params, const ecal_stream *es, const ecal_board_image_options *opt,
+                            uint32_t *img, ecal_board_image_totals *totals, ecal_ring_stats *ring_stats, uint64_t *ring_hist);
+int ecal_solver_board_points(ecal_solver *s, const double *params, const ecal_stream *es, double *xw, uint8_t *flag);
 void ecal_lm_default_options(ecal_lm_options *opt);
 int ecal_solver_solve(ecal_solver *s, double *params /*in: start, out: solution*/, const ecal_lm_options *opt,
                       ecal_lm_summary *summary);
