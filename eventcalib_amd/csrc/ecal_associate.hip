@@ -7,6 +7,10 @@
 // keyframe, accepted if |dist - radius| < 5 px; the event then becomes one residual (pixel, time,
 // landmark of that circle).  Output order = event (time) order, as relationContainer_ (:181-183).
 // Ties (equidistant keyframes / centres) go to the smaller index; nanoflann's choice is unpinned.
+// PRECONDITION: kf_time is STRICTLY ascending.  The nearest keyframe is looked for among the first index with kf_time >= t
+// and its predecessor only, so with repeated times ([1, 1, 5], t = 2: index 1, where the rule says 0) the smaller-index rule
+// would not hold.  The entry points that have the table on the host (ecal_associate, ecal_solver_create_from_stream) check
+// and return ECAL_ERR_INVALID; the _dev forms cannot.
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
 
@@ -268,6 +272,18 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(const uint32_t *__res
 
 using namespace ecal;
 
+// the keyframe search's precondition (header comment), for the entry points whose table is on the host
+static int check_kf_time_ascending(ecal_ctx *ctx, const char *who, const double *kf_time, uint32_t n_keyframes) {
+    for (uint32_t k = 0; k < n_keyframes; k++) {
+        const bool ok = kf_time[k] == kf_time[k] && (k == 0 || kf_time[k - 1] < kf_time[k]);
+        if (!ok) {   // (also catches NaN times)
+            ctx->last_error = std::string(who) + ": the keyframe times must be strictly ascending (keyframe " + std::to_string(k) + ")";
+            return ECAL_ERR_INVALID;
+        }
+    }
+    return ECAL_OK;
+}
+
 static int associate_common(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const double *d_kf_time,
                             const double *d_kf_circles, uint32_t n_keyframes, uint32_t n_circles, double t_min, double t_max,
                             const double *d_ranges, uint32_t n_ranges, double max_dt, double edge_tol, double *d_obs, double *d_time,
@@ -337,12 +353,14 @@ extern "C" int ecal_associate(ecal_ctx *ctx, const ecal_stream *es, const double
     *count = 0;
     if (n == 0 || n_keyframes == 0) return ECAL_OK;
     if (!kf_time || !kf_circles) return ECAL_ERR_INVALID;
+    int rc = check_kf_time_ascending(ctx, "ecal_associate", kf_time, n_keyframes);
+    if (rc) return rc;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t kb = (size_t) n_keyframes * 8, cb = (size_t) n_keyframes * n_circles * 24;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_kt = 0, o_kc = up(kb), o_obs = o_kc + up(cb), o_tm = o_obs + up(n * 16), o_lm = o_tm + up(n * 8),
                  o_cnt = o_lm + up(n * 4), total = o_cnt + 256;
-    int rc = ecal_ensure(ctx, ctx->as_host, total);
+    rc = ecal_ensure(ctx, ctx->as_host, total);
     if (rc) return rc;
     char *base = (char *) ctx->as_host.ptr;
     hipStream_t st = ctx->stream;
@@ -389,6 +407,8 @@ extern "C" int ecal_solver_create_from_stream(ecal_ctx *ctx, const ecal_stream *
             return ECAL_ERR_INVALID;
         }
     }
+    int rc = check_kf_time_ascending(ctx, "ecal_solver_create_from_stream", kf_time, n_keyframes);
+    if (rc) return rc;
     const uint64_t n = ecal_stream_size(es);
     if (n > 0xFFFFFFFFull) return ECAL_ERR_RANGE;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -396,7 +416,7 @@ extern "C" int ecal_solver_create_from_stream(ecal_ctx *ctx, const ecal_stream *
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_kt = 0, o_kc = up(kb), o_rg = o_kc + up(cb), o_obs = o_rg + up(rb), o_tm = o_obs + up(n * 16), o_lm = o_tm + up(n * 8),
                  o_sg = o_lm + up(n * 4), o_cnt = o_sg + up(n * 4), total = o_cnt + 256;
-    int rc = ecal_ensure(ctx, ctx->as_host, total);
+    rc = ecal_ensure(ctx, ctx->as_host, total);
     if (rc) return rc;
     char *base = (char *) ctx->as_host.ptr;
     hipStream_t st = ctx->stream;

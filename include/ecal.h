@@ -547,7 +547,12 @@ int ecal_rectify_keyframes(ecal_ctx *ctx, const ecal_stream *es, const double *d
  * centre (d_kf_circles [K][n_circles][3] = cx, cy, radius in pixels, grid order), accepted if
  * | |pixel - centre| - radius | < edge_tol (5 px).  Accepted events are written in event order:
  * d_obs[j] = pixel, d_time[j] = t, d_lm_id[j] = circle index (= landmark index); *d_count = how many
- * (outputs need room for n_events entries).  These arrays are ecal_spline_problem's obs/time/lm_id. */
+ * (outputs need room for n_events entries).  These arrays are ecal_spline_problem's obs/time/lm_id.
+ * Ties (an event equally far from two keyframes, a pixel equally far from two centres) go to the smaller index.
+ * d_kf_time is REQUIRED STRICTLY ascending (kf_time[k - 1] < kf_time[k], no NaN): the search compares the first keyframe not
+ * before the event with its predecessor only, so repeated times would break the tie rule ([1, 1, 5], t = 2 gives 1, not 0).
+ * The _dev forms cannot report a violation from a device table; ecal_associate and ecal_solver_create_from_stream, which take
+ * the table from the host, check and return ECAL_ERR_INVALID (ecal_last_error names the keyframe). */
 int ecal_associate_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const double *d_kf_time,
                        const double *d_kf_circles, uint32_t n_keyframes, uint32_t n_circles, double t_min, double t_max,
                        double max_dt, double edge_tol, double *d_obs, double *d_time, uint32_t *d_lm_id,
@@ -566,7 +571,8 @@ int ecal_associate_ranges_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n
                               uint32_t *d_seg_id, uint32_t *d_count, void *stream);
 
 /* host-buffer form: events from an ecal_stream (resident in HBM), keyframe tables and results in host memory;
- * obs/time/lm_id need room for `capacity` records, *count = records found (ECAL_ERR_RANGE if more than capacity) */
+ * obs/time/lm_id need room for `capacity` records, *count = records found (ECAL_ERR_RANGE if more than capacity: nothing is
+ * copied then).  kf_time not strictly ascending (or NaN): ECAL_ERR_INVALID, ecal_last_error names the keyframe. */
 int ecal_associate(ecal_ctx *ctx, const ecal_stream *es, const double *kf_time, const double *kf_circles, uint32_t n_keyframes,
                    uint32_t n_circles, double t_min, double t_max, double max_dt, double edge_tol, uint64_t capacity, double *obs,
                    double *time, uint32_t *lm_id, uint64_t *count);
@@ -685,7 +691,8 @@ uint64_t ecal_solver_num_residuals(const ecal_solver *s);
 /* Host-pointer convenience of the two (what host/event_calib_spline.hpp calls): the association of every spline segment over a
  * resident ecal_stream + the solver built on the result, the residual arrays never leaving HBM.  kf_time / kf_circles / ranges
  * [n_ranges][2] are host tables (ecal_associate_ranges_dev's arguments); layout = the problem without its residual arrays (obs,
- * time, lm_id, seg_id, n_res ignored); n_ranges must equal layout->n_segments.  ecal_solver_num_residuals says how many were found. */
+ * time, lm_id, seg_id, n_res ignored); n_ranges must equal layout->n_segments.  ecal_solver_num_residuals says how many were found.
+ * ECAL_ERR_INVALID (ecal_last_error names the entry) if the ranges are not ascending and disjoint or kf_time is not strictly ascending. */
 int ecal_solver_create_from_stream(ecal_ctx *ctx, const ecal_stream *es, const double *kf_time, const double *kf_circles,
                                    uint32_t n_keyframes, uint32_t n_circles, const double *ranges, uint32_t n_ranges, double max_dt,
                                    double edge_tol, const ecal_spline_problem *layout, ecal_solver **out);
