@@ -94,7 +94,8 @@ def check_pose(R_ref, twb_ref, t_ref, R_cur, twb_cur, t_cur, step):
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
-                     gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False):
+                     gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
+                     refine_rounds=0, refine_ring_tol=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     gate_mode: capi.GATE_SHARED_MAP (default: the reference's keyframe gate as its single-worker run computes it — one keyframe
@@ -112,7 +113,14 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     the board, per 16-pixel cell of the sensor, histogram; board units) into out["report"] — a stage of its own, `report`.
     board_image: also carry EVERY event of the stream through the solution onto the board (capi.Solver.board_image: the
     motion-compensated image per polarity and the ring profile of every circle) into out["board_image"] — a stage of its own,
-    `board_image`."""
+    `board_image`.
+    refine_rounds (opt-in, default 0: nothing changes): after the solve, that many rounds of "look at ALL events, solve on what
+    fits" — capi.Solver.reassociated at the current solution (every event of the stream whose board point lies within
+    refine_ring_tol board units of a circle's rim becomes a residual, wherever it sits relative to a keyframe; None: the Huber
+    width), the previous solver closed, a solve from the current solution with the same options.  out["refine"] has one entry per
+    round (totals, residuals, initial and final cost, iterations), `report` / `board_image` then run on the last solver at the last
+    solution, out["spline"] stays the keyframe-gated solve's summary; a stage of its own, `refine`.  Whether the refined camera is
+    the more accurate one has not been established (design/09_measured.md has what the synthetic streams gave).  Single process."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -298,6 +306,20 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     opt = solver.default_options()
     opt.max_num_iterations = max_num_iterations
     x, summ = solver.solve(x0, opt)
+    if refine_rounds:
+        mark("lm_solve")
+        out["refine"] = []
+        for k in range(int(refine_rounds)):
+            refined, tot = solver.reassociated(x, events, refine_ring_tol, stream=st)
+            solver.close()
+            solver = refined
+            if solver.n_res == 0:
+                solver.close()
+                raise RuntimeError("refine round %d: no event within the ring tolerance" % k)
+            x, sm = solver.solve(x, opt)
+            out["refine"].append({"totals": tot, "residuals": int(solver.n_res), "initial_cost": float(sm.initial_cost),
+                                  "final_cost": float(sm.final_cost), "iterations": int(sm.iterations)})
+        mark("refine")
     if report:
         mark("lm_solve")
         out["report"] = solver.report(x, kf["time"][kf_idx], width=int(width), height=int(height))

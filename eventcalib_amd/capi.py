@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "ecal_slice_events_packed_dev", "ecal_dbscan_batch_packed_dev", "ecal_extract_batch_packed_dev", "ecal_unpack_points_dev",
     "ecal_report_default_options", "ecal_solver_report_dev", "ecal_solver_report", "ecal_solver_num_landmarks",
     "ecal_board_image_default_options", "ecal_solver_board_image_dev", "ecal_solver_board_image", "ecal_solver_board_points_dev", "ecal_solver_board_points",
+    "ecal_solver_reassociate_dev", "ecal_solver_reassociate", "ecal_solver_create_reassociated",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -522,6 +523,9 @@ BOARD_IMAGE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.ui
                                ("n_outside_image", np.uint64), ("n_image", np.uint64, (2,)), ("n_ring", np.uint64)])
 RING_STATS = np.dtype([("n", np.uint64), ("sum_d", np.float64), ("sum_d2", np.float64)])
 BOARD_IMAGE_BLOCK, BOARD_IMAGE_CP_LDS = 4096, 16
+# ecal_reassociate_totals
+REASSOCIATE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
+                               ("n_off_ring", np.uint64), ("n_kept", np.uint64)])
 
 
 def _declare_solver(L):
@@ -536,6 +540,12 @@ def _declare_solver(L):
     L.ecal_solver_board_points_dev.restype = i32
     L.ecal_solver_board_points.argtypes = [vp, vp, vp, vp, vp]
     L.ecal_solver_board_points.restype = i32
+    L.ecal_solver_reassociate_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, f64, vp, vp, vp, vp, vp, vp, vp]
+    L.ecal_solver_reassociate_dev.restype = i32
+    L.ecal_solver_reassociate.argtypes = [vp, vp, vp, f64, ctypes.c_uint64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), vp]
+    L.ecal_solver_reassociate.restype = i32
+    L.ecal_solver_create_reassociated.argtypes = [vp, vp, vp, f64, ctypes.POINTER(vp), vp]
+    L.ecal_solver_create_reassociated.restype = i32
     L.ecal_report_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
     L.ecal_report_default_options.restype = None
     L.ecal_solver_report_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
@@ -655,11 +665,19 @@ class Solver:
         self.huber_a = P.huber_a
         P.use_so3 = int(bool(problem.get("use_so3", False)))
         P.camera_model = CAMERA_FISHEYE if problem.get("fisheye", False) else CAMERA_RADIAL
+        # the problem without its residual arrays: what Solver.reassociated builds the next solver from
+        self._layout = dict(seg_cp_off=keep["seg_cp_off"], knots=keep["knots"], landmarks=keep["landmarks"], circle_radius=P.circle_radius,
+                            huber_a=P.huber_a, use_so3=bool(P.use_so3), fisheye=P.camera_model == CAMERA_FISHEYE)
         h = ctypes.c_void_p()
         if device_arrays is None:
             ctx._check(L.ecal_solver_create(ctx._h, ctypes.byref(P), ctypes.byref(h)))
         else:
             ctx._check(L.ecal_solver_create_dev(ctx._h, ctypes.byref(P), device_arrays[5], stream, ctypes.byref(h)))
+        self._adopt(h)
+
+    def _adopt(self, h):
+        """take over the ecal_solver handle h (the constructor; Solver.reassociated)"""
+        L = self.ctx._L
         self._h = h
         self.n_params = int(L.ecal_solver_param_size(h))
         self.n_normal = int(L.ecal_solver_normal_size(h))
@@ -911,6 +929,92 @@ class Solver:
         self._with_stream(events, lambda h, m: self.ctx._check(self.ctx._L.ecal_solver_board_points(
             self._h, _ptr(p), h, _ptr(xw) if n else None, _ptr(flag) if n else None)))
         return xw, flag
+
+    # ---- re-association through the solved spline (ecal_solver_reassociate*) ----
+    def reassociate_dev(self, d_params, d_events, n_events, ring_tol, d_obs, d_time, d_lm_id, d_seg_id, d_count, d_totals=None, stream=0):
+        """ecal_solver_reassociate_dev: raw device pointers; the record arrays need room for n_events entries, d_count is one
+        uint32, d_totals (or None) one REASSOCIATE_TOTALS record; ring_tol None or <= 0: the solver's huber_a.  No host
+        synchronisation."""
+        self.ctx._check(self.ctx._L.ecal_solver_reassociate_dev(self._h, d_params, d_events, int(n_events),
+                                                                0.0 if ring_tol is None else float(ring_tol), d_obs, d_time, d_lm_id,
+                                                                d_seg_id, d_count, d_totals, stream))
+
+    def reassociate(self, x, events, ring_tol=None):
+        """Every event of the packed, time-sorted stream `events` whose board point at the parameters x lies within ring_tol
+        (board units; None: the solver's huber_a) of a circle's rim, as residual records in event order.  Returns a dict: `obs`
+        [m, 2], `time` [m], `lm_id` [m], `seg_id` [m], `count` = m and `totals` (one REASSOCIATE_TOTALS record: n_events =
+        n_outside_time + n_behind + n_off_ring + n_kept, n_kept = m)."""
+        import torch
+        p = torch.as_tensor(np.ascontiguousarray(x, np.float64), device="cuda")
+        assert p.shape[0] == self.n_params
+        d_ev, n, keep = self._events_arg(events)
+        obs = torch.empty((max(n, 1), 2), dtype=torch.float64, device="cuda")
+        tm = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
+        lm = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+        sg = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+        cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+        tot = torch.zeros(5, dtype=torch.int64, device="cuda")
+        self.reassociate_dev(p.data_ptr(), d_ev, n, ring_tol, obs.data_ptr(), tm.data_ptr(), lm.data_ptr(), sg.data_ptr(), cnt.data_ptr(),
+                             tot.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        del keep
+        m = int(cnt.cpu().numpy().view(np.uint32)[0])
+        return {"obs": obs[:m].cpu().numpy(), "time": tm[:m].cpu().numpy(), "lm_id": lm[:m].cpu().numpy().view(np.uint32),
+                "seg_id": sg[:m].cpu().numpy().view(np.uint32), "count": m, "totals": tot.cpu().numpy().view(REASSOCIATE_TOTALS)[0]}
+
+    def reassociate_host(self, x, events, capacity, ring_tol=None, buffers=None):
+        """ecal_solver_reassociate, the host-buffer form over an ecal_stream made of the host records `events`: (obs, time, lm_id,
+        seg_id, count, totals record); the arrays (or `buffers`, four arrays of at least `capacity` records) are written up to
+        `count` — and not at all when count > capacity (EcalError, ECAL_ERR_RANGE)."""
+        p = np.ascontiguousarray(x, np.float64)
+        assert p.shape[0] == self.n_params
+        c = max(int(capacity), 1)
+        obs, tm, lm, sg = buffers if buffers is not None else (np.zeros((c, 2)), np.zeros(c), np.zeros(c, np.uint32), np.zeros(c, np.uint32))
+        cnt = ctypes.c_uint64(0)
+        tot = np.zeros(1, REASSOCIATE_TOTALS)
+        self._with_stream(events, lambda h, n: self.ctx._check(self.ctx._L.ecal_solver_reassociate(
+            self._h, _ptr(p), h, 0.0 if ring_tol is None else float(ring_tol), int(capacity), _ptr(obs), _ptr(tm), _ptr(lm), _ptr(sg),
+            ctypes.byref(cnt), _ptr(tot))))
+        m = int(cnt.value)
+        return obs[:m], tm[:m], lm[:m], sg[:m], m, tot[0]
+
+    def reassociated(self, x, events, ring_tol=None, stream=None):
+        """A NEW Solver with this one's layout (segments, knots, landmarks, radius, Huber width, rotation variant, camera model)
+        on the records of reassociate(x, events, ring_tol), built in place on the GPU: nothing proportional to the events crosses
+        PCIe.  events: a torch uint8 CUDA tensor (ecal_solver_reassociate_dev into device arrays, ecal_solver_create_dev on
+        them — the chain's way, calibrate_stream), or host records / bytes (uploaded into an ecal_stream, then
+        ecal_solver_create_reassociated, the C++ shim's way).  Returns (solver, totals record); this solver is left untouched and
+        both are closed independently."""
+        import torch
+        p = np.ascontiguousarray(x, np.float64)
+        assert p.shape[0] == self.n_params
+        if not (isinstance(events, torch.Tensor) and events.is_cuda):
+            tot = np.zeros(1, REASSOCIATE_TOTALS)
+            h = ctypes.c_void_p()
+            ev = events.numpy() if isinstance(events, torch.Tensor) else (
+                np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray)) else events)
+            self._with_stream(ev, lambda es, n: self.ctx._check(self.ctx._L.ecal_solver_create_reassociated(
+                self._h, _ptr(p), es, 0.0 if ring_tol is None else float(ring_tol), ctypes.byref(h), _ptr(tot))))
+            new = Solver.__new__(Solver)
+            new.ctx, new.huber_a, new._layout = self.ctx, self.huber_a, self._layout
+            new._adopt(h)
+            return new, tot[0]
+        dev = events.device
+        st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        d_p = torch.as_tensor(p, device=dev)
+        d_ev, n, keep = self._events_arg(events)
+        obs = torch.empty((max(n, 1), 2), dtype=torch.float64, device=dev)
+        tm = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        lm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        sg = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        tot = torch.zeros(5, dtype=torch.int64, device=dev)
+        self.reassociate_dev(d_p.data_ptr(), d_ev, n, ring_tol, obs.data_ptr(), tm.data_ptr(), lm.data_ptr(), sg.data_ptr(), cnt.data_ptr(),
+                             tot.data_ptr(), st)
+        new = Solver(self.ctx, self._layout, device_arrays=(obs.data_ptr(), tm.data_ptr(), lm.data_ptr(), sg.data_ptr(), n, cnt.data_ptr()),
+                     stream=st)      # (synchronises: the records are consumed when it returns)
+        del keep
+        return new, tot.cpu().numpy().view(REASSOCIATE_TOTALS)[0]
 
     def default_options(self):
         o = LmOptions()

@@ -272,6 +272,12 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(const uint32_t *__res
 
 using namespace ecal;
 
+int ecal_scan_blocks(ecal_ctx *ctx, const uint32_t *d_cnt, uint32_t nb, uint32_t *d_off, hipStream_t st) {
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, st, d_cnt, nb, d_off);
+    ECAL_HIP_TRY(ctx, hipGetLastError());
+    return ECAL_OK;
+}
+
 // the keyframe search's precondition (header comment), for the entry points whose table is on the host
 static int check_kf_time_ascending(ecal_ctx *ctx, const char *who, const double *kf_time, uint32_t n_keyframes) {
     for (uint32_t k = 0; k < n_keyframes; k++) {

@@ -22,19 +22,18 @@
 #pragma clang fp contract(off)
 #include "ecal_solver_state.hpp"
 #include "block_utils.hpp"
+#include "board_nearest.hpp"
+#include "board_block.hpp"
 
 #include <algorithm>
 
 namespace ecal {
 
-constexpr int BI_T = 256;
-constexpr uint32_t BI_BLOCK = ECAL_BOARD_IMAGE_BLOCK, BI_CP = ECAL_BOARD_IMAGE_CP_LDS, BI_KN = BI_CP + 4;
-constexpr uint32_t BI_MAX_LM = 128, BI_MAX_RING = 256, BI_SEG_LDS = 32;
+constexpr uint32_t BI_MAX_RING = 256;
 constexpr uint32_t BI_NTOT = 7;   // words of ecal_board_image_totals
 
 struct BoardArgs {
-    const double *seg_range;   // [n_seg][2]
-    uint32_t n_seg, n_lm, n_cp_total;
+    uint32_t n_lm;
     double x0, y0, bin;
     uint32_t width, height, ring_bins;
     double ring_range, radius;
@@ -46,60 +45,18 @@ struct BoardArgs {
     uint8_t *flag;
 };
 
-__device__ __forceinline__ double bi_load_f64(const uint8_t *p) {
-    double v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-
-// the number of leading elements of the ascending p[0], p[stride], .. (K of them) that are < t (LE: <= t), by one wave: a 64-ary
-// search as wave_lower_bound (block_utils.hpp).  Every lane of the wave calls it with the same arguments.
-template <bool LE>
-__device__ __forceinline__ uint32_t bi_wave_count(const double *p, uint32_t stride, uint32_t K, double t) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t lo = 0, hi = K;
-    while (lo < hi) {
-        const uint32_t step = (hi - lo + 63u) / 64u;
-        const uint32_t idx = lo + lane * step;
-        bool less = false;
-        if (idx < hi) {
-            const double x = p[(size_t) idx * stride];
-            less = LE ? x <= t : x < t;
-        }
-        const uint32_t c = (uint32_t) __popcll(__ballot(less));
-        if (c == 0) {
-            hi = lo;
-        } else {
-            const uint32_t nhi = lo + c * step < hi ? lo + c * step : hi;
-            lo = lo + (c - 1u) * step + 1u;
-            hi = nhi;
-        }
-    }
-    return lo;
-}
-
-// the segment g with range[2 g] <= t <= range[2 g + 1], or -1 (also for a NaN).  The ranges are ascending and disjoint (what
-// ecal_solver_create_from_stream checks); where two of them touch at one time, that time belongs to the EARLIER one: here, in the
-// block's plan below (the first segment whose end is not below the time) and in include/ecal.h.
-__device__ __forceinline__ int bi_segment_of(double t, const double *range, uint32_t n_seg) {
-    uint32_t a = 0, b = n_seg;   // first segment whose end is not below t
-    while (a < b) {
-        const uint32_t m = (a + b) >> 1;
-        if (range[2 * m + 1] < t) a = m + 1; else b = m;
-    }
-    return (a < n_seg && t >= range[2 * a]) ? (int) a : -1;
-}
-
-enum { BI_NONE = 0, BI_STAGED = 1, BI_GLOBAL = 2 };
+// (the block's plan and the per-event pose fetch: board_block.hpp, shared with ecal_reassociate.hip)
 
 template <bool SO3, bool FISHEYE, bool POINTS>
-__global__ __launch_bounds__(BI_T) void board_image_kernel(const uint8_t *__restrict__ rec, uint64_t n_events,
+__global__ __launch_bounds__(BI_T, 2) void board_image_kernel(const uint8_t *__restrict__ rec, uint64_t n_events,
                                                           const double *__restrict__ knots, const uint32_t *__restrict__ knot_off,
                                                           const uint32_t *__restrict__ cp_off, const double *__restrict__ params,
+                                                          const double *__restrict__ seg_range, uint32_t n_seg, uint32_t n_cp_total,
                                                           const double *__restrict__ landmarks, const BoardArgs A) {
+    const BoardSpline S{knots, knot_off, cp_off, params, seg_range, n_seg, n_cp_total};
     extern __shared__ __attribute__((aligned(16))) double dyn[];   // landmarks [n_lm][2] | ring sums [2][n_lm][2] | ring counts [n_lm][2] | ring hist
-    __shared__ double s_q[BI_CP][4], s_t[BI_CP][3], s_kn[BI_KN], s_seg[2 * BI_SEG_LDS];
-    __shared__ uint32_t s_plan[8], s_red[(BI_T / 64) * BI_NTOT];
+    __shared__ BoardBlockLds s_blk;
+    __shared__ uint32_t s_red[(BI_T / 64) * BI_NTOT];
     const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * BI_BLOCK;
     const uint32_t count = (uint32_t) (n_events - base < (uint64_t) BI_BLOCK ? n_events - base : (uint64_t) BI_BLOCK);
@@ -116,52 +73,7 @@ __global__ __launch_bounds__(BI_T) void board_image_kernel(const uint8_t *__rest
         for (uint32_t i = (uint32_t) tid; i < 4 * n_lm; i += BI_T) s_rsum[i] = 0.0;
         for (uint32_t i = (uint32_t) tid; i < 2 * n_lm + n_hist; i += BI_T) s_rcnt[i] = 0u;
     }
-    const bool seg_lds = A.n_seg <= BI_SEG_LDS;
-    if (seg_lds && (uint32_t) tid < 2 * A.n_seg) s_seg[tid] = A.seg_range[tid];
-
-    // The block's plan, once per workgroup.  Wave 0 takes the block's first time, wave 1 its last: the first segment whose end is
-    // not below it, and the span of that time (clamped into the segment) there.
-    if (tid < 128) {
-        const int wv = tid >> 6;
-        const double tq = bi_load_f64(blk + (size_t) (wv ? count - 1u : 0u) * 25);
-        uint32_t g = bi_wave_count<false>(A.seg_range + 1, 2u, A.n_seg, tq);   // ends < tq
-        bool any = g < A.n_seg;
-        if (wv == 1 && (g == A.n_seg || tq < A.seg_range[2 * (size_t) g])) {     // the last time lies behind segment g - 1
-            any = g > 0;
-            g = g > 0 ? g - 1u : 0u;
-        }
-        uint32_t span = 3;
-        if (any) {
-            const double *kn = knots + knot_off[g];
-            const uint32_t ncp = cp_off[g + 1] - cp_off[g];
-            double tc = tq;
-            tc = tc < kn[3] ? kn[3] : tc;
-            tc = tc > kn[ncp] ? kn[ncp] : tc;
-            span = 3u + bi_wave_count<true>(kn + 4, 1u, ncp - 4u, tc);           // the last span whose first knot is <= tc
-        }
-        if ((tid & 63) == 0) {
-            s_plan[4 * wv] = any ? 1u : 0u;
-            s_plan[4 * wv + 1] = g;
-            s_plan[4 * wv + 2] = span;
-        }
-    }
-    __syncthreads();
-    int mode = BI_GLOBAL;
-    const uint32_t g_blk = s_plan[1], span_first = s_plan[2], span_last = s_plan[6];
-    if (!s_plan[0] || !s_plan[4] || s_plan[1] > s_plan[5]) mode = BI_NONE;       // no segment between the block's first and last time
-    else if (s_plan[1] == s_plan[5] && span_last >= span_first && span_last - span_first + 4u <= BI_CP) mode = BI_STAGED;
-    const double *const qall = params + 9, *const tall = params + 9 + 4 * (size_t) A.n_cp_total;
-    double seg_t0 = 0.0, seg_t1 = 0.0;
-    if (mode == BI_STAGED) {
-        const uint32_t n_st = span_last - span_first + 4u, c0 = cp_off[g_blk] + span_first - 3u;
-        const double *kn = knots + knot_off[g_blk] + (span_first - 3u);
-        if ((uint32_t) tid < 4 * n_st) s_q[tid >> 2][tid & 3] = qall[4 * (size_t) c0 + tid];
-        if ((uint32_t) tid < 3 * n_st) s_t[tid / 3][tid % 3] = tall[3 * (size_t) c0 + tid];
-        if ((uint32_t) tid < n_st + 4u) s_kn[tid] = kn[tid];
-        seg_t0 = A.seg_range[2 * (size_t) g_blk];
-        seg_t1 = A.seg_range[2 * (size_t) g_blk + 1];
-    }
-    __syncthreads();
+    const BoardBlockPlan P = board_block_plan(blk, count, S, s_blk);   // (its barriers also publish the ring's LDS)
 
     double pin[9];
     for (int i = 0; i < 9; i++) pin[i] = params[i];
@@ -177,32 +89,7 @@ __global__ __launch_bounds__(BI_T) void board_image_kernel(const uint8_t *__rest
         const uint32_t pol = r[24] ? 1u : 0u;
         tot[0]++;
         double q[4][4], t[4][3], b[4];
-        bool in_time = false;
-        if (mode == BI_STAGED) {
-            in_time = et >= seg_t0 && et <= seg_t1;
-            if (in_time) {
-                uint32_t sp = span_first;
-                while (sp < span_last && s_kn[sp + 1u - (span_first - 3u)] <= et) sp++;
-                spline_basis(s_kn, sp - (span_first - 3u), et, b);
-                const uint32_t j0 = sp - span_first;
-                for (int j = 0; j < 4; j++) {
-                    for (int c = 0; c < 4; c++) q[j][c] = s_q[j0 + j][c];
-                    for (int c = 0; c < 3; c++) t[j][c] = s_t[j0 + j][c];
-                }
-            }
-        } else if (mode == BI_GLOBAL) {
-            const int g = bi_segment_of(et, seg_lds ? s_seg : A.seg_range, A.n_seg);
-            in_time = g >= 0;
-            if (in_time) {
-                const double *kn = knots + knot_off[g];
-                const uint32_t sp = spline_find_span(kn, cp_off[g + 1] - cp_off[g], et), c0 = cp_off[g] + sp - 3u;
-                spline_basis(kn, sp, et, b);
-                for (int j = 0; j < 4; j++) {
-                    for (int c = 0; c < 4; c++) q[j][c] = qall[4 * (size_t) (c0 + j) + c];
-                    for (int c = 0; c < 3; c++) t[j][c] = tall[3 * (size_t) (c0 + j) + c];
-                }
-            }
-        }
+        const bool in_time = board_event_pose(P, S, s_blk, et, b, q, t);
         double Xw[2] = {0.0, 0.0};
         bool ok = false;
         if (in_time) {
@@ -233,16 +120,8 @@ __global__ __launch_bounds__(BI_T) void board_image_kernel(const uint8_t *__rest
             tot[3]++;
         }
         if (ring) {
-            double best = __builtin_inf();
-            uint32_t bi = 0;
-            for (uint32_t i = 0; i < n_lm; i++) {
-                const double dx = Xw[0] - s_lm[2 * i], dy = Xw[1] - s_lm[2 * i + 1];
-                const double d2 = dx * dx + dy * dy;
-                if (d2 < best) {
-                    best = d2;
-                    bi = i;
-                }
-            }
+            double best;
+            const uint32_t bi = board_nearest(s_lm, n_lm, Xw[0], Xw[1], &best);
             const double d = __dsqrt_rn(best) - A.radius;
             if (fabs(d) < A.ring_range) {
                 double hb = floor(__ddiv_rn(__dmul_rn(__dadd_rn(d, A.ring_range), (double) A.ring_bins), ring_den));
@@ -351,7 +230,7 @@ static int board_launch(ecal_solver *s, const double *d_params, const uint8_t *d
     const uint32_t nb = (uint32_t) ((n_events + BI_BLOCK - 1) / BI_BLOCK);
 #define ECAL_BI_LAUNCH(SO3_, FISH_)                                                                                                \
     hipLaunchKernelGGL((board_image_kernel<SO3_, FISH_, POINTS>), dim3(nb), dim3(BI_T), lds, st, d_events, n_events, s->d_knots,       \
-                       s->d_knot_off, s->d_cp_off, d_params, s->d_landmarks, A)
+                       s->d_knot_off, s->d_cp_off, d_params, s->d_seg_range, s->n_seg, s->n_cp, s->d_landmarks, A)
     if (s->use_so3) {
         if (s->fisheye) ECAL_BI_LAUNCH(true, true); else ECAL_BI_LAUNCH(true, false);
     } else {
@@ -389,10 +268,7 @@ extern "C" int ecal_solver_board_image_dev(ecal_solver *s, const double *d_param
         ECAL_HIP_TRY(ctx, hipMemsetAsync(d_ring_hist, 0, (size_t) s->n_lm * opt.ring_bins * sizeof(uint64_t), st));
     if (!n_events) return ECAL_OK;
     BoardArgs A{};
-    A.seg_range = s->d_seg_range;
-    A.n_seg = s->n_seg;
     A.n_lm = s->n_lm;
-    A.n_cp_total = s->n_cp;
     A.x0 = opt.x0;
     A.y0 = opt.y0;
     A.bin = opt.bin;
@@ -426,10 +302,7 @@ extern "C" int ecal_solver_board_points_dev(ecal_solver *s, const double *d_para
     if (!n_events) return ECAL_OK;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     BoardArgs A{};
-    A.seg_range = s->d_seg_range;
-    A.n_seg = s->n_seg;
     A.n_lm = s->n_lm;
-    A.n_cp_total = s->n_cp;
     A.xw = d_xw;
     A.flag = d_flag;
     return board_launch<true>(s, d_params, d_events, n_events, A, 0, (hipStream_t) stream);

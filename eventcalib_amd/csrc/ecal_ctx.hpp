@@ -114,6 +114,8 @@ struct ecal_ctx {
     ecal_devbuf as_host;         // staging of ecal_associate
     ecal_devbuf report_scratch;  // ecal_solver_report: the outputs' device images and the keyframe table
     ecal_devbuf board_scratch;   // ecal_solver_board_image / _board_points: the outputs' device images
+    ecal_devbuf reassoc_scratch;   // ecal_solver_reassociate_dev: one verdict byte per event, per-block counts / offsets
+    ecal_devbuf reassoc_records;   // ecal_solver_reassociate / _create_reassociated: the record arrays, the count, the totals
     ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks
     hipStream_t copy_stream = nullptr;  // uploads of the double-buffered ingest
     ecal_pinned pass_pinned;            // ecal_detect_pass: window times in, packed verdicts out; the keyframe search: counters, report ring, handed-over frame
@@ -181,6 +183,8 @@ int ecal_extract_for_ctx(ecal_ctx *ctx, const double *d_xy, const uint32_t *d_se
                          uint32_t need_clusters, double radius_threshold, int fit_circle, uint32_t knn_num, uint32_t *d_win_info,
                          uint32_t *d_cand_pair, double *d_cand_xyr, int32_t *d_kept_labels, uint32_t *d_rep, void *stream,
                          const ecal_packed_points *pk = nullptr);
+// exclusive scan of nb per-block counts by one workgroup, off[nb] = the total (ecal_associate.hip: scan_blocks_kernel)
+int ecal_scan_blocks(ecal_ctx *ctx, const uint32_t *d_cnt, uint32_t nb, uint32_t *d_off, hipStream_t st);
 // reference element order: the per-pixel bucket table of the hot-path slicer, built on first use (ecal_events.hip)
 int ecal_ensure_bucket_table(ecal_ctx *ctx, hipStream_t st);
 // tail scheduling (see ecal_ctx::tail_seen): slots of the stages' lists, and "may this call run lean?"

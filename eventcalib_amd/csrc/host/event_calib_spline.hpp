@@ -70,6 +70,16 @@ public:
         }
     };
 
+    // One opt-in refinement round (ecal_solver_create_reassociated): every event of the stream whose board point at the current
+    // solution lies within the ring tolerance of a circle's rim becomes a residual, and the solve is repeated from that solution
+    // on those records.  refine() has one entry per round; empty unless the constructor is asked for rounds.  Single process.
+    struct RefineRound {
+        ecal_reassociate_totals totals{};
+        size_t residuals = 0;
+        int iterations = 0;
+        double initial_cost = 0, final_cost = 0;
+    };
+
     // rotation matrix (row-major) -> quaternion xyzw, Eigen::Quaterniond(Matrix3d)'s branch structure
     static void quaternionFromMatrix(const double *m, double *q) {
         double t = m[0] + m[4] + m[8];
@@ -115,10 +125,11 @@ public:
 
     EventCalibSpline(std::vector<Frame> frames, EventContainer::Ptr eventContainer, CirclePatternParameters::Ptr pattern, bool useSO3,
                      double motionTimeStep, const double K[4], const double distCoeffs[5], int maxIterations = 50,
-                     bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false)
+                     bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false,
+                     int refineRounds = 0, double refineRingTol = 0.0 /* board units; <= 0: the Huber width */)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
           fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations),
-          wantBoardImage_(wantBoardImage) {
+          wantBoardImage_(wantBoardImage), refineRounds_(refineRounds > 0 ? refineRounds : 0), refineRingTol_(refineRingTol) {
         if (reportOptions) {
             report_.options = *reportOptions;
             wantReport_ = true;
@@ -177,6 +188,7 @@ public:
     const Summary &summary() const { return summary_; }
     const Report &report() const { return report_; }
     const BoardImage &boardImage() const { return boardImage_; }
+    const std::vector<RefineRound> &refine() const { return refine_; }
     size_t splineNum() const { return segments_.size(); }
 
     int time2splineIdx(double t) const {
@@ -262,11 +274,12 @@ private:
                                                 5 * motionTimeStep_, 5.0, &prob, &solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_create_from_stream: ") + ecal_last_error(ctx));
         (void) n_events;
-        if (!wantBoardImage_) eventContainer_->release();  // eventContainer_->container.clear() (:194); the board image reads the stream once more
+        const bool keepStream = wantBoardImage_ || refineRounds_ > 0;   // the board image and the refinement read the stream once more
+        if (!keepStream) eventContainer_->release();  // eventContainer_->container.clear() (:194)
         summary_.residuals = ecal_solver_num_residuals(solver);
         if (summary_.residuals == 0) {
             ecal_solver_destroy(solver);
-            if (wantBoardImage_) eventContainer_->release();
+            if (keepStream) eventContainer_->release();
             return false;
         }
         std::vector<double> x(ecal_solver_param_size(solver));
@@ -278,6 +291,31 @@ private:
         opt.max_num_iterations = maxIterations_;
         ecal_lm_summary sm;
         rc = ecal_solver_solve(solver, x.data(), &opt, &sm);
+        // opt-in: look at ALL events through the solution, solve on the ones that fit (the reference's TODO at :192)
+        for (int round = 0; rc == ECAL_OK && round < refineRounds_; round++) {
+            RefineRound r;
+            ecal_solver *next = nullptr;
+            rc = ecal_solver_create_reassociated(solver, x.data(), es, refineRingTol_, &next, &r.totals);
+            if (rc != ECAL_OK) {
+                ecal_solver_destroy(solver);
+                eventContainer_->release();
+                throw std::runtime_error(std::string("ecal_solver_create_reassociated: ") + ecal_last_error(ctx));
+            }
+            ecal_solver_destroy(solver);
+            solver = next;
+            r.residuals = ecal_solver_num_residuals(solver);
+            if (r.residuals == 0) {
+                ecal_solver_destroy(solver);
+                eventContainer_->release();
+                throw std::runtime_error("refine round: no event within the ring tolerance");
+            }
+            ecal_lm_summary rs;
+            rc = ecal_solver_solve(solver, x.data(), &opt, &rs);
+            r.iterations = rs.iterations;
+            r.initial_cost = rs.initial_cost;
+            r.final_cost = rs.final_cost;
+            refine_.push_back(r);
+        }
         if (rc == ECAL_OK && wantReport_) {   // at the solution, on the records the solve ran on
             Report &r = report_;
             const ecal_report_options &o = r.options;
@@ -294,7 +332,7 @@ private:
             r.valid = rc == ECAL_OK;
             if (rc != ECAL_OK) {
                 ecal_solver_destroy(solver);
-                if (wantBoardImage_) eventContainer_->release();
+                if (keepStream) eventContainer_->release();
                 throw std::runtime_error(std::string("ecal_solver_report: ") + ecal_last_error(ctx));
             }
         }
@@ -312,7 +350,7 @@ private:
                 throw std::runtime_error(std::string("ecal_solver_board_image: ") + ecal_last_error(ctx));
             }
         }
-        if (wantBoardImage_) eventContainer_->release();
+        if (keepStream) eventContainer_->release();
         ecal_solver_destroy(solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_solve: ") + ecal_last_error(ctx));
         std::copy(x.begin(), x.begin() + 9, intrinsics_);
@@ -357,6 +395,9 @@ private:
     bool wantReport_ = false;
     BoardImage boardImage_;
     bool wantBoardImage_ = false;
+    int refineRounds_ = 0;
+    double refineRingTol_ = 0.0;
+    std::vector<RefineRound> refine_;
 };
 
 }  // namespace opengv2

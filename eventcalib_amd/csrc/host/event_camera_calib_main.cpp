@@ -176,11 +176,23 @@ int main(int argc, char **argv) {
     // (ecal_solver_board_image), written to saveDir/board_image.png and saveDir/BoardImage.txt; absent or 0: nothing changes
     int wantBoardImage = 0;
     fsSettings["BoardImage"] >> wantBoardImage;
+    // RefineRounds / RefineRingTol (keys of this build, optional): N rounds of re-association through the solution — every event of
+    // the stream within RefineRingTol board units (absent or <= 0: the Huber width) of a circle's rim becomes a residual — each
+    // followed by a solve from that solution, one `refine round k ...` line per round; absent or 0: nothing changes
+    int refineRounds = 0;
+    fsSettings["RefineRounds"] >> refineRounds;
+    double refineRingTol = 0.0;
+    fsSettings["RefineRingTol"] >> refineRingTol;
     EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
-                            wantBoardImage != 0);
+                            wantBoardImage != 0, refineRounds, refineRingTol);
     const double *x = spline.intrinsics();
     std::printf("refined %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g residuals %zu iterations %d splines %zu\n", x[0], x[1], x[2], x[3],
                 x[4], x[5], x[6], x[7], x[8], spline.summary().residuals, spline.summary().iterations, spline.splineNum());
+    for (size_t k = 0; k < spline.refine().size(); k++) {
+        const EventCalibSpline::RefineRound &r = spline.refine()[k];
+        std::printf("refine round %zu events %llu kept %llu cost %.9g -> %.9g iterations %d\n", k, (unsigned long long) r.totals.n_events,
+                    (unsigned long long) r.totals.n_kept, r.initial_cost, r.final_cost, r.iterations);
+    }
     stage("spline_fit_association_lm");
     spline.saveKeyFrameTrajectoryTUM(std::string(argv[3]) + "/TrajectoryByEvent.txt");   // :212
     stage("save_trajectory");

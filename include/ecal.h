@@ -799,6 +799,37 @@ int ecal_solver_board_points_dev(ecal_solver *s, const double *d_params, const u
 int ecal_solver_board_image(ecal_solver *s, const double *params, const ecal_stream *es, const ecal_board_image_options *opt,
                             uint32_t *img, ecal_board_image_totals *totals, ecal_ring_stats *ring_stats, uint64_t *ring_hist);
 int ecal_solver_board_points(ecal_solver *s, const double *params, const ecal_stream *es, double *xw, uint8_t *flag);
+/* Re-association through the solved spline: the association in the BOARD frame, at the current solution.  The keyframe
+ * association above keeps an event only near a keyframe's time and near the ring that keyframe's circle had at its instant; this
+ * pass makes, per event of the packed, time-sorted stream, exactly the board image's decisions — segment (ranges inclusive, a
+ * time two segments share to the earlier, a NaN to none: n_outside_time), board point (depth not finite or <= 0: n_behind),
+ * nearest landmark (squared distance in the plane, ties to the lower index; at most 128 landmarks: ECAL_ERR_RANGE),
+ * d = |Xw - lm| - circle_radius — and KEEPS the event as a residual of that landmark when |d| < ring_tol (else n_off_ring),
+ * wherever it sits relative to a keyframe.  Outputs in event order = (segment, time) order, what ecal_solver_create_dev takes:
+ * d_obs[j] / d_time[j] = the event's own bytes, d_lm_id[j], d_seg_id[j]; *d_count = how many (device; room for n_events records
+ * each).  ring_tol: board units, <= 0 = the solver's huber_a (the convention of ecal_report_options.outlier_thresh), not finite =
+ * ECAL_ERR_INVALID.  n_events = n_outside_time + n_behind + n_off_ring + n_kept and n_kept = *d_count; every count is an integer
+ * atomic.  The call zeroes *d_count and the totals itself on `stream` and does not synchronise with the host; n_events == 0 is
+ * valid; more than 2^32-1 events is ECAL_ERR_RANGE.  Three launches, no waiting between workgroups: a verdict byte per event and
+ * a count per block, the scan of the counts, the ordered copy (scratch from the context: one byte per event + the block tables).
+ * Rank-local and single-process: the multi-GPU solves (ecal_lm_options.distributed) do not use it. */
+typedef struct ecal_reassociate_totals {
+    uint64_t n_events, n_outside_time, n_behind, n_off_ring, n_kept;
+} ecal_reassociate_totals;
+int ecal_solver_reassociate_dev(ecal_solver *s, const double *d_params, const uint8_t *d_events, uint64_t n_events,
+                                double ring_tol, double *d_obs, double *d_time, uint32_t *d_lm_id, uint32_t *d_seg_id,
+                                uint32_t *d_count, ecal_reassociate_totals *d_totals /*or NULL*/, void *stream);
+/* host-buffer form over a resident ecal_stream, synchronous: obs / time / lm_id / seg_id need room for `capacity` records,
+ * *count = records found (ECAL_ERR_RANGE if more than capacity: nothing is copied then, as ecal_associate) */
+int ecal_solver_reassociate(ecal_solver *s, const double *params, const ecal_stream *es, double ring_tol, uint64_t capacity,
+                            double *obs, double *time, uint32_t *lm_id, uint32_t *seg_id, uint64_t *count,
+                            ecal_reassociate_totals *totals /*or NULL*/);
+/* ... and a NEW solver built in place on those records (ecal_solver_create_dev), with the layout of s — segments, knots,
+ * landmarks, radius, Huber width, rotation variant, camera model — from the host copies s keeps: nothing proportional to the
+ * events crosses PCIe (the count and the totals come back).  s is left untouched; both solvers are destroyed independently.
+ * Scratch from the context: 33 bytes per event plus the block tables. */
+int ecal_solver_create_reassociated(ecal_solver *s, const double *params, const ecal_stream *es, double ring_tol,
+                                    ecal_solver **out, ecal_reassociate_totals *totals /*or NULL*/);
 void ecal_lm_default_options(ecal_lm_options *opt);
 int ecal_solver_solve(ecal_solver *s, double *params /*in: start, out: solution*/, const ecal_lm_options *opt,
                       ecal_lm_summary *summary);
