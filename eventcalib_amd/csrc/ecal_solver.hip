@@ -766,12 +766,6 @@ extern "C" int ecal_solver_create_dev(ecal_ctx *ctx, const ecal_spline_problem *
 
 extern "C" uint64_t ecal_solver_num_residuals(const ecal_solver *s) { return s ? s->n_res : 0; }
 
-static int solver_evaluate_dev(ecal_solver *s, const double *d_params, int with_jacobian, double *d_accum, void *stream,
-                               const NeProgress *d_prog, uint32_t epoch);
-extern "C" int ecal_solver_evaluate_dev(ecal_solver *s, const double *d_params, int with_jacobian, double *d_accum,
-                                        void *stream) {
-    return solver_evaluate_dev(s, d_params, with_jacobian, d_accum, stream, nullptr, 0);
-}
 // d_prog (with_jacobian only): the streamed form — the records reach the host's pinned buffer group by group (NeProgress)
 static int solver_evaluate_dev(ecal_solver *s, const double *d_params, int with_jacobian, double *d_accum, void *stream,
                                const NeProgress *d_prog, uint32_t epoch) {
@@ -805,6 +799,10 @@ static int solver_evaluate_dev(ecal_solver *s, const double *d_params, int with_
         ECAL_HIP_TRY(ctx, hipGetLastError());
     }
     return ECAL_OK;
+}
+extern "C" int ecal_solver_evaluate_dev(ecal_solver *s, const double *d_params, int with_jacobian, double *d_accum,
+                                        void *stream) {
+    return solver_evaluate_dev(s, d_params, with_jacobian, d_accum, stream, nullptr, 0);
 }
 
 extern "C" int ecal_residuals_dev(ecal_solver *s, const double *d_params, double *d_r, double *d_J, uint32_t *d_cp0, void *stream) {
@@ -881,24 +879,235 @@ extern "C" int ecal_solver_evaluate(ecal_solver *s, const double *params, int wi
 // Host side: block-banded arrow system and Levenberg-Marquardt (Ceres 1.x trust-region loop restated)
 // ------------------------------------------------------------------------------------------------
 namespace {
-
 #include "arrow_host.hpp"
+#include "lm_loop.hpp"
 
-// x (+) delta: intrinsics and translations add, quaternions take exp(delta) (x) q
-void plus(const double *x, const std::vector<double> &d, uint32_t n_cp, bool so3, double *out, uint32_t c_lo = 0, uint32_t c_hi = 0xFFFFFFFFu) {
-    const size_t nc = 6 * (size_t) n_cp;
-    if (c_lo == 0)
-        for (int i = 0; i < 9; i++) out[i] = x[i] + d[nc + i];
-    for (uint32_t c = c_lo; c < std::min(c_hi, n_cp); c++) {
-        if (so3)
-            so3_plus(x + 9 + 4 * (size_t) c, &d[6 * (size_t) c], out + 9 + 4 * (size_t) c);
-        else
-            quaternion_plus(x + 9 + 4 * (size_t) c, &d[6 * (size_t) c], out + 9 + 4 * (size_t) c);
-        for (int k = 0; k < 3; k++)
-            out[9 + 4 * (size_t) n_cp + 3 * (size_t) c + k] = x[9 + 4 * (size_t) n_cp + 3 * (size_t) c + k] + d[6 * (size_t) c + 3 + k];
+// a NULL all-reduce is a rank-local solve, whether or not the context has joined a communicator: collectives are the
+// caller's explicit choice (opt.allreduce = ecal_comm_allreduce, opt.allreduce_user = ctx, rank / world_size set)
+int solve_validate(const ecal_solver *s, const ecal_lm_options &opt, RankShare &share) {
+    ecal_ctx *ctx = s->ctx;
+    if (opt.allreduce == ecal_comm_allreduce && (opt.allreduce_user != ctx || opt.rank != ctx->comm_rank || opt.world_size != ctx->comm_size)) {
+        ctx->last_error = "ecal_solver_solve: ecal_comm_allreduce needs allreduce_user = the solver's context and its rank / world_size";
+        return ECAL_ERR_INVALID;
     }
+    share.mode = opt.allreduce && (opt.distributed == 1 || opt.distributed == 2) ? opt.distributed : 0;
+    if (!share.mode) return ECAL_OK;
+    share.world = std::max(1, opt.world_size), share.rank = opt.rank;
+    if (share.rank < 0 || share.rank >= share.world || share.world > 1024) return ECAL_ERR_INVALID;
+    if (share.mode == 2 && (s->n_seg != 1 || (uint32_t) (7 * share.world) > s->n_cp)) {
+        ctx->last_error = "time-sharded solve: one spline segment with at least 7 control points per rank";
+        return ECAL_ERR_INVALID;
+    }
+    if (share.mode == 2) arrow_partition(s->n_cp, share.world, share.ts_first, share.ts_num);
+    return ECAL_OK;
 }
-
+// the sharded modes' small exchange buffers (device, pinned host), gone at the end of the solve whichever way it ends
+struct ExchangeBuffers {
+    double *d = nullptr, *h = nullptr;
+    int alloc(ecal_ctx *ctx, size_t n) {
+        ECAL_HIP_TRY(ctx, hipMalloc((void **) &d, n * sizeof(double)));
+        return hipHostMalloc((void **) &h, n * sizeof(double), hipHostMallocDefault) == hipSuccess ? ECAL_OK : ECAL_ERR_NOMEM;
+    }
+    ~ExchangeBuffers() { (void) hipFree(d), (void) hipHostFree(h); }   // (a null pointer is fine with both)
+};
+// The HIP side of the loop's seam (LmDevice) for one ecal_solver_solve
+struct SolveDevice {
+    ecal_solver *const s;
+    const ecal_lm_options &opt;
+    const RankShare &share;
+    ecal_ctx *const ctx = s->ctx;
+    const hipStream_t st = ctx->stream;
+    const size_t np = s->n_params(), na = s->n_accum();
+    ExchangeBuffers small;
+    HostPool *pool = nullptr;   // (the solver keeps the threads: starting fifteen of them costs as much as a tenth of an iteration each)
+    int n_parts = 1;
+    double t_eval = 0, t_pool = 0, t_tail = 0, tl_run = 0, tl_sync = 0;
+    std::vector<double> tl_arrive, tl_done;   // ECAL_TRACE=solver: the last streamed evaluation's timeline (seconds from its start)
+    const uint32_t epoch_at_start = s->stream_epoch;
+    // pinned staging (the solver keeps it): the 3 MB buffer comes back every evaluation; the sharded modes' exchange buffers
+    int alloc() {
+        if (!s->h_acc) ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_acc, na * sizeof(double), hipHostMallocDefault));
+        if (!s->h_x) ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_x, np * sizeof(double), hipHostMallocDefault));
+        const size_t W = (size_t) share.world;
+        return share.mode ? small.alloc(ctx, std::max<size_t>(128 + W, share.mode == 2 ? std::max<size_t>(TS_G * W, ACC_HEAD + 3 * ACC_PER_CP * (W - 1)) : 0)) : ECAL_OK;
+    }
+    bool upload(const double *x) {
+        memcpy(s->h_x, x, np * sizeof(double));
+        return hipMemcpyAsync(s->d_params, s->h_x, np * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    int synchronize(hipError_t e = hipSuccess) {   // (e: of the call before it)
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) ctx->last_error = std::string("solver evaluate: ") + hipGetErrorString(e);
+        return e == hipSuccess ? ECAL_OK : ECAL_ERR_HIP;
+    }
+    // time shards: the head and the separators' records (3 control points per cut) are what two ranks both add to
+    bool copy_shared_records(bool to_small) {
+        size_t at = 0;
+        for (int c = -1; c + 1 < share.world; c++) {
+            double *a = c < 0 ? s->d_accum : s->d_accum + ACC_HEAD + ACC_PER_CP * (size_t) (share.ts_first[c] + share.ts_num[c]), *b = small.d + at;
+            const size_t n = c < 0 ? ACC_HEAD : 3 * ACC_PER_CP;
+            if (hipMemcpyAsync(to_small ? b : a, to_small ? a : b, n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+            at += n;
+        }
+        return true;
+    }
+    int evaluate(const double *xp, int with_jac, double *cost) {
+        const auto te = lm_now();
+        if (!upload(xp)) return ECAL_ERR_HIP;
+        if (int rc = ecal_solver_evaluate_dev(s, s->d_params, with_jac, s->d_accum, st)) return rc;
+        const size_t n = with_jac ? na : 1;
+        if (opt.allreduce && share.mode == 2 && with_jac) {
+            if (!copy_shared_records(true)) return ECAL_ERR_HIP;
+            if (opt.allreduce(opt.allreduce_user, small.d, ACC_HEAD + 3 * ACC_PER_CP * (size_t) (share.world - 1), st) != 0) return ECAL_ERR_HIP;
+            if (!copy_shared_records(false)) return ECAL_ERR_HIP;
+        } else if (opt.allreduce) {  // per-GPU partials summed over ranks (RCCL all-reduce supplied by the caller)
+            // distributed segments: only the head (cost, intrinsics gradient and block) is shared between ranks
+            if (opt.allreduce(opt.allreduce_user, s->d_accum, share.mode ? std::min(n, (size_t) ACC_HEAD) : n, st) != 0) return ECAL_ERR_HIP;
+        }
+        if (int rc = synchronize(hipMemcpyAsync(s->h_acc, s->d_accum, n * sizeof(double), hipMemcpyDeviceToHost, st))) return rc;
+        *cost = s->h_acc[0], t_eval += lm_secs(te, lm_now());
+        return ECAL_OK;
+    }
+    // sum v[0..n) over ranks in place, through the device buffer d and the pinned buffer h
+    bool reduce_through(double *v, size_t n, double *d, double *h) {
+        memcpy(h, v, n * sizeof(double));
+        if (hipMemcpyAsync(d, h, n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+        if (opt.allreduce(opt.allreduce_user, d, n, st) != 0) return false;
+        if (hipMemcpyAsync(h, d, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        memcpy(v, h, n * sizeof(double));
+        return true;
+    }
+    bool reduce_small(double *v, size_t n) { return reduce_through(v, n, small.d, small.h); }
+    // time shards: the ranks' parts of the solution summed into the whole (9 + 7 n_cp doubles, through the parameter buffers)
+    bool gather(std::vector<double> &x) {
+        x = share.gather_part(x, s->n_cp);
+        return reduce_through(x.data(), np, s->d_params, s->h_x);
+    }
+    // one rank, a long spline: the parts of the host's linear solve and the threads for them
+    void acquire_pool() {
+        n_parts = arrow_parts_for(s->n_cp);
+        if ((uint32_t) (7 * n_parts) > s->n_cp) n_parts = 1;
+        if (n_parts <= 1) return;
+        const auto tp = lm_now();
+        const int workers = std::max(0, std::min(n_parts, host_usable_cpus()) - 1);   // (affinity ∩ cgroup quota ÷ the node's ranks — not hardware_concurrency())
+        if (!s->host_pool || s->host_pool_workers != workers) {
+            try {
+                s->host_pool = std::shared_ptr<void>(new HostPool(workers), [](void *q) { delete static_cast<HostPool *>(q); });
+                s->host_pool_workers = workers;
+            } catch (...) {   // no threads to be had: the sequential routines
+                s->host_pool.reset();
+                s->host_pool_workers = -1, n_parts = 1;
+            }
+        }
+        pool = static_cast<HostPool *>(s->host_pool.get());
+        t_pool = lm_secs(tp, lm_now());
+    }
+    // the streamed evaluation's progress block (NeProgress) for the host's partition into n_parts groups; *ok: there is a stream to use
+    int setup_stream(bool *ok) {
+        *ok = !opt.allreduce && pool && n_parts > 1 && !share.mode && n_parts <= NE_MAX_GROUPS && !ctx->sw.solver_no_stream && s->n_chunks > 0;
+        if (!*ok) return ECAL_OK;
+        NeProgress &pg = s->prog;
+        if (pg.n_groups == (uint32_t) n_parts) {
+            // the kernel restores the groups' counters itself as it finishes each group — unless an earlier evaluation on this
+            // solver stopped half way (an error, a stream that failed to deliver): a solve starts from the full counts whatever
+            // the last one left behind (128 words; nothing of this solver is in flight here)
+            ECAL_HIP_TRY(ctx, hipMemcpyAsync(s->d_left, pg.init, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            return ECAL_OK;
+        }
+        // first solve with this partition: the groups' chunk counts, the buffers
+        std::vector<uint32_t> part_first, part_num;
+        arrow_partition_stream(s->n_cp, n_parts, part_first, part_num);
+        std::vector<Chunk> ch(s->n_chunks);
+        ECAL_HIP_TRY(ctx, hipMemcpy(ch.data(), s->d_chunks, ch.size() * sizeof(Chunk), hipMemcpyDeviceToHost));
+        memset(&pg, 0, sizeof(pg));   // (n_groups = 0 until the last step below has succeeded: a failed set-up is redone at the next solve)
+        pg.n_cp = s->n_cp;
+        for (int g = 0; g < n_parts; g++) pg.cut[g] = part_first[g];
+        pg.cut[n_parts] = s->n_cp;
+        for (const Chunk &c : ch) {
+            const uint32_t sg = s->cp_off[c.seg] + c.span;
+            uint32_t g = 0;
+            while (g + 1 < (uint32_t) n_parts && pg.cut[g + 1] <= sg) g++;
+            pg.init[g]++;
+        }
+        for (int b = 0; b + 1 < n_parts; b++) pg.init[NE_MAX_GROUPS + b] = (pg.init[b] ? 1u : 0u) + (pg.init[b + 1] ? 1u : 0u);
+        if (!s->h_flag) {
+            ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_flag, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipHostMallocDefault));
+            memset(s->h_flag, 0, 2 * NE_MAX_GROUPS * sizeof(uint32_t));
+        }
+        if (!s->d_left) ECAL_HIP_TRY(ctx, hipMalloc((void **) &s->d_left, 2 * NE_MAX_GROUPS * sizeof(uint32_t)));
+        if (!s->d_prog) ECAL_HIP_TRY(ctx, hipMalloc((void **) &s->d_prog, sizeof(NeProgress)));
+        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
+        ECAL_HIP_TRY(ctx, hipMemcpy(s->d_left, pg.init, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipMemcpyHostToDevice));
+        pg.left = s->d_left;
+        ECAL_HIP_TRY(ctx, hipHostGetDevicePointer((void **) &pg.host_acc, s->h_acc, 0));
+        ECAL_HIP_TRY(ctx, hipHostGetDevicePointer((void **) &pg.host_flag, s->h_flag, 0));
+        NeProgress ready = pg;
+        ready.n_groups = (uint32_t) n_parts;
+        ECAL_HIP_TRY(ctx, hipMemcpy(s->d_prog, &ready, sizeof(ready), hipMemcpyHostToDevice));
+        pg = ready;
+        return ECAL_OK;
+    }
+    int evaluate_streamed(LmStreamJob &job) {
+        const auto te = lm_now();
+        const NeProgress &pg = s->prog;
+        const int P = n_parts;
+        double *const acc = s->h_acc;
+        ArrowSystem &An = *job.An;
+        if (!upload(job.x)) return ECAL_ERR_HIP;
+        const uint32_t epoch = ++s->stream_epoch;
+        // records that no chunk touches never arrive: they are zero
+        for (int g = 0; g < P; g++) {
+            if (!pg.init[g]) memset(acc + ACC_HEAD + ACC_PER_CP * (size_t) pg.cut[g], 0,
+                                    ACC_PER_CP * (size_t) ((g + 1 < P ? pg.cut[g + 1] - 3 : pg.cut[g + 1]) - pg.cut[g]) * sizeof(double));
+            if (g + 1 < P && !pg.init[NE_MAX_GROUPS + g]) memset(acc + ACC_HEAD + ACC_PER_CP * (size_t) (pg.cut[g + 1] - 3), 0, 3 * ACC_PER_CP * sizeof(double));
+        }
+        if (int rc = solver_evaluate_dev(s, s->d_params, 1, s->d_accum, st, s->d_prog, epoch)) return rc;
+        if (hipMemcpyAsync(acc, s->d_accum, ACC_HEAD * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return ECAL_ERR_HIP;
+        if (job.after_launch) (*job.after_launch)();
+        unpack_alloc(s->n_cp, An);
+        if (job.factor) arrow_parts_setup(An.nc, P, *job.ws, *job.parts, true);
+        job.reduced_ok = false;
+        const bool trace_ev = ctx->sw.solver_trace;
+        tl_arrive.assign(P + 1, 0.0), tl_done.assign(P + 1, 0.0);
+        // the host tasks (arrow_host.hpp: an interior per task as its records arrive, the separators behind them)
+        const StreamedSource src{pg.init, pg.cut, s->h_flag, epoch, [&]() -> bool { return hipStreamQuery(st) != hipErrorNotReady; }};
+        const bool delivered = arrow_streamed_tasks(pool, P, src, acc, An, job.factor, job.r_fact, job.scale, job.dd_next, opt.min_lm_diagonal,
+                                                    opt.max_lm_diagonal, *job.ws, *job.parts, &job.reduced_ok, trace_ev ? tl_arrive.data() : nullptr,
+                                                    trace_ev ? tl_done.data() : nullptr, te);
+        tl_run = lm_secs(te, lm_now());
+        if (int rc = synchronize()) return rc;
+        const auto tt = lm_now();
+        job.streamed = delivered;
+        if (!delivered) {
+            if (hipMemcpy(acc, s->d_accum, na * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return ECAL_ERR_HIP;
+            unpack(acc, s->n_cp, An);
+        } else {
+            unpack_head(acc, An);
+            for (int p = 0; p + 1 < P && !job.factor; p++) unpack_rows(acc, An, pg.cut[p + 1] - 3, pg.cut[p + 1]);
+        }
+        job.cost = acc[0];
+        tl_sync = lm_secs(te, tt), t_tail += lm_secs(tt, lm_now()), t_eval += lm_secs(te, lm_now());
+        return ECAL_OK;
+    }
+    // ecal_debug_solver_last_solve's words and the ECAL_TRACE=solver lines
+    void report(const ecal_lm_summary &S, const LmCounters &K) const {
+        const uint32_t words[7] = {(uint32_t) n_parts, s->stream_epoch - epoch_at_start, (uint32_t) K.n_prefactored, pool ? (uint32_t) pool->workers() : 0u,
+                                   K.stream_ok ? 1u : 0u, (uint32_t) S.iterations, (uint32_t) (share.mode != 0) | (share.mode == 2 ? 2u : 0u)};
+        memcpy(s->last_solve, words, sizeof(words));
+        if (!ctx->sw.solver_trace) return;
+        fprintf(stderr, "ecal_solver_solve: total %.4f s | evaluate %.4f | linear solve %.4f (%d parts) | unpack %.4f | pool %.4f | streamed evaluations: "
+                        "%u, behind the kernel %.4f, %d of %d linear solves found their interiors factorised\n", S.seconds,
+                t_eval, S.seconds_linear_solve, n_parts, K.t_unpack, t_pool, s->stream_epoch, t_tail, K.n_prefactored, S.iterations);
+        fprintf(stderr, "  host items, ms over the solve: LM diagonal %.3f | factorise / finish %.3f | scaling + quadratic forms %.3f | plus %.3f | "
+                        "verdict, norms, swap / unpack, gradient norm %.3f | of the finishes: corner %.3f, back-substitution %.3f\n", 1e3 * K.t_dd, 1e3 * K.t_fin,
+                1e3 * K.t_quad, 1e3 * K.t_plus, 1e3 * K.t_book, 1e3 * K.t_fin_end, 1e3 * K.t_fin_back);
+        if (tl_arrive.empty()) return;
+        fprintf(stderr, "  last streamed evaluation, ms from its start: interiors arrived / factorised");
+        for (size_t p = 0; p + 1 < tl_arrive.size(); p++) fprintf(stderr, " %.2f/%.2f", 1e3 * tl_arrive[p], 1e3 * tl_done[p]);
+        fprintf(stderr, " | separators done %.2f | tasks joined %.2f | stream synchronised %.2f\n", 1e3 * tl_done.back(), 1e3 * tl_run, 1e3 * tl_sync);
+    }
+};
 }  // namespace
 
 extern "C" void ecal_lm_default_options(ecal_lm_options *o) {
@@ -926,578 +1135,26 @@ extern "C" int ecal_solver_solve(ecal_solver *s, double *params, const ecal_lm_o
     if (!s || !params) return ECAL_ERR_INVALID;
     ecal_lm_options opt;
     if (opt_in) opt = *opt_in; else ecal_lm_default_options(&opt);
-    ecal_ctx *ctx = s->ctx;
-    // a NULL all-reduce is a rank-local solve, whether or not the context has joined a communicator: collectives are the
-    // caller's explicit choice (opt.allreduce = ecal_comm_allreduce, opt.allreduce_user = ctx, rank / world_size set)
-    if (opt.allreduce == ecal_comm_allreduce && (opt.allreduce_user != ctx || opt.rank != ctx->comm_rank || opt.world_size != ctx->comm_size)) {
-        ctx->last_error = "ecal_solver_solve: ecal_comm_allreduce needs allreduce_user = the solver's context and its rank / world_size";
-        return ECAL_ERR_INVALID;
-    }
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t np = s->n_params(), na = s->n_accum(), nc = 6 * (size_t) s->n_cp, nt = nc + 9;
-    std::vector<double> x(params, params + np), xc(np), delta, scale(nt, 1.0), dd(nt);
-    ArrowSystem A;
-    ArrowWorkspace ws;
-    const auto t_begin = std::chrono::steady_clock::now();
-    // pinned staging (the solver keeps it): the 3 MB buffer comes back every evaluation
-    if (!s->h_acc) ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_acc, na * sizeof(double), hipHostMallocDefault));
-    if (!s->h_x) ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_x, np * sizeof(double), hipHostMallocDefault));
-    double *const acc = s->h_acc, *const xpin = s->h_x;
-    double t_eval = 0, t_lin = 0;
-    // Distributed segments (ecal_lm_options.distributed): every rank owns its own spline segments in its own
-    // ecal_solver; only the 9 intrinsics are shared.  Per evaluation the 91-double head is all-reduced; per linear solve
-    // the 10 x 10 Schur sums (+ a failure flag and one slot per rank for the gradient max-norm); per step four scalars.
-    // distributed == 2, time shards of ONE spline: every rank holds the whole spline layout and the residuals
-    // of its time range — the spline's control points cut into `world` interiors with 3-control-point separators
-    // (arrow_partition; ecal_solver_time_shard_cuts gives the caller the cut times).  Per evaluation the head and the
-    // separators' records are all-reduced (91 + 612 (N - 1) doubles), per linear solve the interiors' 46 x 46 Gram blocks
-    // (1082 N doubles); every rank factorises its own interior, solves the small reduced system redundantly and
-    // back-substitutes its own control points.  Nothing proportional to the number of control points crosses the links
-    // until the solution is put together at the end (one all-reduce of the parameter vector).
-    const bool ts_mode = opt.distributed == 2 && opt.allreduce != nullptr;
-    const bool dist_mode = (opt.distributed == 1 && opt.allreduce != nullptr) || ts_mode;
-    const int world = dist_mode ? std::max(1, opt.world_size) : 1, my_rank = dist_mode ? opt.rank : 0;
-    if (dist_mode && (my_rank < 0 || my_rank >= world || world > 1024)) return ECAL_ERR_INVALID;
-    std::vector<uint32_t> ts_first, ts_num;   // interiors (control points) of the time shards
-    if (ts_mode) {
-        if (s->n_seg != 1 || (uint32_t) (7 * world) > s->n_cp) {
-            ctx->last_error = "time-sharded solve: one spline segment with at least 7 control points per rank";
-            return ECAL_ERR_INVALID;
-        }
-        arrow_partition(s->n_cp, world, ts_first, ts_num);
-    }
-    constexpr size_t TS_G = (size_t) APZ * (APZ + 1) / 2 + 1;   // upper triangle of an interior's Gram block + its flag
-    double *d_small = nullptr, *h_small = nullptr;
-    const size_t n_small = std::max<size_t>(128 + (size_t) world, ts_mode ? std::max<size_t>(TS_G * (size_t) world, ACC_HEAD + 3 * ACC_PER_CP * (size_t) (world - 1)) : 0);
-    if (dist_mode) {
-        ECAL_HIP_TRY(ctx, hipMalloc((void **) &d_small, n_small * sizeof(double)));
-        if (hipHostMalloc((void **) &h_small, n_small * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-            (void) hipFree(d_small);
-            return ECAL_ERR_NOMEM;
-        }
-    }
-    struct FreeSmall {
-        double *d, *h;
-        ~FreeSmall() {
-            if (d) (void) hipFree(d);
-            if (h) (void) hipHostFree(h);
-        }
-    } free_small{d_small, h_small};
-    auto reduce_small = [&](double *v, size_t n) -> bool {  // sum v[0..n) over ranks in place
-        memcpy(h_small, v, n * sizeof(double));
-        if (hipMemcpyAsync(d_small, h_small, n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return false;
-        if (opt.allreduce(opt.allreduce_user, d_small, n, st) != 0) return false;
-        if (hipMemcpyAsync(h_small, d_small, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
-        if (hipStreamSynchronize(st) != hipSuccess) return false;
-        memcpy(v, h_small, n * sizeof(double));
-        return true;
-    };
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double>(b - a).count();
-    };
-
-    auto evaluate = [&](const double *xp, int with_jac, double *cost) -> int {
-        const auto te = now();
-        memcpy(xpin, xp, np * sizeof(double));
-        hipError_t e = hipMemcpyAsync(s->d_params, xpin, np * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return ECAL_ERR_HIP;
-        int rc = ecal_solver_evaluate_dev(s, s->d_params, with_jac, s->d_accum, st);
-        if (rc) return rc;
-        const size_t n = with_jac ? na : 1;
-        if (opt.allreduce && ts_mode && with_jac) {
-            // time shards: the head and the separators' records (3 control points per cut) are what two ranks both add to
-            size_t at = ACC_HEAD;
-            hipError_t e2 = hipMemcpyAsync(d_small, s->d_accum, ACC_HEAD * sizeof(double), hipMemcpyDeviceToDevice, st);
-            for (int c = 0; c + 1 < world && e2 == hipSuccess; c++, at += 3 * ACC_PER_CP)
-                e2 = hipMemcpyAsync(d_small + at, s->d_accum + ACC_HEAD + ACC_PER_CP * (size_t) (ts_first[c] + ts_num[c]),
-                                    3 * ACC_PER_CP * sizeof(double), hipMemcpyDeviceToDevice, st);
-            if (e2 != hipSuccess) return ECAL_ERR_HIP;
-            if (opt.allreduce(opt.allreduce_user, d_small, at, st) != 0) return ECAL_ERR_HIP;
-            e2 = hipMemcpyAsync(s->d_accum, d_small, ACC_HEAD * sizeof(double), hipMemcpyDeviceToDevice, st);
-            at = ACC_HEAD;
-            for (int c = 0; c + 1 < world && e2 == hipSuccess; c++, at += 3 * ACC_PER_CP)
-                e2 = hipMemcpyAsync(s->d_accum + ACC_HEAD + ACC_PER_CP * (size_t) (ts_first[c] + ts_num[c]), d_small + at,
-                                    3 * ACC_PER_CP * sizeof(double), hipMemcpyDeviceToDevice, st);
-            if (e2 != hipSuccess) return ECAL_ERR_HIP;
-        } else if (opt.allreduce) {  // per-GPU partials summed over ranks (RCCL all-reduce supplied by the caller)
-            // distributed segments: only the head (cost, intrinsics gradient and block) is shared between ranks
-            rc = opt.allreduce(opt.allreduce_user, s->d_accum, dist_mode ? std::min(n, (size_t) ACC_HEAD) : n, st);
-            if (rc) return ECAL_ERR_HIP;
-        }
-        e = hipMemcpyAsync(acc, s->d_accum, n * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("solver evaluate: ") + hipGetErrorString(e);
-            return ECAL_ERR_HIP;
-        }
-        *cost = acc[0];
-        t_eval += secs(te, now());
-        return ECAL_OK;
-    };
-
-    // one rank, a long spline: the factorisation, the unpacking and the quadratic forms run on several host cores
-    // (arrow_host_parts.hpp); the sharded modes keep the sequential routines (their segments are short, and the sequential
-    // routine's 10 x 10 Schur sums are what the ranks exchange)
-    ArrowParts parts;
-    int n_parts = arrow_parts_for(s->n_cp);
-    if ((uint32_t) (7 * n_parts) > s->n_cp) n_parts = 1;
-    // (sharded segments: unpacking and the quadratic forms still use the pool, the factorisation stays the sequential routine)
-    const bool parts_solve = !dist_mode;
-    // time shards: the interiors' Gram blocks (upper triangles) + a "positive definite" flag, one slot per rank, summed
-    ArrowParts ts_parts;
-    const std::function<bool(ArrowParts &)> ts_exchange = [&](ArrowParts &pt) -> bool {
-        std::vector<double> buf(TS_G * (size_t) world, 0.0);
-        double *mine = buf.data() + TS_G * (size_t) my_rank;
-        const double *G = pt.G.data() + (size_t) my_rank * APZ * APZ;
-        size_t k = 0;
-        bool finite = true;
-        for (int i = 0; i < APZ; i++)
-            for (int j = i; j < APZ; j++) {
-                finite = finite && std::isfinite(G[(size_t) i * APZ + j]);
-                mine[k++] = G[(size_t) i * APZ + j];
-            }
-        if (!finite)
-            for (size_t q = 0; q + 1 < TS_G; q++) mine[q] = 0.0;
-        mine[TS_G - 1] = (pt.ok[my_rank] && finite) ? 1.0 : 0.0;
-        if (!reduce_small(buf.data(), buf.size())) return false;
-        for (int p = 0; p < world; p++) {
-            const double *src = buf.data() + TS_G * (size_t) p;
-            double *Gp = pt.G.data() + (size_t) p * APZ * APZ;
-            size_t q = 0;
-            for (int i = 0; i < APZ; i++)
-                for (int j = i; j < APZ; j++) Gp[(size_t) i * APZ + j] = src[q++];
-            pt.ok[p] = src[TS_G - 1] == 1.0 ? 1 : 0;
-        }
-        return true;
-    };
-    const uint32_t epoch_at_start = s->stream_epoch;
-    HostPool *pool = nullptr;   // (the solver keeps the threads: starting fifteen of them costs as much as a tenth of an iteration each)
-    double t_unpack = 0, t_pool = 0;
-    if (n_parts > 1) {
-        const auto tp = now();
-        const int hw = host_usable_cpus();   // (affinity ∩ cgroup quota ÷ the node's ranks — not hardware_concurrency())
-        const int workers = std::max(0, std::min(n_parts, hw) - 1);
-        if (!s->host_pool || s->host_pool_workers != workers) {
-            try {
-                s->host_pool = std::shared_ptr<void>(new HostPool(workers), [](void *q) { delete static_cast<HostPool *>(q); });
-                s->host_pool_workers = workers;
-            } catch (...) {   // no threads to be had: the sequential routines
-                s->host_pool.reset();
-                s->host_pool_workers = -1;
-                n_parts = 1;
-            }
-        }
-        pool = static_cast<HostPool *>(s->host_pool.get());
-        t_pool = secs(tp, now());
-    }
-    auto unpack_acc = [&]() {
-        const auto tu = now();
-        if (pool) {   // band rows by ranges of control points, one range per task
-            unpack_alloc(s->n_cp, A);
-            unpack_head(acc, A);
-            const uint32_t T = 4u * (uint32_t) n_parts, per = (s->n_cp + T - 1) / T;
-            pool->run((int) T, [&](int t) { unpack_rows(acc, A, std::min(s->n_cp, (uint32_t) t * per), std::min(s->n_cp, ((uint32_t) t + 1) * per)); });
-        } else {
-            unpack(acc, s->n_cp, A);
-        }
-        t_unpack += secs(tu, now());
-    };
-
-    // Streamed evaluation (one rank, the multi-part host solve): NeProgress above — the kernel delivers the records group by
-    // group, the pool's threads unpack an interior's rows and, when the trust-region radius the next linear solve will use
-    // can be predicted, factorise it while the kernel is still busy with the later control points.  What is left behind the
-    // kernel: the last interior, the separators' rows, the reduced system, the back-substitution.
-    bool stream_ok = !opt.allreduce && pool && n_parts > 1 && parts_solve && n_parts <= NE_MAX_GROUPS && !ctx->sw.solver_no_stream &&
-                     s->n_chunks > 0;
-    std::vector<uint32_t> part_first, part_num;
-    if (stream_ok) {
-        arrow_partition_stream(s->n_cp, n_parts, part_first, part_num);
-        if (s->prog.n_groups != (uint32_t) n_parts) {   // first solve with this partition: the groups' chunk counts, the buffers
-            std::vector<Chunk> ch(s->n_chunks);
-            ECAL_HIP_TRY(ctx, hipMemcpy(ch.data(), s->d_chunks, ch.size() * sizeof(Chunk), hipMemcpyDeviceToHost));
-            NeProgress &pg = s->prog;
-            memset(&pg, 0, sizeof(pg));
-            pg.n_cp = s->n_cp;
-            for (int g = 0; g < n_parts; g++) pg.cut[g] = part_first[g];
-            pg.cut[n_parts] = s->n_cp;
-            for (const Chunk &c : ch) {
-                const uint32_t sg = s->cp_off[c.seg] + c.span;
-                uint32_t g = 0;
-                while (g + 1 < (uint32_t) n_parts && pg.cut[g + 1] <= sg) g++;
-                pg.init[g]++;
-            }
-            for (int b = 0; b + 1 < n_parts; b++) pg.init[NE_MAX_GROUPS + b] = (pg.init[b] ? 1u : 0u) + (pg.init[b + 1] ? 1u : 0u);
-            if (!s->h_flag) {
-                ECAL_HIP_TRY(ctx, hipHostMalloc((void **) &s->h_flag, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipHostMallocDefault));
-                memset(s->h_flag, 0, 2 * NE_MAX_GROUPS * sizeof(uint32_t));
-            }
-            if (!s->d_left) ECAL_HIP_TRY(ctx, hipMalloc((void **) &s->d_left, 2 * NE_MAX_GROUPS * sizeof(uint32_t)));
-            if (!s->d_prog) ECAL_HIP_TRY(ctx, hipMalloc((void **) &s->d_prog, sizeof(NeProgress)));
-            ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-            ECAL_HIP_TRY(ctx, hipMemcpy(s->d_left, pg.init, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipMemcpyHostToDevice));
-            pg.left = s->d_left;
-            ECAL_HIP_TRY(ctx, hipHostGetDevicePointer((void **) &pg.host_acc, s->h_acc, 0));
-            ECAL_HIP_TRY(ctx, hipHostGetDevicePointer((void **) &pg.host_flag, s->h_flag, 0));
-            ECAL_HIP_TRY(ctx, hipMemcpy(s->d_prog, &pg, sizeof(pg), hipMemcpyHostToDevice));
-            pg.n_groups = (uint32_t) n_parts;
-            ECAL_HIP_TRY(ctx, hipMemcpy(s->d_prog, &pg, sizeof(pg), hipMemcpyHostToDevice));
-        } else {
-            // the kernel restores the groups' counters itself as it finishes each group — unless an earlier evaluation on this
-            // solver stopped half way (an error, a stream that failed to deliver): a solve starts from the full counts whatever
-            // the last one left behind (128 words; nothing of this solver is in flight here)
-            ECAL_HIP_TRY(ctx, hipMemcpyAsync(s->d_left, s->prog.init, 2 * NE_MAX_GROUPS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-    }
-    ArrowSystem A_next;
-    std::vector<double> dd_next(nt);
-    bool reduced_ok = false;   // a streamed evaluation with `factor`: every separator of the reduced system eliminated
-    std::vector<double> tl_arrive, tl_done;   // ECAL_TRACE=solver: the last streamed evaluation's timeline (seconds from its start)
-    double tl_run = 0, tl_sync = 0;
-    double t_tail = 0;
-    // An: the system at xp.  factor: also arrow_part_factor of every interior, with the LM diagonal of trust-region radius
-    // r_fact (ws / parts then hold what arrow_parts_finish needs).  *streamed = false: the stream failed to deliver (nothing this
-    // code can name should make it) and the buffer was fetched and unpacked the plain way, nothing factorised.
-    auto evaluate_streamed = [&](const double *xp, ArrowSystem &An, bool factor, double r_fact, double *cost, bool *streamed,
-                                 const std::function<void()> *after_launch = nullptr) -> int {
-        const auto te = now();
-        const NeProgress &pg = s->prog;
-        const int P = n_parts;
-        memcpy(xpin, xp, np * sizeof(double));
-        if (hipMemcpyAsync(s->d_params, xpin, np * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return ECAL_ERR_HIP;
-        const uint32_t epoch = ++s->stream_epoch;
-        // records that no chunk touches never arrive: they are zero
-        for (int g = 0; g < P; g++) {
-            if (!pg.init[g]) memset(acc + ACC_HEAD + ACC_PER_CP * (size_t) pg.cut[g], 0,
-                                    ACC_PER_CP * (size_t) ((g + 1 < P ? pg.cut[g + 1] - 3 : pg.cut[g + 1]) - pg.cut[g]) * sizeof(double));
-            if (g + 1 < P && !pg.init[NE_MAX_GROUPS + g]) memset(acc + ACC_HEAD + ACC_PER_CP * (size_t) (pg.cut[g + 1] - 3), 0, 3 * ACC_PER_CP * sizeof(double));
-        }
-        int rc2 = solver_evaluate_dev(s, s->d_params, 1, s->d_accum, st, s->d_prog, epoch);
-        if (rc2) return rc2;
-        if (hipMemcpyAsync(acc, s->d_accum, ACC_HEAD * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return ECAL_ERR_HIP;
-        if (after_launch) (*after_launch)();   // (host work of the caller that only has to be done by the time the kernel is)
-        unpack_alloc(s->n_cp, An);
-        if (factor) arrow_parts_setup(An.nc, P, ws, parts, true);
-        reduced_ok = false;
-        const bool trace_ev = ctx->sw.solver_trace;
-        tl_arrive.assign(P + 1, 0.0);
-        tl_done.assign(P + 1, 0.0);
-        // the host tasks (arrow_host.hpp: an interior per task as its records arrive, the separators behind them)
-        StreamedSource src;
-        src.init = pg.init;
-        src.cut = pg.cut;
-        src.flag = s->h_flag;
-        src.epoch = epoch;
-        src.producer_gone = [&]() -> bool { return hipStreamQuery(st) != hipErrorNotReady; };
-        const bool delivered = arrow_streamed_tasks(pool, P, src, acc, An, factor, r_fact, scale.data(), dd_next.data(), opt.min_lm_diagonal,
-                                                    opt.max_lm_diagonal, ws, parts, &reduced_ok, trace_ev ? tl_arrive.data() : nullptr,
-                                                    trace_ev ? tl_done.data() : nullptr, te);
-        tl_run = secs(te, now());
-        const hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("solver evaluate: ") + hipGetErrorString(e);
-            return ECAL_ERR_HIP;
-        }
-        const auto tt = now();
-        *streamed = delivered;
-        if (!delivered) {
-            if (hipMemcpy(acc, s->d_accum, na * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return ECAL_ERR_HIP;
-            unpack(acc, s->n_cp, An);
-        } else {
-            unpack_head(acc, An);
-            if (!factor)
-                for (int p = 0; p + 1 < P; p++) unpack_rows(acc, An, pg.cut[p + 1] - 3, pg.cut[p + 1]);
-        }
-        *cost = acc[0];
-        tl_sync = secs(te, tt);
-        t_tail += secs(tt, now());
-        t_eval += secs(te, now());
-        return ECAL_OK;
-    };
-
+    RankShare share;
+    int rc = solve_validate(s, opt, share);
+    if (rc) return rc;
+    ECAL_HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
+    const auto t_begin = lm_now();
+    SolveDevice backend{s, opt, share};
+    if ((rc = backend.alloc())) return rc;
+    backend.acquire_pool();
+    LmCounters K;
+    if ((rc = backend.setup_stream(&K.stream_ok))) return rc;
+    const LmDevice dev{[&backend](const double *x, int with_jac, double *cost) { return backend.evaluate(x, with_jac, cost); },
+                       [&backend](double *v, size_t n) { return backend.reduce_small(v, n); },
+                       [&backend](LmStreamJob &job) { return backend.evaluate_streamed(job); }, s->h_acc};
+    std::vector<double> x(params, params + backend.np);
     ecal_lm_summary S;
-    memset(&S, 0, sizeof(S));
-    double cost = 0, radius = opt.initial_trust_region_radius, decrease_factor = 2.0;
-    int rc;
-    bool fact_ready = false;      // ws / parts hold the interiors' factors for A with the diagonal of radius fact_radius
-    double fact_radius = 0;
-    int n_prefactored = 0;
-    if (stream_ok) {
-        bool streamed = false;
-        rc = evaluate_streamed(x.data(), A, false, 0.0, &cost, &streamed, nullptr);   // (the column scaling comes from this evaluation: nothing to factorise with yet)
-        if (rc) return rc;
-        if (!streamed) stream_ok = false;
-    } else {
-        rc = evaluate(x.data(), 1, &cost);
-        if (rc) return rc;
-        unpack_acc();
-    }
-    S.jacobian_evaluations = 1;
-    S.initial_cost = cost;
-    if (opt.jacobi_scaling) {  // computed once from the initial Jacobian, as Ceres does
-        for (size_t i = 0; i < nc; i++) scale[i] = 1.0 / (1.0 + std::sqrt(A.band[i * BW]));
-        for (int i = 0; i < 9; i++) scale[nc + i] = 1.0 / (1.0 + std::sqrt(A.corner[10 * i]));
-    }
-    S.termination = 1;  // NO_CONVERGENCE unless a test fires
-    auto gmax = [&]() {
-        double m = 0;
-        for (size_t i = 0; i < nc; i++) m = std::max(m, std::fabs(A.gc[i]));
-        if (dist_mode) {  // one slot per rank, summed: a max over ranks without a max collective
-            std::vector<double> v((size_t) world, 0.0);
-            v[(size_t) my_rank] = m;
-            if (reduce_small(v.data(), v.size()))
-                for (double x : v) m = std::max(m, x);
-        }
-        for (int i = 0; i < 9; i++) m = std::max(m, std::fabs(A.gi[i]));
-        return m;
-    };
-    if (dist_mode)
-        ws.reduce_G = [&](double *G) -> bool {
-            double buf[101];
-            bool bad = false;
-            for (int i = 0; i < 100; i++) {
-                buf[i] = G[i];
-                bad = bad || !std::isfinite(G[i]);
-            }
-            buf[100] = bad ? 1.0 : 0.0;
-            if (bad)
-                for (int i = 0; i < 100; i++) buf[i] = 0.0;
-            if (!reduce_small(buf, 101)) return false;
-            for (int i = 0; i < 100; i++) G[i] = buf[i];
-            return buf[100] == 0.0;
-        };
-    if (gmax() <= opt.gradient_tolerance) S.termination = 0;
-    bool last_step_ok = true;
-    // the interiors factorised and the separators eliminated while the kernel ran: the intrinsics' corner and the way back
-    double t_fin_end = 0, t_fin_back = 0;
-    auto prefactored_finish = [&]() -> bool {
-        const auto ta = now();
-        if (!reduced_ok || !arrow_reduced_end(A, scale.data(), dd.data(), parts)) return false;
-        const auto tb = now();
-        arrow_parts_backsub(A.nc, delta, ws, parts, pool, n_parts);
-        t_fin_end += secs(ta, tb);
-        t_fin_back += secs(tb, now());
-        return true;
-    };
-    double t_dd = 0, t_fin = 0, t_quad = 0, t_plus = 0, t_book = 0;   // ECAL_TRACE=solver: the host's share of an iteration, by item
-    while (S.termination == 1 && S.iterations < opt.max_num_iterations) {
-        S.iterations++;
-        const auto t_it = now();
-        // Levenberg-Marquardt diagonal on the scaled system (the streamed evaluation left the control points' part behind when
-        // its radius is the one in force)
-        const bool prefactored = fact_ready && fact_radius == radius && reduced_ok;
-        if (prefactored) memcpy(dd.data(), dd_next.data(), nc * sizeof(double));
-        for (size_t i = prefactored ? nc : 0; i < nt; i++) {
-            const double h = (i < nc ? A.band[i * BW] : A.corner[10 * (i - nc)]) * scale[i] * scale[i];
-            dd[i] = std::min(std::max(h, opt.min_lm_diagonal), opt.max_lm_diagonal) / radius;
-        }
-        const auto tl = now();
-        t_dd += secs(t_it, tl);
-        bool ok = ts_mode ? solve_arrow_parts(A, scale, dd, delta, ws, ts_parts, nullptr, world, my_rank, &ts_exchange)
-                  : (n_parts > 1 && parts_solve)
-                      ? (fact_ready && fact_radius == radius ? prefactored_finish()   // (false when an interior or a separator was not positive definite)
-                                                             : solve_arrow_parts(A, scale, dd, delta, ws, parts, pool, n_parts))   // (a whole factorisation: the even partition — the streamed evaluation sets up its own)
-                      : solve_arrow(A, scale, dd, delta, ws);
-        if (fact_ready && fact_radius == radius) n_prefactored++;
-        fact_ready = false;
-        const auto t_q = now();
-        t_fin += secs(tl, t_q);
-        double model_change = 0;
-        // After a successful step the next one is usually successful too: evaluate the candidate WITH its normal
-        // equations in one pass (4.8 ms) instead of a cost-only pass (1.0 ms + a host round trip) followed, on
-        // acceptance, by the full pass at the same point.  After a rejected step fall back to the cost-only probe.
-        const bool speculate = last_step_ok;
-        // streamed evaluation ahead: the quadratic forms of the model are computed once the kernel is running (they gate the
-        // evaluation only when the step is no descent step of the model, which a positive definite system rules out up to rounding)
-        const bool defer_quad = ok && !dist_mode && speculate && stream_ok;
-        double gTd_late = 0, dHd_late = 0;
-        if (defer_quad) {
-            for (size_t i = 0; i < nt; i++) delta[i] *= scale[i];
-            model_change = 1.0;   // (placeholder until the forms are in)
-        } else if (ok && ts_mode) {
-            // the step solves (H + D) y = -g exactly, so y^T H y = -g^T y - y^T D y and the model change -g^T y - y^T H y / 2 is
-            // (y^T D y - g^T y) / 2: sums over unknowns — this rank's interior, rank 0 also the separators and the intrinsics
-            // (every rank holds the same values for those)
-            double two[2] = {0, 0};
-            auto add = [&](size_t i) {
-                const double g = i < nc ? A.gc[i] : A.gi[i - nc];
-                two[0] += g * scale[i] * delta[i];
-                two[1] += dd[i] * delta[i] * delta[i];
-            };
-            for (size_t i = 6 * (size_t) ts_first[my_rank]; i < 6 * (size_t) (ts_first[my_rank] + ts_num[my_rank]); i++) add(i);
-            if (my_rank == 0) {
-                for (int c = 0; c + 1 < world; c++)
-                    for (size_t i = 6 * (size_t) (ts_first[c] + ts_num[c]); i < 6 * (size_t) (ts_first[c] + ts_num[c] + 3); i++) add(i);
-                for (size_t i = nc; i < nt; i++) add(i);
-            }
-            if (!reduce_small(two, 2)) return ECAL_ERR_HIP;
-            for (size_t i = 0; i < nt; i++) delta[i] *= scale[i];
-            model_change = 0.5 * (two[1] - two[0]);
-            ok = model_change > 0.0;
-        } else if (ok) {
-            for (size_t i = 0; i < nt; i++) delta[i] *= scale[i];
-            double gTd, dHd;
-            quad_forms(A, delta, &gTd, &dHd, dist_mode && my_rank != 0, pool, n_parts);
-            if (dist_mode) {
-                double two[2] = {gTd, dHd};
-                if (!reduce_small(two, 2)) return ECAL_ERR_HIP;
-                gTd = two[0];
-                dHd = two[1];
-            }
-            model_change = -gTd - 0.5 * dHd;
-            ok = model_change > 0.0;
-        }  // (a failed factorisation was agreed on through reduce_G: every rank skips the reduction above together)
-        t_lin += secs(tl, now());
-        t_quad += secs(t_q, now());
-        if (!ok) {  // invalid step: shrink the region
-            radius /= decrease_factor;
-            decrease_factor *= 2.0;
-            S.unsuccessful_steps++;
-            continue;
-        }
-        const auto t_p = now();
-        plus(x.data(), delta, s->n_cp, s->use_so3, xc.data());   // (on the pool's threads: measured slower, 47 against 28 us)
-        t_plus += secs(t_p, now());
-        double new_cost;
-        // streamed: the interiors are factorised for the radius a step with rel >= 0.937 leads to (the usual one while the
-        // model is good: radius / max(1/3, 1 - (2 rel - 1)^3) = 3 radius); any other verdict factorises again as before
-        const double r_pred = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 0.0));
-        bool cand_in_next = false, cand_factored = false;   // the candidate's system sits unpacked in A_next / its interiors are factorised
-        if (speculate && stream_ok) {
-            const std::function<void()> late = [&] { quad_forms(A, delta, &gTd_late, &dHd_late, false, pool, n_parts); };
-            rc = evaluate_streamed(xc.data(), A_next, true, r_pred, &new_cost, &cand_factored, defer_quad ? &late : nullptr);
-            cand_in_next = true;
-            if (!rc && !cand_factored) stream_ok = false;   // (fetched the plain way: carry on without the stream)
-        } else {
-            rc = evaluate(xc.data(), speculate ? 1 : 0, &new_cost);
-        }
-        if (rc) return rc;
-        const auto t_b = now();
-        if (defer_quad) {
-            model_change = -gTd_late - 0.5 * dHd_late;
-            if (!(model_change > 0.0)) {   // invalid step after all: the evaluation is dropped, the region shrinks
-                S.jacobian_evaluations++;
-                radius /= decrease_factor;
-                decrease_factor *= 2.0;
-                S.unsuccessful_steps++;
-                continue;
-            }
-        }
-        if (speculate) S.jacobian_evaluations++;
-        else S.cost_evaluations++;
-        const double rel = (cost - new_cost) / model_change;
-        double step2 = 0, x2 = 0;
-        if (ts_mode) {   // own interior from every rank; separators and intrinsics once (rank 0)
-            auto own = [&](uint32_t c) {
-                for (int k = 0; k < 6; k++) step2 += delta[6 * (size_t) c + k] * delta[6 * (size_t) c + k];
-                for (int k = 0; k < 4; k++) x2 += x[9 + 4 * (size_t) c + k] * x[9 + 4 * (size_t) c + k];
-                for (int k = 0; k < 3; k++) x2 += x[9 + 4 * (size_t) s->n_cp + 3 * (size_t) c + k] * x[9 + 4 * (size_t) s->n_cp + 3 * (size_t) c + k];
-            };
-            for (uint32_t c = ts_first[my_rank]; c < ts_first[my_rank] + ts_num[my_rank]; c++) own(c);
-            if (my_rank == 0) {
-                for (int q = 0; q + 1 < world; q++)
-                    for (uint32_t c = ts_first[q] + ts_num[q]; c < ts_first[q] + ts_num[q] + 3; c++) own(c);
-                for (size_t i = nc; i < nt; i++) step2 += delta[i] * delta[i];
-                for (size_t i = 0; i < 9; i++) x2 += x[i] * x[i];
-            }
-            double two[2] = {step2, x2};
-            if (!reduce_small(two, 2)) return ECAL_ERR_HIP;
-            step2 = two[0];
-            x2 = two[1];
-        } else if (dist_mode) {  // own control points from every rank, the shared intrinsics once
-            for (size_t i = 0; i < nc; i++) step2 += delta[i] * delta[i];
-            for (size_t i = 9; i < np; i++) x2 += x[i] * x[i];
-            double two[2] = {step2, x2};
-            if (!reduce_small(two, 2)) return ECAL_ERR_HIP;
-            step2 = two[0];
-            x2 = two[1];
-            for (size_t i = nc; i < nt; i++) step2 += delta[i] * delta[i];
-            for (size_t i = 0; i < 9; i++) x2 += x[i] * x[i];
-        } else {
-            for (size_t i = 0; i < nt; i++) step2 += delta[i] * delta[i];
-            for (size_t i = 0; i < np; i++) x2 += x[i] * x[i];
-        }
-        if (rel > opt.min_relative_decrease) {
-            const double cost_change = cost - new_cost;
-            x.swap(xc);
-            const double prev = cost;
-            if (speculate) {
-                cost = new_cost;  // the buffer of the speculative pass is the one to unpack
-            } else {
-                rc = evaluate(x.data(), 1, &cost);
-                if (rc) return rc;
-                S.jacobian_evaluations++;
-            }
-            if (cand_in_next) std::swap(A, A_next);   // (unpacked while the kernel ran)
-            else unpack_acc();
-            S.successful_steps++;
-            last_step_ok = true;
-            const double t = 2.0 * rel - 1.0;
-            radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-            if (cand_factored) {
-                fact_ready = true;
-                fact_radius = r_pred;
-            }
-            decrease_factor = 2.0;
-            if (gmax() <= opt.gradient_tolerance) S.termination = 0;
-            else if (std::fabs(cost_change) <= opt.function_tolerance * prev) S.termination = 0;
-        } else {
-            radius /= decrease_factor;
-            decrease_factor *= 2.0;
-            S.unsuccessful_steps++;
-            last_step_ok = false;
-        }
-        if (S.termination == 1 && std::sqrt(step2) <= opt.parameter_tolerance * (std::sqrt(x2) + opt.parameter_tolerance))
-            S.termination = 0;
-        t_book += secs(t_b, now());
-    }
-    if (ts_mode) {
-        // the solution put together: every rank contributes its interior, rank 0 the separators and the intrinsics (the one
-        // exchange proportional to the spline's length, once per solve)
-        std::vector<double> mine(np, 0.0);
-        auto take = [&](uint32_t c) {
-            for (int k = 0; k < 4; k++) mine[9 + 4 * (size_t) c + k] = x[9 + 4 * (size_t) c + k];
-            for (int k = 0; k < 3; k++) mine[9 + 4 * (size_t) s->n_cp + 3 * (size_t) c + k] = x[9 + 4 * (size_t) s->n_cp + 3 * (size_t) c + k];
-        };
-        for (uint32_t c = ts_first[my_rank]; c < ts_first[my_rank] + ts_num[my_rank]; c++) take(c);
-        if (my_rank == 0) {
-            for (int q = 0; q + 1 < world; q++)
-                for (uint32_t c = ts_first[q] + ts_num[q]; c < ts_first[q] + ts_num[q] + 3; c++) take(c);
-            for (int i = 0; i < 9; i++) mine[i] = x[i];
-        }
-        memcpy(xpin, mine.data(), np * sizeof(double));
-        if (hipMemcpyAsync(s->d_params, xpin, np * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return ECAL_ERR_HIP;
-        if (opt.allreduce(opt.allreduce_user, s->d_params, np, st) != 0) return ECAL_ERR_HIP;
-        if (hipMemcpyAsync(xpin, s->d_params, np * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return ECAL_ERR_HIP;
-        if (hipStreamSynchronize(st) != hipSuccess) return ECAL_ERR_HIP;
-        memcpy(x.data(), xpin, np * sizeof(double));
-    }
-    S.final_cost = cost;
-    S.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    S.seconds_evaluate = t_eval;
-    S.seconds_linear_solve = t_lin;
-    s->last_solve[0] = (uint32_t) n_parts;
-    s->last_solve[1] = s->stream_epoch - epoch_at_start;
-    s->last_solve[2] = (uint32_t) n_prefactored;
-    s->last_solve[3] = pool ? (uint32_t) pool->workers() : 0u;
-    s->last_solve[4] = stream_ok ? 1u : 0u;
-    s->last_solve[5] = (uint32_t) S.iterations;
-    s->last_solve[6] = (uint32_t) dist_mode | (ts_mode ? 2u : 0u);
-    if (s->ctx->sw.solver_trace)
-        fprintf(stderr, "ecal_solver_solve: total %.4f s | evaluate %.4f | linear solve %.4f (%d parts) | unpack %.4f | pool %.4f | streamed evaluations: "
-                        "%u, behind the kernel %.4f, %d of %d linear solves found their interiors factorised\n", S.seconds,
-                t_eval, t_lin, n_parts, t_unpack, t_pool, s->stream_epoch, t_tail, n_prefactored, S.iterations);
-    if (s->ctx->sw.solver_trace)
-        fprintf(stderr, "  host items, ms over the solve: LM diagonal %.3f | factorise / finish %.3f | scaling + quadratic forms %.3f | plus %.3f | "
-                        "verdict, norms, swap / unpack, gradient norm %.3f | of the finishes: corner %.3f, back-substitution %.3f\n", 1e3 * t_dd, 1e3 * t_fin,
-                1e3 * t_quad, 1e3 * t_plus, 1e3 * t_book, 1e3 * t_fin_end, 1e3 * t_fin_back);
-    if (s->ctx->sw.solver_trace && !tl_arrive.empty()) {
-        fprintf(stderr, "  last streamed evaluation, ms from its start: interiors arrived / factorised");
-        for (size_t p = 0; p + 1 < tl_arrive.size(); p++) fprintf(stderr, " %.2f/%.2f", 1e3 * tl_arrive[p], 1e3 * tl_done[p]);
-        fprintf(stderr, " | separators done %.2f | tasks joined %.2f | stream synchronised %.2f\n", 1e3 * tl_done.back(), 1e3 * tl_run, 1e3 * tl_sync);
-    }
-    memcpy(params, x.data(), np * sizeof(double));
+    if ((rc = lm_loop(dev, opt, share, s->n_cp, s->use_so3, backend.pool, backend.n_parts, x, S, K))) return rc;
+    if (share.mode == 2 && !backend.gather(x)) return ECAL_ERR_HIP;
+    S.seconds = lm_secs(t_begin, lm_now()), S.seconds_evaluate = backend.t_eval;
+    backend.report(S, K);
+    memcpy(params, x.data(), backend.np * sizeof(double));
     if (sum) *sum = S;
     return ECAL_OK;
 }
