@@ -91,6 +91,14 @@ def check_pose(R_ref, twb_ref, t_ref, R_cur, twb_cur, t_cur, step):
     return v_t < (2.5e-1 / step) * 2 and v_r < (5e-4 * math.pi) * 2 / step
 
 
+def load_events_text(ctx, path, **options):
+    """A text event file ("stamp x y polarity" lines, the input of the reference's txt2bin) -> (events, t_first, t_last) as
+    calibrate_stream takes them: uploaded and parsed on the device (capi.Context.stream_from_text_file), in time order.
+    options: capi.Context.text_options' (time_magnitude, time_base, end_stamp, start_time, end_time, duplicate_last)."""
+    events, _info, t_first, t_last = ctx.stream_from_text_file(path, **options)
+    return events, t_first, t_last
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "ecal_report_default_options", "ecal_solver_report_dev", "ecal_solver_report", "ecal_solver_num_landmarks",
     "ecal_board_image_default_options", "ecal_solver_board_image_dev", "ecal_solver_board_image", "ecal_solver_board_points_dev", "ecal_solver_board_points",
     "ecal_solver_reassociate_dev", "ecal_solver_reassociate", "ecal_solver_create_reassociated",
+    "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -43,6 +44,23 @@ class RectifyParams(ctypes.Structure):
                 ("dist", ctypes.c_double * 5), ("width", ctypes.c_double), ("height", ctypes.c_double),
                 ("rows", ctypes.c_uint32), ("cols", ctypes.c_uint32), ("asymmetric", ctypes.c_int),
                 ("circle_radius", ctypes.c_double), ("fit_circle", ctypes.c_int), ("model", ctypes.c_int)]
+
+
+class TextOptions(ctypes.Structure):
+    """ecal_text_options (include/ecal.h, text ingest)."""
+    _fields_ = [("time_magnitude", ctypes.c_double), ("has_time_base", ctypes.c_int), ("time_base", ctypes.c_int64),
+                ("has_end_stamp", ctypes.c_int), ("end_stamp", ctypes.c_int64), ("start_time", ctypes.c_double),
+                ("has_end_time", ctypes.c_int), ("end_time", ctypes.c_double), ("duplicate_last", ctypes.c_int)]
+
+
+class TextInfo(ctypes.Structure):
+    """ecal_text_info (include/ecal.h, text ingest)."""
+    _fields_ = [("n_lines", ctypes.c_uint64), ("n_blank", ctypes.c_uint64), ("n_events", ctypes.c_uint64),
+                ("n_negative", ctypes.c_uint64), ("n_after_end", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64),
+                ("n_host_lines", ctypes.c_uint64), ("first_bad_line", ctypes.c_uint64), ("time_base", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 import weakref
@@ -306,6 +324,124 @@ class Context:
 
     def check_sorted_dev(self, d_events, n_events, d_flag, stream=0):
         self._check(self._L.ecal_check_sorted_dev(self._h, d_events, int(n_events), d_flag, stream))
+
+    # ---- text ingest: "stamp x y polarity" lines parsed in HBM (ecal_events_from_text_dev and the file forms) ----
+    def text_options(self, time_magnitude=1e-6, time_base=None, end_stamp=None, start_time=None, end_time=None, duplicate_last=True):
+        """ecal_text_options from ecal_text_default_options: time_base None = the first record line's stamp, end_stamp None = no
+        break, start_time None = -inf, end_time None = to the end, duplicate_last = the reference's repeated last record."""
+        L = self._L
+        L.ecal_text_default_options.argtypes = [ctypes.POINTER(TextOptions)]
+        L.ecal_text_default_options.restype = None
+        o = TextOptions()
+        L.ecal_text_default_options(ctypes.byref(o))
+        o.time_magnitude = float(time_magnitude)
+        if time_base is not None:
+            o.has_time_base, o.time_base = 1, int(time_base)
+        if end_stamp is not None:
+            o.has_end_stamp, o.end_stamp = 1, int(end_stamp)
+        if start_time is not None:
+            o.start_time = float(start_time)
+        if end_time is not None:
+            o.has_end_time, o.end_time = 1, float(end_time)
+        o.duplicate_last = 1 if duplicate_last else 0
+        return o
+
+    def _text_fail(self, st, info):
+        """EcalError of a text entry point, with the ecal_text_info it filled (first_bad_line, the needed n_events) as .info"""
+        try:
+            self._check(st)
+        except EcalError as e:
+            e.info = info.as_dict()
+            raise
+
+    @staticmethod
+    def _text_tensor(text):
+        """bytes / numpy uint8 / torch uint8 (any device) as a CUDA uint8 tensor whose storage starts 16-byte aligned"""
+        import torch
+        if isinstance(text, torch.Tensor):
+            t = text.contiguous().view(torch.uint8).reshape(-1)
+        else:
+            a = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8).ravel()
+            t = torch.from_numpy(a.copy()) if a.size else torch.zeros(0, dtype=torch.uint8)
+        t = t.cuda()
+        if t.numel() and t.data_ptr() % 16:    # (a view into a larger tensor: the kernels load 16 bytes at a time)
+            t = t.clone()
+        return t
+
+    def text_count_lines(self, text):
+        """ecal_text_count_lines_dev: the lines of the text (lines + 1 bounds the records)."""
+        import torch
+        L = self._L
+        L.ecal_text_count_lines_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.ecal_text_count_lines_dev.restype = ctypes.c_int
+        t = self._text_tensor(text)
+        n = ctypes.c_uint64()
+        self._check(L.ecal_text_count_lines_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(n),
+                                                torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def events_from_text(self, text, capacity=None, **options):
+        """ecal_events_from_text_dev: text (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is parsed where it is)
+        -> (packed 25-byte records in file order as a uint8 CUDA tensor [n_events * 25], info dict).  options: text_options'.
+        capacity None: lines + 1 records (always enough); a smaller one raises EcalError with status -6 and .info["n_events"] =
+        the count needed.  A malformed line raises EcalError with status -1 and .info["first_bad_line"]."""
+        import torch
+        L = self._L
+        L.ecal_events_from_text_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(TextOptions), ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.POINTER(TextInfo), ctypes.c_void_p]
+        L.ecal_events_from_text_dev.restype = ctypes.c_int
+        o = self.text_options(**options)
+        t = self._text_tensor(text)
+        cap = self.text_count_lines(t) + 1 if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        info = TextInfo()
+        st = L.ecal_events_from_text_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(o), out.data_ptr(), cap,
+                                         ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def text_to_bin(self, txt_path, bin_path, **options):
+        """ecal_text_to_bin_file: the .bin the reference's txt2bin tool writes from txt_path (file order, no sort) -> info dict."""
+        L = self._L
+        L.ecal_text_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(TextOptions), ctypes.POINTER(TextInfo)]
+        L.ecal_text_to_bin_file.restype = ctypes.c_int
+        o = self.text_options(**options)
+        info = TextInfo()
+        st = L.ecal_text_to_bin_file(self._h, os.fsencode(txt_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_text_file(self, path, **options):
+        """ecal_stream_create_from_text_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
+        file is not) -> (events, info dict, t_first, t_last)."""
+        import torch
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(TextOptions), ctypes.POINTER(vp), ctypes.POINTER(TextInfo)]
+        L.ecal_stream_create_from_text_file.restype = ctypes.c_int
+        L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
+        L.ecal_stream_data.argtypes, L.ecal_stream_data.restype = [vp], vp
+        L.ecal_stream_times.argtypes, L.ecal_stream_times.restype = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int
+        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
+        o = self.text_options(**options)
+        info = TextInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_text_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        try:
+            n = int(L.ecal_stream_size(h))
+            events = torch.empty(n * 25, dtype=torch.uint8, device="cuda:%d" % self.device)
+            t0, t1 = ctypes.c_double(), ctypes.c_double()
+            self._check(L.ecal_stream_times(h, ctypes.byref(t0), ctypes.byref(t1)))
+            if n:
+                self._check(L.ecal_copy_dev(self._h, events.data_ptr(), L.ecal_stream_data(h), n * 25,
+                                            torch.cuda.current_stream(events.device).cuda_stream, 1))
+        finally:
+            L.ecal_stream_destroy(h)
+        return events, info.as_dict(), t0.value, t1.value
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

@@ -185,6 +185,9 @@ int ecal_extract_for_ctx(ecal_ctx *ctx, const double *d_xy, const uint32_t *d_se
                          const ecal_packed_points *pk = nullptr);
 // exclusive scan of nb per-block counts by one workgroup, off[nb] = the total (ecal_associate.hip: scan_blocks_kernel)
 int ecal_scan_blocks(ecal_ctx *ctx, const uint32_t *d_cnt, uint32_t nb, uint32_t *d_off, hipStream_t st);
+// an ecal_stream over device records the caller allocated (hipMalloc, n_events * 25 + 16 bytes; the stream owns them from here
+// on and frees them on an error), brought into time order like ecal_stream_create's (ecal_host.hip)
+int ecal_stream_adopt(ecal_ctx *ctx, uint8_t *d_events, uint64_t n_events, ecal_stream **out);
 // reference element order: the per-pixel bucket table of the hot-path slicer, built on first use (ecal_events.hip)
 int ecal_ensure_bucket_table(ecal_ctx *ctx, hipStream_t st);
 // tail scheduling (see ecal_ctx::tail_seen): slots of the stages' lists, and "may this call run lean?"

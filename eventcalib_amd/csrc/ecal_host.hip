@@ -52,6 +52,24 @@ extern "C" int ecal_stream_create(ecal_ctx *ctx, const uint8_t *events, uint64_t
     return ECAL_OK;
 }
 
+// A stream over records that are on the device already (d_events: hipMalloc'ed with 16 spare bytes, the stream's from here on,
+// freed on an error): the text ingest's way in (ecal_text.hip)
+int ecal_stream_adopt(ecal_ctx *ctx, uint8_t *d_events, uint64_t n_events, ecal_stream **out) {
+    *out = nullptr;
+    ecal_stream *s = new (std::nothrow) ecal_stream;
+    if (!s) {
+        (void) hipFree(d_events);
+        return ECAL_ERR_NOMEM;
+    }
+    s->ctx = ctx;
+    s->d_events = d_events;
+    s->n_events = n_events;
+    const int rc = finish_stream(ctx, s);
+    if (rc != ECAL_OK) return rc;
+    *out = s;
+    return ECAL_OK;
+}
+
 // The records are on the device: bring them into the multimap's order if they are not in it (frees the stream on an error)
 static int finish_stream(ecal_ctx *ctx, ecal_stream *s) {
     const uint64_t n_events = s->n_events;

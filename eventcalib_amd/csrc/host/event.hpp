@@ -93,6 +93,32 @@ public:
         }
         return counter;
     }
+    // txt2bin on the device (ecal_text_to_bin_file: the text uploaded and parsed in HBM): the same arguments, the same output
+    // file name, the same bytes in it for a text of one record per line, the same returned count.  A malformed line throws
+    // std::invalid_argument naming it (the reference stops silently there and writes a record of stale values).
+    static long long txt2binDevice(const std::string &txtFilePath, double timeMagnitude = 1e-6,
+                                   long long timeBase_in = std::numeric_limits<long long>::min(),
+                                   long long endTime_in = std::numeric_limits<long long>::min()) {
+        const ecal_text_options opt = textOptions(timeMagnitude, timeBase_in, endTime_in);
+        const auto dot = txtFilePath.find_last_of('.');
+        ecal_text_info info;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_text_to_bin_file(ctx, txtFilePath.c_str(), (txtFilePath.substr(0, dot) + ".bin").c_str(), &opt, &info);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("txt2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_text_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        return (long long) info.n_events;
+    }
+    // txt2bin's arguments as ecal_text_options (LLONG_MIN: no base / no end, as there)
+    static ecal_text_options textOptions(double timeMagnitude, long long timeBase_in, long long endTime_in) {
+        ecal_text_options opt;
+        ecal_text_default_options(&opt);
+        opt.time_magnitude = timeMagnitude;
+        opt.has_time_base = timeBase_in != std::numeric_limits<long long>::min();
+        opt.time_base = opt.has_time_base ? timeBase_in : 0;
+        opt.has_end_stamp = endTime_in != std::numeric_limits<long long>::min();
+        opt.end_stamp = opt.has_end_stamp ? endTime_in : 0;
+        return opt;
+    }
 
 private:
     void advance() {
@@ -140,6 +166,28 @@ struct EventContainer {
         if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
         fromFile_ = true;
     }
+    // The same from a text file of "stamp x y polarity" lines (ecal_stream_create_from_text_file): txt2bin's conversion
+    // (timeMagnitude, timeBase_in, endTime_in as EventStream::txt2bin takes them) and the reading loop above in one pass on the
+    // device, without the .bin in between.
+    void loadTextFile(const std::string &txtFilePath, double timeMagnitude = 1e-6,
+                      long long timeBase_in = std::numeric_limits<long long>::min(),
+                      long long endTime_in = std::numeric_limits<long long>::min(),
+                      double startTime = -std::numeric_limits<double>::infinity(), bool customEnd = false, double endTime = 0.0) {
+        release();
+        records.clear();
+        ecal_text_options opt = EventStream::textOptions(timeMagnitude, timeBase_in, endTime_in);
+        opt.start_time = startTime;
+        opt.has_end_time = customEnd ? 1 : 0;
+        opt.end_time = endTime;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_text_file(ctx, txtFilePath.c_str(), &opt, &stream_, &textInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadTextFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_text_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_text_info textInfo{};   // what the last loadTextFile saw (lines, drops, host-parsed lines)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

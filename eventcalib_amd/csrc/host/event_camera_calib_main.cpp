@@ -2,7 +2,8 @@
 // stream -> container -> keyframe search -> EventCalibIni::cvCalibration (+ rectifyFeatures per keyframe) ->
 // EventCalibSpline -> TrajectoryByEvent.txt.  Built by eventcalib_amd/csrc/Makefile (`make driver`, part of `all`) into
 // eventcalib_amd/unit_test_eventCameraCalib next to libecal.so; run by tests/test_gpu_shims.py and bench.py's end_to_end leg.
-//   usage: unit_test_eventCameraCalib settings.yaml events.bin saveDir [batch]     (the reference's argv, eventCameraCalib.cpp:105-110)
+//   usage: unit_test_eventCameraCalib settings.yaml events.bin saveDir [batch]     (the reference's argv, eventCameraCalib.cpp:105-110;
+//   with batch, an events path ending in .txt is a text file of "stamp x y polarity" lines, converted on the device)
 // "batch": rectifyFeatures of all keyframes in one device pass (ecal_rectify_keyframes) instead of one CirclesEventFrame per
 // keyframe, the file read in one piece, and a "stage <name> <seconds>" line per stage of the chain (bench.py's end_to_end leg).
 #include <chrono>
@@ -49,7 +50,18 @@ int main(int argc, char **argv) {
         (void) ecal_host::thread_ctx();   // HIP runtime + context start-up (0.2 - 0.3 s in a cold process): a stage of its own,
         stage("runtime_init");            // not part of reading the file
         es.close();
-        container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
+        const std::string eventsPath = argv[2];
+        if (eventsPath.size() >= 4 && eventsPath.compare(eventsPath.size() - 4, 4, ".txt") == 0) {
+            // a text file of "stamp x y polarity" lines: txt2bin's conversion and the loop below in one device pass.  Keys of this
+            // build, both optional: Text_TimeMagnitude (seconds per stamp unit, 1e-6), Text_TimeBase (absent: the first stamp)
+            double magnitude = 1e-6;
+            fsSettings["Text_TimeMagnitude"] >> magnitude;
+            long long timeBase = std::numeric_limits<long long>::min();
+            if (!fsSettings["Text_TimeBase"].isNone()) timeBase = std::strtoll(((std::string) fsSettings["Text_TimeBase"]).c_str(), nullptr, 10);
+            container->loadTextFile(eventsPath, magnitude, timeBase, std::numeric_limits<long long>::min(), startTime, customEnd, endTimeSetting);
+        } else {
+            container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
+        }
     }
     while (!es.isEnd()) {                                    // :154-163
         if (customEnd && es.current().timeStamp() >= endTimeSetting) break;

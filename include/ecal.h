@@ -961,6 +961,77 @@ int ecal_spline_fit(const double *u, const double *data, uint32_t m, uint32_t di
 int ecal_spline_eval(const double *knots, const double *cp, uint32_t n_cp, uint32_t dim, const double *u, uint32_t m,
                      double *out /*[m][dim]*/);
 
+/* ---- text ingest: "stamp x y polarity" lines into packed records, parsed in HBM ---------------------------
+ * Replaces EventStream::txt2bin (event/src/EventStream.cpp:25-67, tool event/tool/txt2bin.cpp) and the reading loop behind it
+ * (event_camera_calib/test/eventCameraCalib.cpp:154-163) for a text that is resident on the device.
+ *
+ * Input: a byte string.  A line ends at '\n'; a last line without '\n' counts.  One record per line: four fields separated
+ *   by spaces or tabs, blanks before and behind them allowed, one '\r' before the line break allowed.  Lines of blanks only
+ *   are skipped.  stamp = [+-]?[0-9]+ that fits an int64; x and y = [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)?; polarity = 0 or 1.
+ * Conversion: base = time_base when has_time_base, else the stamp of the first record line.  t = (double)(stamp - base) *
+ *   time_magnitude (one integer subtraction, one conversion, one multiplication, as the reference); x, y = the correctly
+ *   rounded doubles of their decimal strings (what `is >> double` gives on glibc); the polarity byte is 0 or 1.
+ * Filter, in file order: with has_end_stamp the first line whose stamp > end_stamp ends the stream (the reference's break: that
+ *   line and everything behind it are dropped); a record with t < 0 is dropped (the reference's continue); then the reading rule
+ *   of ecal_stream_create_from_file: kept if t >= start_time, and with has_end_time the first record with t >= end_time ends
+ *   the stream.
+ * The reference's last record: its loop is `while (is.good()) { is >> ...; write }`, so when the file ends in white space the
+ *   last pass extracts nothing and writes the last line's values once more.  With duplicate_last != 0 and a text that ends in
+ *   a blank, '\r' or '\n', the record of the last record line is emitted twice if it is emitted at all.
+ *   ecal_text_default_options: duplicate_last = 1 (the reference's bytes), time_magnitude = 1e-6, no base, no end stamp, no end
+ *   time, start_time = -inf.
+ * Differences from the reference, deliberate:
+ *   1. the reference reads tokens, so a record may span lines there; here one record is one line.
+ *   2. a malformed line is an error here: ECAL_ERR_INVALID, ecal_last_error and info->first_bad_line name the line (1-based).
+ *      The reference ends its loop silently on a failed read and writes a record of stale values (one record of zeros for a text
+ *      without any record line).
+ *   3. stamp - base outside int64 is undefined in the reference and not defended here (it wraps).
+ * Where the numbers are converted: the kernel converts a decimal of at most 15 significant digits whose decimal exponent
+ *   (written exponent minus fraction digits) lies in [-22, 22] — one exact IEEE operation.  A line with any other well-formed
+ *   number, or of more than 128 bytes, is parsed on the host with strtoll / strtod (info->n_host_lines counts them; the text and
+ *   its line table are downloaded for that, which a text without such lines never pays).
+ *
+ * ecal_events_from_text_dev: d_text (DEVICE, 16-byte aligned, n_bytes bytes; nothing behind n_bytes is read) into d_events
+ *   (DEVICE, room for `capacity` records, file order, not sorted).  info (HOST) is filled on ECAL_OK, on ECAL_ERR_RANGE
+ *   (capacity too small: info->n_events = the count needed, call again; also more than 2^32-1 lines) and on ECAL_ERR_INVALID
+ *   for a malformed line (first_bad_line).  On an error the contents of d_events are undefined.  Enqueues on `stream` and waits
+ *   for it: the call returns with the records in place.
+ * ecal_text_count_lines_dev: *n_lines (HOST) = lines of the text; lines + 1 is an upper bound for `capacity`.  Waits for `stream`.
+ * ecal_stream_create_from_text_file: the file through pinned buffers into HBM (reads overlapped with the uploads, as
+ *   ecal_stream_create_from_file), parsed there, the text freed, then the stream brought into time order if it is not
+ *   (ecal_stream_create's rule).  ECAL_ERR_RANGE beyond 2^32-1 events.  info may be NULL.
+ * ecal_text_to_bin_file: the .bin the reference's tool would write — the records in file order, no sort. */
+typedef struct ecal_text_options {
+    double time_magnitude;   /* seconds per stamp unit */
+    int has_time_base;       /* 0: the first record line's stamp */
+    int64_t time_base;
+    int has_end_stamp;
+    int64_t end_stamp;
+    double start_time;       /* seconds */
+    int has_end_time;
+    double end_time;         /* seconds */
+    int duplicate_last;
+} ecal_text_options;
+typedef struct ecal_text_info {
+    uint64_t n_lines;          /* lines of the text */
+    uint64_t n_blank;          /* lines of blanks only */
+    uint64_t n_events;         /* records written (the duplicated last record included), or needed */
+    uint64_t n_negative;       /* record lines dropped for t < 0 */
+    uint64_t n_after_end;      /* record lines from the one that ended the stream on (end stamp or end time) */
+    uint64_t n_before_start;   /* record lines dropped for t < start_time */
+    uint64_t n_host_lines;     /* lines parsed on the host */
+    uint64_t first_bad_line;   /* 1-based number of the first malformed line, 0: none */
+    int64_t time_base;         /* the base in force (0 for a text without a record line and without a given base) */
+} ecal_text_info;
+void ecal_text_default_options(ecal_text_options *opt);
+int ecal_events_from_text_dev(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const ecal_text_options *opt,
+                              uint8_t *d_events /*room for capacity records*/, uint64_t capacity, ecal_text_info *info, void *stream);
+int ecal_text_count_lines_dev(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t *n_lines, void *stream);
+int ecal_stream_create_from_text_file(ecal_ctx *ctx, const char *path, const ecal_text_options *opt, ecal_stream **out,
+                                      ecal_text_info *info);
+int ecal_text_to_bin_file(ecal_ctx *ctx, const char *txt_path, const char *bin_path, const ecal_text_options *opt,
+                          ecal_text_info *info);
+
 #ifdef __cplusplus
 }
 #endif
