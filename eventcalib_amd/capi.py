@@ -1284,9 +1284,10 @@ def calibrate_views(ctx: Context, obj, img, width, height, model=0, flags=0, asp
             "error_evaluations": res.error_evaluations, "seconds": res.seconds}
 
 
-def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspect_ratio=1.0, allreduce=None):
+def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspect_ratio=1.0, allreduce=None, intr_guess=None):
     """ecal_calibrate_fisheye_views: the fisheye init calibration with the library's start procedure (the reference's own start
-    first, the radial model's focal lengths as a guess when that fails).  Returns calibrate_views' dict + "start_used"."""
+    first, the radial model's focal lengths as a guess when that fails).  Returns calibrate_views' dict + "start_used".
+    intr_guess [12] goes with CALIB_USE_INTRINSIC_GUESS in flags (one run, start_used 2)."""
     L = ctx._L
     _declare_calib(L)
     obj = np.ascontiguousarray(obj, np.float64)
@@ -1301,6 +1302,9 @@ def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspe
         else:
             opt.allreduce = allreduce
     res = CalibResult()
+    if intr_guess is not None:
+        for j, v in enumerate(np.asarray(intr_guess, np.float64)[:12]):
+            res.intr[j] = float(v)
     rv, tv, pe = np.zeros((V, 3)), np.zeros((V, 3)), np.zeros(V)
     used = ctypes.c_int(-1)
     L.ecal_calibrate_fisheye_views.restype = ctypes.c_int
@@ -1327,6 +1331,27 @@ def pnp_batch_dev(ctx: Context, d_obj, n_pts, d_img, d_valid, n_frames, model, d
     _declare_calib(ctx._L)
     ctx._check(ctx._L.ecal_pnp_batch_dev(ctx._h, d_obj, n_pts, d_img, d_valid, n_frames, model, d_intr, float(reproj_thresh),
                                          int(rounds), int(refine_iters), d_pose, d_inlier, d_err, d_ok, stream))
+
+
+def pnp_batch(ctx: Context, obj, img, valid, model, intr, reproj_thresh, rounds, refine_iters):
+    """ecal_pnp_batch, the host-buffer form of pnp_batch_dev: obj [n][3], img [F][n][2], valid [F][n] uint32 or None, intr [12].
+    Returns {"pose" [F][6], "inlier" [F][n] uint32, "err" [F], "ok" [F] uint32}."""
+    L = ctx._L
+    vp, i32, u32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_double
+    L.ecal_pnp_batch.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp, f64, i32, i32, vp, vp, vp, vp]
+    L.ecal_pnp_batch.restype = i32
+    obj = np.ascontiguousarray(obj, np.float64)
+    n = obj.shape[0]
+    img = np.ascontiguousarray(img, np.float64).reshape(-1, n, 2)
+    F = img.shape[0]
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64)[:12])
+    if valid is not None:
+        valid = np.ascontiguousarray(valid, np.uint32).reshape(F, n)
+    pose, inl, err, ok = np.zeros((F, 6)), np.zeros((F, n), np.uint32), np.zeros(F), np.zeros(F, np.uint32)
+    ctx._check(L.ecal_pnp_batch(ctx._h, _ptr(obj), n, _ptr(img), _ptr(valid) if valid is not None else None, F, int(model),
+                                _ptr(intr), float(reproj_thresh), int(rounds), int(refine_iters), _ptr(pose), _ptr(inl), _ptr(err),
+                                _ptr(ok)))
+    return {"pose": pose, "inlier": inl, "err": err, "ok": ok}
 
 
 def spline_fit(u, data, n_cp):
