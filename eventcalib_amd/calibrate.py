@@ -99,6 +99,15 @@ def load_events_text(ctx, path, **options):
     return events, t_first, t_last
 
 
+def load_events_raw(ctx, path, **options):
+    """A Prophesee .raw recording (EVT3 or EVT2, the format from its header) -> (events, t_first, t_last) as calibrate_stream takes
+    them: uploaded and decoded on the device (capi.Context.stream_from_raw_file), in time order.
+    options: capi.Context.raw_options' (format, time_base, width, height, start_time, end_time).  These sensors are 640x480 and
+    larger: their windows run through the general detection tiers, not the 346x260 fast path."""
+    events, _info, t_first, t_last = ctx.stream_from_raw_file(path, **options)
+    return events, t_first, t_last
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,

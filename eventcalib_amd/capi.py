@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "ecal_board_image_default_options", "ecal_solver_board_image_dev", "ecal_solver_board_image", "ecal_solver_board_points_dev", "ecal_solver_board_points",
     "ecal_solver_reassociate_dev", "ecal_solver_reassociate", "ecal_solver_create_reassociated",
     "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
+    "ecal_raw_default_options", "ecal_raw_block_words", "ecal_raw_count_events_dev", "ecal_events_from_raw_dev", "ecal_stream_create_from_raw_file", "ecal_raw_to_bin_file",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -58,6 +59,34 @@ class TextInfo(ctypes.Structure):
     _fields_ = [("n_lines", ctypes.c_uint64), ("n_blank", ctypes.c_uint64), ("n_events", ctypes.c_uint64),
                 ("n_negative", ctypes.c_uint64), ("n_after_end", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64),
                 ("n_host_lines", ctypes.c_uint64), ("first_bad_line", ctypes.c_uint64), ("time_base", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+RAW_AUTO, RAW_EVT2, RAW_EVT3 = 0, 2, 3   # ECAL_RAW_AUTO / _EVT2 / _EVT3
+_RAW_FORMATS = {None: RAW_AUTO, "auto": RAW_AUTO, "evt2": RAW_EVT2, "evt3": RAW_EVT3}
+
+
+def raw_format(fmt):
+    """"EVT2" / "EVT3" / None (from the file header), or the ECAL_RAW_* number, as the number"""
+    if isinstance(fmt, str) or fmt is None:
+        return _RAW_FORMATS[fmt.lower() if fmt else None]
+    return int(fmt)
+
+
+class RawOptions(ctypes.Structure):
+    """ecal_raw_options (include/ecal.h, raw ingest)."""
+    _fields_ = [("format", ctypes.c_int), ("time_base", ctypes.c_int64), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("start_time", ctypes.c_double), ("has_end_time", ctypes.c_int), ("end_time", ctypes.c_double)]
+
+
+class RawInfo(ctypes.Structure):
+    """ecal_raw_info (include/ecal.h, raw ingest)."""
+    _fields_ = [("n_words", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("n_no_state", ctypes.c_uint64),
+                ("n_outside", ctypes.c_uint64), ("n_negative", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64),
+                ("n_after_end", ctypes.c_uint64), ("n_other_words", ctypes.c_uint64), ("n_trailing_bytes", ctypes.c_uint64),
+                ("n_time_wraps", ctypes.c_uint64), ("format", ctypes.c_int), ("header_bytes", ctypes.c_uint64)]
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
@@ -421,16 +450,24 @@ class Context:
         vp = ctypes.c_void_p
         L.ecal_stream_create_from_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(TextOptions), ctypes.POINTER(vp), ctypes.POINTER(TextInfo)]
         L.ecal_stream_create_from_text_file.restype = ctypes.c_int
-        L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
-        L.ecal_stream_data.argtypes, L.ecal_stream_data.restype = [vp], vp
-        L.ecal_stream_times.argtypes, L.ecal_stream_times.restype = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int
-        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
         o = self.text_options(**options)
         info = TextInfo()
         h = vp()
         st = L.ecal_stream_create_from_text_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
         if st != 0:
             self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    def _stream_records(self, h):
+        """the records of the ecal_stream h copied into a uint8 CUDA tensor, its first and last time; destroys the stream"""
+        import torch
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
+        L.ecal_stream_data.argtypes, L.ecal_stream_data.restype = [vp], vp
+        L.ecal_stream_times.argtypes, L.ecal_stream_times.restype = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int
+        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
         try:
             n = int(L.ecal_stream_size(h))
             events = torch.empty(n * 25, dtype=torch.uint8, device="cuda:%d" % self.device)
@@ -441,7 +478,90 @@ class Context:
                                             torch.cuda.current_stream(events.device).cuda_stream, 1))
         finally:
             L.ecal_stream_destroy(h)
-        return events, info.as_dict(), t0.value, t1.value
+        return events, t0.value, t1.value
+
+    # ---- raw ingest: Prophesee EVT3 / EVT2 payloads decoded in HBM (ecal_events_from_raw_dev and the file forms) ----
+    def raw_options(self, format=None, time_base=0, width=0, height=0, start_time=None, end_time=None):
+        """ecal_raw_options from ecal_raw_default_options: format "EVT2" / "EVT3" / None (from the file header), time_base in
+        microseconds of the camera's clock, width / height 0 = no bound, start_time None = -inf, end_time None = to the end."""
+        L = self._L
+        L.ecal_raw_default_options.argtypes = [ctypes.POINTER(RawOptions)]
+        L.ecal_raw_default_options.restype = None
+        o = RawOptions()
+        L.ecal_raw_default_options(ctypes.byref(o))
+        o.format, o.time_base, o.width, o.height = raw_format(format), int(time_base), int(width), int(height)
+        if start_time is not None:
+            o.start_time = float(start_time)
+        if end_time is not None:
+            o.has_end_time, o.end_time = 1, float(end_time)
+        return o
+
+    def raw_block_words(self, format):
+        """ecal_raw_block_words: words per decode block of this build."""
+        self._L.ecal_raw_block_words.argtypes, self._L.ecal_raw_block_words.restype = [ctypes.c_int], ctypes.c_uint32
+        return int(self._L.ecal_raw_block_words(raw_format(format)))
+
+    def raw_count_events(self, payload, format):
+        """ecal_raw_count_events_dev: the events the payload's words emit before any drop (always a sufficient capacity)."""
+        import torch
+        L = self._L
+        L.ecal_raw_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.c_void_p]
+        L.ecal_raw_count_events_dev.restype = ctypes.c_int
+        t = self._text_tensor(payload)
+        n = ctypes.c_uint64()
+        self._check(L.ecal_raw_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), raw_format(format), ctypes.byref(n),
+                                                torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def events_from_raw(self, payload, format, capacity=None, **options):
+        """ecal_events_from_raw_dev: payload (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where it
+        is; no file header) -> (packed 25-byte records in file order as a uint8 CUDA tensor [n_events * 25], info dict).  options:
+        raw_options'.  capacity None: raw_count_events (always enough); a smaller one raises EcalError with status -6 and
+        .info["n_events"] = the count needed."""
+        import torch
+        L = self._L
+        L.ecal_events_from_raw_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(RawOptions), ctypes.c_void_p,
+                                               ctypes.c_uint64, ctypes.POINTER(RawInfo), ctypes.c_void_p]
+        L.ecal_events_from_raw_dev.restype = ctypes.c_int
+        o = self.raw_options(format=format, **options)
+        t = self._text_tensor(payload)
+        cap = self.raw_count_events(t, format) if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        info = RawInfo()
+        st = L.ecal_events_from_raw_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(o), out.data_ptr(), cap,
+                                        ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def raw_to_bin(self, raw_path, bin_path, **options):
+        """ecal_raw_to_bin_file: the records of the .raw file (file order, no sort) as a .bin of the reference's layout -> info dict."""
+        L = self._L
+        L.ecal_raw_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(RawOptions), ctypes.POINTER(RawInfo)]
+        L.ecal_raw_to_bin_file.restype = ctypes.c_int
+        o = self.raw_options(**options)
+        info = RawInfo()
+        st = L.ecal_raw_to_bin_file(self._h, os.fsencode(raw_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_raw_file(self, path, **options):
+        """ecal_stream_create_from_raw_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
+        file is not) -> (events, info dict, t_first, t_last)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_raw_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(RawOptions), ctypes.POINTER(vp), ctypes.POINTER(RawInfo)]
+        L.ecal_stream_create_from_raw_file.restype = ctypes.c_int
+        o = self.raw_options(**options)
+        info = RawInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_raw_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

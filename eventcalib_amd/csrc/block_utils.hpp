@@ -85,4 +85,19 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const double *kf_time, uint
     return lo;
 }
 
+// 16 bytes at text + off as four words, bytes at or behind n_scan as zeros: nothing behind n_scan is read
+__device__ __forceinline__ uint4 load16_clipped(const uint8_t *__restrict__ text, uint64_t off, uint64_t n_scan) {
+    uint4 w = make_uint4(0u, 0u, 0u, 0u);
+    if (off + 16u <= n_scan) {
+        w = *reinterpret_cast<const uint4 *>(text + off);   // (16-byte aligned: the buffer is, off is a multiple of 16)
+    } else if (off < n_scan) {
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++)
+            if (off + j < n_scan) v[j >> 2] |= (uint32_t) text[off + j] << (8u * (j & 3u));
+        w = make_uint4(v[0], v[1], v[2], v[3]);
+    }
+    return w;
+}
+
 }  // namespace ecal

@@ -188,6 +188,38 @@ int ecal_scan_blocks(ecal_ctx *ctx, const uint32_t *d_cnt, uint32_t nb, uint32_t
 // an ecal_stream over device records the caller allocated (hipMalloc, n_events * 25 + 16 bytes; the stream owns them from here
 // on and frees them on an error), brought into time order like ecal_stream_create's (ecal_host.hip)
 int ecal_stream_adopt(ecal_ctx *ctx, uint8_t *d_events, uint64_t n_events, ecal_stream **out);
+// The bytes of a file from file_offset on into a device buffer (16-byte aligned, 16 spare bytes behind; the caller's to hipFree):
+// chunks read by a few threads into pinned buffers of their own, every chunk's upload enqueued as soon as it is read.  `who`
+// opens the error texts.  (ecal_text.hip; the text ingest and the raw ingest)
+int ecal_upload_file(ecal_ctx *ctx, const char *who, const char *path, uint64_t file_offset, uint8_t **d_out, uint64_t *n_bytes_out);
+// n_events packed records on the device into the file bin_path, through pinned staging, a chunk at a time (ecal_text.hip)
+int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path);
+// ECAL_TRACE=load: device time of an ingest's phases, "ecal <what> ingest: <phase> <ms>" lines on stderr when it goes out of scope
+struct ecal_load_timer {
+    const char *what;
+    bool on;
+    hipStream_t st;
+    hipEvent_t ev[8] = {};
+    const char *name[8] = {};
+    int n = 0;
+    ecal_load_timer(const char *what_, bool enabled, hipStream_t s) : what(what_), on(enabled), st(s) {}
+    void mark(const char *phase) {
+        if (!on || n >= 8) return;
+        if (hipEventCreate(&ev[n]) != hipSuccess) {
+            on = false;
+            return;
+        }
+        (void) hipEventRecord(ev[n], st);
+        name[n++] = phase;
+    }
+    ~ecal_load_timer() {
+        for (int i = 1; i < n && on; i++) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) fprintf(stderr, "ecal %s ingest: %-24s %.3f ms\n", what, name[i], ms);
+        }
+        for (int i = 0; i < n; i++) (void) hipEventDestroy(ev[i]);
+    }
+};
 // reference element order: the per-pixel bucket table of the hot-path slicer, built on first use (ecal_events.hip)
 int ecal_ensure_bucket_table(ecal_ctx *ctx, hipStream_t st);
 // tail scheduling (see ecal_ctx::tail_seen): slots of the stages' lists, and "may this call run lean?"

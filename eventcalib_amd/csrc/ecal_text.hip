@@ -66,21 +66,6 @@ __device__ __forceinline__ uint32_t tx_newline_mask(uint32_t w) {
     return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
 }
 
-// the thread's 16 bytes of the span as four words, bytes at or behind n_scan as zeros
-__device__ __forceinline__ uint4 tx_load16(const uint8_t *__restrict__ text, uint64_t off, uint64_t n_scan) {
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    if (off + 16u <= n_scan) {
-        w = *reinterpret_cast<const uint4 *>(text + off);   // (16-byte aligned: the text is, off is a multiple of 16)
-    } else if (off < n_scan) {
-        uint32_t v[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (uint32_t j = 0; j < 16; j++)
-            if (off + j < n_scan) v[j >> 2] |= (uint32_t) text[off + j] << (8u * (j & 3u));
-        w = make_uint4(v[0], v[1], v[2], v[3]);
-    }
-    return w;
-}
-
 __device__ __forceinline__ uint32_t tx_count16(const uint4 &w) {
     return (uint32_t) (__popc(tx_newline_mask(w.x)) + __popc(tx_newline_mask(w.y)) + __popc(tx_newline_mask(w.z)) +
                        __popc(tx_newline_mask(w.w)));
@@ -92,7 +77,7 @@ __global__ __launch_bounds__(TX_T) void text_count_kernel(const uint8_t *__restr
     __shared__ uint32_t s_red[TX_T / 64];
     const int tid = threadIdx.x;
     const uint64_t off = (uint64_t) blockIdx.x * TX_SPAN + (uint64_t) tid * 16u;
-    uint32_t c = tx_count16(tx_load16(text, off, n_scan));
+    uint32_t c = tx_count16(load16_clipped(text, off, n_scan));
     for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
     if ((tid & 63) == 0) s_red[tid >> 6] = c;
     __syncthreads();
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(TX_T) void text_offsets_kernel(const uint8_t *__res
     __shared__ unsigned long long s_red[TX_T / 64];
     const int tid = threadIdx.x;
     const uint64_t off = (uint64_t) blockIdx.x * TX_SPAN + (uint64_t) tid * 16u;
-    const uint4 w = tx_load16(text, off, n_scan);
+    const uint4 w = load16_clipped(text, off, n_scan);
     const uint32_t words[4] = {w.x, w.y, w.z, w.w};
     uint32_t ex, eb, tot, tb;
     block_exscan_pair<TX_T>(tx_count16(w), 0u, s_red, &ex, &eb, &tot, &tb);
@@ -367,31 +352,6 @@ extern "C" void ecal_text_default_options(ecal_text_options *opt) {
 
 namespace {
 
-struct TextTimer {   // ECAL_TRACE=load: device time of the phases, on stderr
-    bool on;
-    hipStream_t st;
-    hipEvent_t ev[8] = {};
-    const char *name[8] = {};
-    int n = 0;
-    TextTimer(bool enabled, hipStream_t s) : on(enabled), st(s) {}
-    void mark(const char *what) {
-        if (!on || n >= 8) return;
-        if (hipEventCreate(&ev[n]) != hipSuccess) {
-            on = false;
-            return;
-        }
-        (void) hipEventRecord(ev[n], st);
-        name[n++] = what;
-    }
-    ~TextTimer() {
-        for (int i = 1; i < n && on; i++) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) fprintf(stderr, "ecal text ingest: %-24s %.3f ms\n", name[i], ms);
-        }
-        for (int i = 0; i < n; i++) (void) hipEventDestroy(ev[i]);
-    }
-};
-
 struct TextArrays {
     uint64_t *line_off;
     int64_t *stamp;
@@ -500,7 +460,7 @@ int text_ingest(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const ec
         return ECAL_OK;
     }
     const bool trace = ctx->sw.load_trace;
-    TextTimer tm(trace, st);
+    ecal_load_timer tm("text", trace, st);
     ecal_devbuf idx, lines, words;
     int rc = ecal_ensure(ctx, words, sizeof(TextWords));
     if (rc) return rc;
@@ -604,23 +564,41 @@ int text_check_args(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes) {
     return ECAL_OK;
 }
 
-// the whole file into a device buffer (the caller's to hipFree): chunks read by a few threads into pinned buffers of their own,
-// every chunk's upload enqueued as soon as it is read
-int text_upload_file(ecal_ctx *ctx, const char *path, uint8_t **d_text_out, uint64_t *n_bytes_out) {
+// file -> text in HBM -> records in a device buffer of their own (null for none), the text freed
+int text_file_to_events(ecal_ctx *ctx, const char *path, const ecal_text_options *opt, uint8_t **d_events, ecal_text_info *info) {
+    *d_events = nullptr;
+    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool trace = ctx->sw.load_trace;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t *d_text = nullptr;
+    uint64_t n_bytes = 0;
+    int rc = ecal_upload_file(ctx, "text ingest", path, 0, &d_text, &n_bytes);
+    if (rc) return rc;
+    if (trace)
+        fprintf(stderr, "ecal text ingest: %-24s %.3f ms\n", "file read + upload",
+                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    rc = text_ingest(ctx, d_text, n_bytes, opt, nullptr, 0, d_events, info, ctx->stream);
+    (void) hipFree(d_text);
+    return rc;
+}
+
+}  // namespace
+
+int ecal_upload_file(ecal_ctx *ctx, const char *who, const char *path, uint64_t file_offset, uint8_t **d_text_out, uint64_t *n_bytes_out) {
     *d_text_out = nullptr;
     *n_bytes_out = 0;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) {
-        ctx->last_error = std::string("text ingest: cannot open ") + path;
+        ctx->last_error = std::string(who) + ": cannot open " + path;
         return ECAL_ERR_INVALID;
     }
     struct stat sb;
     if (fstat(fd, &sb) != 0) {
         close(fd);
-        ctx->last_error = std::string("text ingest: cannot stat ") + path;
+        ctx->last_error = std::string(who) + ": cannot stat " + path;
         return ECAL_ERR_INVALID;
     }
-    const uint64_t n = (uint64_t) sb.st_size;
+    const uint64_t n = (uint64_t) sb.st_size > file_offset ? (uint64_t) sb.st_size - file_offset : 0;
     constexpr uint64_t CH = 16ull << 20;
     constexpr int NT = 6;
     uint8_t *pin[NT] = {};
@@ -642,7 +620,7 @@ int text_upload_file(ecal_ctx *ctx, const char *path, uint8_t **d_text_out, uint
                 if (k >= (uint64_t) nt && hipEventSynchronize(done[b]) != hipSuccess) io_error = true;   // the buffer's previous upload
                 uint64_t got = 0;
                 while (got < want && !io_error) {
-                    const ssize_t rd = pread(fd, pin[b] + got, want - got, (off_t) (b0 + got));
+                    const ssize_t rd = pread(fd, pin[b] + got, want - got, (off_t) (file_offset + b0 + got));
                     if (rd <= 0) io_error = true;
                     else got += (uint64_t) rd;
                 }
@@ -664,8 +642,8 @@ int text_upload_file(ecal_ctx *ctx, const char *path, uint8_t **d_text_out, uint
     }
     close(fd);
     if (e != hipSuccess || io_error) {
-        ctx->last_error = e != hipSuccess ? std::string("text ingest: ") + hipGetErrorString(e)
-                                          : std::string("text ingest: read or copy failed for ") + path;
+        ctx->last_error = e != hipSuccess ? std::string(who) + ": " + hipGetErrorString(e)
+                                          : std::string(who) + ": read or copy failed for " + path;
         if (d_text) (void) hipFree(d_text);
         return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
     }
@@ -674,25 +652,44 @@ int text_upload_file(ecal_ctx *ctx, const char *path, uint8_t **d_text_out, uint
     return ECAL_OK;
 }
 
-// file -> text in HBM -> records in a device buffer of their own (null for none), the text freed
-int text_file_to_events(ecal_ctx *ctx, const char *path, const ecal_text_options *opt, uint8_t **d_events, ecal_text_info *info) {
-    *d_events = nullptr;
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool trace = ctx->sw.load_trace;
-    const auto t0 = std::chrono::steady_clock::now();
-    uint8_t *d_text = nullptr;
-    uint64_t n_bytes = 0;
-    int rc = text_upload_file(ctx, path, &d_text, &n_bytes);
-    if (rc) return rc;
-    if (trace)
-        fprintf(stderr, "ecal text ingest: %-24s %.3f ms\n", "file read + upload",
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    rc = text_ingest(ctx, d_text, n_bytes, opt, nullptr, 0, d_events, info, ctx->stream);
-    (void) hipFree(d_text);
+int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path) {
+    const int fd = open(bin_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) {
+        ctx->last_error = std::string(who) + ": cannot write " + bin_path;
+        return ECAL_ERR_INVALID;
+    }
+    // the records come down through pinned staging, a chunk at a time
+    const uint64_t bytes = n_events * 25;
+    const size_t CH = 32u << 20;
+    unsigned char *stage = bytes ? ecal_fetch_pinned(ctx, (size_t) std::min<uint64_t>(CH, bytes)) : nullptr;
+    std::vector<unsigned char> pageable;
+    if (bytes && !stage) {
+        pageable.resize((size_t) std::min<uint64_t>(CH, bytes));
+        stage = pageable.data();
+    }
+    int rc = ECAL_OK;
+    for (uint64_t at = 0; at < bytes && rc == ECAL_OK; at += CH) {
+        const size_t n = (size_t) std::min<uint64_t>(CH, bytes - at);
+        if (hipMemcpy(stage, d_events + at, n, hipMemcpyDeviceToHost) != hipSuccess) {
+            ctx->last_error = std::string(who) + ": download failed";
+            rc = ECAL_ERR_HIP;
+        }
+        for (size_t put = 0; put < n && rc == ECAL_OK;) {
+            const ssize_t wr = write(fd, stage + put, n - put);
+            if (wr <= 0) {
+                ctx->last_error = std::string(who) + ": write failed for " + bin_path;
+                rc = ECAL_ERR_INVALID;
+            } else {
+                put += (size_t) wr;
+            }
+        }
+    }
+    if (close(fd) != 0 && rc == ECAL_OK) {
+        ctx->last_error = std::string(who) + ": write failed for " + bin_path;
+        rc = ECAL_ERR_INVALID;
+    }
     return rc;
 }
-
-}  // namespace
 
 extern "C" int ecal_text_count_lines_dev(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t *n_lines, void *stream) {
     if (!ctx || !n_lines) return ECAL_ERR_INVALID;
@@ -758,42 +755,7 @@ extern "C" int ecal_text_to_bin_file(ecal_ctx *ctx, const char *txt_path, const 
     int rc = text_file_to_events(ctx, txt_path, opt, &d_events, &I);
     if (info) *info = I;
     if (rc) return rc;
-    const int fd = open(bin_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) {
-        if (d_events) (void) hipFree(d_events);
-        ctx->last_error = std::string("ecal_text_to_bin_file: cannot write ") + bin_path;
-        return ECAL_ERR_INVALID;
-    }
-    // the records come down through pinned staging, a chunk at a time
-    const uint64_t bytes = I.n_events * 25;
-    const size_t CH = 32u << 20;
-    unsigned char *stage = bytes ? ecal_fetch_pinned(ctx, (size_t) std::min<uint64_t>(CH, bytes)) : nullptr;
-    std::vector<unsigned char> pageable;
-    if (bytes && !stage) {
-        pageable.resize((size_t) std::min<uint64_t>(CH, bytes));
-        stage = pageable.data();
-    }
-    rc = ECAL_OK;
-    for (uint64_t at = 0; at < bytes && rc == ECAL_OK; at += CH) {
-        const size_t n = (size_t) std::min<uint64_t>(CH, bytes - at);
-        if (hipMemcpy(stage, d_events + at, n, hipMemcpyDeviceToHost) != hipSuccess) {
-            ctx->last_error = "ecal_text_to_bin_file: download failed";
-            rc = ECAL_ERR_HIP;
-        }
-        for (size_t put = 0; put < n && rc == ECAL_OK;) {
-            const ssize_t wr = write(fd, stage + put, n - put);
-            if (wr <= 0) {
-                ctx->last_error = std::string("ecal_text_to_bin_file: write failed for ") + bin_path;
-                rc = ECAL_ERR_INVALID;
-            } else {
-                put += (size_t) wr;
-            }
-        }
-    }
-    if (close(fd) != 0 && rc == ECAL_OK) {
-        ctx->last_error = std::string("ecal_text_to_bin_file: write failed for ") + bin_path;
-        rc = ECAL_ERR_INVALID;
-    }
+    rc = ecal_write_records_file(ctx, "ecal_text_to_bin_file", d_events, I.n_events, bin_path);
     if (d_events) (void) hipFree(d_events);
     return rc;
 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../../include/ecal.h"
+#include "../raw_events.hpp"
 #include "dbscan.h"
 
 namespace opengv2 {
@@ -108,6 +109,52 @@ public:
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_text_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
         return (long long) info.n_events;
     }
+    // A Prophesee .raw recording (EVT3 / EVT2; include/ecal.h, "raw ingest") -> .bin beside it, on one host thread: the header,
+    // then the plain sequential decoder of raw_events.hpp, the records in file order.  The baseline of raw2binDevice, and its
+    // check: both write the same bytes.  opt null: the defaults (format from the header, the camera's clock, no bounds).
+    static long long raw2bin(const std::string &rawFilePath, const ecal_raw_options *opt = nullptr, ecal_raw_info *info = nullptr) {
+        std::ifstream is(rawFilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + rawFilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("raw2bin: cannot read " + rawFilePath);
+        ecal_raw_options o;
+        if (opt) o = *opt; else ecal_raw_default_options(&o);
+        int headerFormat = ECAL_RAW_AUTO;
+        uint64_t headerBytes = 0;
+        (void) ecal_raw::raw_parse_header(bytes.data(), bytes.size(), true, &headerFormat, &headerBytes);
+        const int format = o.format != ECAL_RAW_AUTO ? o.format : headerFormat;
+        if (format != ECAL_RAW_EVT2 && format != ECAL_RAW_EVT3) throw std::invalid_argument("raw2bin: no format option and no format line in the header of " + rawFilePath);
+        const ecal_raw::RawFilter f{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time};
+        ecal_raw::RawCounts c;
+        std::vector<uint8_t> out;
+        auto put = [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); };
+        const uint8_t *payload = bytes.data() + headerBytes;
+        const uint64_t n = bytes.size() - headerBytes;
+        if (format == ECAL_RAW_EVT3) ecal_raw::raw_decode_sequential<ecal_raw::Evt3>(payload, n, f, c, put);
+        else ecal_raw::raw_decode_sequential<ecal_raw::Evt2>(payload, n, f, c, put);
+        const auto dot = rawFilePath.find_last_of('.');
+        std::ofstream os(rawFilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info)
+            *info = ecal_raw_info{c.n_words, c.n_events, c.n_no_state, c.n_outside, c.n_negative, c.n_before_start, c.n_after_end,
+                                  c.n_other_words, c.n_trailing_bytes, c.n_time_wraps, format, headerBytes};
+        return (long long) c.n_events;
+    }
+    // raw2bin on the device (ecal_raw_to_bin_file: the payload uploaded and decoded in HBM): the same arguments, the same output
+    // file name, the same bytes in it, the same returned count
+    static long long raw2binDevice(const std::string &rawFilePath, const ecal_raw_options *opt = nullptr, ecal_raw_info *info = nullptr) {
+        const auto dot = rawFilePath.find_last_of('.');
+        ecal_raw_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_raw_to_bin_file(ctx, rawFilePath.c_str(), (rawFilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("raw2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_raw_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // txt2bin's arguments as ecal_text_options (LLONG_MIN: no base / no end, as there)
     static ecal_text_options textOptions(double timeMagnitude, long long timeBase_in, long long endTime_in) {
         ecal_text_options opt;
@@ -188,6 +235,20 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_text_info textInfo{};   // what the last loadTextFile saw (lines, drops, host-parsed lines)
+    // The same from a Prophesee .raw recording (ecal_stream_create_from_raw_file): decoded on the device, without a .bin in
+    // between.  opt null: the defaults; the reading loop's startTime / customEnd / endTime go into opt's start_time / end_time.
+    void loadRawFile(const std::string &rawFilePath, const ecal_raw_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_raw_file(ctx, rawFilePath.c_str(), opt, &stream_, &rawInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadRawFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_raw_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_raw_info rawInfo{};     // what the last loadRawFile saw (words, drops, wraps, the format in force)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

@@ -59,6 +59,23 @@ int main(int argc, char **argv) {
             long long timeBase = std::numeric_limits<long long>::min();
             if (!fsSettings["Text_TimeBase"].isNone()) timeBase = std::strtoll(((std::string) fsSettings["Text_TimeBase"]).c_str(), nullptr, 10);
             container->loadTextFile(eventsPath, magnitude, timeBase, std::numeric_limits<long long>::min(), startTime, customEnd, endTimeSetting);
+        } else if (eventsPath.size() >= 4 && eventsPath.compare(eventsPath.size() - 4, 4, ".raw") == 0) {
+            // a Prophesee recording (EVT3 / EVT2) decoded on the device.  Keys of this build, both optional: Raw_Format ("EVT2" /
+            // "EVT3"; absent: from the file's header), Raw_TimeBase (microseconds of the camera's clock, 0).  Events outside
+            // Camera.width x Camera.height are dropped.
+            ecal_raw_options opt;
+            ecal_raw_default_options(&opt);
+            if (!fsSettings["Raw_Format"].isNone()) {
+                const std::string fmt = fsSettings["Raw_Format"];
+                opt.format = fmt == "EVT2" ? ECAL_RAW_EVT2 : fmt == "EVT3" ? ECAL_RAW_EVT3 : -1;   // (-1: refused by the library)
+            }
+            if (!fsSettings["Raw_TimeBase"].isNone()) opt.time_base = std::strtoll(((std::string) fsSettings["Raw_TimeBase"]).c_str(), nullptr, 10);
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            opt.start_time = startTime;
+            opt.has_end_time = customEnd ? 1 : 0;
+            opt.end_time = endTimeSetting;
+            container->loadRawFile(eventsPath, &opt);
         } else {
             container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
         }

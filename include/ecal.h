@@ -1032,6 +1032,88 @@ int ecal_stream_create_from_text_file(ecal_ctx *ctx, const char *path, const eca
 int ecal_text_to_bin_file(ecal_ctx *ctx, const char *txt_path, const char *bin_path, const ecal_text_options *opt,
                           ecal_text_info *info);
 
+/* ---- raw ingest: Prophesee EVT3 / EVT2 recordings into packed records, decoded in HBM -----------------------
+ * A camera's .raw file, without a host converter in front.  Nothing in the reference reads these encodings: this contract is the
+ * specification (eventcalib_amd/csrc/raw_events.hpp restates it for the kernels, the host decoder and the tests).
+ *
+ * File header (file entry points only): the maximal run of lines that begin with '%' at the start of the file, each ending at
+ *   '\n'.  A line that is exactly "% end" closes the header even if more '%' lines follow.  The format is taken from the first
+ *   line of one of the forms "% evt 3.0", "% evt 2.0", "% format EVT3", "% format EVT2" (the last two optionally followed by
+ *   ";key=value...").  options.format other than ECAL_RAW_AUTO overrides the header; no format from either source is
+ *   ECAL_ERR_INVALID.  The payload starts behind the header.  The header must end within the first MiB of the file.  The _dev entry
+ *   points take the payload only, with an explicit format.
+ * EVT3 payload: little-endian 16-bit words, type = bits 15..12; a trailing odd byte is ignored (info.n_trailing_bytes).
+ *   0x0 ADDR_Y       y = bits 10..0 (bit 11 is ignored)
+ *   0x2 ADDR_X       emits one event: x = bits 10..0, polarity = bit 11, the current y.  Changes no state.
+ *   0x3 VECT_BASE_X  base_x = bits 10..0, vector polarity = bit 11
+ *   0x4 VECT_12      for every set bit i of bits 11..0, ascending: an event at x = base_x + i with the vector polarity; then
+ *                    base_x += 12 (base_x is held in 32 bits)
+ *   0x5 VECT_8       the same with bits 7..0 and += 8 (bits 11..8 are ignored)
+ *   0x6 TIME_LOW     low = bits 11..0
+ *   0x8 TIME_HIGH    high = bits 11..0.  Between two consecutive TIME_HIGH words with values p then q one wrap is counted when
+ *                    q < p and p - q > 2048; a smaller backward step is taken as is (time then runs backwards; a stream sorts)
+ *   every other type (0x7, 0xA, 0xE, 0xF, the unassigned ones: triggers among them) is skipped and counted in info.n_other_words.
+ *   Event time in microseconds: t_us = (wraps << 24) | (high << 12) | low, an int64; low is 0 until the first TIME_LOW and
+ *   persists across TIME_HIGH words.  An event emitted before the first TIME_HIGH, before the first ADDR_Y, or — a vector event —
+ *   before the first VECT_BASE_X is dropped and counted in info.n_no_state (a vector word without a base advances nothing).
+ * EVT2 payload: little-endian 32-bit words, type = bits 31..28; 1 - 3 trailing bytes are ignored and counted.
+ *   0x0 CD_OFF / 0x1 CD_ON  one event of polarity 0 / 1: low6 = bits 27..22, x = bits 21..11, y = bits 10..0
+ *   0x8 TIME_HIGH           high = bits 27..0
+ *   t_us = (high << 6) | low6.  There is NO wrap handling: 2^34 us are 4.7 h, a longer recording's time starts again.  Events
+ *   before the first TIME_HIGH are dropped (n_no_state); other types are counted in n_other_words.
+ * Conversion and filter, in file order: t = (double)(t_us - time_base) * 1e-6 (one integer subtraction, one conversion, one
+ *   multiplication, as the text ingest; time_base defaults to 0, the camera's clock); x, y = the doubles of the integers; the
+ *   polarity byte is 0 or 1.  With width / height non-zero an event with x >= width or y >= height is dropped (n_outside); then
+ *   t < 0 is dropped (n_negative); then the reading rule of ecal_stream_create_from_file: kept if t >= start_time
+ *   (else n_before_start), and with has_end_time the first event with t >= end_time ends the stream: it and every event the words
+ *   behind it emit count as n_after_end and as nothing else.  No record is duplicated at the end (that was a quirk of the text
+ *   tool).  n_words, n_other_words, n_trailing_bytes and n_time_wraps are those of the whole payload, wherever the stream ends.
+ *
+ * ecal_raw_block_words: words per decode block of this build (0 for an unknown format) — a fact for tests that place block
+ *   boundaries, not a tuning knob.
+ * ecal_raw_count_events_dev: *n_events (HOST) = the events the words emit before any drop: always a sufficient `capacity`.  Waits
+ *   for `stream`.
+ * ecal_events_from_raw_dev: d_payload (DEVICE, 16-byte aligned, n_bytes bytes; nothing behind n_bytes is read) into d_events
+ *   (DEVICE, room for `capacity` records, file order, not sorted); opt->format must be ECAL_RAW_EVT2 or _EVT3.  info (HOST) is
+ *   filled on ECAL_OK and on ECAL_ERR_RANGE (capacity too small: info->n_events = the count needed, call again; also more than
+ *   2^32-1 emitted events).  On an error the contents of d_events are undefined.  Enqueues on `stream` and waits for it: the call
+ *   returns with the records in place.
+ * ecal_stream_create_from_raw_file: the header read on the host, the payload through pinned buffers into HBM (reads overlapped with
+ *   the uploads), decoded there, the payload freed, then the stream brought into time order if it is not (ecal_stream_create's
+ *   rule).  info may be NULL.
+ * ecal_raw_to_bin_file: the same records in file order, no sort, as a .bin of the reference's layout. */
+enum { ECAL_RAW_AUTO = 0, ECAL_RAW_EVT2 = 2, ECAL_RAW_EVT3 = 3 };
+typedef struct ecal_raw_options {
+    int format;              /* ECAL_RAW_AUTO: from the file header */
+    int64_t time_base;       /* microseconds of the camera's clock */
+    uint32_t width, height;  /* 0: no bound */
+    double start_time;       /* seconds */
+    int has_end_time;
+    double end_time;         /* seconds */
+} ecal_raw_options;
+typedef struct ecal_raw_info {
+    uint64_t n_words;          /* words of the payload */
+    uint64_t n_events;         /* records written, or needed */
+    uint64_t n_no_state;       /* events dropped for a missing TIME_HIGH / ADDR_Y / VECT_BASE_X */
+    uint64_t n_outside;        /* events dropped for x >= width or y >= height */
+    uint64_t n_negative;       /* events dropped for t < 0 */
+    uint64_t n_before_start;   /* events dropped for t < start_time */
+    uint64_t n_after_end;      /* events from the one that ended the stream on */
+    uint64_t n_other_words;    /* words of other types (triggers, ...) */
+    uint64_t n_trailing_bytes; /* bytes behind the last whole word */
+    uint64_t n_time_wraps;     /* EVT3: wraps of TIME_HIGH */
+    int format;                /* ECAL_RAW_EVT2 / _EVT3: the format in force */
+    uint64_t header_bytes;     /* file entry points: bytes in front of the payload */
+} ecal_raw_info;
+void ecal_raw_default_options(ecal_raw_options *opt);
+uint32_t ecal_raw_block_words(int format);
+int ecal_raw_count_events_dev(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, int format, uint64_t *n_events, void *stream);
+int ecal_events_from_raw_dev(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const ecal_raw_options *opt,
+                             uint8_t *d_events /*room for capacity records*/, uint64_t capacity, ecal_raw_info *info, void *stream);
+int ecal_stream_create_from_raw_file(ecal_ctx *ctx, const char *path, const ecal_raw_options *opt, ecal_stream **out,
+                                     ecal_raw_info *info);
+int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const char *bin_path, const ecal_raw_options *opt, ecal_raw_info *info);
+
 #ifdef __cplusplus
 }
 #endif
