@@ -629,6 +629,26 @@ class Context:
                                                    d_frame_window, d_pose, int(F), d_landmarks, ctypes.byref(params),
                                                    d_feat_xyr, d_feat_valid, d_frame_info, stream))
 
+    def rectify_batch(self, xy, seg_off, seg_cnt, kept_labels, pose, landmarks, params):
+        """ecal_rectify_batch, the host-buffer form: keyframe f owns segments 2f and 2f + 1 of xy [n_points, 2] / kept_labels.
+        Returns (feat_xyr [F, n, 3], feat_valid [F, n] u32, frame_info [F, 2] u32); no points at all go down as NULL arrays."""
+        L = self._L
+        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+        L.ecal_rectify_batch.argtypes = [vp, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.POINTER(RectifyParams), vp, vp, vp]
+        L.ecal_rectify_batch.restype = ctypes.c_int
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        kept = np.ascontiguousarray(kept_labels, np.int32)
+        off, cnt = np.ascontiguousarray(seg_off, np.uint32), np.ascontiguousarray(seg_cnt, np.uint32)
+        pose = np.ascontiguousarray(pose, np.float64).reshape(-1, 12)
+        lm = np.ascontiguousarray(landmarks, np.float64).reshape(-1, 3)
+        F, n = pose.shape[0], int(params.rows) * int(params.cols)
+        assert len(off) == 2 * F and len(cnt) == 2 * F and len(kept) == len(xy)
+        feat = np.zeros((F, n, 3))
+        valid, info = np.zeros((F, n), np.uint32), np.zeros((F, 2), np.uint32)
+        self._check(L.ecal_rectify_batch(self._h, _ptr(xy) if len(xy) else None, _ptr(off), _ptr(cnt), _ptr(kept) if len(xy) else None,
+                                         len(xy), _ptr(pose), F, _ptr(lm), ctypes.byref(params), _ptr(feat), _ptr(valid), _ptr(info)))
+        return feat, valid, info
+
     # ---- event -> residual association ----
     def associate_dev(self, d_events, n_events, d_kf_time, d_kf_circles, n_keyframes, n_circles, t_min, t_max,
                       max_dt, edge_tol, d_obs, d_time, d_lm_id, d_count, stream=0):

@@ -505,6 +505,9 @@ int ecal_grid_order(ecal_ctx *ctx, const double *cand_xyr, uint32_t n, uint32_t 
  *   d_feat_xyr[3(f*n + k)..] = rectified centre x, y, radius (NaN when erased).
  *   d_frame_info[2f..] = { return value of rectifyFeatures (border score :587-622 with fit_circle == 0, 20 % rule
  *   :625-627), number of erased features }.
+ * A keyframe whose window has status 4, or more than 2048 kept clusters in a polarity (d_win_info words 1 and 2), is not
+ * worked on and comes back all erased: d_feat_valid 0 and d_feat_xyr NaN for every circle, d_frame_info = { 0, rows*cols };
+ * ECAL_WIN_TIE_FALLBACK in the status word changes nothing (the window counts as status 0).
  * The outlierIdxs argument of the reference is unused there and has no counterpart.  d_feat_xyr of the accepted
  * keyframes is what ecal_associate_dev takes as d_kf_circles (NaN rows never match an event).
  * cv::projectPoints (OpenCV, third party) is restated: 5 distortion coefficients k1 k2 p1 p2 k3. */
