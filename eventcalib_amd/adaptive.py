@@ -59,8 +59,10 @@ def orientation_gate(ref_feat, ref_t, cur_feat, cur_t, rows, cols, motion_time_s
 
 
 def detect_keyframes(pipe: DetectPipeline, events, motion_time_step, frame_event_num_threshold, piece_num,
-                     start_time, end_time, eps=4.0, minpts=2, rows=9, cols=4, max_steps=1_000_000, n_threads=1):
-    """Returns dict(time [K], duration [K,2], events_num [K], features [K, rows*cols, 3]) sorted by time, plus
+                     start_time, end_time, eps=4.0, minpts=2, rows=9, cols=4, max_steps=1_000_000, n_threads=1,
+                     radius_threshold=15.511363636363637):
+    """radius_threshold: circleRadiusThreshold_ of the sensor (Context.circle_radius_threshold; the default is 346x260's).
+    Returns dict(time [K], duration [K,2], events_num [K], features [K, rows*cols, 3]) sorted by time, plus
     `steps` and `windows` (how many batched passes / windows were evaluated).
 
     n_threads > 1: the pieces are dealt round-robin to that many host threads, each with its OWN ecal_ctx (own stream
@@ -76,7 +78,8 @@ def detect_keyframes(pipe: DetectPipeline, events, motion_time_step, frame_event
 
         def work(t):
             outs[t] = _detect_pieces(ctxs[t], events, motion_time_step, frame_event_num_threshold, piece_num,
-                                     np.arange(t, piece_num, n_threads), start_time, end_time, eps, minpts, rows, cols, max_steps)
+                                     np.arange(t, piece_num, n_threads), start_time, end_time, eps, minpts, rows, cols, max_steps,
+                                     radius_threshold)
         th = [threading.Thread(target=work, args=(t,)) for t in range(n_threads)]
         for x in th:
             x.start()
@@ -88,7 +91,8 @@ def detect_keyframes(pipe: DetectPipeline, events, motion_time_step, frame_event
         steps, windows = max(o[1] for o in outs), sum(o[2] for o in outs)
     else:
         keys, steps, windows = _detect_pieces(pipe.ctx, events, motion_time_step, frame_event_num_threshold, piece_num,
-                                              np.arange(piece_num), start_time, end_time, eps, minpts, rows, cols, max_steps)
+                                              np.arange(piece_num), start_time, end_time, eps, minpts, rows, cols, max_steps,
+                                              radius_threshold)
     n = rows * cols
     keys.sort(key=lambda r: r[0])
     K = len(keys)
@@ -99,7 +103,7 @@ def detect_keyframes(pipe: DetectPipeline, events, motion_time_step, frame_event
 
 def detect_keyframes_device(ctx, events, motion_time_step, frame_event_num_threshold, piece_num, start_time, end_time, eps=4.0,
                             minpts=2, rows=9, cols=4, max_passes=0, gate_mode=0, n_threads=1, contexts=None, piece_first=0,
-                            piece_count=0, handover=None):
+                            piece_count=0, handover=None, radius_threshold=15.511363636363637):
     """Same result as detect_keyframes, with the policy on the device (ecal_detect_keyframes): no per-pass host round trip.
     gate_mode = capi.GATE_SHARED_MAP: the reference's single-worker run (one keyframe map for all pieces) instead of the
     own-piece gate.  Slots and the keyframe capacity are estimated and doubled when the library reports them too small.
@@ -112,13 +116,16 @@ def detect_keyframes_device(ctx, events, motion_time_step, frame_event_num_thres
 
     piece_count != 0: only the pieces piece_first .. piece_first + piece_count - 1 (one rank's share of a search cut over
     GPUs; `events` then only has to hold those pieces' time range).  Under capi.GATE_SHARED_MAP such a share needs the frame of
-    the pieces before it: handover (DistHandover below; ecal_detect_keyframes_sharded)."""
+    the pieces before it: handover (DistHandover below; ecal_detect_keyframes_sharded).
+
+    radius_threshold: circleRadiusThreshold_, which the reference derives from the sensor's size (CirclesEventFrame.cpp:19-33;
+    Context.circle_radius_threshold).  The default is the 346x260 sensor's; with it a larger sensor's circles are all rejected."""
     torch.cuda.synchronize(events.device)   # the passes run on the contexts' own streams: `events` must be complete
     n_ev = events.numel() // 25
     n_threads = max(1, min(int(n_threads), int(piece_num)))
     if n_threads == 1 or gate_mode != 0 or piece_count:
         return _detect_group(ctx, events, n_ev, motion_time_step, frame_event_num_threshold, piece_num, start_time, end_time, eps, minpts,
-                             rows, cols, max_passes, gate_mode, piece_first, piece_count, handover)
+                             rows, cols, max_passes, gate_mode, piece_first, piece_count, handover, radius_threshold)
     import threading
     from .capi import Context
     own = contexts is None
@@ -129,7 +136,8 @@ def detect_keyframes_device(ctx, events, motion_time_step, frame_event_num_thres
     def work(g):
         try:
             outs[g] = _detect_group(ctxs[g], events, n_ev, motion_time_step, frame_event_num_threshold, piece_num, start_time, end_time,
-                                    eps, minpts, rows, cols, max_passes, gate_mode, cuts[g], cuts[g + 1] - cuts[g])
+                                    eps, minpts, rows, cols, max_passes, gate_mode, cuts[g], cuts[g + 1] - cuts[g],
+                                    radius_threshold=radius_threshold)
         except BaseException as e:   # noqa: BLE001 — re-raised in the caller's thread
             errs[g] = e
     th = [threading.Thread(target=work, args=(g,)) for g in range(n_threads)]
@@ -188,7 +196,7 @@ class DistHandover:
 
 
 def _detect_group(ctx, events, n_ev, motion_time_step, frame_event_num_threshold, piece_num, start_time, end_time, eps, minpts, rows,
-                  cols, max_passes, gate_mode, piece_first, piece_count, handover=None):
+                  cols, max_passes, gate_mode, piece_first, piece_count, handover=None, radius_threshold=15.511363636363637):
     span = max(end_time - start_time, 1e-9)
     n_mine = piece_count if piece_count else piece_num
     # a pass covers a chain of windows per piece: the library's own estimate, doubled whenever it reports it too small
@@ -202,7 +210,8 @@ def _detect_group(ctx, events, n_ev, motion_time_step, frame_event_num_threshold
         try:
             t, d, e, f, passes, windows = capi.detect_keyframes_dev(ctx, events.data_ptr(), n_ev, motion_time_step,
                                                                     frame_event_num_threshold, piece_num, start_time, end_time, cap,
-                                                                    max_keys, eps, minpts, 5, rows, cols, max_passes=max_passes,
+                                                                    max_keys, eps, minpts, 5, rows, cols, radius_threshold=radius_threshold,
+                                                                    max_passes=max_passes,
                                                                     gate_mode=gate_mode, piece_first=piece_first,
                                                                     piece_count=piece_count, handover=handover)
             break
@@ -223,7 +232,7 @@ def _detect_group(ctx, events, n_ev, motion_time_step, frame_event_num_threshold
 
 
 def _detect_pieces(ctx, events, motion_time_step, frame_event_num_threshold, piece_num, which, start_time, end_time, eps, minpts,
-                   rows, cols, max_steps):
+                   rows, cols, max_steps, radius_threshold=15.511363636363637):
     """The lock-step loop over the pieces `which` (indices into the piece_num pieces of [start_time, end_time])."""
     n_ev = events.numel() // 25
     ln, gap = 3 * motion_time_step, 5 * motion_time_step
@@ -249,7 +258,7 @@ def _detect_pieces(ctx, events, motion_time_step, frame_event_num_threshold, pie
         while True:   # slots for the pass: windows x (a bound on the events of one window); doubled if a window was denser
             try:
                 packed = capi.detect_pass(ctx, events.data_ptr(), n_ev, first[idx], second[idx], min(n_ev, S * per_window), eps,
-                                          minpts, 5, rows, cols)
+                                          minpts, 5, rows, cols, radius_threshold)
                 break
             except capi.EcalError as e:
                 if e.status != -6 or S * per_window >= n_ev:

@@ -115,6 +115,11 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
                      refine_rounds=0, refine_ring_tol=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
+    width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
+    of both detection passes (the keyframe search and the rectify-stage pipeline) is derived from it as the reference does
+    (Context.circle_radius_threshold, CirclesEventFrame.cpp:19-33).  For a sensor larger than 346x260 the caller scales
+    frame_event_num_threshold too (the events a window may hold before it slides instead of growing: it is a count of events, and a
+    larger sensor's circles have longer rims); its default is the 346x260 example's.
     gate_mode: capi.GATE_SHARED_MAP (default: the reference's keyframe gate as its single-worker run computes it — one keyframe
     map for all pieces) or capi.GATE_OWN_PIECE (the schedule-free own-piece gate: 2 - 3 x faster keyframe search, every piece's
     first success ungated).
@@ -163,9 +168,11 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
             ctx._calibrate_pipe = pipe
         except AttributeError:
             pass
+    # circleRadiusThreshold_ of this sensor and board, for both detection passes (346x260, 9x4: the pipeline's default, bit for bit)
+    radius_threshold = ctx.circle_radius_threshold(width, height, rows, cols, True, square, circle_radius)
     # -- 1. keyframes
     kf = detect_keyframes_device(pipe.ctx, events, step, frame_event_num_threshold, piece_num, t_first, t_last, eps, minpts, rows, cols,
-                                 gate_mode=gate_mode)
+                                 gate_mode=gate_mode, radius_threshold=radius_threshold)
     K = len(kf["time"])
     out = {"keyframes": K, "stage_seconds": stages}
     mark("keyframe_search")
@@ -207,6 +214,9 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     mark("pnp")
     # rectifyFeatures for all keyframes at once: their windows go through the detection pipeline again
     pipe.set_windows(kf["duration"][:, 0], kf["duration"][:, 1])
+    if not hasattr(pipe, "det"):
+        pipe.set_detect_params()
+    pipe.set_detect_params(pipe.det[0], pipe.det[1], radius_threshold, pipe.det[3], pipe.det[4])
     # (every size tier at work: these windows are 4 - 10 steps long, and what the stages' previous call saw — the search's last
     # pass, its lists all but empty — would send the whole batch through the one slow general launch: 9.4 ms instead of 3)
     was_mode = ctx.get_tail_mode()      # (the caller's choice comes back afterwards, as in ecal_rectify_keyframes)

@@ -261,6 +261,35 @@ class Context:
                                               _ptr(labels), _ptr(ncl)))
         return labels, ncl
 
+    def debug_px_todo_counts(self, stream=None):
+        """ecal_debug_px_todo_counts (tests): how many segments the first and the second pixel pass of the last dbscan_batch* call
+        on this context left on their to-do lists -> (first, second); second is None when no second pass ran (no segment of the
+        call could need it, or the lean tail).  stream: the stream that call ran on (None: the context's own, dbscan_batch's)."""
+        L = self._L
+        L.ecal_debug_px_todo_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+        L.ecal_debug_px_todo_counts.restype = ctypes.c_int
+        if stream is None:
+            self.sync()
+            stream = 0
+        out = (ctypes.c_uint32 * 2)(0xFFFFFFFF, 0xFFFFFFFF)
+        self._check(L.ecal_debug_px_todo_counts(self._h, out, stream))
+        return int(out[0]), (None if out[1] == 0xFFFFFFFF else int(out[1]))
+
+    def debug_tail_plans(self):
+        """ecal_debug_tail_seen (tests), read as ecal_tail_plan (ecal_ctx.hpp) reads it under tail mode "auto": the plan the NEXT call
+        of the slicing and of the DBSCAN stage takes, by what the stage's last call saw on its two lists -> {"slice": p, "dbscan": p},
+        p = "lean" (both lists were empty), "semi" (the second was) or "tiered".  The caller has drained the stream of those calls."""
+        L = self._L
+        L.ecal_debug_tail_seen.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        L.ecal_debug_tail_seen.restype = ctypes.c_int
+        seen = (ctypes.c_uint32 * 16)()
+        self._check(L.ecal_debug_tail_seen(self._h, seen))
+
+        def plan(first):
+            a, b = int(seen[first]), int(seen[first + 1])
+            return "lean" if a == 0 and b == 0 else ("semi" if a != 0xFFFFFFFF and b == 0 else "tiered")
+        return {"slice": plan(0), "dbscan": plan(2)}
+
     # ---- DBSCAN (device buffers, raw pointers) ----
     def dbscan_batch_dev(self, d_xy, d_seg_off, d_seg_cnt, S, n_points, max_seg_points, eps, minpts, d_labels,
                          d_n_clusters, stream=0):

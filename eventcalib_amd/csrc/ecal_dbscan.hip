@@ -302,6 +302,7 @@ extern "C" int ecal_dbscan_batch_packed_dev(ecal_ctx *ctx, double *d_xy, const u
     int rc = set_attrs(ctx);
     if (rc) return rc;
     hipStream_t st = (hipStream_t) stream;
+    ctx->px_count_last[0] = ctx->px_count_last[1] = nullptr;   // (ecal_debug_px_todo_counts)
     ctx->px_tree_labels = nullptr;   // (whatever trees an earlier call left belong to ITS labels; set again below when this call exports its own)
     const uint32_t mx = max_seg_points ? max_seg_points : 0xFFFFFFFFu;
     const bool second_pass_wanted = mx > (uint32_t) PX_CAP;
@@ -351,6 +352,8 @@ extern "C" int ecal_dbscan_batch_packed_dev(ecal_ctx *ctx, double *d_xy, const u
         const bool second_pass = second_pass_wanted && !lean;
         cnt_a = cnt;
         cnt_b = second_pass ? cnt2 : nullptr;
+        ctx->px_count_last[0] = cnt_a;
+        ctx->px_count_last[1] = cnt_b;
         // floor(eps^2) == 16 (the shipped eps = 4): the disc is compiled in; any other radius takes the generic form
         if (geom.e2i == 16 && !ctx->sw.dbscan_generic_disc) {
             if (ecal_latency_level(ctx) && second_pass)   // (few windows at work: a segment goes through the pass its size asks for in ONE launch)
@@ -426,6 +429,23 @@ extern "C" int ecal_dbscan_batch_packed_dev(ecal_ctx *ctx, double *d_xy, const u
                            (uint8_t *) ctx->big_flags.ptr, S, todo, todo_count, seen, cnt_a, cnt_b);
     }
     ECAL_HIP_TRY(ctx, hipGetLastError());
+    return ECAL_OK;
+}
+
+// tests: how many segments the first and the second pixel pass of the last ecal_dbscan_batch*_dev call on this context put on their
+// to-do lists (out[0]: left by the first pass — every segment beyond its capacity among them; out[1]: left by the second pass to
+// the general tiers, 0xFFFFFFFF when no second pass ran); ECAL_ERR_INVALID when that call ran no pixel pass; synchronises `stream`.
+// In the latency form (dbscan_pixel_both_kernel: a segment goes through the pass its size asks for in ONE launch, and what the
+// first pass's code gives up goes on to the second pass's code in the same workgroup) the first pass keeps no list: out[0] is 0
+// whatever the first pass took, and only out[1] — what went to the general tiers — says something.
+extern "C" int ecal_debug_px_todo_counts(ecal_ctx *ctx, uint32_t *out, void *stream) {
+    if (!ctx || !out || !ctx->px_count_last[0]) return ECAL_ERR_INVALID;
+    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    out[1] = 0xFFFFFFFFu;
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->px_count_last[0], sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t) stream));
+    if (ctx->px_count_last[1])
+        ECAL_HIP_TRY(ctx, hipMemcpyAsync(out + 1, ctx->px_count_last[1], sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t) stream));
+    ECAL_HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) stream));
     return ECAL_OK;
 }
 

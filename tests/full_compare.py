@@ -22,16 +22,18 @@ def _first_bad_window(bad_slot_mask, win_base, torch):
 
 
 def compare_all_windows(pipe, rec, t0, t1, torch, eps=4.0, minpts=2, det=(5, 36, 15.511363636363637), fit_circle=False, knn_num=3,
-                        n_threads=None, xyr_exact=True):
+                        n_threads=None, xyr_exact=True, oracle=None):
     """pipe: a DetectPipeline after run() on the packed records `rec` (numpy uint8, host copy of what the device holds) with
     windows t0 / t1.  Asserts that window bounds, point sets in the reference's order, event->point map, labels, cluster
     counts, kept labels, window verdicts, representatives, pairs and circles of ALL windows equal the oracle's, bit for bit.
+    oracle: what O.detect_windows_full returned for these windows and parameters (several runs compared with one reference).
     Returns counts for the caller's sanity floor (windows, paired, tied, points, candidates, seconds of oracle time)."""
     S = len(t0)
     wb = pipe.win_base[:S + 1].cpu().numpy().astype(np.uint64)
     slots = int(wb[-1])
     tic = time.time()
-    f = O.detect_windows_full(rec, t0, t1, wb, slots, eps, minpts, det[0], det[1], det[2], fit_circle, knn_num, n_threads)
+    f = oracle if oracle is not None else O.detect_windows_full(rec, t0, t1, wb, slots, eps, minpts, det[0], det[1], det[2], fit_circle,
+                                                               knn_num, n_threads)
     oracle_s = time.time() - tic
     assert np.array_equal(pipe.win_lo[:S].cpu().numpy().astype(np.uint64), f["win_lo"]), "window lower bounds"
     assert np.array_equal(pipe.win_hi[:S].cpu().numpy().astype(np.uint64), f["win_hi"]), "window upper bounds"

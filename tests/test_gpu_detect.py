@@ -508,3 +508,62 @@ def test_tie_paths_by_cluster_size_against_the_oracle(env, eps, monkeypatch):
     assert tied >= S // 2, tied                                   # most windows hold tied clusters ...
     assert max(sizes) > 64 and min(sizes) <= 16                   # ... of every size class
     assert 0 < counts[0] < counts[1], counts                      # windows with a tied cluster beyond 64 members stay on the list, the others do not
+
+
+# (name, window length at 2 Mev/s, the windows' largest x, largest y).  0.9 ms: 1800 events and <= 1408 points a window, the
+# extraction's first LDS pass, whose composite member word takes |coordinate| <= 1023; 1.5 ms: 3000 events and 1409 .. 2816 points,
+# the second LDS pass, <= 723 (extract_window.hpp: KEY_LIM).  The slicer packs a window of <= 2047 events with x <= 2047 and
+# y <= 1023 and one of <= 4095 events with x, y <= 1023: every case stays packed — int16 points, composite or not.
+_KEY_RANGE_CASES = [
+    ("first_x_1023", 0.9e-3, 1023, 359), ("first_x_1024", 0.9e-3, 1024, 359), ("first_y_1023", 0.9e-3, 445, 1023),
+    ("first_x_2045_y_1019", 0.9e-3, 345 + 1700, 259 + 760),
+    ("second_x_723", 1.5e-3, 723, 359), ("second_x_724", 1.5e-3, 724, 359), ("second_y_723", 1.5e-3, 445, 723),
+    ("second_y_724", 1.5e-3, 445, 724), ("second_x_1023_y_1019", 1.5e-3, 1023, 259 + 760)]
+
+
+def _key_range_stream(length, xmax, ymax, S=20, rate=2.0e6):
+    """S tiled windows of the dense synthetic stream, translated so that every window's largest x and y are exactly xmax and ymax
+    (the first event of every window is moved to the sensor's last pixel)."""
+    n = int(round(rate * length * S))
+    buf = SS.make_stream(n, rate=rate, device="cpu", seed=31)
+    rec = buf.numpy().reshape(-1, 25)
+    t, _, _ = SS.unpack_records(buf)
+    t0, t1 = SS.tiled_windows(float(t[0]), float(t[-1]), length)
+    assert len(t0) == S
+    xy = rec[:, 8:24].copy().view(np.float64)
+    xy[np.searchsorted(t.numpy(), t0)] = [SS.SENSOR_W - 1, SS.SENSOR_H - 1]
+    xy += np.array([xmax - (SS.SENSOR_W - 1), ymax - (SS.SENSOR_H - 1)], np.float64)
+    rec[:, 8:24] = xy.view(np.uint8)
+    return buf, t0, t1
+
+
+@pytest.mark.parametrize("name,length,xmax,ymax", _KEY_RANGE_CASES, ids=[c[0] for c in _KEY_RANGE_CASES])
+def test_extraction_key_ranges(env, name, length, xmax, ymax):
+    """The dense synthetic stream translated so that every window's largest x and y are exactly the given values — at, one
+    beyond and far beyond the composite word's range, x beyond with y inside and the other way round: what a 1280 x 720 sensor's
+    windows hold.  Every window == the oracle with either tie rule and with and without the circle fit."""
+    ctx, pipe, torch = env
+    S = 20
+    buf, t0, t1 = _key_range_stream(length, xmax, ymax, S)
+    ev = buf.cuda()
+    pipe.set_windows(t0, t1)
+    ctx.set_tail_mode("tiered")      # (every hash pass of the slicer runs: under "auto" a call after one with empty lists sends what
+    try:                             # its first pass leaves through the general tail, which writes doubles)
+        for fit_circle in (False, True):
+            pipe.set_detect_params(5, 36, THR, fit_circle=fit_circle)
+            for exact_ties in (True, False):
+                pipe.run(ev, exact_ties=exact_ties)
+                torch.cuda.synchronize()
+                assert pipe.seg_fmt[:2 * S].cpu().numpy().all(), "a window's points are not packed"
+                off, cnt = pipe.seg_off[:2 * S].cpu().numpy(), pipe.seg_cnt[:2 * S].cpu().numpy()
+                pts = pipe.xy.cpu().numpy()
+                n_all = cnt[0::2] + cnt[1::2]
+                assert (n_all <= 1408).all() if length < 1e-3 else ((n_all > 1408) & (n_all <= 2816)).all()
+                for s in range(S):
+                    w = pts[off[2 * s]:off[2 * s] + n_all[s]]
+                    assert w[:, 0].max() == xmax and w[:, 1].max() == ymax, s
+                exact, tied = _check_windows(pipe, torch, buf.numpy(), t0, t1, 5, 36, THR, fit_circle, exact_ties=exact_ties)
+                assert exact + tied >= 0.7 * S, (exact, tied, S)
+    finally:
+        ctx.set_tail_mode("auto")
+        pipe.set_detect_params(5, 36, THR)

@@ -401,6 +401,92 @@ def test_third_pass_edges_equal_the_oracle(env):
         assert [int(v != 0) for v in fmt] == [1, 1, 0, 1, 1, 0, 0, 1, 0, 1]
 
 
+def _hand_windows():
+    """Windows built by hand, 1 ms apart: window(x, y, p) appends one, finish() -> (records, t0, t1)."""
+    recs, bounds, t_at = [], [], [0.0]
+
+    def window(x, y, p):
+        t = t_at[0] + 1e-6 * (1 + np.arange(len(x)))
+        recs.append(O.pack_events(t, np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(p, np.uint8)))
+        bounds.append((t[0], t[-1]))
+        t_at[0] = t[-1] + 1e-3
+
+    def finish():
+        return np.concatenate(recs), [b[0] for b in bounds], [b[1] + 5e-7 for b in bounds]
+    return window, finish
+
+
+# (events per window, coordinate, last value the pass's table word holds): PixHash<LOGC>::XMAX / YMAX, slice_hash.hpp — the first
+# pass (<= 2047 events) x <= 2047, y <= 1023; the second (2048 .. 4095) x, y <= 1023; the third (4096 .. 5119, reference order) x <= 511
+_PASS_RANGES = [(1900, 0, 2047), (1900, 1, 1023), (3000, 0, 1023), (3000, 1, 1023), (4600, 0, 511)]
+
+
+def test_hash_pass_coordinate_ranges(env):
+    """One event per window at the last coordinate a hash pass takes and at the first it does not, once in the first wave and once in
+    the last occupied slot; every other event of the window is a sensor pixel of a 60 x 50 patch (set sizes within every pass's).
+    Every window equals the oracle; in reference point order seg_fmt says packed (= taken by a hash pass) for the in-range window
+    and doubles (= the general tiers') for the other: a 640-wide sensor crosses the third pass's limit, a 1280-wide one the second's."""
+    ctx, pipe, torch = env
+    rng = np.random.default_rng(91)
+    window, finish = _hand_windows()
+    want = []
+    for n, axis, last in _PASS_RANGES:
+        for value in (last, last + 1):
+            for at in (5, n - 1):
+                xy = np.stack([rng.integers(100, 160, n), rng.integers(100, 150, n)])
+                xy[axis, at] = value
+                window(xy[0], xy[1], rng.integers(0, 2, n))
+                want.append((n, int(value == last)))
+    rec, t0, t1 = finish()
+    pipe.set_windows(t0, t1)
+    ctx.set_tail_mode("tiered")      # (every hash pass runs: under "auto" a call after one with empty lists sends what its first pass
+    try:                             # leaves through the general tail, and seg_fmt would say doubles for a window the second pass takes)
+        pipe.run(torch.from_numpy(rec).cuda(), slots=rec.size // 25 + 64)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_tail_mode("auto")
+    _compare(pipe, torch, rec, t0, t1, check_labels=False)
+    fmt = pipe.seg_fmt[:2 * len(t0)].cpu().numpy()
+    for k, (n, packed) in enumerate(want):
+        if n > 4095 and ctx.point_order() != "reference":
+            continue                                   # (the third pass exists in the reference order only)
+        assert (int(fmt[2 * k] != 0), int(fmt[2 * k + 1] != 0)) == (packed, packed), (k, n, packed)
+
+
+def test_hash_pass_full_coordinate_range(env):
+    """Windows whose pixels span all a pass admits — x to 2047 with y to 1023 in the first pass, 1023 / 1023 in the second —, the
+    four corner pixels present in both polarities (they cancel: EventFrame.cpp:24-32) and their neighbours in one: the top
+    coordinate bits of the table word pixel << LOGC | index carry data."""
+    ctx, pipe, torch = env
+    rng = np.random.default_rng(92)
+    window, finish = _hand_windows()
+    for n, xmax, ymax in ((1900, 2047, 1023), (3000, 1023, 1023)):
+        x, y, p = rng.integers(0, xmax + 1, n), rng.integers(0, ymax + 1, n), rng.integers(0, 2, n)
+        k = rng.choice(n, 12, replace=False)
+        corners = [(0, 0), (xmax, 0), (0, ymax), (xmax, ymax)]
+        for i, (cx, cy) in enumerate(corners):
+            x[k[2 * i]], y[k[2 * i]], p[k[2 * i]] = cx, cy, 1
+            x[k[2 * i + 1]], y[k[2 * i + 1]], p[k[2 * i + 1]] = cx, cy, 0
+        for i, (cx, cy, cp) in enumerate([(xmax, ymax - 1, 1), (xmax - 1, ymax, 0), (xmax, 1, 0), (1, ymax, 1)]):
+            x[k[8 + i]], y[k[8 + i]], p[k[8 + i]] = cx, cy, cp
+        window(x, y, p)
+    rec, t0, t1 = finish()
+    pipe.set_windows(t0, t1)
+    ctx.set_tail_mode("tiered")      # (every hash pass runs: under "auto" a call after one with empty lists sends what its first pass
+    try:                             # leaves through the general tail, and seg_fmt would say doubles for a window the second pass takes)
+        pipe.run(torch.from_numpy(rec).cuda(), slots=rec.size // 25 + 64)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_tail_mode("auto")
+    _compare(pipe, torch, rec, t0, t1, check_labels=False)
+    assert pipe.seg_fmt[:4].cpu().numpy().all()        # both taken by a hash pass
+    xy = pipe.xy.cpu().numpy()
+    off, cnt = pipe.seg_off[:4].cpu().numpy(), pipe.seg_cnt[:4].cpu().numpy()
+    for w, (xmax, ymax) in enumerate(((2047, 1023), (1023, 1023))):
+        pts = {tuple(q) for q in xy[off[2 * w]:off[2 * w] + cnt[2 * w]]} | {tuple(q) for q in xy[off[2 * w + 1]:off[2 * w + 1] + cnt[2 * w + 1]]}
+        assert (xmax, ymax) not in pts and (0, 0) not in pts and (xmax, ymax - 1) in pts and (xmax - 1, ymax) in pts
+
+
 def test_golden_eventframe_order_fixtures(env):
     """`.bin` records -> the reference's point order -> DBSCAN labels, against the committed fixtures
     (tests/golden/eventframe_order_*.npz: real std::unordered_set + the reference's kd-tree, made in the build container)."""
