@@ -161,6 +161,17 @@ __device__ __forceinline__ uint32_t mod_hash(uint64_t h, const ModB m) {
     return (uint32_t) mod_step(__builtin_fma(r1, 0x1p40, d0), m);
 }
 
+// ref_epochs(m) for the sets of the pixel passes (m <= 5119 keys) in scalar compares against constants: the constexpr form walks
+// ref_bucket_step()'s table, which at run time is a chain of dependent scalar loads from constant memory, one per step and each
+// waited for — seven in a row for a set of 700 keys, for both polarities, between two barriers of every window.
+// (m > 5087 gives 10 like ref_epochs() up to 10273 keys: more than any pass's MAX_EPOCHS.)
+__device__ __forceinline__ int ref_epochs_pixel(uint32_t m) {
+    int e = 1;
+#pragma unroll
+    for (int i = 0; i < 9; i++) e += m > (uint32_t) ref_bucket_step(i) ? 1 : 0;
+    return e;
+}
+
 // workgroup barrier that orders LDS traffic only: global loads issued before it stay in flight (__syncthreads() drains them)
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -261,7 +272,7 @@ __device__ __forceinline__ void early_epochs_packed(uint32_t m, uint32_t *fa, ui
 // Returns false when the window is not this pass's (too many events or keys, a non-pixel coordinate): it is then put on `todo`, or —
 // todo == nullptr — left to the caller (nothing has been written for it yet except, with seg_fmt, its "doubles" mark).
 // PER = event slots per thread (event k = tid + 256 j, j < PER): the caller's window has at most 256 PER - 1 events.
-template <int LOGC, bool REFORDER, int PER>
+template <int LOGC, bool REFORDER, int PER, int NFULL = 0>
 __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, const uint32_t s, const uint8_t *__restrict__ rec,
                                                         const uint32_t *__restrict__ win_lo, const uint32_t *__restrict__ win_hi,
                                                         const uint32_t *__restrict__ win_base, uint32_t cap_points,
@@ -317,20 +328,32 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
     uint32_t *const red = reinterpret_cast<uint32_t *>(smem + L::red_off);
     uint32_t *const badf = red + 32;
 
+    // NFULL: the caller's window has at least 256 NFULL events, so the slots j < NFULL hold an event in every lane.  Their bodies
+    // below (phases a, b, c, d' and the outputs) run without the test k < n — no change of the exec mask — and without the values the
+    // empty lanes of a partial slot need; the slots behind them are tested lane by lane as before.  The number has to be a template
+    // parameter: a wave-uniform test per slot at run time (`(j + 1) T <= n`) in front of two copies of a body is folded by the
+    // compiler back into one body under the mask  uniform | k < n  (profiles/slice_predication.md).
+    static_assert(NFULL >= 0 && NFULL < PER, "the last slot of a form is never full: its windows end at 256 PER - 1 events");
+    auto slot_full = [&](int j) -> bool { return j < NFULL; };
     // a. decode (Event.hpp:41-47); the records' loads are all issued before the tables are cleared behind them
     double vx[PXH_PER], vy[PXH_PER];
     uint32_t vp[PXH_PER];
+    auto decode = [&](int j, uint32_t k) {
+        const uint8_t *r = rec + (uint64_t) (lo + k) * RECORD_BYTES;
+        vx[j] = load_f64_unaligned(r + 8);
+        vy[j] = load_f64_unaligned(r + 16);
+        vp[j] = r[24];
+    };
 #pragma unroll
     for (int j = 0; j < PXH_PER; j++) {
         const uint32_t k = tid + j * T;
-        vx[j] = 0;
-        vy[j] = 0;
-        vp[j] = 0;
-        if (k < n) {
-            const uint8_t *r = rec + (uint64_t) (lo + k) * RECORD_BYTES;
-            vx[j] = load_f64_unaligned(r + 8);
-            vy[j] = load_f64_unaligned(r + 16);
-            vp[j] = r[24];
+        if (slot_full(j)) {
+            decode(j, k);
+        } else {
+            vx[j] = 0;
+            vy[j] = 0;
+            vp[j] = 0;
+            if (k < n) decode(j, k);
         }
     }
     {
@@ -347,13 +370,12 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
     uint32_t pix[PXH_PER];
 #pragma unroll
     for (int j = 0; j < PXH_PER; j++) {
-        const uint32_t k = tid + j * T;
         const double x = vx[j], y = vy[j];
         // the sign bit rejects negative coordinates and -0.0 (a valid pixel for operator==, but the emitted element keeps
         // its sign: general path); the upper bounds are what the table word holds
         const bool okc = x == floor(x) && y == floor(y) && x <= L::XMAX && y <= L::YMAX && __double_as_longlong(x) >= 0 &&
                          __double_as_longlong(y) >= 0;
-        bad = bad || (k < n && !okc);
+        bad = bad || !okc;   // (a lane without an event holds (+0.0, +0.0): a pixel)
         pix[j] = ((((uint32_t) (int) x << 10) | ((uint32_t) (int) y & 0x3FFu)) & PIXM) | (vp[j] ? POLB : 0u);
     }
     const bool wave_bad = __any(bad);
@@ -373,7 +395,8 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
     uint2 bw[EARLY_GATHER ? PXH_PER : 1];
     if constexpr (EARLY_GATHER) {
 #pragma unroll
-        for (int j = 0; j < PXH_PER; j++) bw[j] = (tid + j * T < n) ? bucket_tab[PIX_OF(pix[j])] : make_uint2(0u, 0u);
+        for (int j = 0; j < PXH_PER; j++)
+            bw[j] = (slot_full(j) || tid + j * T < n) ? bucket_tab[PIX_OF(pix[j])] : make_uint2(0u, 0u);
     }
     // b. every event into its polarity's table: the slot of its pixel ends up holding the smallest event index
     // (The first probe of all of a thread's events is read before any is looked at: the probes of different events are
@@ -387,24 +410,29 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
             hs[j] = L::slot(PIX_OF(pix[j]));
             w0[j] = tab[(POL_OF(pix[j]) ? PXH_SLOTS : 0u) + hs[j]];
         }
+        auto insert = [&](int j, uint32_t k) {
+            uint32_t *const t = tab + (POL_OF(pix[j]) ? PXH_SLOTS : 0u);
+            const uint32_t mine = (pix[j] << LOGC) | k;   // (PIXB + LOGC = 32: the polarity bit falls off)
+            uint32_t h = hs[j], w = w0[j];
+            for (;;) {
+                if (w == EMPTY) w = atomicCAS(&t[h], EMPTY, mine);   // EMPTY back: the slot is mine
+                if (w == EMPTY) break;
+                if ((w >> LOGC) == PIX_OF(pix[j])) {
+                    atomicMin(&t[h], mine);
+                    break;
+                }
+                h = (h + 1u) & (PXH_SLOTS - 1u);
+                w = t[h];
+            }
+            hs[j] = h;
+        };
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
-            if (k < n) {
-                uint32_t *const t = tab + (POL_OF(pix[j]) ? PXH_SLOTS : 0u);
-                const uint32_t mine = (pix[j] << LOGC) | k;   // (PIXB + LOGC = 32: the polarity bit falls off)
-                uint32_t h = hs[j], w = w0[j];
-                for (;;) {
-                    if (w == EMPTY) w = atomicCAS(&t[h], EMPTY, mine);   // EMPTY back: the slot is mine
-                    if (w == EMPTY) break;
-                    if ((w >> LOGC) == PIX_OF(pix[j])) {
-                        atomicMin(&t[h], mine);
-                        break;
-                    }
-                    h = (h + 1u) & (PXH_SLOTS - 1u);
-                    w = t[h];
-                }
-                hs[j] = h;
+            if (slot_full(j)) {
+                insert(j, k);
+            } else if (k < n) {
+                insert(j, k);
             }
         }
     }
@@ -420,28 +448,33 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
             fw[j] = tab[(POL_OF(pix[j]) ? PXH_SLOTS : 0u) + hs[j]];
             ow[j] = tab[(POL_OF(pix[j]) ? 0u : PXH_SLOTS) + L::slot(PIX_OF(pix[j]))];
         }
+        auto look_up = [&](int j) {
+            const uint32_t first = fw[j] & IDXM;
+            const uint32_t *const o = tab + (POL_OF(pix[j]) ? 0u : PXH_SLOTS);
+            uint32_t h = L::slot(PIX_OF(pix[j])), w = ow[j];
+            bool both = false;
+            for (;;) {
+                if (w == EMPTY) break;
+                if ((w >> LOGC) == PIX_OF(pix[j])) {
+                    both = true;
+                    break;
+                }
+                h = (h + 1u) & (PXH_SLOTS - 1u);
+                w = o[h];
+            }
+            repk[j] = both ? NONE : first;
+            firstk[j] = first | (both ? 0x8000u : 0u);
+        };
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
-            if (k < n) {
-                const uint32_t first = fw[j] & IDXM;
-                const uint32_t *const o = tab + (POL_OF(pix[j]) ? 0u : PXH_SLOTS);
-                uint32_t h = L::slot(PIX_OF(pix[j])), w = ow[j];
-                bool both = false;
-                for (;;) {
-                    if (w == EMPTY) break;
-                    if ((w >> LOGC) == PIX_OF(pix[j])) {
-                        both = true;
-                        break;
-                    }
-                    h = (h + 1u) & (PXH_SLOTS - 1u);
-                    w = o[h];
-                }
-                repk[j] = both ? NONE : first;
-                firstk[j] = first | (both ? 0x8000u : 0u);
+            if (slot_full(j)) {
+                look_up(j);
+            } else if (k < n) {
+                look_up(j);
             } else {
                 repk[j] = NONE;
-                firstk[j] = 0xFFFFu;
+                firstk[j] = 0xFFFFu;   // (no event: not a key — no index reaches 0x7FFF — and "erased")
             }
         }
     }
@@ -469,15 +502,20 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
 #pragma unroll
         for (int j = 0; j < PXH_PER; j++) {
             const uint32_t k = tid + j * T;
-            const bool isu = k < n && (firstk[j] & 0x7FFFu) == k;
+            const bool live = slot_full(j) || k < n;
+            const bool isu = live && (firstk[j] & 0x7FFFu) == k;
             const bool pol_ = POL_OF(pix[j]);
             const unsigned long long mP = __ballot(isu && pol_), mN = __ballot(isu && !pol_);
             const unsigned long long lower = (1ull << lane) - 1ull;
             const uint32_t below = (uint32_t) __popcll((pol_ ? mP : mN) & lower);
             if (lane == 0) bcnt[j * (T / 64) + wave] = (uint32_t) __popcll(mP) | ((uint32_t) __popcll(mN) << 16);
-            meta[j] = k < n ? ((firstk[j] & M_IDX) | ((firstk[j] & 0x8000u) ? M_ER : 0u) | (pol_ ? M_POL : 0u) |
-                               (isu ? M_KEY : 0u) | (below << 16))
-                            : M_ER;   // (no event: "erased", not a key)
+            const uint32_t word = (firstk[j] & M_IDX) | ((firstk[j] & 0x8000u) ? M_ER : 0u) | (pol_ ? M_POL : 0u) |
+                                  (isu ? M_KEY : 0u) | (below << 16);
+            if (slot_full(j)) {
+                meta[j] = word;
+            } else {
+                meta[j] = k < n ? word : M_ER;   // (no event: "erased", not a key)
+            }
         }
         if constexpr (EARLY_GATHER) lds_barrier(); else __syncthreads();
     RO_MARK(2);
@@ -509,7 +547,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
         if constexpr (EARLY_GATHER) lds_barrier(); else __syncthreads();
     RO_MARK(3);
         const uint32_t totals = bcnt[NBATCH], mP = totals & 0xFFFFu, mN = totals >> 16;
-        const int EP = mP ? ref_epochs(mP) : 0, EN = mN ? ref_epochs(mN) : 0;
+        const int EP = mP ? ref_epochs_pixel(mP) : 0, EN = mN ? ref_epochs_pixel(mN) : 0;
         {
             const uint32_t need = (EP ? (uint32_t) ref_bucket_step(EP - 1) : 0u) + (EN ? (uint32_t) ref_bucket_step(EN - 1) : 0u);
             if (need > L::FA_CAP || EP > L::MAX_EPOCHS || EN > L::MAX_EPOCHS || mP > 128u * (uint32_t) L::NI ||
@@ -524,6 +562,11 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
         {
             // ---- one wave PAIR per polarity: early epochs (13 .. 127 buckets) by one wave each, the rest by the pair ----
             constexpr int NI = L::NI;
+            // the epoch with 2357 buckets keeps its bucket numbers in the upper half of the keys' position words cu[]; a pass of seven
+            // epochs never gets there and its cu[] is the list position alone: said at compile time, the selects between the two bucket
+            // words and the masks around the upper half go
+            constexpr bool HAS_E7 = L::MAX_EPOCHS > 7;
+            auto cu_pos = [](uint32_t w) -> uint32_t { return HAS_E7 ? (w & 0xFFFFu) : w; };   // list position of a word of cu[]
             const uint32_t faN = EP ? (uint32_t) ref_bucket_step(EP - 1) : 0u;   // the - set's bucket table starts here
             {
 #pragma unroll
@@ -576,7 +619,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
             __syncthreads();
     RO_MARK(6);
             if (ECAL_RO_STOP == 3) return true;
-            if (l128 < (m < 127u ? m : 127u)) cu[0] = (cu[0] & 0xFFFF0000u) | (uint32_t) ecurp[l128];
+            if (l128 < (m < 127u ? m : 127u)) cu[0] = (HAS_E7 ? (cu[0] & 0xFFFF0000u) : 0u) | (uint32_t) ecurp[l128];
             const int EMAX = EP > EN ? EP : EN;
             if (E > 4) {
                 for (uint32_t b = l128; b < 257u; b += 128u) fap[b] = 0xFFFFFFFFu;
@@ -589,7 +632,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
                 const uint32_t n_e = on ? (m < B ? m : B) : 0u;
                 const uint32_t sh = e == 4 ? 0u : (e == 5 ? 9u : (e == 6 ? 19u : 16u)),
                                bmask = e == 4 ? 0x1FFu : (e == 5 ? 0x3FFu : (e == 6 ? 0x7FFu : 0xFFFu));
-                const bool e7 = e == 7;   // (its buckets sit in cu[]'s upper half)
+                const bool e7 = HAS_E7 && e == 7;   // (its buckets sit in cu[]'s upper half)
                 const uint32_t per = (n_e + 127u) >> 7;   // sequence positions per thread in the scan
                 uint32_t fq[NI];                          // first position of the key's bucket
                 // first sequence position per bucket  (and W, last read before the barrier that ended the previous epoch, is cleared)
@@ -598,7 +641,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
                 for (int i = 0; i < NI; i++) {
                     const uint32_t u = l128 + 128u * i;
                     if (128u * i >= n_e) break;
-                    if (u < n_e) atomicMin(&fap[((e7 ? cu[i] : bk[i]) >> sh) & bmask], u < Bprev ? (cu[i] & 0xFFFFu) : u);
+                    if (u < n_e) atomicMin(&fap[((e7 ? cu[i] : bk[i]) >> sh) & bmask], u < Bprev ? cu_pos(cu[i]) : u);
                 }
                 __syncthreads();
                 // members per bucket, counted at the bucket's first position; the arrival number is the member's slot
@@ -647,7 +690,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
                     if (u < n_e) {
                         const uint32_t f = fq[i] & 0xFFFu, w = Wp[f];
                         if ((w & 0x3FFu) > 2u)
-                            regp[(w >> 10) + (f >= carry_from ? carry : 0u) + (fq[i] >> 12)] = (uint16_t) (u < Bprev ? (cu[i] & 0xFFFFu) : u);
+                            regp[(w >> 10) + (f >= carry_from ? carry : 0u) + (fq[i] >> 12)] = (uint16_t) (u < Bprev ? cu_pos(cu[i]) : u);
                     }
                 }
                 __syncthreads();
@@ -659,14 +702,14 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
                     if (128u * i >= n_e) break;
                     if (u < n_e) {
                         const uint32_t f = fq[i] & 0xFFFu, w = Wp[f], b0 = (w >> 10) + (f >= carry_from ? carry : 0u), cnt = w & 0x3FFu;
-                        const uint32_t q = u < Bprev ? (cu[i] & 0xFFFFu) : u;
+                        const uint32_t q = u < Bprev ? cu_pos(cu[i]) : u;
                         uint32_t within = (q != f) ? 1u : 0u;
                         if (cnt > 2u) {   // (buckets of five and more are rare: four slots read at once, a loop for the rest)
                             const uint32_t r0 = regp[b0], r1 = regp[b0 + 1u], r2 = regp[b0 + 2u], r3 = regp[b0 + 3u];
                             within = (r0 < q ? 1u : 0u) + (r1 < q ? 1u : 0u) + (r2 < q ? 1u : 0u) + ((cnt > 3u && r3 < q) ? 1u : 0u);
                             for (uint32_t t = 4; t < cnt; t++) within += ((uint32_t) regp[b0 + t] < q) ? 1u : 0u;
                         }
-                        cu[i] = (cu[i] & 0xFFFF0000u) | (n_e - 1u - (b0 + within));
+                        cu[i] = (HAS_E7 ? (cu[i] & 0xFFFF0000u) : 0u) | (n_e - 1u - (b0 + within));
                     }
                 }
                 __syncthreads();
@@ -686,7 +729,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
 #pragma unroll
             for (int i = 0; i < NI; i++) {
                 const uint32_t u = l128 + 128u * i;
-                if (u < m && !(bk[i] >> 31)) atomicOr(&kW[(cu[i] & 0xFFFFu) >> 5], 1u << (cu[i] & 31u));
+                if (u < m && !(bk[i] >> 31)) atomicOr(&kW[cu_pos(cu[i]) >> 5], 1u << (cu[i] & 31u));
             }
             __syncthreads();
     RO_MARK(11);
@@ -705,7 +748,7 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
             for (int i = 0; i < NI; i++) {
                 const uint32_t u = l128 + 128u * i;
                 if (u < m && !(bk[i] >> 31))
-                    curp[u] = (uint16_t) (kPre[(cu[i] & 0xFFFFu) >> 5] + (uint32_t) __popc(kW[(cu[i] & 0xFFFFu) >> 5] & ((1u << (cu[i] & 31u)) - 1u)));
+                    curp[u] = (uint16_t) (kPre[cu_pos(cu[i]) >> 5] + (uint32_t) __popc(kW[cu_pos(cu[i]) >> 5] & ((1u << (cu[i] & 31u)) - 1u)));
             }
             __syncthreads();
     RO_MARK(13);
@@ -725,28 +768,33 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
     RO_MARK(14);
             double2 *out2 = reinterpret_cast<double2 *>(xy_out) + base;
             int32_t *ep = want_ep ? event_point + base : nullptr;
+            auto emit = [&](int j, uint32_t k) {
+                if (meta[j] & M_ER) {
+                    if (want_ep) ep[k] = -1;
+                } else if (want_ep || (meta[j] & M_KEY)) {
+                    const uint32_t at = want_ep ? posE[meta[j] & M_IDX]
+                                                : (uint32_t) cur[((meta[j] & M_POL) ? 0u : L::NOFF) + (meta[j] >> 16)];
+                    if (want_ep) ep[k] = (int32_t) at;
+                    if (meta[j] & M_KEY) {
+                        const uint32_t slot = (meta[j] & M_POL) ? at : nP + at;
+                        if (xy16) {
+                            xy16[base + slot] = (PIX_OF(pix[j]) >> 10) | ((pix[j] & 0x3FFu) << 16);
+                        } else {
+                            double2 v;
+                            v.x = (double) (PIX_OF(pix[j]) >> 10);
+                            v.y = (double) (pix[j] & 0x3FFu);
+                            out2[slot] = v;
+                        }
+                    }
+                }
+            };
 #pragma unroll
             for (int j = 0; j < PXH_PER; j++) {
                 const uint32_t k = tid + j * T;
-                if (k < n) {
-                    if (meta[j] & M_ER) {
-                        if (want_ep) ep[k] = -1;
-                    } else if (want_ep || (meta[j] & M_KEY)) {
-                        const uint32_t at = want_ep ? posE[meta[j] & M_IDX]
-                                                    : (uint32_t) cur[((meta[j] & M_POL) ? 0u : L::NOFF) + (meta[j] >> 16)];
-                        if (want_ep) ep[k] = (int32_t) at;
-                        if (meta[j] & M_KEY) {
-                            const uint32_t slot = (meta[j] & M_POL) ? at : nP + at;
-                            if (xy16) {
-                                xy16[base + slot] = (PIX_OF(pix[j]) >> 10) | ((pix[j] & 0x3FFu) << 16);
-                            } else {
-                                double2 v;
-                                v.x = (double) (PIX_OF(pix[j]) >> 10);
-                                v.y = (double) (pix[j] & 0x3FFu);
-                                out2[slot] = v;
-                            }
-                        }
-                    }
+                if (slot_full(j)) {
+                    emit(j, k);
+                } else if (k < n) {
+                    emit(j, k);
                 }
             }
             if (tid == 0) {
@@ -846,6 +894,9 @@ __device__ __forceinline__ bool slice_hash_window_slots(unsigned char *smem, con
 // goes through the six-slot form, one of 1536 .. 2047 through the eight-slot form: the slots j = 6, 7 of the eight-slot code
 // are empty in every lane of such a window, yet its pixel tests, first probes, ballots and packing still run for them.  The
 // choice is uniform over the workgroup; tables, limits (CAP = 2047) and results are the same.
+// Reference order: a window of 1280 .. 1535 events — five full slots and a partial one, the shipped windows again — takes the
+// six-slot form with NFULL = 5: slice stage 0.834 -> 0.781 ms on the 50 M-event stream (profiles/slice_predication.md).  A third
+// copy of the form in the kernel (89 KB of code instead of 60); a workgroup runs one of the three, the others are code it jumps over.
 constexpr int PXH_SHORT_PER = 6;
 template <int LOGC, bool REFORDER>
 __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uint32_t s, const uint8_t *__restrict__ rec,
@@ -858,7 +909,14 @@ __device__ __forceinline__ bool slice_hash_window(unsigned char *smem, const uin
                                                   uint32_t *__restrict__ xy16 = nullptr, uint32_t *__restrict__ seg_fmt = nullptr) {
     if constexpr (LOGC == 11) {
         static_assert(PXH_SHORT_PER < PixHash<11>::PER, "the short form");
-        if (win_hi[s] - win_lo[s] < (uint32_t) PXH_SHORT_PER * PXH_T)
+        const uint32_t n_ = win_hi[s] - win_lo[s];
+        if constexpr (REFORDER) {
+            if (n_ < (uint32_t) PXH_SHORT_PER * PXH_T && n_ >= (uint32_t) (PXH_SHORT_PER - 1) * PXH_T)
+                return slice_hash_window_slots<11, true, PXH_SHORT_PER, PXH_SHORT_PER - 1>(smem, s, rec, win_lo, win_hi, win_base, cap_points,
+                                                                                          xy_out, seg_off, seg_cnt, event_point, overflow, todo,
+                                                                                          todo_count, bucket_tab, xy16, seg_fmt);
+        }
+        if (n_ < (uint32_t) PXH_SHORT_PER * PXH_T)
             return slice_hash_window_slots<11, REFORDER, PXH_SHORT_PER>(smem, s, rec, win_lo, win_hi, win_base, cap_points, xy_out, seg_off,
                                                                         seg_cnt, event_point, overflow, todo, todo_count, bucket_tab, xy16,
                                                                         seg_fmt);
