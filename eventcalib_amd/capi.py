@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "ecal_solver_reassociate_dev", "ecal_solver_reassociate", "ecal_solver_create_reassociated",
     "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
     "ecal_raw_default_options", "ecal_raw_block_words", "ecal_raw_count_events_dev", "ecal_events_from_raw_dev", "ecal_stream_create_from_raw_file", "ecal_raw_to_bin_file",
+    "ecal_aedat_default_options", "ecal_aedat_block_events", "ecal_aedat_parse_header", "ecal_aedat_index_packets", "ecal_aedat_count_events_dev", "ecal_events_from_aedat_dev", "ecal_stream_create_from_aedat_file", "ecal_aedat_to_bin_file",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -90,6 +91,44 @@ class RawInfo(ctypes.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+AEDAT_AUTO, AEDAT_2_0, AEDAT_3_1 = 0, 20, 31   # ECAL_AEDAT_AUTO / _2_0 / _3_1
+_AEDAT_FORMATS = {None: AEDAT_AUTO, "auto": AEDAT_AUTO, "2.0": AEDAT_2_0, "3.1": AEDAT_3_1}
+
+
+def aedat_format(fmt):
+    """"3.1" / "2.0" / None (from the file's version line), or the ECAL_AEDAT_* number, as the number"""
+    if isinstance(fmt, str) or fmt is None:
+        return _AEDAT_FORMATS[fmt.lower() if fmt else None]
+    return int(fmt)
+
+
+class AedatOptions(ctypes.Structure):
+    """ecal_aedat_options (include/ecal.h, aedat ingest)."""
+    _fields_ = [("format", ctypes.c_int), ("source", ctypes.c_int), ("time_base", ctypes.c_int64), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("flip_x", ctypes.c_int), ("flip_y", ctypes.c_int), ("start_time", ctypes.c_double),
+                ("has_end_time", ctypes.c_int), ("end_time", ctypes.c_double)]
+
+
+class AedatInfo(ctypes.Structure):
+    """ecal_aedat_info (include/ecal.h, aedat ingest)."""
+    _fields_ = [("n_raw_events", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("n_invalid", ctypes.c_uint64),
+                ("n_outside", ctypes.c_uint64), ("n_negative", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64),
+                ("n_after_end", ctypes.c_uint64), ("n_packets", ctypes.c_uint64), ("n_other_packets", ctypes.c_uint64),
+                ("n_records", ctypes.c_uint64), ("n_other_records", ctypes.c_uint64), ("n_trailing_bytes", ctypes.c_uint64),
+                ("n_time_wraps", ctypes.c_uint64), ("header_bytes", ctypes.c_uint64), ("format", ctypes.c_int)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class AedatPacket(ctypes.Structure):
+    """ecal_aedat_packet (include/ecal.h, aedat ingest): 16 bytes."""
+    _fields_ = [("offset_of_first_event", ctypes.c_uint64), ("n_events", ctypes.c_uint32), ("ts_overflow", ctypes.c_int32)]
+
+
+AEDAT_PACKET_DTYPE = np.dtype([("offset_of_first_event", "<u8"), ("n_events", "<u4"), ("ts_overflow", "<i4")])
 
 
 import weakref
@@ -587,6 +626,139 @@ class Context:
         info = RawInfo()
         h = vp()
         st = L.ecal_stream_create_from_raw_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    # ---- aedat ingest: iniVation AEDAT 3.1 / 2.0 payloads decoded in HBM (ecal_events_from_aedat_dev and the file forms) ----
+    def aedat_options(self, format=None, source=-1, time_base=0, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
+                      end_time=None):
+        """ecal_aedat_options from ecal_aedat_default_options: format "3.1" / "2.0" / None (from the file's version line), source >= 0
+        = only polarity packets of that eventSource (3.1 file forms and the indexer), time_base in microseconds of the camera's clock,
+        width / height 0 = no bound, flip_x / flip_y need them, start_time None = -inf, end_time None = to the end."""
+        L = self._L
+        L.ecal_aedat_default_options.argtypes = [ctypes.POINTER(AedatOptions)]
+        L.ecal_aedat_default_options.restype = None
+        o = AedatOptions()
+        L.ecal_aedat_default_options(ctypes.byref(o))
+        o.format, o.source, o.time_base, o.width, o.height = aedat_format(format), int(source), int(time_base), int(width), int(height)
+        o.flip_x, o.flip_y = int(bool(flip_x)), int(bool(flip_y))
+        if start_time is not None:
+            o.start_time = float(start_time)
+        if end_time is not None:
+            o.has_end_time, o.end_time = 1, float(end_time)
+        return o
+
+    def aedat_block_events(self, format):
+        """ecal_aedat_block_events: event slots / records per decode block of this build."""
+        self._L.ecal_aedat_block_events.argtypes, self._L.ecal_aedat_block_events.restype = [ctypes.c_int], ctypes.c_uint32
+        return int(self._L.ecal_aedat_block_events(aedat_format(format)))
+
+    def aedat_parse_header(self, data, format=None):
+        """ecal_aedat_parse_header: the first bytes of a file -> (format number in force, header_bytes)."""
+        L = self._L
+        L.ecal_aedat_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]
+        L.ecal_aedat_parse_header.restype = ctypes.c_int
+        data = bytes(data)
+        fmt, hb = ctypes.c_int(aedat_format(format)), ctypes.c_uint64()
+        self._check(L.ecal_aedat_parse_header(self._h, data, len(data), ctypes.byref(fmt), ctypes.byref(hb)))
+        return int(fmt.value), int(hb.value)
+
+    def aedat_index_packets(self, payload, source=-1, capacity=None):
+        """ecal_aedat_index_packets over a 3.1 payload in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
+        AEDAT_PACKET_DTYPE, info dict).  capacity None: counted first; a smaller one raises EcalError with status -6 and
+        .info["n_packets"] = the count needed."""
+        L = self._L
+        L.ecal_aedat_index_packets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(AedatInfo)]
+        L.ecal_aedat_index_packets.restype = ctypes.c_int
+        a = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, np.uint8).ravel()
+        ptr = a.ctypes.data if a.size else None
+        n, info = ctypes.c_uint64(), AedatInfo()
+        if capacity is None:
+            st = L.ecal_aedat_index_packets(self._h, ptr, a.size, int(source), None, 0, ctypes.byref(n), ctypes.byref(info))
+            if st not in (0, -6):
+                self._text_fail(st, info)
+            capacity = int(n.value)
+        table = np.zeros(int(capacity), AEDAT_PACKET_DTYPE)
+        st = L.ecal_aedat_index_packets(self._h, ptr, a.size, int(source), table.ctypes.data if table.size else None, table.size,
+                                        ctypes.byref(n), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return table[: int(n.value)], info.as_dict()
+
+    def _aedat_table_tensor(self, packets, device):
+        """a packet table (numpy AEDAT_PACKET_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
+        import torch
+        if packets is None:
+            return torch.zeros(0, dtype=torch.uint8, device=device), 0
+        if isinstance(packets, torch.Tensor):
+            t = packets.contiguous().view(torch.uint8).reshape(-1).to(device)
+        else:
+            a = np.ascontiguousarray(packets, AEDAT_PACKET_DTYPE)
+            t = torch.from_numpy(a.view(np.uint8).copy()).to(device) if a.size else torch.zeros(0, dtype=torch.uint8, device=device)
+        return t, t.numel() // 16
+
+    def aedat_count_events(self, payload, format, packets=None):
+        """ecal_aedat_count_events_dev: the events before any drop (always a sufficient capacity)."""
+        import torch
+        L = self._L
+        L.ecal_aedat_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.ecal_aedat_count_events_dev.restype = ctypes.c_int
+        t = self._text_tensor(payload)
+        pk, n_pk = self._aedat_table_tensor(packets, t.device)
+        n = ctypes.c_uint64()
+        self._check(L.ecal_aedat_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
+                                                  aedat_format(format), ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def events_from_aedat(self, payload, format, packets=None, capacity=None, **options):
+        """ecal_events_from_aedat_dev: payload (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where it
+        is; no file header) and, for "3.1", the packet table of aedat_index_packets -> (packed 25-byte records in file order as a
+        uint8 CUDA tensor [n_events * 25], info dict).  options: aedat_options'.  capacity None: aedat_count_events (always enough); a
+        smaller one raises EcalError with status -6 and .info["n_events"] = the count needed."""
+        import torch
+        L = self._L
+        L.ecal_events_from_aedat_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.POINTER(AedatOptions), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AedatInfo), ctypes.c_void_p]
+        L.ecal_events_from_aedat_dev.restype = ctypes.c_int
+        o = self.aedat_options(format=format, **options)
+        t = self._text_tensor(payload)
+        pk, n_pk = self._aedat_table_tensor(packets, t.device)
+        cap = self.aedat_count_events(t, format, pk) if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        info = AedatInfo()
+        st = L.ecal_events_from_aedat_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
+                                          ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def aedat_to_bin(self, aedat_path, bin_path, **options):
+        """ecal_aedat_to_bin_file: the records of the .aedat file (file order, no sort) as a .bin of the reference's layout -> info dict."""
+        L = self._L
+        L.ecal_aedat_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(AedatOptions), ctypes.POINTER(AedatInfo)]
+        L.ecal_aedat_to_bin_file.restype = ctypes.c_int
+        o = self.aedat_options(**options)
+        info = AedatInfo()
+        st = L.ecal_aedat_to_bin_file(self._h, os.fsencode(aedat_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_aedat_file(self, path, **options):
+        """ecal_stream_create_from_aedat_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
+        file is not) -> (events, info dict, t_first, t_last)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_aedat_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AedatOptions), ctypes.POINTER(vp), ctypes.POINTER(AedatInfo)]
+        L.ecal_stream_create_from_aedat_file.restype = ctypes.c_int
+        o = self.aedat_options(**options)
+        info = AedatInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_aedat_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
         if st != 0:
             self._text_fail(st, info)
         events, t_first, t_last = self._stream_records(h)

@@ -20,6 +20,7 @@
 
 #include "../../../include/ecal.h"
 #include "../raw_events.hpp"
+#include "../aedat_events.hpp"
 #include "dbscan.h"
 
 namespace opengv2 {
@@ -155,6 +156,60 @@ public:
         if (info) *info = I;
         return (long long) I.n_events;
     }
+    // An iniVation .aedat recording (AEDAT 3.1 / 2.0; include/ecal.h, "aedat ingest") -> .bin beside it, on one host thread: the
+    // header, then the plain sequential decoder of aedat_events.hpp, the records in file order.  The baseline of aedat2binDevice,
+    // and its check: both write the same bytes.  opt null: the defaults (version from the first line, every source, the camera's
+    // clock, no bounds, no flips).
+    static long long aedat2bin(const std::string &aedatFilePath, const ecal_aedat_options *opt = nullptr, ecal_aedat_info *info = nullptr) {
+        std::ifstream is(aedatFilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + aedatFilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("aedat2bin: cannot read " + aedatFilePath);
+        ecal_aedat_options o;
+        if (opt) o = *opt; else ecal_aedat_default_options(&o);
+        if ((o.flip_x && !o.width) || (o.flip_y && !o.height)) throw std::invalid_argument("aedat2bin: flip_x / flip_y need width / height");
+        int format = ECAL_AEDAT_AUTO;
+        uint64_t headerBytes = 0;
+        std::string err;
+        const size_t headBytes = std::min<size_t>(bytes.size(), (size_t) 1 << 20);   // (the header lies within the first MiB)
+        if (ecal_aedat::aedat_parse_header(bytes.data(), headBytes, headBytes == bytes.size(), o.format, &format, &headerBytes, &err))
+            throw std::invalid_argument("aedat2bin: " + err + " (" + aedatFilePath + ")");
+        const ecal_aedat::AedatFilter f{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+        ecal_aedat::AedatCounts c;
+        std::vector<uint8_t> out;
+        auto put = [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); };
+        const uint8_t *payload = bytes.data() + headerBytes;
+        const uint64_t n = bytes.size() - headerBytes;
+        if (format == ECAL_AEDAT_3_1) {
+            if (ecal_aedat::aedat31_decode_sequential(payload, n, o.source, f, c, put, &err))
+                throw std::invalid_argument("aedat2bin: " + err + " (" + aedatFilePath + ")");
+        } else {
+            ecal_aedat::aedat20_decode_sequential(payload, n, f, c, put);
+        }
+        const auto dot = aedatFilePath.find_last_of('.');
+        std::ofstream os(aedatFilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info)
+            *info = ecal_aedat_info{c.n_raw_events, c.n_events, c.n_invalid, c.n_outside, c.n_negative, c.n_before_start, c.n_after_end,
+                                    c.n_packets, c.n_other_packets, c.n_records, c.n_other_records, c.n_trailing_bytes, c.n_time_wraps,
+                                    headerBytes, format};
+        return (long long) c.n_events;
+    }
+    // aedat2bin on the device (ecal_aedat_to_bin_file: the packets indexed on the host, the payload uploaded and decoded in HBM): the
+    // same arguments, the same output file name, the same bytes in it, the same returned count
+    static long long aedat2binDevice(const std::string &aedatFilePath, const ecal_aedat_options *opt = nullptr, ecal_aedat_info *info = nullptr) {
+        const auto dot = aedatFilePath.find_last_of('.');
+        ecal_aedat_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_aedat_to_bin_file(ctx, aedatFilePath.c_str(), (aedatFilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("aedat2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_aedat_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // txt2bin's arguments as ecal_text_options (LLONG_MIN: no base / no end, as there)
     static ecal_text_options textOptions(double timeMagnitude, long long timeBase_in, long long endTime_in) {
         ecal_text_options opt;
@@ -249,6 +304,20 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_raw_info rawInfo{};     // what the last loadRawFile saw (words, drops, wraps, the format in force)
+    // The same from an iniVation .aedat recording (ecal_stream_create_from_aedat_file): decoded on the device, without a .bin in
+    // between.  opt null: the defaults; the reading loop's startTime / customEnd / endTime go into opt's start_time / end_time.
+    void loadAedatFile(const std::string &aedatFilePath, const ecal_aedat_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_aedat_file(ctx, aedatFilePath.c_str(), opt, &stream_, &aedatInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadAedatFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_aedat_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_aedat_info aedatInfo{}; // what the last loadAedatFile saw (packets, records, drops, wraps, the format in force)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

@@ -76,6 +76,31 @@ int main(int argc, char **argv) {
             opt.has_end_time = customEnd ? 1 : 0;
             opt.end_time = endTimeSetting;
             container->loadRawFile(eventsPath, &opt);
+        } else if (eventsPath.size() >= 7 && eventsPath.compare(eventsPath.size() - 7, 7, ".aedat4") == 0) {
+            std::fprintf(stderr, "AEDAT 4 (%s) is not read: export the recording as AEDAT 3.1 or 2.0\n", eventsPath.c_str());
+            return 4;
+        } else if (eventsPath.size() >= 6 && eventsPath.compare(eventsPath.size() - 6, 6, ".aedat") == 0) {
+            // an iniVation recording (AEDAT 3.1 / 2.0, the version from its first line) decoded on the device.  Keys of this build,
+            // all optional: Aedat_TimeBase (microseconds of the camera's clock, 0), Aedat_FlipX / Aedat_FlipY (0; which a
+            // recorder's files need is the user's knowledge), Aedat_Source (3.1: only polarity packets of this eventSource; absent:
+            // every source).  Events outside Camera.width x Camera.height are dropped.
+            ecal_aedat_options opt;
+            ecal_aedat_default_options(&opt);
+            if (!fsSettings["Aedat_TimeBase"].isNone()) opt.time_base = std::strtoll(((std::string) fsSettings["Aedat_TimeBase"]).c_str(), nullptr, 10);
+            if (!fsSettings["Aedat_FlipX"].isNone()) opt.flip_x = (int) fsSettings["Aedat_FlipX"] ? 1 : 0;
+            if (!fsSettings["Aedat_FlipY"].isNone()) opt.flip_y = (int) fsSettings["Aedat_FlipY"] ? 1 : 0;
+            if (!fsSettings["Aedat_Source"].isNone()) opt.source = (int) fsSettings["Aedat_Source"];
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            opt.start_time = startTime;
+            opt.has_end_time = customEnd ? 1 : 0;
+            opt.end_time = endTimeSetting;
+            try {
+                container->loadAedatFile(eventsPath, &opt);
+            } catch (const std::exception &e) {   // (a version that is not read, a broken packet: said plainly, no abort)
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
         } else {
             container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
         }

@@ -1117,6 +1117,124 @@ int ecal_stream_create_from_raw_file(ecal_ctx *ctx, const char *path, const ecal
                                      ecal_raw_info *info);
 int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const char *bin_path, const ecal_raw_options *opt, ecal_raw_info *info);
 
+/* ---- aedat ingest: iniVation AEDAT 3.1 / 2.0 recordings into packed records, decoded in HBM ------------------
+ * A DAVIS camera's .aedat file, without a host converter in front.  Nothing in the reference reads these formats and no such file
+ * was at hand when this was written: the layouts are restated from the published format descriptions, and this contract is the
+ * specification (eventcalib_amd/csrc/aedat_events.hpp restates it for the kernels, the host decoder and the tests).  The first real
+ * recording should be checked against the vendor's own export.  AEDAT 4 (compressed packets), 1.0, 3.0 and ROS bags are not read.
+ *
+ * File header (file entry points and ecal_aedat_parse_header): the first line is "#!AER-DAT3.1\r\n" or "#!AER-DAT2.0\r\n"; any
+ *   other version is ECAL_ERR_INVALID with a text that names the version.  options.format other than ECAL_AEDAT_AUTO overrides the
+ *   line (which then need not be there); no version from either source is ECAL_ERR_INVALID.
+ *   3.1: the header runs up to and including the line "#!END-HEADER\r\n", which must lie within the first MiB (else
+ *        ECAL_ERR_INVALID); a line "#Format: <value>" whose value is not RAW is ECAL_ERR_INVALID.
+ *   2.0: the header is the maximal run of header lines at the start of the file.  A header line starts with '#', reaches its '\n'
+ *        within 4096 bytes and holds nothing but bytes 0x20..0x7E, '\t' and '\r' before it.  (The rule is needed because the first
+ *        byte of a 2.0 record can be 0x23.)
+ *   info.header_bytes = where the payload starts.  The _dev entry points take the payload only, with an explicit format.
+ * AEDAT 3.1 payload: a chain of packets, each a 28-byte little-endian header followed by eventCapacity x eventSize body bytes
+ *   (a 64-bit product).  NO alignment of a packet may be assumed: frame packets have arbitrary sizes.  Header, by byte offset:
+ *     0 i16 eventType    2 i16 eventSource    4 i32 eventSize    8 i32 eventTSOffset    12 i32 eventTSOverflow
+ *     16 i32 eventCapacity    20 i32 eventNumber    24 i32 eventValid
+ *   Only packets with eventType == 1 (polarity) carry events — with options.source >= 0 only those whose eventSource is that
+ *   number.  Every other packet is stepped over and counted in n_other_packets.  Every packet must have eventSize, eventCapacity,
+ *   eventNumber and eventValid >= 0 and eventNumber <= eventCapacity; a packet that carries events must have eventSize == 8 and
+ *   eventTSOffset == 4.  A packet that breaks a rule is ECAL_ERR_INVALID; ecal_last_error names the packet's number (0-based, over
+ *   all packets) and its byte offset in the payload.
+ *   A polarity event is a u32 `data` followed by an i32 `ts`: bit 0 of data = valid, bit 1 = polarity, y = bits 16..2,
+ *   x = bits 31..17; t_us = ((int64) eventTSOverflow << 31) + (ts & 0x7FFFFFFF).  The first eventNumber events of the body are
+ *   decoded (eventValid is not relied on); an event with valid == 0 is dropped and counted in n_invalid.
+ *   A header or a body that runs past the end of the payload ends the chain.  Of a body cut short the events wholly present
+ *   (and in front of eventNumber) are decoded.  n_trailing_bytes: for a header cut short, the bytes from its start; for a body cut
+ *   short, the bytes behind its last whole record of eventSize bytes.  The packet cut short is counted as its type says.
+ * AEDAT 2.0 payload: big-endian 8-byte records, u32 address then u32 ts in microseconds; 1 - 7 trailing bytes are ignored and
+ *   counted.  A DVS event has bit 31 == 0 and bit 10 == 0 of the address: x = bits 21..12, y = bits 30..22, polarity = bit 11.
+ *   Every other record (APS, IMU, external input) is counted in n_other_records.  Time wraps are counted over ALL records, of
+ *   every type: between consecutive records with stamps p then q one wrap is counted when q < p and p - q > 2^31; a smaller
+ *   backward step is taken as it is (time then runs backwards; a stream sorts).  t_us = (wraps << 32) | ts with the wraps counted up
+ *   to and including the record.  n_time_wraps, n_records, n_other_records are those of the whole payload, wherever the stream ends.
+ * Conversion and filter, in file order — the raw ingest's: t = (double)(t_us - time_base) * 1e-6 (one integer subtraction, one
+ *   conversion, one multiplication, no contraction); x, y = the doubles of the integers; the polarity byte is 0 or 1.  With width /
+ *   height non-zero an event with x >= width or y >= height is dropped (n_outside).  flip_x / flip_y give x = width - 1 - x /
+ *   y = height - 1 - y, applied BEHIND the bounds test; they need width / height non-zero (else ECAL_ERR_INVALID) and default to 0.
+ *   Which flips a given recorder's files need (the origin's corner differs between tools) is the caller's knowledge and is not
+ *   decided here.  Then t < 0 is dropped (n_negative); then kept if t >= start_time (else n_before_start), and with has_end_time the
+ *   first event with t >= end_time ends the stream: it and every event behind it count as n_after_end and as nothing else.
+ *   n_events + n_invalid + n_outside + n_negative + n_before_start + n_after_end = n_raw_events = what
+ *   ecal_aedat_count_events_dev returns.
+ *
+ * ecal_aedat_block_events: event slots (3.1) / records (2.0) per decode block of this build (0 for an unknown format) — a fact
+ *   for tests that place block boundaries, not a tuning knob.
+ * ecal_aedat_parse_header: data (HOST) = the first n_bytes of a file (at most the first MiB is needed).  *format on entry is the
+ *   option (ECAL_AEDAT_AUTO: from the version line), on return the format in force; *header_bytes as above.  ctx may be NULL (no
+ *   error text then).
+ * ecal_aedat_index_packets: a HOST function over a 3.1 payload in host memory.  One entry per polarity packet that carries events by
+ *   the rules above (also one of no events), in file order.  *n_packets = the count; ECAL_ERR_RANGE when it exceeds `capacity`
+ *   (out holds the first `capacity`; out may be NULL with capacity 0: a count).  info (optional): n_packets, n_other_packets,
+ *   n_raw_events, n_trailing_bytes.  Only the headers are read.  ctx may be NULL (no error text then).
+ *   The chain is not walked on the device: a packet is found only through the header before it.
+ * ecal_aedat_count_events_dev: *n_events (HOST) = the events before any drop (3.1: the table's sum; 2.0: the DVS records): always
+ *   a sufficient `capacity`.  Waits for `stream`.
+ * ecal_events_from_aedat_dev: d_payload (DEVICE, 16-byte aligned, n_bytes bytes; nothing behind n_bytes is read) and, for 3.1,
+ *   d_packets (DEVICE, 8-byte aligned, n_packets entries as ecal_aedat_index_packets writes them; ignored for 2.0) into d_events
+ *   (DEVICE, room for `capacity` records, file order, not sorted); opt->format must be ECAL_AEDAT_3_1 or _2_0; opt->source is not
+ *   looked at (the table is already of one source).  A table whose packets do not lie within the payload is ECAL_ERR_INVALID
+ *   (nothing outside the payload is read).  info (HOST) is filled on ECAL_OK and on ECAL_ERR_RANGE (capacity too small:
+ *   info->n_events = the count needed, call again; also more than 2^32-1 events or records); n_other_packets and the 3.1
+ *   n_trailing_bytes are the indexer's to report, not this call's.  On an error the contents of d_events are undefined.  Enqueues
+ *   on `stream` and waits for it: the call returns with the records in place.
+ * ecal_stream_create_from_aedat_file: the header read on the host, for 3.1 the packet headers read and indexed on the host (28 bytes
+ *   a packet), the payload through pinned buffers into HBM (reads overlapped with the uploads), decoded there, the payload freed,
+ *   then the stream brought into time order if it is not (ecal_stream_create's rule).  info may be NULL.
+ * ecal_aedat_to_bin_file: the same records in file order, no sort, as a .bin of the reference's layout. */
+enum { ECAL_AEDAT_AUTO = 0, ECAL_AEDAT_2_0 = 20, ECAL_AEDAT_3_1 = 31 };
+typedef struct ecal_aedat_options {
+    int format;              /* ECAL_AEDAT_AUTO: from the file's version line */
+    int source;              /* 3.1 file forms: >= 0, only polarity packets of this eventSource; -1: of every source */
+    int64_t time_base;       /* microseconds of the camera's clock */
+    uint32_t width, height;  /* 0: no bound */
+    int flip_x, flip_y;      /* need width / height */
+    double start_time;       /* seconds */
+    int has_end_time;
+    double end_time;         /* seconds */
+} ecal_aedat_options;
+typedef struct ecal_aedat_info {
+    uint64_t n_raw_events;     /* events before any drop */
+    uint64_t n_events;         /* records written, or needed */
+    uint64_t n_invalid;        /* 3.1: events dropped for a clear valid bit */
+    uint64_t n_outside;        /* events dropped for x >= width or y >= height */
+    uint64_t n_negative;       /* events dropped for t < 0 */
+    uint64_t n_before_start;   /* events dropped for t < start_time */
+    uint64_t n_after_end;      /* events from the one that ended the stream on */
+    uint64_t n_packets;        /* 3.1: packets that carry events */
+    uint64_t n_other_packets;  /* 3.1: packets stepped over (frames, IMU, special, other sources) */
+    uint64_t n_records;        /* 2.0: records of the payload */
+    uint64_t n_other_records;  /* 2.0: records that are no DVS event */
+    uint64_t n_trailing_bytes; /* bytes behind the last whole record */
+    uint64_t n_time_wraps;     /* 2.0: wraps of the 32-bit stamp */
+    uint64_t header_bytes;     /* file entry points: bytes in front of the payload */
+    int format;                /* ECAL_AEDAT_3_1 / _2_0: the format in force */
+} ecal_aedat_info;
+typedef struct ecal_aedat_packet {
+    uint64_t offset_of_first_event; /* bytes from the start of the payload */
+    uint32_t n_events;              /* events to decode */
+    int32_t ts_overflow;            /* the packet's eventTSOverflow */
+} ecal_aedat_packet;
+void ecal_aedat_default_options(ecal_aedat_options *opt);
+uint32_t ecal_aedat_block_events(int format);
+int ecal_aedat_parse_header(ecal_ctx *ctx, const uint8_t *data, uint64_t n_bytes, int *format, uint64_t *header_bytes);
+int ecal_aedat_index_packets(ecal_ctx *ctx, const uint8_t *payload_host, uint64_t n_bytes, int source, ecal_aedat_packet *out,
+                             uint64_t capacity, uint64_t *n_packets, ecal_aedat_info *info);
+int ecal_aedat_count_events_dev(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const ecal_aedat_packet *d_packets,
+                                uint64_t n_packets, int format, uint64_t *n_events, void *stream);
+int ecal_events_from_aedat_dev(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const ecal_aedat_packet *d_packets,
+                               uint64_t n_packets, const ecal_aedat_options *opt, uint8_t *d_events /*room for capacity records*/,
+                               uint64_t capacity, ecal_aedat_info *info, void *stream);
+int ecal_stream_create_from_aedat_file(ecal_ctx *ctx, const char *path, const ecal_aedat_options *opt, ecal_stream **out,
+                                       ecal_aedat_info *info);
+int ecal_aedat_to_bin_file(ecal_ctx *ctx, const char *aedat_path, const char *bin_path, const ecal_aedat_options *opt,
+                           ecal_aedat_info *info);
+
 #ifdef __cplusplus
 }
 #endif
