@@ -117,6 +117,15 @@ def load_events_aedat(ctx, path, **options):
     return events, t_first, t_last
 
 
+def load_events_bag(ctx, path, **options):
+    """A ROS 1 .bag of dvs_msgs/EventArray messages (as rpg_dvs_ros records them) -> (events, t_first, t_last) as calibrate_stream
+    takes them: uploaded and decoded on the device (capi.Context.stream_from_bag_file), in time order.  options:
+    capi.Context.bag_options' (topic, type, time_base, width, height, flip_x, flip_y, start_time, end_time).  Times count from the
+    first event's whole second unless time_base (nanoseconds of epoch time) is given."""
+    events, _info, t_first, t_last = ctx.stream_from_bag_file(path, **options)
+    return events, t_first, t_last
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,

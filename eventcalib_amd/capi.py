@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
     "ecal_raw_default_options", "ecal_raw_block_words", "ecal_raw_count_events_dev", "ecal_events_from_raw_dev", "ecal_stream_create_from_raw_file", "ecal_raw_to_bin_file",
     "ecal_aedat_default_options", "ecal_aedat_block_events", "ecal_aedat_parse_header", "ecal_aedat_index_packets", "ecal_aedat_count_events_dev", "ecal_events_from_aedat_dev", "ecal_stream_create_from_aedat_file", "ecal_aedat_to_bin_file",
+    "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -129,6 +130,34 @@ class AedatPacket(ctypes.Structure):
 
 
 AEDAT_PACKET_DTYPE = np.dtype([("offset_of_first_event", "<u8"), ("n_events", "<u4"), ("ts_overflow", "<i4")])
+
+
+class BagOptions(ctypes.Structure):
+    """ecal_bag_options (include/ecal.h, bag ingest).  topic / type are byte strings that must outlive the call (Context.bag_options
+    keeps them on the object)."""
+    _fields_ = [("topic", ctypes.c_char_p), ("type", ctypes.c_char_p), ("auto_time_base", ctypes.c_int), ("time_base", ctypes.c_int64),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("flip_x", ctypes.c_int), ("flip_y", ctypes.c_int),
+                ("start_time", ctypes.c_double), ("has_end_time", ctypes.c_int), ("end_time", ctypes.c_double)]
+
+
+class BagInfo(ctypes.Structure):
+    """ecal_bag_info (include/ecal.h, bag ingest)."""
+    _fields_ = [("n_raw_events", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("n_outside", ctypes.c_uint64),
+                ("n_negative", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64), ("n_after_end", ctypes.c_uint64),
+                ("n_messages", ctypes.c_uint64), ("n_other_messages", ctypes.c_uint64), ("n_chunks", ctypes.c_uint64),
+                ("n_connections", ctypes.c_uint64), ("n_trailing_bytes", ctypes.c_uint64), ("first_stamp_ns", ctypes.c_int64),
+                ("time_base", ctypes.c_int64), ("msg_width", ctypes.c_uint32), ("msg_height", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class BagMessage(ctypes.Structure):
+    """ecal_bag_message (include/ecal.h, bag ingest): 16 bytes."""
+    _fields_ = [("offset_of_first_event", ctypes.c_uint64), ("n_events", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+BAG_MESSAGE_DTYPE = np.dtype([("offset_of_first_event", "<u8"), ("n_events", "<u4"), ("reserved", "<u4")])
 
 
 import weakref
@@ -759,6 +788,135 @@ class Context:
         info = AedatInfo()
         h = vp()
         st = L.ecal_stream_create_from_aedat_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    # ---- bag ingest: ROS 1 bags of dvs_msgs/EventArray messages decoded in HBM (ecal_events_from_bag_dev and the file forms) ----
+    def bag_options(self, topic=None, type=None, time_base=None, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
+                    end_time=None):
+        """ecal_bag_options from ecal_bag_default_options: topic / type None = every connection of an event type (one topic),
+        time_base None = automatic (the first event's whole seconds), else int64 nanoseconds of epoch time, width / height 0 = no
+        bound, flip_x / flip_y need them, start_time None = -inf, end_time None = to the end."""
+        L = self._L
+        L.ecal_bag_default_options.argtypes = [ctypes.POINTER(BagOptions)]
+        L.ecal_bag_default_options.restype = None
+        o = BagOptions()
+        L.ecal_bag_default_options(ctypes.byref(o))
+        o.topic = os.fsencode(topic) if topic else None
+        o.type = os.fsencode(type) if type else None
+        if time_base is not None:
+            o.auto_time_base, o.time_base = 0, int(time_base)
+        o.width, o.height = int(width), int(height)
+        o.flip_x, o.flip_y = int(bool(flip_x)), int(bool(flip_y))
+        if start_time is not None:
+            o.start_time = float(start_time)
+        if end_time is not None:
+            o.has_end_time, o.end_time = 1, float(end_time)
+        return o
+
+    def bag_block_events(self):
+        """ecal_bag_block_events: event slots per decode block of this build."""
+        self._L.ecal_bag_block_events.argtypes, self._L.ecal_bag_block_events.restype = [], ctypes.c_uint32
+        return int(self._L.ecal_bag_block_events())
+
+    def bag_index_messages(self, data, topic=None, type=None, capacity=None):
+        """ecal_bag_index_messages over a bag's bytes in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
+        BAG_MESSAGE_DTYPE, info dict; info["first_stamp_ns"] is the automatic time base).  capacity None: counted first; a smaller
+        one raises EcalError with status -6 and .info["n_messages"] = the count needed."""
+        L = self._L
+        L.ecal_bag_index_messages.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(BagOptions), ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(BagInfo)]
+        L.ecal_bag_index_messages.restype = ctypes.c_int
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).ravel()
+        ptr = a.ctypes.data if a.size else None
+        o = self.bag_options(topic=topic, type=type)
+        n, info = ctypes.c_uint64(), BagInfo()
+        if capacity is None:
+            st = L.ecal_bag_index_messages(self._h, ptr, a.size, ctypes.byref(o), None, 0, ctypes.byref(n), ctypes.byref(info))
+            if st not in (0, -6):
+                self._text_fail(st, info)
+            capacity = int(n.value)
+        table = np.zeros(int(capacity), BAG_MESSAGE_DTYPE)
+        st = L.ecal_bag_index_messages(self._h, ptr, a.size, ctypes.byref(o), table.ctypes.data if table.size else None, table.size,
+                                       ctypes.byref(n), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return table[: int(n.value)], info.as_dict()
+
+    def _bag_table_tensor(self, messages, device):
+        """a message table (numpy BAG_MESSAGE_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
+        import torch
+        if messages is None:
+            return torch.zeros(0, dtype=torch.uint8, device=device), 0
+        if isinstance(messages, torch.Tensor):
+            t = messages.contiguous().view(torch.uint8).reshape(-1).to(device)
+        else:
+            a = np.ascontiguousarray(messages, BAG_MESSAGE_DTYPE)
+            t = torch.from_numpy(a.view(np.uint8).copy()).to(device) if a.size else torch.zeros(0, dtype=torch.uint8, device=device)
+        return t, t.numel() // 16
+
+    def bag_count_events(self, data, messages):
+        """ecal_bag_count_events_dev: the events before any drop (always a sufficient capacity)."""
+        import torch
+        L = self._L
+        L.ecal_bag_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.ecal_bag_count_events_dev.restype = ctypes.c_int
+        t = self._text_tensor(data)
+        mt, n_m = self._bag_table_tensor(messages, t.device)
+        n = ctypes.c_uint64()
+        self._check(L.ecal_bag_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), mt.data_ptr() if n_m else None, n_m,
+                                                ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def events_from_bag(self, data, messages, capacity=None, **options):
+        """ecal_events_from_bag_dev: the whole bag (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where
+        it is) and the message table of bag_index_messages -> (packed 25-byte records in file order as a uint8 CUDA tensor
+        [n_events * 25], info dict).  options: bag_options' — the device form needs an explicit time_base (the indexer's
+        first_stamp_ns is the automatic one); without one the library refuses the call.  capacity None: bag_count_events (always
+        enough); a smaller one raises EcalError with status -6 and .info["n_events"] = the count needed."""
+        import torch
+        L = self._L
+        L.ecal_events_from_bag_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(BagOptions), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(BagInfo), ctypes.c_void_p]
+        L.ecal_events_from_bag_dev.restype = ctypes.c_int
+        o = self.bag_options(**options)
+        t = self._text_tensor(data)
+        mt, n_m = self._bag_table_tensor(messages, t.device)
+        cap = self.bag_count_events(t, mt) if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        info = BagInfo()
+        st = L.ecal_events_from_bag_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), mt.data_ptr() if n_m else None, n_m,
+                                        ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def bag_to_bin(self, bag_path, bin_path, **options):
+        """ecal_bag_to_bin_file: the records of the .bag file (file order, no sort) as a .bin of the reference's layout -> info dict."""
+        L = self._L
+        L.ecal_bag_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(BagOptions), ctypes.POINTER(BagInfo)]
+        L.ecal_bag_to_bin_file.restype = ctypes.c_int
+        o = self.bag_options(**options)
+        info = BagInfo()
+        st = L.ecal_bag_to_bin_file(self._h, os.fsencode(bag_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_bag_file(self, path, **options):
+        """ecal_stream_create_from_bag_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the file
+        is not) -> (events, info dict, t_first, t_last).  info["time_base"] is the base in force (nanoseconds)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_bag_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(BagOptions), ctypes.POINTER(vp), ctypes.POINTER(BagInfo)]
+        L.ecal_stream_create_from_bag_file.restype = ctypes.c_int
+        o = self.bag_options(**options)
+        info = BagInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_bag_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
         if st != 0:
             self._text_fail(st, info)
         events, t_first, t_last = self._stream_records(h)

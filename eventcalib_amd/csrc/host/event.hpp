@@ -21,6 +21,7 @@
 #include "../../../include/ecal.h"
 #include "../raw_events.hpp"
 #include "../aedat_events.hpp"
+#include "../bag_events.hpp"
 #include "dbscan.h"
 
 namespace opengv2 {
@@ -210,6 +211,52 @@ public:
         if (info) *info = I;
         return (long long) I.n_events;
     }
+    // A ROS 1 .bag of dvs_msgs/EventArray messages (format 2.0; include/ecal.h, "bag ingest") -> .bin beside it, on one host thread:
+    // the plain sequential decoder of bag_events.hpp, the records in file order.  The baseline of bag2binDevice, and its check: both
+    // write the same bytes.  opt null: the defaults (every connection of an event type, the automatic time base, no bounds, no flips).
+    static long long bag2bin(const std::string &bagFilePath, const ecal_bag_options *opt = nullptr, ecal_bag_info *info = nullptr) {
+        std::ifstream is(bagFilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + bagFilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("bag2bin: cannot read " + bagFilePath);
+        ecal_bag_options o;
+        if (opt) o = *opt; else ecal_bag_default_options(&o);
+        if ((o.flip_x && !o.width) || (o.flip_y && !o.height)) throw std::invalid_argument("bag2bin: flip_x / flip_y need width / height");
+        ecal_bag::BagChoice choice;
+        if (o.topic) choice.topic = o.topic;
+        if (o.type) choice.type = o.type;
+        const ecal_bag::BagFilter f{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+        ecal_bag::BagCounts c;
+        std::vector<uint8_t> out;
+        auto put = [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); };
+        std::string err;
+        int64_t base = 0;
+        if (ecal_bag::bag_decode_sequential(bytes.data(), bytes.size(), choice, o.auto_time_base, f, c, put, &base, &err))
+            throw std::invalid_argument("bag2bin: " + err + " (" + bagFilePath + ")");
+        const auto dot = bagFilePath.find_last_of('.');
+        std::ofstream os(bagFilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info)
+            *info = ecal_bag_info{c.n_raw_events, c.n_events, c.n_outside, c.n_negative, c.n_before_start, c.n_after_end, c.n_messages,
+                                  c.n_other_messages, c.n_chunks, c.n_connections, c.n_trailing_bytes, c.first_stamp_ns, base, c.msg_width,
+                                  c.msg_height};
+        return (long long) c.n_events;
+    }
+    // bag2bin on the device (ecal_bag_to_bin_file: the messages indexed on the host, the file uploaded and decoded in HBM): the same
+    // arguments, the same output file name, the same bytes in it, the same returned count
+    static long long bag2binDevice(const std::string &bagFilePath, const ecal_bag_options *opt = nullptr, ecal_bag_info *info = nullptr) {
+        const auto dot = bagFilePath.find_last_of('.');
+        ecal_bag_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_bag_to_bin_file(ctx, bagFilePath.c_str(), (bagFilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("bag2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_bag_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // txt2bin's arguments as ecal_text_options (LLONG_MIN: no base / no end, as there)
     static ecal_text_options textOptions(double timeMagnitude, long long timeBase_in, long long endTime_in) {
         ecal_text_options opt;
@@ -318,6 +365,20 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_aedat_info aedatInfo{}; // what the last loadAedatFile saw (packets, records, drops, wraps, the format in force)
+    // The same from a ROS 1 .bag of event arrays (ecal_stream_create_from_bag_file): decoded on the device, without a .bin in between.
+    // opt null: the defaults; the reading loop's startTime / customEnd / endTime go into opt's start_time / end_time.
+    void loadBagFile(const std::string &bagFilePath, const ecal_bag_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_bag_file(ctx, bagFilePath.c_str(), opt, &stream_, &bagInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadBagFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_bag_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_bag_info bagInfo{};     // what the last loadBagFile saw (messages, chunks, drops, the time base in force)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

@@ -101,6 +101,36 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "%s\n", e.what());
                 return 4;
             }
+        } else if (eventsPath.size() >= 4 && eventsPath.compare(eventsPath.size() - 4, 4, ".bag") == 0) {
+            // a ROS 1 bag of dvs_msgs/EventArray messages (as rpg_dvs_ros records them) decoded on the device.  Keys of this build,
+            // all optional: Bag_Topic (absent: the one topic of events), Bag_Type (absent: dvs_msgs/EventArray and
+            // prophesee_event_msgs/EventArray), Bag_TimeBase (nanoseconds of epoch time; absent: the first event's whole second),
+            // Bag_FlipX / Bag_FlipY (0).  Events outside Camera.width x Camera.height are dropped.
+            ecal_bag_options opt;
+            ecal_bag_default_options(&opt);
+            std::string bagTopic, bagType;
+            if (!fsSettings["Bag_Topic"].isNone()) bagTopic = (std::string) fsSettings["Bag_Topic"];
+            if (!fsSettings["Bag_Type"].isNone()) bagType = (std::string) fsSettings["Bag_Type"];
+            opt.topic = bagTopic.c_str();
+            opt.type = bagType.c_str();
+            if (!fsSettings["Bag_TimeBase"].isNone()) {
+                opt.auto_time_base = 0;
+                opt.time_base = std::strtoll(((std::string) fsSettings["Bag_TimeBase"]).c_str(), nullptr, 10);
+            }
+            if (!fsSettings["Bag_FlipX"].isNone()) opt.flip_x = (int) fsSettings["Bag_FlipX"] ? 1 : 0;
+            if (!fsSettings["Bag_FlipY"].isNone()) opt.flip_y = (int) fsSettings["Bag_FlipY"] ? 1 : 0;
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            opt.start_time = startTime;
+            opt.has_end_time = customEnd ? 1 : 0;
+            opt.end_time = endTimeSetting;
+            try {
+                container->loadBagFile(eventsPath, &opt);
+            } catch (const std::exception &e) {   // (compressed chunks, a ROS 2 file, another message layout: said plainly, no abort)
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
+            std::printf("bag_time_base %lld\n", (long long) container->bagInfo.time_base);   // nanoseconds: t = 0 of this run
         } else {
             container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
         }

@@ -1121,7 +1121,8 @@ int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const char *bin_pa
  * A DAVIS camera's .aedat file, without a host converter in front.  Nothing in the reference reads these formats and no such file
  * was at hand when this was written: the layouts are restated from the published format descriptions, and this contract is the
  * specification (eventcalib_amd/csrc/aedat_events.hpp restates it for the kernels, the host decoder and the tests).  The first real
- * recording should be checked against the vendor's own export.  AEDAT 4 (compressed packets), 1.0, 3.0 and ROS bags are not read.
+ * recording should be checked against the vendor's own export.  AEDAT 4 (compressed packets), 1.0 and 3.0 are not read; a ROS 1 bag of
+ * event arrays goes through the bag ingest below.
  *
  * File header (file entry points and ecal_aedat_parse_header): the first line is "#!AER-DAT3.1\r\n" or "#!AER-DAT2.0\r\n"; any
  *   other version is ECAL_ERR_INVALID with a text that names the version.  options.format other than ECAL_AEDAT_AUTO overrides the
@@ -1234,6 +1235,129 @@ int ecal_stream_create_from_aedat_file(ecal_ctx *ctx, const char *path, const ec
                                        ecal_aedat_info *info);
 int ecal_aedat_to_bin_file(ecal_ctx *ctx, const char *aedat_path, const char *bin_path, const ecal_aedat_options *opt,
                            ecal_aedat_info *info);
+
+/* ---- bag ingest: ROS 1 bags (format 2.0) of dvs_msgs/EventArray messages into packed records, decoded in HBM ----
+ * The file that rpg_dvs_ros records from a DAVIS camera, without a host converter in front.  Nothing in the reference reads a bag and
+ * no bag was at hand when this was written: the layout is restated from the published descriptions (ROS bag format 2.0, ROS 1
+ * message serialisation), and this contract is the specification (eventcalib_amd/csrc/bag_events.hpp restates it for the kernels,
+ * the host decoder and the tests).  The first real bag should be checked against `rostopic echo` or a text dump: the event count,
+ * the first and last stamps, a handful of coordinates.  Compressed chunks, format 1.2, ROS 2 containers and message packages of
+ * another layout are refused by name.
+ *
+ * File: the 13 bytes "#ROSBAG V2.0\n", then a chain of records.  Any other "#ROSBAG V..." line is ECAL_ERR_INVALID with a text that
+ *   names the version; a file that starts with "SQLite format 3\0" is refused by name as a ROS 2 bag, one that starts with
+ *   "\x89MCAP0\r\n" as a ROS 2 / MCAP file; anything else is ECAL_ERR_INVALID.
+ * Record: u32 header_len, header bytes, u32 data_len, data bytes; all integers of the format are little-endian.  A header is a run
+ *   of fields: u32 field_len, then name=value — the name is ASCII up to the first '=', the value is binary.  Unknown fields are
+ *   ignored.  A field that runs past its header (or has no '=') is ECAL_ERR_INVALID, and so is a header without a 1-byte `op`
+ *   field.  Error texts name the record's number (0-based, over all records, inner and outer, in file order) and its byte offset in
+ *   the file.  By op:
+ *     0x03 bag header: its data is padding and is stepped over; index_pos, conn_count and chunk_count are not relied on.
+ *     0x05 chunk: field `compression` must be "none" — bz2 or lz4 is ECAL_ERR_INVALID with a text that names the compression and
+ *          says `rosbag decompress`; field `size` (u32) must equal data_len; the data is a chain of records walked in turn.  Inside
+ *          a chunk only 0x02 and 0x07 are expected: any other op there is ECAL_ERR_INVALID, and so is an inner record that runs
+ *          past the end of a chunk that is wholly present.
+ *     0x07 connection, inside chunks and at top level: header fields `conn` (u32) and `topic`; the data is a second field list, of
+ *          which `type` is read.  A connection seen again with the same id must name the same topic and type (else
+ *          ECAL_ERR_INVALID).
+ *     0x02 message data, inside chunks — at top level (an unchunked bag) it is accepted too: header fields `conn` (u32) and `time`
+ *          (not used); the data is the serialised message.  A message whose connection is not defined in front of it is
+ *          ECAL_ERR_INVALID.
+ *     0x04 index data and 0x06 chunk info are stepped over: the index section is not used, and a bag that was never closed
+ *          (index_pos == 0) reads the same as a closed one.
+ *     Any other op is ECAL_ERR_INVALID.
+ *   A record whose header or data runs past the end of the file ends the chain, like a recording cut short: of a chunk cut short
+ *   the inner records wholly present are walked; a message cut short is not decoded at all (nor counted).  n_trailing_bytes = the
+ *   bytes from the start of the first record (inner or outer) that is not wholly present.
+ * Which messages carry events: chosen by their connection's type and topic.  Accepted types are dvs_msgs/EventArray and
+ *   prophesee_event_msgs/EventArray (the same layout); with options.type non-empty that one name is accepted instead.  The md5sum is
+ *   not looked at.  With options.topic non-empty only connections of that topic are chosen; with it empty all connections of an
+ *   accepted type are, provided they share one topic: two or more event topics without a choice (a stereo bag) is
+ *   ECAL_ERR_INVALID with a text that lists the topics.  No chosen connection at all is ECAL_ERR_INVALID with a text that lists the
+ *   topics and types that are there.  Every message of another connection is counted in n_other_messages.
+ * Message, by byte offset in the record's data:   0 u32 seq   4 u32 stamp.secs   8 u32 stamp.nsecs   12 u32 L   16 L bytes of
+ *   frame_id   16+L u32 height   20+L u32 width   24+L u32 n   28+L n events of 13 bytes:
+ *     0 u16 x   2 u16 y   4 u32 ts.secs   8 u32 ts.nsecs   12 u8 polarity
+ *   28 + L + 13 n must equal the record's data_len, else ECAL_ERR_INVALID naming the message (this catches a message package of
+ *   another layout).  NO alignment of anything may be assumed.
+ * Conversion and filter, in file order — the raw and AEDAT ingests' with nanoseconds: t_ns = (int64) secs * 1 000 000 000 + nsecs
+ *   (nsecs taken as it is, also >= 1e9); t = (double)(t_ns - time_base) * 1e-9 (one integer subtraction, one conversion, one
+ *   multiplication, no contraction); x, y = the doubles of the integers; the polarity byte of the record is byte != 0.  With width /
+ *   height non-zero an event with x >= width or y >= height is dropped (n_outside).  flip_x / flip_y give x = width - 1 - x /
+ *   y = height - 1 - y, applied BEHIND the bounds test; they need width / height non-zero (else ECAL_ERR_INVALID).  Then t < 0 is
+ *   dropped (n_negative); then kept if t >= start_time (else n_before_start), and with has_end_time the first event with
+ *   t >= end_time ends the stream: it and every event behind it count as n_after_end and as nothing else.
+ *   n_events + n_outside + n_negative + n_before_start + n_after_end = n_raw_events, always.
+ * Time base: ROS stamps are epoch time; at 1.6e9 s a double resolves only 2.4e-7 s, so base 0 is useless.  options.auto_time_base
+ *   (default 1): the base is secs * 1 000 000 000 of the first event, in file order, of the first chosen message that has events
+ *   (0 when none has); the indexer reports that value as first_stamp_ns.  With auto_time_base == 0, options.time_base (int64
+ *   nanoseconds) is taken.  info.time_base = the base in force.  The _dev entry point takes an explicit base only:
+ *   auto_time_base != 0 there is ECAL_ERR_INVALID.
+ *
+ * ecal_bag_block_events: event slots per decode block of this build — a fact for tests that place block boundaries.
+ * ecal_bag_index_messages: a HOST function over the file's bytes in host memory.  One 16-byte entry per chosen message (also one
+ *   of no events), in file order; offsets count from byte 0 of the file.  opt (may be NULL): only topic and type are looked at.
+ *   *n_messages = the count; ECAL_ERR_RANGE when it exceeds `capacity` (out holds the first `capacity`; out may be NULL with
+ *   capacity 0: a count).  info (optional): n_messages, n_other_messages, n_chunks, n_connections, n_raw_events, n_trailing_bytes,
+ *   msg_width, msg_height, first_stamp_ns.  ctx may be NULL (no error text then).
+ *   The chain is not walked on the device: a message is found only through the record header before it.
+ * ecal_bag_count_events_dev: *n_events (HOST) = the events before any drop (the table's sum): always a sufficient `capacity`.  Waits
+ *   for `stream`.
+ * ecal_events_from_bag_dev: d_file (DEVICE, 16-byte aligned, the whole file, n_bytes bytes; nothing behind n_bytes is read) and
+ *   d_messages (DEVICE, 8-byte aligned, n_messages entries as ecal_bag_index_messages writes them) into d_events (DEVICE, room for
+ *   `capacity` records, file order, not sorted).  opt->topic / type are not looked at (the table is already a choice).  A table
+ *   entry that does not lie within the file is ECAL_ERR_INVALID, and nothing outside the file is loaded.  info (HOST) is filled on
+ *   ECAL_OK and on ECAL_ERR_RANGE (capacity too small: info->n_events = the count needed, call again; also more than 2^32-1
+ *   events: event indices are 32-bit per call, byte offsets 64-bit); n_other_messages, n_chunks, n_connections, n_trailing_bytes,
+ *   msg_width / msg_height and first_stamp_ns are the indexer's to report, not this call's.  On an error the contents of d_events
+ *   are undefined.  Enqueues on `stream` and waits for it: the call returns with the records in place.
+ * ecal_stream_create_from_bag_file: the file through pinned buffers into HBM (reads overlapped with the uploads), the message table
+ *   built on the host beside the upload from record headers only, decoded on the device, the file's bytes freed, then the stream
+ *   brought into time order if it is not (ecal_stream_create's rule).  info may be NULL.
+ * ecal_bag_to_bin_file: the same records in file order, no sort, as a .bin of the reference's layout. */
+typedef struct ecal_bag_options {
+    const char *topic;       /* NULL or "": every connection of an accepted type (they must share one topic) */
+    const char *type;        /* NULL or "": dvs_msgs/EventArray and prophesee_event_msgs/EventArray */
+    int auto_time_base;      /* 1: the base is the first event's whole seconds */
+    int64_t time_base;       /* nanoseconds of epoch time, with auto_time_base == 0 */
+    uint32_t width, height;  /* 0: no bound */
+    int flip_x, flip_y;      /* need width / height */
+    double start_time;       /* seconds */
+    int has_end_time;
+    double end_time;         /* seconds */
+} ecal_bag_options;
+typedef struct ecal_bag_info {
+    uint64_t n_raw_events;     /* events before any drop */
+    uint64_t n_events;         /* records written, or needed */
+    uint64_t n_outside;        /* events dropped for x >= width or y >= height */
+    uint64_t n_negative;       /* events dropped for t < 0 */
+    uint64_t n_before_start;   /* events dropped for t < start_time */
+    uint64_t n_after_end;      /* events from the one that ended the stream on */
+    uint64_t n_messages;       /* chosen messages (also those of no events) */
+    uint64_t n_other_messages; /* messages of other connections */
+    uint64_t n_chunks;
+    uint64_t n_connections;    /* distinct connection ids */
+    uint64_t n_trailing_bytes; /* bytes from the first record that is not wholly present */
+    int64_t first_stamp_ns;    /* the first event's secs * 1e9: the automatic base */
+    int64_t time_base;         /* the base in force */
+    uint32_t msg_width, msg_height; /* the first chosen message's own; may differ from the options */
+} ecal_bag_info;
+typedef struct ecal_bag_message {
+    uint64_t offset_of_first_event; /* bytes from byte 0 of the file */
+    uint32_t n_events;
+    uint32_t reserved;              /* 0 */
+} ecal_bag_message;
+void ecal_bag_default_options(ecal_bag_options *opt);
+uint32_t ecal_bag_block_events(void);
+int ecal_bag_index_messages(ecal_ctx *ctx, const uint8_t *file_host, uint64_t n_bytes, const ecal_bag_options *opt, ecal_bag_message *out,
+                            uint64_t capacity, uint64_t *n_messages, ecal_bag_info *info);
+int ecal_bag_count_events_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const ecal_bag_message *d_messages,
+                              uint64_t n_messages, uint64_t *n_events, void *stream);
+int ecal_events_from_bag_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const ecal_bag_message *d_messages,
+                             uint64_t n_messages, const ecal_bag_options *opt, uint8_t *d_events /*room for capacity records*/,
+                             uint64_t capacity, ecal_bag_info *info, void *stream);
+int ecal_stream_create_from_bag_file(ecal_ctx *ctx, const char *path, const ecal_bag_options *opt, ecal_stream **out, ecal_bag_info *info);
+int ecal_bag_to_bin_file(ecal_ctx *ctx, const char *bag_path, const char *bin_path, const ecal_bag_options *opt, ecal_bag_info *info);
 
 #ifdef __cplusplus
 }
