@@ -126,11 +126,21 @@ def load_events_bag(ctx, path, **options):
     return events, t_first, t_last
 
 
+def remove_hot_pixels(ctx, events, width=346, height=260, extra_mask=None, **options):
+    """The events without those of hot pixels — pixels that fire whatever the scene does: (events, info) as
+    capi.Context.remove_hot_pixels returns them.  A per-pixel count of the whole stream on the GPU, the rule on the host (a pixel
+    is hot when it counts at least min_count events and more than factor x the quantile_permille quantile of the non-zero counts;
+    defaults 64, 8 and 990), an order-preserving filter on the GPU: the records that stay are byte for byte the input's, in the
+    input's order.  extra_mask [height, width]: pixels to remove whatever they count.  Events whose coordinates are not whole
+    numbers inside the sensor are never counted and never removed."""
+    return ctx.remove_hot_pixels(events, width=width, height=height, extra_mask=extra_mask, **options)
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
-                     refine_rounds=0, refine_ring_tol=None):
+                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -160,7 +170,11 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     width), the previous solver closed, a solve from the current solution with the same options.  out["refine"] has one entry per
     round (totals, residuals, initial and final cost, iterations), `report` / `board_image` then run on the last solver at the last
     solution, out["spline"] stays the keyframe-gated solve's summary; a stage of its own, `refine`.  Whether the refined camera is
-    the more accurate one has not been established (design/09_measured.md has what the synthetic streams gave).  Single process."""
+    the more accurate one has not been established (design/09_measured.md has what the synthetic streams gave).  Single process.
+    hot_pixels (opt-in; None or False: nothing changes): True or a dict of options (quantile_permille, min_count, factor, extra_mask)
+    removes the events of hot pixels first (remove_hot_pixels below, on a width x height sensor) and runs everything on the filtered
+    stream — a stage of its own, `hot_pixels`; out["hot_pixels"] is the filter's info (counts of events and pixels, `mask`,
+    `counts`).  t_first and t_last stay the caller's.  No default of the rule has met a real recording (design/17_hot_pixels.md)."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -188,11 +202,18 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
             pass
     # circleRadiusThreshold_ of this sensor and board, for both detection passes (346x260, 9x4: the pipeline's default, bit for bit)
     radius_threshold = ctx.circle_radius_threshold(width, height, rows, cols, True, square, circle_radius)
+    hot_info = None
+    if hot_pixels is not None and hot_pixels is not False:
+        events, hot_info = remove_hot_pixels(ctx, events, width=int(width), height=int(height),
+                                             **(dict(hot_pixels) if isinstance(hot_pixels, dict) else {}))
+        mark("hot_pixels")
     # -- 1. keyframes
     kf = detect_keyframes_device(pipe.ctx, events, step, frame_event_num_threshold, piece_num, t_first, t_last, eps, minpts, rows, cols,
                                  gate_mode=gate_mode, radius_threshold=radius_threshold)
     K = len(kf["time"])
     out = {"keyframes": K, "stage_seconds": stages}
+    if hot_info is not None:
+        out["hot_pixels"] = hot_info
     mark("keyframe_search")
     if K == 0:
         raise RuntimeError("no keyframe found")

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "ecal_raw_default_options", "ecal_raw_block_words", "ecal_raw_count_events_dev", "ecal_events_from_raw_dev", "ecal_stream_create_from_raw_file", "ecal_raw_to_bin_file",
     "ecal_aedat_default_options", "ecal_aedat_block_events", "ecal_aedat_parse_header", "ecal_aedat_index_packets", "ecal_aedat_count_events_dev", "ecal_events_from_aedat_dev", "ecal_stream_create_from_aedat_file", "ecal_aedat_to_bin_file",
     "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
+    "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -262,6 +263,78 @@ def load_library():
     L.ecal_copy_dev.restype = i32
     _LIB = L
     return L
+
+
+class HotPixelOptions(ctypes.Structure):
+    """ecal_hot_pixel_options (include/ecal.h, pixel activity / hot pixels)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("quantile_permille", ctypes.c_uint32),
+                ("min_count", ctypes.c_uint32), ("factor", ctypes.c_double)]
+
+
+class HotPixelInfo(ctypes.Structure):
+    """ecal_hot_pixel_info (include/ecal.h, pixel activity / hot pixels)."""
+    _fields_ = [("n_events", ctypes.c_uint64), ("n_off_grid", ctypes.c_uint64), ("n_removed", ctypes.c_uint64), ("n_kept", ctypes.c_uint64),
+                ("n_active_pixels", ctypes.c_uint32), ("n_hot_pixels", ctypes.c_uint32), ("n_masked_pixels", ctypes.c_uint32),
+                ("quantile_count", ctypes.c_uint32), ("max_count", ctypes.c_uint32), ("max_kept_count", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+# ecal_activity_totals / ecal_filter_totals as numpy records
+ACTIVITY_TOTALS = np.dtype([("n_events", np.uint64), ("n_on_grid", np.uint64), ("n_off_grid", np.uint64)])
+FILTER_TOTALS = np.dtype([("n_events", np.uint64), ("n_off_grid", np.uint64), ("n_removed", np.uint64), ("n_kept", np.uint64)])
+
+
+def hot_pixel_options(width=None, height=None, quantile_permille=None, min_count=None, factor=None):
+    """ecal_hot_pixel_options from ecal_hot_pixel_default_options (346 x 260, the 99 % quantile, 64 events, factor 8); None keeps
+    the default."""
+    L = load_library()
+    L.ecal_hot_pixel_default_options.argtypes, L.ecal_hot_pixel_default_options.restype = [ctypes.POINTER(HotPixelOptions)], None
+    o = HotPixelOptions()
+    L.ecal_hot_pixel_default_options(ctypes.byref(o))
+    if width is not None:
+        o.width = int(width)
+    if height is not None:
+        o.height = int(height)
+    if quantile_permille is not None:
+        o.quantile_permille = int(quantile_permille)
+    if min_count is not None:
+        o.min_count = int(min_count)
+    if factor is not None:
+        o.factor = float(factor)
+    return o
+
+
+def hot_pixel_mask(counts, extra_mask=None, **options):
+    """ecal_hot_pixel_mask (host arrays; no context, no device): counts [2, H, W] (any integer type whose values fit uint32) and
+    an optional extra_mask [H, W] (non-zero: remove whatever it counts) -> (mask [H, W] bool, info dict).  options:
+    quantile_permille, min_count, factor; width and height come from the shape of counts."""
+    L = load_library()
+    L.ecal_hot_pixel_mask.argtypes = [ctypes.c_void_p, ctypes.POINTER(HotPixelOptions), ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.POINTER(HotPixelInfo)]
+    L.ecal_hot_pixel_mask.restype = ctypes.c_int
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[0] != 2:
+        raise ValueError("counts must be [2, H, W]")
+    if c.size and (int(c.min()) < 0 or int(c.max()) > 0xFFFFFFFF):
+        raise ValueError("counts must fit uint32")
+    c = np.ascontiguousarray(c, np.uint32)
+    H, W = c.shape[1:]
+    o = hot_pixel_options(width=W, height=H, **options)
+    extra = None
+    if extra_mask is not None:
+        extra = np.ascontiguousarray(np.asarray(extra_mask) != 0, np.uint8)
+        if extra.shape != (H, W):
+            raise ValueError("extra_mask must be [H, W]")
+    mask = np.zeros((H, W), np.uint8)
+    info = HotPixelInfo()
+    st = L.ecal_hot_pixel_mask(c.ctypes.data if c.size else None, ctypes.byref(o), extra.ctypes.data if extra is not None and extra.size else None,
+                               mask.ctypes.data if mask.size else None, ctypes.byref(info))
+    if st != 0:
+        raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_hot_pixel_mask (width and height from 1 to 4096, quantile_permille <= 1000, "
+                        "a finite factor >= 0)")
+    return mask.astype(bool), info.as_dict()
 
 
 def _ptr(a):
@@ -921,6 +994,122 @@ class Context:
             self._text_fail(st, info)
         events, t_first, t_last = self._stream_records(h)
         return events, info.as_dict(), t_first, t_last
+
+    # ---- pixel activity / hot pixels (ecal_pixel_activity_dev, ecal_filter_events_dev and the chain) ----
+    def _records_arg(self, events):
+        """packed 25-byte records (a torch uint8 tensor on any device, a numpy array, bytes) -> (contiguous uint8 CUDA tensor, count);
+        a contiguous CUDA tensor is taken where it is, whatever its alignment"""
+        import torch
+        if isinstance(events, torch.Tensor):
+            t = events if events.is_cuda else events.to("cuda:%d" % self.device)
+        else:
+            a = np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else np.asarray(events, np.uint8).ravel()
+            t = torch.from_numpy(np.ascontiguousarray(a).copy()).to("cuda:%d" % self.device)
+        t = t.contiguous().view(torch.uint8).reshape(-1)
+        assert t.numel() % 25 == 0, "packed 25-byte event records"
+        return t, t.numel() // 25
+
+    def pixel_activity_dev(self, d_events, n_events, width, height, d_counts, d_totals=None, stream=0):
+        """ecal_pixel_activity_dev: raw device pointers; d_counts [2][height][width] u32 and d_totals (ACTIVITY_TOTALS, or None) are
+        zeroed by the call; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_pixel_activity_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+        L.ecal_pixel_activity_dev.restype = ctypes.c_int
+        self._check(L.ecal_pixel_activity_dev(self._h, d_events, int(n_events), int(width), int(height), d_counts, d_totals, stream))
+
+    def filter_events_dev(self, d_events, n_events, d_mask, width, height, d_out, d_count, d_totals=None, stream=0):
+        """ecal_filter_events_dev: raw device pointers; d_mask [height * width] u8 (non-zero: remove), d_out room for n_events
+        records, d_count one u32, d_totals FILTER_TOTALS or None; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_filter_events_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
+        L.ecal_filter_events_dev.restype = ctypes.c_int
+        self._check(L.ecal_filter_events_dev(self._h, d_events, int(n_events), d_mask, int(width), int(height), d_out, d_count, d_totals, stream))
+
+    def pixel_activity(self, events, width, height):
+        """How many events every pixel fired: (counts [2, H, W] int64 CUDA tensor whose values are the call's uint32 counts — plane 0
+        the events with polarity byte 0, plane 1 the others —, totals: one ACTIVITY_TOTALS record).  Events whose x or y is not a
+        whole number inside the sensor are counted in totals["n_off_grid"] and nowhere in the map."""
+        import torch
+        t, n = self._records_arg(events)
+        W, H = int(width), int(height)
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):   # (sizes that the call itself refuses must not be allocated first)
+            raise EcalError(-1, "invalid argument: ecal_pixel_activity: width and height from 1 to 4096")
+        counts = torch.empty((2, H, W), dtype=torch.int32, device=t.device)
+        tot = torch.empty(3, dtype=torch.int64, device=t.device)
+        with torch.cuda.device(t.device):
+            self.pixel_activity_dev(t.data_ptr() if n else None, n, W, H, counts.data_ptr(), tot.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        return counts.to(torch.int64) & 0xFFFFFFFF, tot.cpu().numpy().view(ACTIVITY_TOTALS)[0]
+
+    def filter_events(self, events, mask):
+        """The events whose pixel is not masked, byte for byte and in input order: (events: uint8 CUDA tensor [n_kept * 25], totals: one
+        FILTER_TOTALS record).  mask: [H, W], non-zero / True = remove (a numpy array or a torch tensor).  Off-grid events stay."""
+        import torch
+        t, n = self._records_arg(events)
+        if isinstance(mask, torch.Tensor):
+            m = (mask != 0).to(torch.uint8).to(t.device).contiguous()
+        else:
+            m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)).to(t.device)
+        if m.dim() != 2:
+            raise ValueError("mask must be [H, W]")
+        H, W = int(m.shape[0]), int(m.shape[1])
+        out = torch.empty(n * 25, dtype=torch.uint8, device=t.device)
+        cnt = torch.empty(1, dtype=torch.int32, device=t.device)
+        tot = torch.empty(4, dtype=torch.int64, device=t.device)
+        with torch.cuda.device(t.device):
+            self.filter_events_dev(t.data_ptr() if n else None, n, m.data_ptr() if m.numel() else None, W, H, out.data_ptr() if n else None,
+                                   cnt.data_ptr(), tot.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        kept = int(cnt.item()) & 0xFFFFFFFF
+        return out[: kept * 25], tot.cpu().numpy().view(FILTER_TOTALS)[0]
+
+    def remove_hot_pixels(self, events, width=346, height=260, extra_mask=None, **options):
+        """The chain of ecal_stream_remove_hot_pixels on a tensor of records: pixel_activity -> the counts to the host ->
+        hot_pixel_mask (options: quantile_permille, min_count, factor) -> filter_events.  Returns (events, info): info is
+        ecal_hot_pixel_info as a dict whose event fields are the filter's totals, with `mask` [H, W] bool and `counts` [2, H, W]
+        uint32 (numpy)."""
+        t, n = self._records_arg(events)
+        counts, _ = self.pixel_activity(t, width, height)
+        counts = counts.cpu().numpy().astype(np.uint32)
+        mask, info = hot_pixel_mask(counts, extra_mask=extra_mask, **options)
+        out, tot = self.filter_events(t, mask)
+        for k in ("n_events", "n_off_grid", "n_removed", "n_kept"):
+            info[k] = int(tot[k])
+        info["mask"], info["counts"] = mask, counts
+        return out, info
+
+    def stream_remove_hot_pixels(self, events, width=346, height=260, extra_mask=None, **options):
+        """ecal_stream_remove_hot_pixels over an ecal_stream made of the host records `events` (the C++ shim's way) -> (events as a
+        uint8 CUDA tensor, info dict with `mask` and `counts`)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
+        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
+        L.ecal_stream_remove_hot_pixels.argtypes = [vp, vp, ctypes.POINTER(HotPixelOptions), vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(HotPixelInfo)]
+        L.ecal_stream_remove_hot_pixels.restype = ctypes.c_int
+        ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
+        assert ev.size % 25 == 0, "packed 25-byte event records"
+        o = hot_pixel_options(width=width, height=height, **options)
+        H, W = int(o.height), int(o.width)
+        ok = 1 <= W <= 4096 and 1 <= H <= 4096
+        extra = np.ascontiguousarray(np.asarray(extra_mask) != 0, np.uint8) if extra_mask is not None else None
+        mask = np.zeros((H, W) if ok else (0, 0), np.uint8)
+        counts = np.zeros((2, H, W) if ok else (2, 0, 0), np.uint32)
+        info = HotPixelInfo()
+        h_in, h_out = vp(), vp()
+        self._check(L.ecal_stream_create(self._h, _ptr(ev) if ev.size else None, ev.size // 25, ctypes.byref(h_in)))
+        try:
+            self._check(L.ecal_stream_remove_hot_pixels(self._h, h_in, ctypes.byref(o), extra.ctypes.data if extra is not None and extra.size else None,
+                                                        ctypes.byref(h_out), mask.ctypes.data if mask.size else None,
+                                                        counts.ctypes.data if counts.size else None, ctypes.byref(info)))
+        finally:
+            L.ecal_stream_destroy(h_in)
+        out, _, _ = self._stream_records(h_out)
+        d = info.as_dict()
+        d["mask"], d["counts"] = mask.astype(bool), counts
+        return out, d
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

@@ -117,6 +117,8 @@ struct ecal_ctx {
     ecal_devbuf board_scratch;   // ecal_solver_board_image / _board_points: the outputs' device images
     ecal_devbuf reassoc_scratch;   // ecal_solver_reassociate_dev: one verdict byte per event, per-block counts / offsets
     ecal_devbuf reassoc_records;   // ecal_solver_reassociate / _create_reassociated: the record arrays, the count, the totals
+    ecal_devbuf activity_scratch;  // ecal_filter_events_dev: one verdict byte per event, per-block counts / offsets
+    ecal_devbuf activity_maps;     // ecal_stream_remove_hot_pixels: the count map, the mask, the totals, the count
     ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks
     hipStream_t copy_stream = nullptr;  // uploads of the double-buffered ingest
     ecal_pinned pass_pinned;            // ecal_detect_pass: window times in, packed verdicts out; the keyframe search: counters, report ring, handed-over frame

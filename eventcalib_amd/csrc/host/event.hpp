@@ -379,6 +379,23 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_bag_info bagInfo{};     // what the last loadBagFile saw (messages, chunks, drops, the time base in force)
+    // The events of hot pixels taken out of a file-backed container (ecal_stream_remove_hot_pixels: a per-pixel count, the rule, an
+    // order-preserving filter; opt null: the defaults on a 346 x 260 sensor): the stream is swapped for the filtered one.
+    // firstTime() / lastTime() stay the loaded stream's.  maskOut [height * width] / countsOut [2][height][width]: may be null.
+    void removeHotPixels(const ecal_hot_pixel_options *opt = nullptr, ecal_hot_pixel_info *info = nullptr, uint8_t *maskOut = nullptr,
+                         uint32_t *countsOut = nullptr) {
+        if (!fromFile_ || !stream_) throw std::logic_error("EventContainer: removeHotPixels needs a file-backed container (loadFile and its kin)");
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        ecal_stream *filtered = nullptr;
+        const int rc = ecal_stream_remove_hot_pixels(ctx, stream_, opt, nullptr, &filtered, maskOut, countsOut, &hotPixelInfo);
+        if (info) *info = hotPixelInfo;
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("removeHotPixels: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_remove_hot_pixels: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        ecal_stream_destroy(stream_);
+        stream_ = filtered;
+    }
+    ecal_hot_pixel_info hotPixelInfo{};   // what the last removeHotPixels saw (events and pixels, removed and kept)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

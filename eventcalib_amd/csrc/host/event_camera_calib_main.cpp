@@ -134,6 +134,45 @@ int main(int argc, char **argv) {
         } else {
             container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
         }
+        // HotPixels (a key of this build, optional): 1 = the events of hot pixels — pixels that fire whatever the scene does — are
+        // taken out of the loaded stream on the device (ecal_stream_remove_hot_pixels on Camera.width x Camera.height) before
+        // anything looks at it, one line on stdout, the masked pixels with their counts in saveDir/HotPixels.txt.  The rule's
+        // numbers, all optional: HotPixels_Factor (8), HotPixels_QuantilePermille (990), HotPixels_MinCount (64).  Absent or 0:
+        // nothing changes
+        int wantHotPixels = 0;
+        fsSettings["HotPixels"] >> wantHotPixels;
+        if (wantHotPixels) {
+            ecal_hot_pixel_options opt;
+            ecal_hot_pixel_default_options(&opt);
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            int quantilePermille = (int) opt.quantile_permille, minCount = (int) opt.min_count;
+            fsSettings["HotPixels_Factor"] >> opt.factor;
+            fsSettings["HotPixels_QuantilePermille"] >> quantilePermille;
+            fsSettings["HotPixels_MinCount"] >> minCount;
+            opt.quantile_permille = (uint32_t) quantilePermille;   // (a negative number: refused by the library)
+            opt.min_count = (uint32_t) std::max(0, minCount);
+            const size_t plane = width > 0 && height > 0 ? (size_t) width * (size_t) height : 0;
+            std::vector<uint8_t> hotMask(plane);
+            std::vector<uint32_t> hotCounts(2 * plane);
+            ecal_hot_pixel_info hp;
+            try {
+                container->removeHotPixels(&opt, &hp, hotMask.data(), hotCounts.data());
+            } catch (const std::exception &e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
+            std::printf("hot pixels: %u pixels, %llu of %llu events removed\n", hp.n_hot_pixels, (unsigned long long) hp.n_removed,
+                        (unsigned long long) hp.n_events);
+            std::FILE *f = std::fopen((std::string(argv[3]) + "/HotPixels.txt").c_str(), "w");
+            if (!f) {
+                std::fprintf(stderr, "cannot write %s/HotPixels.txt\n", argv[3]);
+                return 3;
+            }
+            for (size_t p = 0; p < plane; p++)   // x y count_negative count_positive
+                if (hotMask[p]) std::fprintf(f, "%zu %zu %u %u\n", p % (size_t) width, p / (size_t) width, hotCounts[p], hotCounts[plane + p]);
+            std::fclose(f);
+        }
     }
     while (!es.isEnd()) {                                    // :154-163
         if (customEnd && es.current().timeStamp() >= endTimeSetting) break;

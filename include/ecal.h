@@ -1359,6 +1359,57 @@ int ecal_events_from_bag_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_by
 int ecal_stream_create_from_bag_file(ecal_ctx *ctx, const char *path, const ecal_bag_options *opt, ecal_stream **out, ecal_bag_info *info);
 int ecal_bag_to_bin_file(ecal_ctx *ctx, const char *bag_path, const char *bin_path, const ecal_bag_options *opt, ecal_bag_info *info);
 
+/* ---- pixel activity / hot pixels: a per-pixel count map, a mask, the stream without the masked pixels' events ----
+ * A hot pixel fires events whatever the scene does.  Three stages, each callable on its own, and one call that chains them; all of
+ * it opt-in (nothing else in this header calls it).  New functionality: the reference has no such filter.
+ * eventcalib_amd/csrc/pixel_activity.hpp restates everything that decides for host and device; design/17_hot_pixels.md has the
+ * reasoning, where the defaults come from and what was measured.  No default has met a real recording.
+ *
+ * The pixel of a record: x and y are the f64 at record offsets 8 and 16.  x is on the grid iff x >= 0 && x < width && x == floor(x)
+ *   (NaN and +-inf are not; -0.0 is pixel 0), y the same with height; the pixel index is y * width + x.  An off-grid event is never
+ *   counted in the map and never removed.  The polarity plane is `polarity byte != 0`, the board image's convention.
+ * The rule (exact: integers and one double comparison per pixel):  c[p] = counts[0][p] + counts[1][p];  A = the non-zero c in
+ *   ascending order;  Q = A[((len(A) - 1) * quantile_permille) / 1000] (integer division; A empty: Q = 0 and nothing is hot);
+ *   p is hot iff c[p] >= min_count && (double) c[p] > factor * (double) Q;  mask = hot | extra_mask, 1 = remove.
+ * width and height: 1 .. 4096, else ECAL_ERR_INVALID.  More than 2^32-1 events: ECAL_ERR_RANGE.  n_events == 0 is valid.
+ * The _dev calls take any device memory of the caller's: nothing behind n_events * 25 bytes of d_events is loaded, nothing behind the
+ *   kept records is stored.  They zero their outputs on `stream`, enqueue and do not synchronise.
+ * ecal_pixel_activity_dev: d_counts [2][height][width] u32 (plane 0: polarity byte == 0), zeroed by the call; d_totals may be NULL.
+ *   Integer atomics only: the map does not depend on the order of arrival.
+ * ecal_hot_pixel_mask: HOST arrays, no context, no device.  opt NULL: the defaults.  quantile_permille > 1000, a factor that is
+ *   negative or not finite: ECAL_ERR_INVALID.  info (may be NULL): n_events / n_removed / n_kept speak of the counted (on-grid)
+ *   events alone and n_off_grid is 0; n_active_pixels = len(A), n_hot_pixels by the rule alone, n_masked_pixels with extra_mask,
+ *   quantile_count = Q, max_count = max c, max_kept_count = max c over the pixels that are not masked.
+ * ecal_filter_events_dev: the records whose pixel is not masked (d_mask [height * width] u8 on the DEVICE, non-zero = remove), their
+ *   own 25 bytes each, in input order, into d_out (room for n_events records, not overlapping d_events): a time-sorted stream
+ *   stays time-sorted and equal stamps keep their order.  *d_count = the records written; d_totals may be NULL;
+ *   n_events = n_removed + n_kept.
+ * ecal_stream_remove_hot_pixels: counts -> download -> rule -> mask upload -> filter -> a new stream (*out; `in` is untouched), on the
+ *   context's stream; waits for it.  opt NULL: the defaults.  extra_mask (HOST, [height * width], may be NULL): pixels to remove
+ *   whatever they count.  mask_out [height * width] and counts_out [2][height][width] (HOST, may be NULL) receive the mask and the
+ *   map.  info (may be NULL): the event fields are the filter's totals (off-grid events included in n_events and n_kept). */
+typedef struct ecal_activity_totals { uint64_t n_events, n_on_grid, n_off_grid; } ecal_activity_totals;
+typedef struct ecal_filter_totals { uint64_t n_events, n_off_grid, n_removed, n_kept; } ecal_filter_totals;
+typedef struct ecal_hot_pixel_options {
+    uint32_t width, height, quantile_permille, min_count;
+    double factor;
+} ecal_hot_pixel_options;
+typedef struct ecal_hot_pixel_info {
+    uint64_t n_events, n_off_grid, n_removed, n_kept;
+    uint32_t n_active_pixels, n_hot_pixels, n_masked_pixels, quantile_count, max_count, max_kept_count;
+} ecal_hot_pixel_info;
+void ecal_hot_pixel_default_options(ecal_hot_pixel_options *opt); /* 346 x 260, 990, 64, 8.0 */
+int ecal_pixel_activity_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, uint32_t width, uint32_t height,
+                            uint32_t *d_counts /*[2][H][W]; zeroed by the call*/, ecal_activity_totals *d_totals /*or NULL*/, void *stream);
+int ecal_hot_pixel_mask(const uint32_t *counts /*HOST*/, const ecal_hot_pixel_options *opt, const uint8_t *extra_mask /*[H*W] or NULL*/,
+                        uint8_t *mask /*[H*W], 1 = remove*/, ecal_hot_pixel_info *info);
+int ecal_filter_events_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_mask, uint32_t width, uint32_t height,
+                           uint8_t *d_out /*room for n_events records, not overlapping*/, uint32_t *d_count, ecal_filter_totals *d_totals,
+                           void *stream);
+int ecal_stream_remove_hot_pixels(ecal_ctx *ctx, const ecal_stream *in, const ecal_hot_pixel_options *opt, const uint8_t *extra_mask,
+                                  ecal_stream **out, uint8_t *mask_out /*or NULL*/, uint32_t *counts_out /*or NULL*/,
+                                  ecal_hot_pixel_info *info);
+
 #ifdef __cplusplus
 }
 #endif
