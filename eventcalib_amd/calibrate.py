@@ -117,6 +117,15 @@ def load_events_aedat(ctx, path, **options):
     return events, t_first, t_last
 
 
+def load_events_aedat4(ctx, path, **options):
+    """An iniVation .aedat4 recording (DV; packets with LZ4 or no compression) -> (events, t_first, t_last) as calibrate_stream takes
+    them: uploaded, inflated and decoded on the device (capi.Context.stream_from_aedat4_file), in time order.  options:
+    capi.Context.aedat4_options' (stream_id, time_base, width, height, flip_x, flip_y, start_time, end_time, max_inflated_bytes).
+    Times count from the first event's whole second unless time_base (microseconds of epoch time) is given."""
+    events, _info, t_first, t_last = ctx.stream_from_aedat4_file(path, **options)
+    return events, t_first, t_last
+
+
 def load_events_bag(ctx, path, **options):
     """A ROS 1 .bag of dvs_msgs/EventArray messages (as rpg_dvs_ros records them) -> (events, t_first, t_last) as calibrate_stream
     takes them: uploaded and decoded on the device (capi.Context.stream_from_bag_file), in time order.  options:

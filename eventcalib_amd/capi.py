@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
     "ecal_raw_default_options", "ecal_raw_block_words", "ecal_raw_count_events_dev", "ecal_events_from_raw_dev", "ecal_stream_create_from_raw_file", "ecal_raw_to_bin_file",
     "ecal_aedat_default_options", "ecal_aedat_block_events", "ecal_aedat_parse_header", "ecal_aedat_index_packets", "ecal_aedat_count_events_dev", "ecal_events_from_aedat_dev", "ecal_stream_create_from_aedat_file", "ecal_aedat_to_bin_file",
+    "ecal_aedat4_default_options", "ecal_aedat4_block_events", "ecal_aedat4_parse_header", "ecal_aedat4_index_packets", "ecal_aedat4_count_events_dev", "ecal_events_from_aedat4_dev", "ecal_stream_create_from_aedat4_file", "ecal_aedat4_to_bin_file",
     "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
     "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
@@ -131,6 +132,46 @@ class AedatPacket(ctypes.Structure):
 
 
 AEDAT_PACKET_DTYPE = np.dtype([("offset_of_first_event", "<u8"), ("n_events", "<u4"), ("ts_overflow", "<i4")])
+
+
+AEDAT4_NONE, AEDAT4_LZ4, AEDAT4_LZ4_HIGH, AEDAT4_ZSTD, AEDAT4_ZSTD_HIGH = 0, 1, 2, 3, 4   # ECAL_AEDAT4_*
+_AEDAT4_COMPRESSIONS = {None: AEDAT4_LZ4, "none": AEDAT4_NONE, "lz4": AEDAT4_LZ4, "lz4_high": AEDAT4_LZ4_HIGH, "zstd": AEDAT4_ZSTD,
+                        "zstd_high": AEDAT4_ZSTD_HIGH}
+
+
+def aedat4_compression(c):
+    """"none" / "lz4" / None (lz4), or the ECAL_AEDAT4_* number, as the number"""
+    if isinstance(c, str) or c is None:
+        return _AEDAT4_COMPRESSIONS[c.lower() if c else None]
+    return int(c)
+
+
+class Aedat4Options(ctypes.Structure):
+    """ecal_aedat4_options (include/ecal.h, aedat4 ingest)."""
+    _fields_ = [("compression", ctypes.c_int), ("stream_id", ctypes.c_int), ("auto_time_base", ctypes.c_int), ("flip_x", ctypes.c_int),
+                ("flip_y", ctypes.c_int), ("has_end_time", ctypes.c_int), ("time_base", ctypes.c_int64), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("start_time", ctypes.c_double), ("end_time", ctypes.c_double),
+                ("max_inflated_bytes", ctypes.c_uint64)]
+
+
+class Aedat4Info(ctypes.Structure):
+    """ecal_aedat4_info (include/ecal.h, aedat4 ingest)."""
+    _fields_ = [("n_raw_events", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("n_outside", ctypes.c_uint64),
+                ("n_negative", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64), ("n_after_end", ctypes.c_uint64),
+                ("n_packets", ctypes.c_uint64), ("n_other_packets", ctypes.c_uint64), ("n_trailing_bytes", ctypes.c_uint64),
+                ("n_compressed_bytes", ctypes.c_uint64), ("n_inflated_bytes", ctypes.c_uint64), ("first_stamp_us", ctypes.c_int64),
+                ("time_base", ctypes.c_int64), ("compression", ctypes.c_int), ("stream_id", ctypes.c_int)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class Aedat4Packet(ctypes.Structure):
+    """ecal_aedat4_packet (include/ecal.h, aedat4 ingest): 16 bytes."""
+    _fields_ = [("offset_of_data", ctypes.c_uint64), ("n_bytes", ctypes.c_uint32), ("zero", ctypes.c_uint32)]
+
+
+AEDAT4_PACKET_DTYPE = np.dtype([("offset_of_data", "<u8"), ("n_bytes", "<u4"), ("zero", "<u4")])
 
 
 class BagOptions(ctypes.Structure):
@@ -861,6 +902,145 @@ class Context:
         info = AedatInfo()
         h = vp()
         st = L.ecal_stream_create_from_aedat_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    # ---- aedat4 ingest: iniVation AEDAT 4 files (LZ4 packets) inflated and decoded in HBM (ecal_events_from_aedat4_dev and the file forms) ----
+    def aedat4_options(self, compression=None, stream_id=-1, time_base=None, width=0, height=0, flip_x=False, flip_y=False,
+                       start_time=None, end_time=None, max_inflated_bytes=None):
+        """ecal_aedat4_options from ecal_aedat4_default_options: compression "none" / "lz4" (the _dev forms; the file forms take the
+        header's), stream_id -1 = found by its identifier, time_base None = automatic (the first event's whole second; file forms
+        only), else int64 microseconds of epoch time, width / height 0 = no upper bound, flip_x / flip_y need them, start_time None =
+        -inf, end_time None = to the end, max_inflated_bytes None = the default."""
+        L = self._L
+        L.ecal_aedat4_default_options.argtypes = [ctypes.POINTER(Aedat4Options)]
+        L.ecal_aedat4_default_options.restype = None
+        o = Aedat4Options()
+        L.ecal_aedat4_default_options(ctypes.byref(o))
+        o.compression, o.stream_id, o.width, o.height = aedat4_compression(compression), int(stream_id), int(width), int(height)
+        if time_base is not None:
+            o.auto_time_base, o.time_base = 0, int(time_base)
+        o.flip_x, o.flip_y = int(bool(flip_x)), int(bool(flip_y))
+        if start_time is not None:
+            o.start_time = float(start_time)
+        if end_time is not None:
+            o.has_end_time, o.end_time = 1, float(end_time)
+        if max_inflated_bytes is not None:
+            o.max_inflated_bytes = int(max_inflated_bytes)
+        return o
+
+    def aedat4_block_events(self):
+        """ecal_aedat4_block_events: event slots per decode block of this build."""
+        self._L.ecal_aedat4_block_events.argtypes, self._L.ecal_aedat4_block_events.restype = [], ctypes.c_uint32
+        return int(self._L.ecal_aedat4_block_events())
+
+    def aedat4_parse_header(self, data, file_bytes=None):
+        """ecal_aedat4_parse_header: the first bytes of a file of file_bytes bytes (None: these are all of it) -> (compression,
+        packets_begin, packets_end)."""
+        L = self._L
+        L.ecal_aedat4_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int),
+                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.ecal_aedat4_parse_header.restype = ctypes.c_int
+        data = bytes(data)
+        c, b, e = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(L.ecal_aedat4_parse_header(self._h, data, len(data), len(data) if file_bytes is None else int(file_bytes), ctypes.byref(c),
+                                               ctypes.byref(b), ctypes.byref(e)))
+        return int(c.value), int(b.value), int(e.value)
+
+    def aedat4_index_packets(self, file_bytes, stream_id=-1, capacity=None):
+        """ecal_aedat4_index_packets over a whole file in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
+        AEDAT4_PACKET_DTYPE, info dict).  capacity None: counted first; a smaller one raises EcalError with status -6."""
+        L = self._L
+        L.ecal_aedat4_index_packets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Aedat4Info)]
+        L.ecal_aedat4_index_packets.restype = ctypes.c_int
+        a = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8).ravel()
+        ptr = a.ctypes.data if a.size else None
+        n, info = ctypes.c_uint64(), Aedat4Info()
+        if capacity is None:
+            st = L.ecal_aedat4_index_packets(self._h, ptr, a.size, int(stream_id), None, 0, ctypes.byref(n), ctypes.byref(info))
+            if st not in (0, -6):
+                self._text_fail(st, info)
+            capacity = int(n.value)
+        table = np.zeros(int(capacity), AEDAT4_PACKET_DTYPE)
+        st = L.ecal_aedat4_index_packets(self._h, ptr, a.size, int(stream_id), table.ctypes.data if table.size else None, table.size,
+                                         ctypes.byref(n), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return table[: int(n.value)], info.as_dict()
+
+    def _aedat4_table_tensor(self, packets, device):
+        """a packet table (numpy AEDAT4_PACKET_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
+        import torch
+        if packets is not None and not isinstance(packets, torch.Tensor):
+            a = np.ascontiguousarray(packets, AEDAT4_PACKET_DTYPE)
+            packets = torch.from_numpy(a.view(np.uint8).copy()) if a.size else None
+        return self._aedat_table_tensor(packets, device)
+
+    def aedat4_count_events(self, file_bytes, compression, packets, max_inflated_bytes=None):
+        """ecal_aedat4_count_events_dev: the events before any drop (always a sufficient capacity)."""
+        import torch
+        L = self._L
+        L.ecal_aedat4_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                   ctypes.POINTER(Aedat4Options), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
+        L.ecal_aedat4_count_events_dev.restype = ctypes.c_int
+        t = self._text_tensor(file_bytes)
+        pk, n_pk = self._aedat4_table_tensor(packets, t.device)
+        o = self.aedat4_options(compression=compression, max_inflated_bytes=max_inflated_bytes)
+        n = ctypes.c_uint64()
+        self._check(L.ecal_aedat4_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
+                                                   ctypes.byref(o), ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def events_from_aedat4(self, file_bytes, compression, packets, capacity=None, time_base=0, **options):
+        """ecal_events_from_aedat4_dev: the whole file (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded
+        where it is) and the packet table of aedat4_index_packets -> (packed 25-byte records in file order as a uint8 CUDA tensor
+        [n_events * 25], info dict).  compression "none" / "lz4" is explicit, time_base too (microseconds, default 0).  options:
+        aedat4_options'.  capacity None: aedat4_count_events (always enough); a smaller one raises EcalError with status -6 and
+        .info["n_events"] = the count needed."""
+        import torch
+        L = self._L
+        L.ecal_events_from_aedat4_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                  ctypes.POINTER(Aedat4Options), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Aedat4Info),
+                                                  ctypes.c_void_p]
+        L.ecal_events_from_aedat4_dev.restype = ctypes.c_int
+        o = self.aedat4_options(compression=compression, time_base=time_base, **options)
+        t = self._text_tensor(file_bytes)
+        pk, n_pk = self._aedat4_table_tensor(packets, t.device)
+        cap = self.aedat4_count_events(t, compression, pk, options.get("max_inflated_bytes")) if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        info = Aedat4Info()
+        st = L.ecal_events_from_aedat4_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
+                                           ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def aedat4_to_bin(self, aedat4_path, bin_path, **options):
+        """ecal_aedat4_to_bin_file: the records of the .aedat4 file (file order, no sort) as a .bin of the reference's layout -> info dict."""
+        L = self._L
+        L.ecal_aedat4_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Aedat4Options), ctypes.POINTER(Aedat4Info)]
+        L.ecal_aedat4_to_bin_file.restype = ctypes.c_int
+        o = self.aedat4_options(**options)
+        info = Aedat4Info()
+        st = L.ecal_aedat4_to_bin_file(self._h, os.fsencode(aedat4_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_aedat4_file(self, path, **options):
+        """ecal_stream_create_from_aedat4_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
+        file is not) -> (events, info dict, t_first, t_last)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_aedat4_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(Aedat4Options), ctypes.POINTER(vp), ctypes.POINTER(Aedat4Info)]
+        L.ecal_stream_create_from_aedat4_file.restype = ctypes.c_int
+        o = self.aedat4_options(**options)
+        info = Aedat4Info()
+        h = vp()
+        st = L.ecal_stream_create_from_aedat4_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
         if st != 0:
             self._text_fail(st, info)
         events, t_first, t_last = self._stream_records(h)

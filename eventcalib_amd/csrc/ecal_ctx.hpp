@@ -119,6 +119,9 @@ struct ecal_ctx {
     ecal_devbuf reassoc_records;   // ecal_solver_reassociate / _create_reassociated: the record arrays, the count, the totals
     ecal_devbuf activity_scratch;  // ecal_filter_events_dev: one verdict byte per event, per-block counts / offsets
     ecal_devbuf activity_maps;     // ecal_stream_remove_hot_pixels: the count map, the mask, the totals, the count
+    ecal_devbuf aedat4_tables;     // aedat4 ingest: the packets' inflated sizes, spans, located events, first slots, the counters
+    ecal_devbuf aedat4_inflated;   // aedat4 ingest: the inflated packets, each in its span (padded to 16 bytes)
+    ecal_devbuf aedat4_blocks;     // aedat4 ingest: per-block kept counts / offsets
     ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks
     hipStream_t copy_stream = nullptr;  // uploads of the double-buffered ingest
     ecal_pinned pass_pinned;            // ecal_detect_pass: window times in, packed verdicts out; the keyframe search: counters, report ring, handed-over frame

@@ -21,6 +21,7 @@
 #include "../../../include/ecal.h"
 #include "../raw_events.hpp"
 #include "../aedat_events.hpp"
+#include "../aedat4_events.hpp"
 #include "../bag_events.hpp"
 #include "dbscan.h"
 
@@ -211,6 +212,53 @@ public:
         if (info) *info = I;
         return (long long) I.n_events;
     }
+    // An iniVation .aedat4 recording (DV: LZ4 packets of FlatBuffers; include/ecal.h, "aedat4 ingest") -> .bin beside it, on one host
+    // thread: the plain sequential decoder of aedat4_events.hpp (header, chain, inflate, locate, filter), the records in file order.
+    // The baseline of aedat42binDevice, and its check: both write the same bytes.  opt null: the defaults (the stream found by its
+    // identifier, the automatic time base, no bounds, no flips).
+    static long long aedat42bin(const std::string &aedat4FilePath, const ecal_aedat4_options *opt = nullptr, ecal_aedat4_info *info = nullptr) {
+        std::ifstream is(aedat4FilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + aedat4FilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("aedat42bin: cannot read " + aedat4FilePath);
+        ecal_aedat4_options o;
+        if (opt) o = *opt; else ecal_aedat4_default_options(&o);
+        if ((o.flip_x && !o.width) || (o.flip_y && !o.height)) throw std::invalid_argument("aedat42bin: flip_x / flip_y need width / height");
+        const ecal_aedat4::A4DecodeOptions d{o.stream_id, o.auto_time_base,
+                                             ecal_aedat4::A4Filter{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y},
+                                             o.max_inflated_bytes};
+        ecal_aedat4::A4Counts c;
+        std::vector<uint8_t> out;
+        std::string err;
+        auto put = [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); };
+        static const uint8_t none = 0;
+        const int rc = ecal_aedat4::a4_decode_sequential(bytes.empty() ? &none : bytes.data(), bytes.size(), d, c, put, &err);
+        if (rc == ecal_aedat4::A4_INVALID) throw std::invalid_argument("aedat42bin: " + err + " (" + aedat4FilePath + ")");
+        if (rc) throw std::runtime_error("aedat42bin: " + err + " (" + aedat4FilePath + ")");
+        const auto dot = aedat4FilePath.find_last_of('.');
+        std::ofstream os(aedat4FilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info)
+            *info = ecal_aedat4_info{c.n_raw_events, c.n_events, c.n_outside, c.n_negative, c.n_before_start, c.n_after_end, c.n_packets,
+                                     c.n_other_packets, c.n_trailing_bytes, c.n_compressed_bytes, c.n_inflated_bytes, c.first_stamp_us,
+                                     c.time_base, c.compression, c.stream_id};
+        return (long long) c.n_events;
+    }
+    // aedat42bin on the device (ecal_aedat4_to_bin_file: the packets indexed on the host, the file uploaded, inflated and decoded in
+    // HBM): the same arguments, the same output file name, the same bytes in it, the same returned count
+    static long long aedat42binDevice(const std::string &aedat4FilePath, const ecal_aedat4_options *opt = nullptr, ecal_aedat4_info *info = nullptr) {
+        const auto dot = aedat4FilePath.find_last_of('.');
+        ecal_aedat4_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_aedat4_to_bin_file(ctx, aedat4FilePath.c_str(), (aedat4FilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("aedat42binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_aedat4_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // A ROS 1 .bag of dvs_msgs/EventArray messages (format 2.0; include/ecal.h, "bag ingest") -> .bin beside it, on one host thread:
     // the plain sequential decoder of bag_events.hpp, the records in file order.  The baseline of bag2binDevice, and its check: both
     // write the same bytes.  opt null: the defaults (every connection of an event type, the automatic time base, no bounds, no flips).
@@ -365,6 +413,19 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_aedat_info aedatInfo{}; // what the last loadAedatFile saw (packets, records, drops, wraps, the format in force)
+    // The same from an iniVation .aedat4 recording (ecal_stream_create_from_aedat4_file): inflated and decoded on the device.
+    void loadAedat4File(const std::string &aedat4FilePath, const ecal_aedat4_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_aedat4_file(ctx, aedat4FilePath.c_str(), opt, &stream_, &aedat4Info);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadAedat4File: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_aedat4_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_aedat4_info aedat4Info{}; // what the last loadAedat4File saw (packets, bytes, drops, the stream and the time base in force)
     // The same from a ROS 1 .bag of event arrays (ecal_stream_create_from_bag_file): decoded on the device, without a .bin in between.
     // opt null: the defaults; the reading loop's startTime / customEnd / endTime go into opt's start_time / end_time.
     void loadBagFile(const std::string &bagFilePath, const ecal_bag_options *opt = nullptr) {

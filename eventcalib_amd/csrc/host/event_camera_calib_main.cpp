@@ -3,7 +3,8 @@
 // EventCalibSpline -> TrajectoryByEvent.txt.  Built by eventcalib_amd/csrc/Makefile (`make driver`, part of `all`) into
 // eventcalib_amd/unit_test_eventCameraCalib next to libecal.so; run by tests/test_gpu_shims.py and bench.py's end_to_end leg.
 //   usage: unit_test_eventCameraCalib settings.yaml events.bin saveDir [batch]     (the reference's argv, eventCameraCalib.cpp:105-110;
-//   with batch, an events path ending in .txt is a text file of "stamp x y polarity" lines, converted on the device)
+//   with batch, an events path ending in .txt is a text file of "stamp x y polarity" lines, converted on the device; one ending in
+//   .raw, .aedat, .aedat4 or .bag a camera's or recorder's own file, decoded on the device)
 // "batch": rectifyFeatures of all keyframes in one device pass (ecal_rectify_keyframes) instead of one CirclesEventFrame per
 // keyframe, the file read in one piece, and a "stage <name> <seconds>" line per stage of the chain (bench.py's end_to_end leg).
 #include <chrono>
@@ -77,8 +78,31 @@ int main(int argc, char **argv) {
             opt.end_time = endTimeSetting;
             container->loadRawFile(eventsPath, &opt);
         } else if (eventsPath.size() >= 7 && eventsPath.compare(eventsPath.size() - 7, 7, ".aedat4") == 0) {
-            std::fprintf(stderr, "AEDAT 4 (%s) is not read: export the recording as AEDAT 3.1 or 2.0\n", eventsPath.c_str());
-            return 4;
+            // an iniVation DV recording (AEDAT 4: packets with LZ4 or no compression) inflated and decoded on the device.  Keys of this
+            // build, all optional: Aedat4_Stream (the stream id of the events; absent: found by its identifier), Aedat4_TimeBase
+            // (microseconds of epoch time; absent: the first event's whole second), Aedat4_FlipX / Aedat4_FlipY (0).  Events outside
+            // Camera.width x Camera.height are dropped.
+            ecal_aedat4_options opt;
+            ecal_aedat4_default_options(&opt);
+            if (!fsSettings["Aedat4_Stream"].isNone()) opt.stream_id = (int) fsSettings["Aedat4_Stream"];
+            if (!fsSettings["Aedat4_TimeBase"].isNone()) {
+                opt.auto_time_base = 0;
+                opt.time_base = std::strtoll(((std::string) fsSettings["Aedat4_TimeBase"]).c_str(), nullptr, 10);
+            }
+            if (!fsSettings["Aedat4_FlipX"].isNone()) opt.flip_x = (int) fsSettings["Aedat4_FlipX"] ? 1 : 0;
+            if (!fsSettings["Aedat4_FlipY"].isNone()) opt.flip_y = (int) fsSettings["Aedat4_FlipY"] ? 1 : 0;
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            opt.start_time = startTime;
+            opt.has_end_time = customEnd ? 1 : 0;
+            opt.end_time = endTimeSetting;
+            try {
+                container->loadAedat4File(eventsPath, &opt);
+            } catch (const std::exception &e) {   // (ZSTD packets, a stereo recording, a broken frame, a file cut short: said plainly)
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
+            std::printf("aedat4_time_base %lld\n", (long long) container->aedat4Info.time_base);   // microseconds: t = 0 of this run
         } else if (eventsPath.size() >= 6 && eventsPath.compare(eventsPath.size() - 6, 6, ".aedat") == 0) {
             // an iniVation recording (AEDAT 3.1 / 2.0, the version from its first line) decoded on the device.  Keys of this build,
             // all optional: Aedat_TimeBase (microseconds of the camera's clock, 0), Aedat_FlipX / Aedat_FlipY (0; which a

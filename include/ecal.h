@@ -1121,8 +1121,8 @@ int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const char *bin_pa
  * A DAVIS camera's .aedat file, without a host converter in front.  Nothing in the reference reads these formats and no such file
  * was at hand when this was written: the layouts are restated from the published format descriptions, and this contract is the
  * specification (eventcalib_amd/csrc/aedat_events.hpp restates it for the kernels, the host decoder and the tests).  The first real
- * recording should be checked against the vendor's own export.  AEDAT 4 (compressed packets), 1.0 and 3.0 are not read; a ROS 1 bag of
- * event arrays goes through the bag ingest below.
+ * recording should be checked against the vendor's own export.  AEDAT 1.0 and 3.0 are not read; AEDAT 4 (compressed packets) is not
+ * read HERE — it has entry points of its own, the aedat4 ingest below; a ROS 1 bag of event arrays goes through the bag ingest.
  *
  * File header (file entry points and ecal_aedat_parse_header): the first line is "#!AER-DAT3.1\r\n" or "#!AER-DAT2.0\r\n"; any
  *   other version is ECAL_ERR_INVALID with a text that names the version.  options.format other than ECAL_AEDAT_AUTO overrides the
@@ -1235,6 +1235,141 @@ int ecal_stream_create_from_aedat_file(ecal_ctx *ctx, const char *path, const ec
                                        ecal_aedat_info *info);
 int ecal_aedat_to_bin_file(ecal_ctx *ctx, const char *aedat_path, const char *bin_path, const ecal_aedat_options *opt,
                            ecal_aedat_info *info);
+
+/* ---- aedat4 ingest: iniVation AEDAT 4 (DV) recordings — LZ4 packets of FlatBuffers — into packed records, inflated and decoded in HBM ----
+ * The .aedat4 file DV records from a DAVIS camera, without a host converter in front.  Nothing in the reference reads it, and NO real
+ * AEDAT 4 file and no vendor library was at hand when this was written: the layout is restated from the published descriptions (the DV
+ * file format, FlatBuffers, the LZ4 frame and block formats), and this contract is the specification
+ * (eventcalib_amd/csrc/aedat4_events.hpp restates it for the kernels, the host decoder and the tests).  The first real recording has
+ * to be checked against the vendor's own export: the event count, the first and last stamps, a handful of coordinates.
+ * Everything is little-endian.  Every refusal's text contains the words "AEDAT 4".
+ *
+ * File: bytes 0..13 are "#!AER-DAT4.0\r\n" (anything else, or a file that ends before byte 18: ECAL_ERR_INVALID).  A size-prefixed
+ *   FlatBuffer follows: u32 N, then N bytes, which must lie within the first MiB; its root table is IOHeader, file identifier "IOHE" at
+ *   bytes 4..7 of the N bytes (else ECAL_ERR_INVALID).  Fields by id: 0 compression i32, default 0 (NONE 0, LZ4 1, LZ4_HIGH 2, ZSTD 3,
+ *   ZSTD_HIGH 4); 1 dataTablePosition i64, default -1; 2 infoNode, a string of XML, not parsed.  ZSTD and ZSTD_HIGH are refused by
+ *   name (record with LZ4 or without compression); any other value is refused with its number.
+ *   Packets run from byte 18 + N to dataTablePosition when that is >= 0, else to the end of the file; a position in front of the
+ *   first packet or behind the end of the file is ECAL_ERR_INVALID.  A packet is i32 streamID, i32 size, then `size` bytes of data;
+ *   size < 0 is ECAL_ERR_INVALID naming the packet's number (0-based, over all packets) and byte offset.  A header or data that runs
+ *   past the end ends the chain: a packet cut short is not decoded at all, its bytes from the header on count as n_trailing_bytes.
+ *   The file data table behind the packets is not read: a recording that was never closed reads the same as a closed one.
+ * Packet data: with compression NONE the packet's FlatBuffer itself; with LZ4 or LZ4_HIGH exactly ONE LZ4 frame: magic 04 22 4D 18;
+ *   FLG: bits 7..6 version, must be 01; bit 5 block independence (read, not enforced: a match is held against what the frame has
+ *   produced); bit 4 block checksums; bit 3 content size present; bit 2 content checksum; bit 1 must be 0; bit 0 dictionary id:
+ *   refused.  BD: bits 6..4 the block maximum, 4..7 for 64 KiB, 256 KiB, 1 MiB, 4 MiB; the other bits must be 0.  Then 8 bytes of
+ *   content size if flagged, one header-checksum byte, then blocks: u32 s; s == 0 is the end mark; bit 31 set = a stored block of
+ *   s & 0x7FFFFFFF bytes; else an LZ4 block of s bytes; each block followed by 4 checksum bytes if flagged.  Behind the end mark 4
+ *   bytes if the content checksum is flagged, and nothing else.  CHECKSUMS ARE STEPPED OVER, NOT VERIFIED.  A flagged content size
+ *   that differs from what the blocks inflate to is invalid.
+ *   Block: a chain of sequences.  token: high nibble = literal length, low nibble = match length - 4; a nibble of 15 is extended by
+ *   bytes, each added in, up to and including the first that is not 255.  token, literal extension, literals, u16 offset, match
+ *   extension.  A block's last sequence ends behind its literals (a block that ends anywhere else is invalid).  A match may reach back
+ *   up to 65 535 bytes into what the FRAME has produced, earlier blocks included; it may overlap its own output: byte i of a match is
+ *   the byte at match start + (i mod offset).
+ *   Malformed, all ECAL_ERR_INVALID naming the packet — its index among the event packets (0-based: the table's index) and the byte
+ *   offset of its data in the file: offset 0; an offset in front of the frame's first byte; literals, offset bytes or extensions that
+ *   run past the block; a block that runs past the packet; a block (stored or not) that inflates beyond the block maximum; a missing
+ *   end mark; bytes behind the frame; legacy (02 21 4C 18) or skippable (5x 2A 4D 18) magic; any other magic; a frame cut short.  When
+ *   several packets are malformed the lowest index the refusing pass met is named.  NOTHING outside the file or outside a packet's own
+ *   span of scratch is loaded or stored, whatever the bytes say.
+ * Inflated packet: a size-prefixed FlatBuffer: u32 size (not relied on), u32 root offset at byte 4, identifier at bytes 8..11, which
+ *   must be "EVTS".  The table is at 4 + root, its vtable at table - (i32 at table); the vtable holds u16 vtable_bytes, u16
+ *   table_bytes, u16 field0, ...  vtable_bytes < 6 or field0 == 0: the packet has no events.  Else the vector is at p + (u32 at p),
+ *   p = table + field0: a u32 count, then count events of 16 bytes: i64 t (microseconds, epoch time) at 0, i16 x at 8, i16 y at 10,
+ *   u8 on at 12, 3 bytes of padding.  Every one of these reads and the whole vector must lie inside the inflated packet, else
+ *   ECAL_ERR_INVALID as above.  No alignment of the vector is assumed; the vtable may lie on either side of the table; further fields
+ *   may follow field 0.  An inflated packet of 0 bytes (a frame whose blocks are all empty) is a packet of no events.
+ * The stream: the event packets are those of ONE streamID.  options.stream_id >= 0 names it (its packets must carry EVTS); -1: the
+ *   indexer inflates the first packet of every stream id on the host and takes the stream whose identifier is EVTS — two such streams
+ *   (a stereo recording) and none are ECAL_ERR_INVALID with the ids in the text.  Packets of every other stream (frames, IMU,
+ *   triggers) are stepped over by their header alone and counted in n_other_packets.
+ * Conversion and filter, in file order — the other ingests': t = (double)(t_us - time_base) * 1e-6 (one integer subtraction, one
+ *   conversion, one multiplication, no contraction); x, y = the doubles of the integers; the polarity byte is on != 0.  x < 0 or
+ *   y < 0 is dropped (n_outside) always; with width / height non-zero x >= width or y >= height too.  flip_x / flip_y give
+ *   x = width - 1 - x / y = height - 1 - y, applied BEHIND the bounds test; they need width / height (else ECAL_ERR_INVALID).  Then
+ *   t < 0 is dropped (n_negative); then kept if t >= start_time (else n_before_start), and with has_end_time the first event with
+ *   t >= end_time ends the stream: it and every event behind it count as n_after_end and as nothing else.
+ *   n_events + n_outside + n_negative + n_before_start + n_after_end = n_raw_events = what ecal_aedat4_count_events_dev returns.
+ * Time base: stamps are epoch microseconds.  options.auto_time_base (default 1, file forms): the base is the first event's stamp, in
+ *   file order, rounded down to a whole second (0 when there is no event); the indexer reports that value as first_stamp_us.  With
+ *   auto_time_base == 0 options.time_base is taken.  info.time_base = the base in force.  The _dev form takes an explicit base only:
+ *   auto_time_base != 0 there is ECAL_ERR_INVALID.
+ * options.max_inflated_bytes caps the sum of the packets' inflated sizes (default 2^34 = 16 GiB; an LZ4 block cannot inflate more
+ *   than 255-fold, so 255 x the file is always enough): a total above it is ECAL_ERR_RANGE and the scratch for it is not allocated.
+ *
+ * ecal_aedat4_block_events: event slots per decode block of this build — a fact for tests that place block boundaries.
+ * ecal_aedat4_parse_header: data (HOST) = the first n_bytes of a file of file_bytes bytes (at most the first MiB is needed) ->
+ *   *compression, *packets_begin (18 + N), *packets_end.  ctx may be NULL (no error text then).
+ * ecal_aedat4_index_packets: a HOST function over the whole file in host memory.  One 16-byte entry per packet of the chosen stream
+ *   (also one of no events), in file order; offsets count from byte 0 of the file, so the table fits the file as it is uploaded.
+ *   *n_packets = the count; ECAL_ERR_RANGE when it exceeds `capacity` (out holds the first `capacity`; out may be NULL with capacity
+ *   0: a count).  info (optional): n_packets, n_other_packets, n_trailing_bytes, n_compressed_bytes, compression, stream_id,
+ *   first_stamp_us.  ctx may be NULL.  The chain is not walked on the device: a packet is found only through the header before it.
+ * ecal_aedat4_count_events_dev: *n_events (HOST) = the events before any drop: always a sufficient `capacity`.  It inflates and
+ *   locates every packet to learn it (opt: compression and max_inflated_bytes are looked at).  Waits for `stream`.
+ * ecal_events_from_aedat4_dev: d_file (DEVICE, 16-byte aligned, the whole file, n_bytes bytes; nothing behind n_bytes is read) and
+ *   d_packets (DEVICE, 8-byte aligned, n_packets entries as ecal_aedat4_index_packets writes them) into d_events (DEVICE, room for
+ *   `capacity` records, file order, not sorted).  opt->compression is explicit: ECAL_AEDAT4_NONE or ECAL_AEDAT4_LZ4 (_LZ4_HIGH is the
+ *   same format); opt->stream_id is not looked at (the table is already a choice).  A table entry that does not lie within the file
+ *   is ECAL_ERR_INVALID.  info (HOST) is filled on ECAL_OK and on ECAL_ERR_RANGE (capacity too small: info->n_events = the count
+ *   needed, call again; also more than 2^32-1 events, and max_inflated_bytes); n_other_packets, n_trailing_bytes, stream_id and
+ *   first_stamp_us are the indexer's to report, not this call's.  On an error the contents of d_events are undefined; the context
+ *   stays usable.  Enqueues on `stream` and waits for it: the call returns with the records in place.
+ * ecal_stream_create_from_aedat4_file: the header read on the host; the packet headers (8 bytes a packet) read, and the first packet
+ *   of every stream id read and inflated for its identifier, on a host thread beside the chunked pinned upload of the file; inflated
+ *   and decoded on the device, the file's bytes freed, then the stream brought into time order if it is not.  info may be NULL.
+ * ecal_aedat4_to_bin_file: the same records in file order, no sort, as a .bin of the reference's layout. */
+enum { ECAL_AEDAT4_NONE = 0, ECAL_AEDAT4_LZ4 = 1, ECAL_AEDAT4_LZ4_HIGH = 2, ECAL_AEDAT4_ZSTD = 3, ECAL_AEDAT4_ZSTD_HIGH = 4 };
+typedef struct ecal_aedat4_options {
+    int compression;             /* _dev forms: ECAL_AEDAT4_NONE or _LZ4, explicit; the file forms take the header's */
+    int stream_id;               /* file forms and the indexer: >= 0 the stream of events, -1: found by its identifier */
+    int auto_time_base;          /* 1: the base is the first event's whole second (file forms) */
+    int flip_x, flip_y;          /* need width / height */
+    int has_end_time;
+    int64_t time_base;           /* microseconds of epoch time, with auto_time_base == 0 */
+    uint32_t width, height;      /* 0: no upper bound */
+    double start_time;           /* seconds */
+    double end_time;             /* seconds */
+    uint64_t max_inflated_bytes; /* default 2^34 */
+} ecal_aedat4_options;
+typedef struct ecal_aedat4_info {
+    uint64_t n_raw_events;       /* events before any drop */
+    uint64_t n_events;           /* records written, or needed */
+    uint64_t n_outside;          /* events dropped for x < 0, y < 0, x >= width or y >= height */
+    uint64_t n_negative;         /* events dropped for t < 0 */
+    uint64_t n_before_start;     /* events dropped for t < start_time */
+    uint64_t n_after_end;        /* events from the one that ended the stream on */
+    uint64_t n_packets;          /* packets of the chosen stream (also those of no events) */
+    uint64_t n_other_packets;    /* packets of other streams */
+    uint64_t n_trailing_bytes;   /* bytes from the header of a packet cut short on */
+    uint64_t n_compressed_bytes; /* data bytes of the chosen packets as the file has them */
+    uint64_t n_inflated_bytes;   /* what they inflate to (NONE: the same) */
+    int64_t first_stamp_us;      /* the first event's whole second: the automatic base */
+    int64_t time_base;           /* the base in force */
+    int compression;             /* the file's (file forms, indexer) or the option's (_dev) */
+    int stream_id;               /* the chosen stream; -1: none (a file of no packets, the _dev forms) */
+} ecal_aedat4_info;
+typedef struct ecal_aedat4_packet {
+    uint64_t offset_of_data;     /* bytes from byte 0 of the file */
+    uint32_t n_bytes;            /* the packet's size */
+    uint32_t zero;
+} ecal_aedat4_packet;
+void ecal_aedat4_default_options(ecal_aedat4_options *opt);
+uint32_t ecal_aedat4_block_events(void);
+int ecal_aedat4_parse_header(ecal_ctx *ctx, const uint8_t *data, uint64_t n_bytes, uint64_t file_bytes, int *compression,
+                             uint64_t *packets_begin, uint64_t *packets_end);
+int ecal_aedat4_index_packets(ecal_ctx *ctx, const uint8_t *file_host, uint64_t n_bytes, int stream_id, ecal_aedat4_packet *out,
+                              uint64_t capacity, uint64_t *n_packets, ecal_aedat4_info *info);
+int ecal_aedat4_count_events_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const ecal_aedat4_packet *d_packets,
+                                 uint64_t n_packets, const ecal_aedat4_options *opt, uint64_t *n_events, void *stream);
+int ecal_events_from_aedat4_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const ecal_aedat4_packet *d_packets,
+                                uint64_t n_packets, const ecal_aedat4_options *opt, uint8_t *d_events /*room for capacity records*/,
+                                uint64_t capacity, ecal_aedat4_info *info, void *stream);
+int ecal_stream_create_from_aedat4_file(ecal_ctx *ctx, const char *path, const ecal_aedat4_options *opt, ecal_stream **out,
+                                        ecal_aedat4_info *info);
+int ecal_aedat4_to_bin_file(ecal_ctx *ctx, const char *aedat4_path, const char *bin_path, const ecal_aedat4_options *opt,
+                            ecal_aedat4_info *info);
 
 /* ---- bag ingest: ROS 1 bags (format 2.0) of dvs_msgs/EventArray messages into packed records, decoded in HBM ----
  * The file that rpg_dvs_ros records from a DAVIS camera, without a host converter in front.  Nothing in the reference reads a bag and
