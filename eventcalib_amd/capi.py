@@ -1350,6 +1350,17 @@ class Context:
         self._check(self._L.ecal_grid_order_dev(self._h, d_win_info, d_seg_off, d_cand_xyr, int(S), int(rows), int(cols),
                                                 d_order, d_found, stream))
 
+    def grid_order(self, cand_xyr, rows, cols):
+        """ecal_grid_order, the host-buffer form for one candidate list: cand_xyr [n, 3] -> (order int32 [rows*cols], found)."""
+        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+        self._L.ecal_grid_order.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+        self._L.ecal_grid_order.restype = ctypes.c_int
+        cand = np.ascontiguousarray(cand_xyr, np.float64).reshape(-1, 3)
+        order = np.full(max(int(rows) * int(cols), 1), -1, np.int32)
+        found = np.zeros(1, np.uint32)
+        self._check(self._L.ecal_grid_order(self._h, _ptr(cand) if len(cand) else None, len(cand), int(rows), int(cols), _ptr(order), _ptr(found)))
+        return order[: int(rows) * int(cols)], int(found[0])
+
     # ---- re-detection around predicted projections ----
     def rectify_batch_dev(self, d_xy, d_seg_off, d_seg_cnt, d_kept_labels, d_win_info, d_frame_window, d_pose, F,
                           d_landmarks, params, d_feat_xyr, d_feat_valid, d_frame_info, stream=0):

@@ -1063,7 +1063,8 @@ static int detect_keyframes_impl(ecal_ctx *ctx, const uint8_t *d_events, uint64_
                           "(a piece's gate frame comes from the pieces before it: ecal_detect_keyframes_sharded hands it over)";
         return ECAL_ERR_INVALID;
     }
-    if (P == 0 || M == 0 || M > 128 || prm->rows > (uint32_t) AD_MAX_ROWS || !(ap->motion_time_step > 0) ||
+    if (int bad = ecal_grid_shape_check(ctx, prm->rows, prm->cols, "ecal_detect_keyframes")) return bad;
+    if (P == 0 || prm->rows > (uint32_t) AD_MAX_ROWS || !(ap->motion_time_step > 0) ||
         !(ap->end_time > ap->start_time) || (max_keyframes && (!kf_time || !kf_duration || !kf_events_num || !kf_features)) ||
         (ap->gate_mode != ECAL_GATE_OWN_PIECE && ap->gate_mode != ECAL_GATE_SHARED_MAP)) {
         ctx->last_error = "ecal_detect_keyframes: invalid parameters";

@@ -181,6 +181,9 @@ int ecal_cluster_order_sized(ecal_ctx *ctx, const double *d_xy, const uint32_t *
                              uint32_t *d_status, int only_tied_medians, const uint32_t *d_win_list, const uint32_t *d_win_count,
                              void *stream, const ecal_packed_points *pk = nullptr);
 // extraction as the context's ecal_set_median_ties setting wants it (ecal_detect.hip): the exact form needs the DBSCAN radius
+// the pattern shapes the grid finder handles (ecal_grid.hip, next to GR_L): ECAL_OK, or ECAL_ERR_INVALID with the shape and the
+// limit in ctx->last_error — every entry point that hands rows x cols to the finder asks this before it does any work
+int ecal_grid_shape_check(ecal_ctx *ctx, uint32_t rows, uint32_t cols, const char *who);
 // ecal_grid_order_dev + the found grids' row directions (row_direction.hpp) into d_dirs[S][rows][2] (NULL: none)
 int ecal_grid_order_dirs_dev(ecal_ctx *ctx, const uint32_t *d_win_info, const uint32_t *d_seg_off, const double *d_cand_xyr, uint32_t S,
                              uint32_t rows, uint32_t cols, int32_t *d_order, uint32_t *d_found, double *d_dirs, void *stream);

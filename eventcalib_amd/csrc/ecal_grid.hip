@@ -6,11 +6,15 @@
 // cv_calib/src/circlesgrid.cpp) followed by the nearest-candidate lookup of :340-353 — with a
 // deterministic lattice walk (the reference's finder runs kmeans with random centres, x100 attempts).
 // Output convention = the reference's (circlesgrid.cpp:1258-1291): grid index i*cols + j is the model
-// point ((2j + i%2) s, i s) (EventCalibIni.cpp:102-106).  For rows x cols = 9 x 4 the pattern has no
-// orientation-preserving self-symmetry, so a complete grid has exactly one valid assignment; the walk
+// point ((2j + i%2) s, i s) (EventCalibIni.cpp:102-106).  With an odd number of rows (9 x 4) the pattern has no
+// orientation-preserving self-symmetry, so a complete grid has exactly one valid assignment; with an even number
+// it maps onto itself under a half turn and has two — match_pattern takes the first entry of its transform table
+// that fits, which makes the returned one "the seed's nearest neighbour lies one column step to the right of the
+// seed" (include/ecal.h states the rule, tests/test_gpu_grid_shapes.py checks it).  The walk
 // assumes the board is seen from its front (model -> image mapping with positive determinant).
 // Parity with OpenCV's finder is NOT pinned (third-party algorithm, random by construction); tests check
-// the ordering against synthetic ground truth.
+// the ordering against synthetic ground truth: 9 x 4 in tests/test_gpu_grid.py, every supported shape
+// (grid_shape_supported below) and up to 128 candidates in tests/test_gpu_grid_shapes.py.
 //
 // One wave (64 lanes) per window: lanes share the nearest-candidate searches, lane-uniform control flow
 // does the breadth-first walk over the centred-square lattice (neighbours along the two diagonals).
@@ -26,6 +30,25 @@ constexpr uint32_t GR_MAXC = 128;  // candidates per window handled
 constexpr int GR_L = 32;           // lattice coordinate window (u, v in [-16, 15])
 constexpr uint32_t GR_MAXM = 128;  // pattern points handled (rows * cols)
 constexpr uint32_t GR_PARALLEL_MAX = 1024;   // windows at work up to which the launch takes the latency form (a wave per start)
+
+// The pattern shapes the walk can hold.  Model point (x, y) = (2 j + i % 2, i) sits at lattice cell U = (x + y) / 2,
+// V = (y - x) / 2: over the board U runs over [0, cols - 1 + rows / 2] and V over [-(cols - 1), (rows - 1) / 2] (integer
+// divisions), so the longer of the two spans is E = cols - 1 + rows / 2 cells.  The walk's coordinates are those of its seed,
+// in a basis that is the model's turned by any quarter turn (the seed's nearest neighbour decides): either span may lie along
+// either axis, in either sense, and a cell outside [-GR_L / 2, GR_L / 2 - 1] is never visited.  The seed is the candidate
+// nearest the centroid, and the centroid of the pattern lies within a quarter cell of the middle of both spans; perspective,
+// noise and clutter off the board move the seed, and one cell is allowed for that.  So every cell is reachable when the longer
+// half, (E + 1) / 2, plus that cell stays within the short side of the window, GR_L / 2 - 1:  E <= GR_L - 4 = 28.
+// A single row or column has no second lattice direction: no grid the walk could orient.
+constexpr uint32_t GR_SEED_SLACK = 1;
+__host__ __device__ constexpr uint32_t grid_lattice_span(uint32_t rows, uint32_t cols) { return cols - 1u + rows / 2u; }
+__host__ __device__ constexpr bool grid_shape_supported(uint32_t rows, uint32_t cols) {
+    return rows >= 2u && cols >= 2u && (uint64_t) rows * cols <= GR_MAXM &&
+           (grid_lattice_span(rows, cols) + 1u) / 2u + GR_SEED_SLACK <= (uint32_t) GR_L / 2u - 1u;
+}
+static_assert(grid_shape_supported(9, 4) && grid_shape_supported(16, 8) && grid_shape_supported(4, 27) && !grid_shape_supported(4, 28) &&
+                  !grid_shape_supported(4, 32) && !grid_shape_supported(2, 64) && !grid_shape_supported(1, 36),
+              "the bound of the lattice window");
 
 // the changes of lattice basis the pattern is matched through: the four rotations, then the other integer matrices
 // (a b; c d) of determinant + 1 with entries in [-2, 2], in ascending order of (a + 2) + 5 (b + 2) + 25 (c + 2) + 125 (d + 2)
@@ -518,8 +541,13 @@ __global__ __launch_bounds__(GR_T * NW) void grid_order_kernel(const uint32_t *_
         const double tx = pcx + sxp, ty = pcy + syp;
         // the vendored finder takes the nearest keypoint within minDistanceToAddKeypoint = 20 px of (neighbour + basis
         // vector) as the hole, else the line stays incomplete (circlesgrid.cpp:528,812-840,928-930: a synthetic
-        // keypoint earns no existingVertexGain); capped at tol_frac of the step for small apparent patterns
-        const double lim = fmin(tol_px * tol_px, tol_frac * tol_frac * (sxp * sxp + syp * syp));
+        // keypoint earns no existingVertexGain); capped at tol_frac of the step for small apparent patterns.  The step is the
+        // LATTICE's at this node — the shorter of its two basis vectors —, not the vector this direction walks along: a robust
+        // start's paired basis may hold a longer lattice vector (a diagonal and a row vector, sqrt(2) diagonals long), and
+        // tol_frac of that reached a candidate 0.9 diagonals off its hole — a verdict that depended on where the seed lay
+        // (tests/test_gpu_grid_shapes.py, the small-step cases).  Where the 20 px govern (a step above 28.6 px) nothing changes.
+        const double step2 = fmin(b1x * b1x + b1y * b1y, b2x * b2x + b2y * b2y);
+        const double lim = fmin(tol_px * tol_px, tol_frac * tol_frac * step2);
         unsigned long long r = row_nearest(tx, ty, rfree, false, 0);
         // every row tests its own answer; the usual case — the accepted candidates are different ones — is written by the
         // four rows at once.  Two directions that want the same candidate go through the one-after-the-other form below.
@@ -768,6 +796,15 @@ __global__ __launch_bounds__(GR_T * NW) void grid_order_kernel(const uint32_t *_
                         far2 = fmax(far2, sx_ * sx_ + sy_ * sy_);
                     }
                 }
+                // ... and no longer than the lattice's own step at the cell, the shorter of the homography's steps along the
+                // two axes (as in the first walk: a sheared basis has a neighbour a longer lattice vector away)
+#pragma unroll
+                for (int ax = 0; ax < 2; ax++) {
+                    const int un = u + (ax == 0 ? 1 : 0), vn = v + (ax == 1 ? 1 : 0);
+                    const double wn = hh[6] * un + hh[7] * vn + 1.0;
+                    const double ex = (hh[0] * un + hh[1] * vn + hh[2]) / wn - tx, ey = (hh[3] * un + hh[4] * vn + hh[5]) / wn - ty;
+                    if (wn > 1e-6 && far2 > 0.0) far2 = fmin(far2, ex * ex + ey * ey);
+                }
                 double best = INFINITY;
                 uint32_t bj = 0;
                 for (uint32_t i = 0; i < n; i++) {   // (the same i in every lane: broadcast reads)
@@ -912,6 +949,22 @@ __global__ __launch_bounds__(GR_T * NW) void grid_order_kernel(const uint32_t *_
 
 using namespace ecal;
 
+// ECAL_OK, or ECAL_ERR_INVALID with the shape and the limit in last_error: the one check of rows x cols on every way to the kernel
+int ecal_grid_shape_check(ecal_ctx *ctx, uint32_t rows, uint32_t cols, const char *who) {
+    if (grid_shape_supported(rows, cols)) return ECAL_OK;
+    if (ctx) {
+        const std::string shape = std::string(who) + ": pattern of " + std::to_string(rows) + " rows x " + std::to_string(cols) + " cols is not supported: ";
+        if (rows < 2 || cols < 2)
+            ctx->last_error = shape + "at least 2 rows and 2 cols (a single row or column is no grid the finder can orient)";
+        else if ((uint64_t) rows * cols > GR_MAXM)
+            ctx->last_error = shape + "rows * cols = " + std::to_string((uint64_t) rows * cols) + ", the limit is " + std::to_string(GR_MAXM);
+        else
+            ctx->last_error = shape + "cols - 1 + rows / 2 = " + std::to_string(grid_lattice_span(rows, cols)) + " lattice cells, the limit is " +
+                              std::to_string(GR_L - 2 - 2 * (int) GR_SEED_SLACK) + " (the walk's window of " + std::to_string(GR_L) + " cells around its seed)";
+    }
+    return ECAL_ERR_INVALID;
+}
+
 extern "C" int ecal_grid_order_dev(ecal_ctx *ctx, const uint32_t *d_win_info, const uint32_t *d_seg_off,
                                    const double *d_cand_xyr, uint32_t S, uint32_t rows, uint32_t cols,
                                    int32_t *d_order, uint32_t *d_found, void *stream) {
@@ -924,10 +977,11 @@ int ecal_grid_order_dirs_dev(ecal_ctx *ctx, const uint32_t *d_win_info, const ui
     const ecal_range range__(ctx, "ecal_grid_order");
     if (!ctx) return ECAL_ERR_INVALID;
     if (S == 0) return ECAL_OK;
-    if (!d_win_info || !d_seg_off || !d_cand_xyr || !d_order || !d_found || rows * cols < 4 || rows * cols > GR_MAXM) {
-        ctx->last_error = "null pointer or unsupported pattern size";
+    if (!d_win_info || !d_seg_off || !d_cand_xyr || !d_order || !d_found) {
+        ctx->last_error = "ecal_grid_order: null pointer";
         return ECAL_ERR_INVALID;
     }
+    if (int rc = ecal_grid_shape_check(ctx, rows, cols, "ecal_grid_order")) return rc;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double tol_px = ctx->sw.grid_tol_px;   // (ECAL_GRID_TOL_PX, a debug switch for tests of the tolerance's effect; default = the reference's 20 px)
     const int dbg = (ctx->sw.grid_debug ? 1 : 0) | (ctx->sw.grid_serial_walk ? 2 : 0);
@@ -948,7 +1002,8 @@ int ecal_grid_order_dirs_dev(ecal_ctx *ctx, const uint32_t *d_win_info, const ui
 // CirclesEventFrame.cpp:332-336 (the shim host/cv_calib.hpp sits on this).  order[rows * cols] = candidate index per pattern point.
 extern "C" int ecal_grid_order(ecal_ctx *ctx, const double *cand_xyr, uint32_t n, uint32_t rows, uint32_t cols, int32_t *order,
                                uint32_t *found) {
-    if (!ctx || !order || !found || (n && !cand_xyr) || rows * cols < 4 || rows * cols > GR_MAXM) return ECAL_ERR_INVALID;
+    if (!ctx || !order || !found || (n && !cand_xyr)) return ECAL_ERR_INVALID;
+    if (int rc = ecal_grid_shape_check(ctx, rows, cols, "ecal_grid_order")) return rc;
     const uint32_t M = rows * cols;
     *found = 0;
     for (uint32_t m = 0; m < M; m++) order[m] = -1;

@@ -553,7 +553,7 @@ extern "C" int ecal_detect_pass(ecal_ctx *ctx, const uint8_t *d_events, uint64_t
     if (!ctx || !prm || !packed || (S && (!t0 || !t1)) || (n_events && !d_events)) return ECAL_ERR_INVALID;
     const uint32_t M = prm->rows * prm->cols;
     if (S == 0) return ECAL_OK;
-    if (M == 0 || M > 128) return ECAL_ERR_INVALID;
+    if (int bad = ecal_grid_shape_check(ctx, prm->rows, prm->cols, "ecal_detect_pass")) return bad;
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     int rc;
@@ -603,6 +603,8 @@ extern "C" int ecal_detect_stream_tiled(ecal_ctx *ctx, const uint8_t *events, ui
     if (!ctx || !prm || !n_windows || (n_events && !events) || !(window_len > 0) || windows_per_chunk == 0) return ECAL_ERR_INVALID;
     *n_windows = 0;
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (prm->rows * prm->cols != 0)   // (0: no grid stage)
+        if (int bad = ecal_grid_shape_check(ctx, prm->rows, prm->cols, "ecal_detect_stream_tiled")) return bad;
     if (n_events == 0) return ECAL_OK;
     if (n_events > 0xFFFFFFFFull) return ECAL_ERR_RANGE;
     const double t_last = rec_time(events, n_events - 1);

@@ -483,7 +483,25 @@ int ecal_detect_stream_tiled(ecal_ctx *ctx, const uint8_t *events /*host*/, uint
  *   or d_found[s] = 0 and -1 entries when no complete grid is found (extractFeatures returns false).
  * Deterministic lattice walk, not OpenCV's randomised (kmeans) search: same ordering whenever a complete
  * grid is present and seen from its front; parity with the third-party finder is otherwise unpinned.
- * Up to 128 candidates per window, rows*cols <= 128. */
+ * Candidates: up to 128 per window; a window with fewer than rows*cols or more than 128 gets d_found = 0.
+ * Pattern shapes: rows >= 2, cols >= 2, rows*cols <= 128 and cols - 1 + rows / 2 <= 28 (integer division).  The last bound is
+ *   the walk's: it places the circles on a window of 32 x 32 lattice cells around its seed, the candidate nearest the centroid;
+ *   the board spans cols - 1 + rows / 2 cells along its longer lattice diagonal, and must fit with the seed up to one cell off
+ *   the middle (so 4 x 27, 3 x 28, 5 x 25, 16 x 8 and 50 x 2 are handled; 4 x 28, 4 x 32 and 2 x 64 are not).  Any other shape
+ *   is ECAL_ERR_INVALID, ecal_last_error names the shape and the limit — here, in ecal_grid_order, ecal_detect_pass,
+ *   ecal_detect_keyframes[_sharded] and ecal_detect_stream_tiled alike (one check, on the host, before any work is done; the
+ *   grid stage of ecal_detect_batch makes it too).
+ *   A view whose perspective or off-board clutter moves the centroid more than a cell off the board's middle can still lose a
+ *   board of span 27 or 28 (d_found = 0); boards of span <= 26 (5 x 25) have a second cell to spare.
+ * Self-symmetric boards: a pattern with an EVEN number of rows maps onto itself under a half turn, (i, j) -> (rows - 1 - i,
+ *   cols - 1 - j), so a complete grid has two valid assignments (with odd rows, 9 x 4 among them, exactly one).  The one returned:
+ *   that in which the step from the walk's seed to the seed's nearest neighbour goes one column step to the RIGHT on the board
+ *   (from model x to x + 1, one row up or down).  It follows from the candidates alone — not from the image's orientation, which
+ *   the noise on the seed's four diagonal neighbours outweighs —, and is the same in both launch forms and on every call.
+ *   (Mechanism: that step is the walk's first axis, and the pattern is matched through the table of lattice transforms in order;
+ *   the first two entries map that axis to the model's (+1, +1) and (+1, -1) diagonals, and one of them always fits such a board.)
+ * Hole tolerance: a candidate takes a hole when it lies within min(20 px, 0.7 x the lattice's local step) of the predicted
+ *   position, the step being the shorter of the two lattice vectors the walk holds there. */
 int ecal_grid_order_dev(ecal_ctx *ctx, const uint32_t *d_win_info, const uint32_t *d_seg_off, const double *d_cand_xyr,
                         uint32_t S, uint32_t rows, uint32_t cols, int32_t *d_order /*[S][rows*cols]*/,
                         uint32_t *d_found /*[S]*/, void *stream);
