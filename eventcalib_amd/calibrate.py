@@ -145,11 +145,23 @@ def remove_hot_pixels(ctx, events, width=346, height=260, extra_mask=None, **opt
     return ctx.remove_hot_pixels(events, width=width, height=height, extra_mask=extra_mask, **options)
 
 
+def remove_noise(ctx, events, width=346, height=260, **options):
+    """The events without background activity — isolated events with no neighbour firing near them in time: (events, info) as
+    capi.Context.remove_noise returns them.  An event on the sensor stays iff at least min_support pixels of the (2 radius + 1)^2
+    square around its own (the own pixel only with include_self) fired an earlier event of the stream at most dt before it (the
+    stream's time unit: seconds; defaults radius 1, min_support 1, include_self 0, dt 0.005).  Every event is judged on the GPU
+    from the input stream alone, exactly as the sequential rule of include/ecal.h states it; the records that stay are byte for
+    byte the input's, in the input's order.  Events whose coordinates are not whole numbers inside the sensor are never removed and
+    support nothing.  The first events of a stream have nothing before them and go.  A hot pixel supports its neighbours' noise: run
+    remove_hot_pixels first."""
+    return ctx.remove_noise(events, width=width, height=height, **options)
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
-                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None):
+                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -183,7 +195,12 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     hot_pixels (opt-in; None or False: nothing changes): True or a dict of options (quantile_permille, min_count, factor, extra_mask)
     removes the events of hot pixels first (remove_hot_pixels below, on a width x height sensor) and runs everything on the filtered
     stream — a stage of its own, `hot_pixels`; out["hot_pixels"] is the filter's info (counts of events and pixels, `mask`,
-    `counts`).  t_first and t_last stay the caller's.  No default of the rule has met a real recording (design/17_hot_pixels.md)."""
+    `counts`).  t_first and t_last stay the caller's.  No default of the rule has met a real recording (design/17_hot_pixels.md).
+    noise_filter (opt-in; None or False: nothing changes): True or a dict of options (radius, min_support, include_self, dt) removes
+    the events that have no recent neighbour event (remove_noise below, on a width x height sensor) — after the hot pixels when both
+    are on, since a hot pixel supports its neighbours' noise — and runs everything on the filtered stream; a stage of its own,
+    `noise_filter`; out["noise_filter"] is the options in force and the filter's totals.  The defaults come from the clean synthetic
+    streams and have not met a real recording (design/19_noise_filter.md)."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -216,6 +233,11 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
         events, hot_info = remove_hot_pixels(ctx, events, width=int(width), height=int(height),
                                              **(dict(hot_pixels) if isinstance(hot_pixels, dict) else {}))
         mark("hot_pixels")
+    noise_info = None
+    if noise_filter is not None and noise_filter is not False:
+        events, noise_info = remove_noise(ctx, events, width=int(width), height=int(height),
+                                          **(dict(noise_filter) if isinstance(noise_filter, dict) else {}))
+        mark("noise_filter")
     # -- 1. keyframes
     kf = detect_keyframes_device(pipe.ctx, events, step, frame_event_num_threshold, piece_num, t_first, t_last, eps, minpts, rows, cols,
                                  gate_mode=gate_mode, radius_threshold=radius_threshold)
@@ -223,6 +245,8 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     out = {"keyframes": K, "stage_seconds": stages}
     if hot_info is not None:
         out["hot_pixels"] = hot_info
+    if noise_info is not None:
+        out["noise_filter"] = noise_info
     mark("keyframe_search")
     if K == 0:
         raise RuntimeError("no keyframe found")

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "ecal_aedat4_default_options", "ecal_aedat4_block_events", "ecal_aedat4_parse_header", "ecal_aedat4_index_packets", "ecal_aedat4_count_events_dev", "ecal_events_from_aedat4_dev", "ecal_stream_create_from_aedat4_file", "ecal_aedat4_to_bin_file",
     "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
     "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
+    "ecal_noise_default_options", "ecal_noise_verdict_host", "ecal_noise_verdict_dev", "ecal_denoise_events_dev", "ecal_stream_remove_noise",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -376,6 +377,51 @@ def hot_pixel_mask(counts, extra_mask=None, **options):
         raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_hot_pixel_mask (width and height from 1 to 4096, quantile_permille <= 1000, "
                         "a finite factor >= 0)")
     return mask.astype(bool), info.as_dict()
+
+
+class NoiseOptions(ctypes.Structure):
+    """ecal_noise_options (include/ecal.h, noise filter)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32), ("min_support", ctypes.c_uint32),
+                ("include_self", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("dt", ctypes.c_double)]
+
+
+def noise_options(width=None, height=None, radius=None, min_support=None, include_self=None, dt=None, reserved=None):
+    """ecal_noise_options from ecal_noise_default_options (346 x 260, radius 1, min_support 1, include_self 0, dt 0.005 in the stream's
+    time unit); None keeps the default."""
+    L = load_library()
+    L.ecal_noise_default_options.argtypes, L.ecal_noise_default_options.restype = [ctypes.POINTER(NoiseOptions)], None
+    o = NoiseOptions()
+    L.ecal_noise_default_options(ctypes.byref(o))
+    for name, value in (("width", width), ("height", height), ("radius", radius), ("min_support", min_support),
+                        ("include_self", include_self), ("reserved", reserved)):
+        if value is not None:
+            setattr(o, name, int(value))
+    if dt is not None:
+        o.dt = float(dt)
+    return o
+
+
+NOISE_OPTIONS_RULE = "width and height from 1 to 4096, radius from 1 to 3, min_support at least 1, include_self 0 or 1, reserved 0, dt at least 0 and not NaN"
+
+
+def noise_verdict_host(events, **options):
+    """ecal_noise_verdict_host (host arrays; no context, no device): the sequential walk of the noise filter over packed 25-byte
+    records -> (verdict uint8 [n]: 1 keep, 0 remove; totals: one FILTER_TOTALS record).  options: width, height, radius,
+    min_support, include_self, dt."""
+    L = load_library()
+    L.ecal_noise_verdict_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), ctypes.c_void_p, ctypes.c_void_p]
+    L.ecal_noise_verdict_host.restype = ctypes.c_int
+    ev = np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else np.asarray(events, np.uint8).ravel()
+    ev = np.ascontiguousarray(ev)
+    assert ev.size % 25 == 0, "packed 25-byte event records"
+    n = ev.size // 25
+    o = noise_options(**options)
+    verdict = np.zeros(n, np.uint8)
+    tot = np.zeros(1, FILTER_TOTALS)
+    st = L.ecal_noise_verdict_host(ev.ctypes.data if n else None, n, ctypes.byref(o), verdict.ctypes.data if n else None, tot.ctypes.data)
+    if st != 0:
+        raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_noise_verdict_host (" + NOISE_OPTIONS_RULE + ")")
+    return verdict, tot[0]
 
 
 def _ptr(a):
@@ -1290,6 +1336,88 @@ class Context:
         d = info.as_dict()
         d["mask"], d["counts"] = mask.astype(bool), counts
         return out, d
+
+    # ---- noise filter (ecal_noise_verdict_dev, ecal_denoise_events_dev and the stream call) ----
+    def noise_verdict_dev(self, d_events, n_events, opt, d_verdict, d_totals=None, stream=0):
+        """ecal_noise_verdict_dev: raw device pointers; opt a NoiseOptions or None (the defaults), d_verdict [n_events] u8, d_totals
+        FILTER_TOTALS or None; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_noise_verdict_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), vp, vp, vp]
+        L.ecal_noise_verdict_dev.restype = ctypes.c_int
+        self._check(L.ecal_noise_verdict_dev(self._h, d_events, int(n_events), ctypes.byref(opt) if opt is not None else None, d_verdict, d_totals, stream))
+
+    def denoise_events_dev(self, d_events, n_events, opt, d_out, d_count, d_totals=None, stream=0):
+        """ecal_denoise_events_dev: raw device pointers; d_out room for n_events records (not overlapping the events), d_count one
+        u32, d_totals FILTER_TOTALS or None; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_denoise_events_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), vp, vp, vp, vp]
+        L.ecal_denoise_events_dev.restype = ctypes.c_int
+        self._check(L.ecal_denoise_events_dev(self._h, d_events, int(n_events), ctypes.byref(opt) if opt is not None else None, d_out, d_count,
+                                              d_totals, stream))
+
+    def noise_verdict(self, events, **options):
+        """The noise filter's keep / remove byte per event: (verdict: uint8 CUDA tensor [n], 1 keep; totals: one FILTER_TOTALS
+        record).  options: width, height, radius, min_support, include_self, dt (noise_options).  Byte for byte what
+        noise_verdict_host gives."""
+        import torch
+        t, n = self._records_arg(events)
+        o = noise_options(**options)
+        verdict = torch.empty(n, dtype=torch.uint8, device=t.device)
+        tot = torch.empty(4, dtype=torch.int64, device=t.device)
+        with torch.cuda.device(t.device):
+            self.noise_verdict_dev(t.data_ptr() if n else None, n, o, verdict.data_ptr() if n else None, tot.data_ptr(),
+                                   torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        return verdict, tot.cpu().numpy().view(FILTER_TOTALS)[0]
+
+    def denoise_events(self, events, **options):
+        """The events the noise filter keeps, byte for byte and in input order: (events: uint8 CUDA tensor [n_kept * 25], totals: one
+        FILTER_TOTALS record).  options as noise_verdict's.  Off-grid events stay."""
+        import torch
+        t, n = self._records_arg(events)
+        o = noise_options(**options)
+        out = torch.empty(n * 25, dtype=torch.uint8, device=t.device)
+        cnt = torch.empty(1, dtype=torch.int32, device=t.device)
+        tot = torch.empty(4, dtype=torch.int64, device=t.device)
+        with torch.cuda.device(t.device):
+            self.denoise_events_dev(t.data_ptr() if n else None, n, o, out.data_ptr() if n else None, cnt.data_ptr(), tot.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        kept = int(cnt.item()) & 0xFFFFFFFF
+        return out[: kept * 25], tot.cpu().numpy().view(FILTER_TOTALS)[0]
+
+    def remove_noise(self, events, width=346, height=260, **options):
+        """ecal_stream_remove_noise's work on a tensor of records: (events, info) — info: the options in force (width, height,
+        radius, min_support, include_self, dt) and the filter's totals (n_events, n_off_grid, n_removed, n_kept) as a dict."""
+        o = noise_options(width=width, height=height, **options)
+        out, tot = self.denoise_events(events, width=width, height=height, **options)
+        info = {name: getattr(o, name) for name, _ in NoiseOptions._fields_ if name != "reserved"}
+        info.update({k: int(tot[k]) for k in FILTER_TOTALS.names})
+        return out, info
+
+    def stream_remove_noise(self, events, width=346, height=260, **options):
+        """ecal_stream_remove_noise over an ecal_stream made of the host records `events` (the C++ shim's way) -> (events as a uint8
+        CUDA tensor, totals dict)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
+        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
+        L.ecal_stream_remove_noise.argtypes = [vp, vp, ctypes.POINTER(NoiseOptions), ctypes.POINTER(vp), vp]
+        L.ecal_stream_remove_noise.restype = ctypes.c_int
+        ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
+        assert ev.size % 25 == 0, "packed 25-byte event records"
+        o = noise_options(width=width, height=height, **options)
+        tot = np.zeros(1, FILTER_TOTALS)
+        h_in, h_out = vp(), vp()
+        self._check(L.ecal_stream_create(self._h, _ptr(ev) if ev.size else None, ev.size // 25, ctypes.byref(h_in)))
+        try:
+            self._check(L.ecal_stream_remove_noise(self._h, h_in, ctypes.byref(o), ctypes.byref(h_out), tot.ctypes.data))
+        finally:
+            L.ecal_stream_destroy(h_in)
+        out, _, _ = self._stream_records(h_out)
+        return out, {k: int(tot[0][k]) for k in FILTER_TOTALS.names}
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

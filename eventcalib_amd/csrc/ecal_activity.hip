@@ -11,6 +11,7 @@
 //   activity_write_kernel      reads the verdicts (16 bytes per thread), ranks the kept events inside the block in event order, packs
 //                              their own 25 bytes into LDS a quarter of the block at a time and copies them out with aligned 16-byte
 //                              stores
+// The scan and the writing pass are ecal_compact_by_verdict (ecal_ctx.hpp): the noise filter (ecal_noise.hip) ends in them too.
 // Bytes per event: 25 read + 4 atomic in the activity pass; 17 read (x, y, the mask byte) + 1 written in the verdict pass; 1 read in
 // the writing pass, and per KEPT event 25 read + 25 written.
 // Nothing behind n_events * 25 bytes of the input is loaded and nothing behind the kept records is stored: any caller tensor will do.
@@ -305,15 +306,22 @@ extern "C" int ecal_filter_events_dev(ecal_ctx *ctx, const uint8_t *d_events, ui
     hipLaunchKernelGGL(activity_verdict_kernel, dim3(nb), dim3(PA_T), 0, st, d_events, n_events, d_mask, width, height, verdict, cnt,
                        (unsigned long long *) d_totals);
     tm.mark("verdict");
-    rc = ecal_scan_blocks(ctx, cnt, nb, off, st);
+    rc = ecal_compact_by_verdict(ctx, d_events, n_events, verdict, cnt, off, d_out, d_count, tm, st);
+    if (rc) return rc;
+    if (tm.on) ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (ECAL_TRACE=load alone: the timer reads its events when it goes out of scope)
+    return ECAL_OK;
+}
+
+int ecal_compact_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_verdict, const uint32_t *d_cnt,
+                            uint32_t *d_off, uint8_t *d_out, uint32_t *d_count, ecal_load_timer &tm, hipStream_t st) {
+    const uint32_t nb = (uint32_t) ((n_events + PA_BLOCK - 1) / PA_BLOCK);
+    const int rc = ecal_scan_blocks(ctx, d_cnt, nb, d_off, st);
     if (rc) return rc;
     tm.mark("scan");
-    hipLaunchKernelGGL(activity_write_kernel, dim3(nb), dim3(PA_T), 0, st, d_events, n_events, (const uint8_t *) verdict,
-                       (const uint32_t *) off, d_out);
+    hipLaunchKernelGGL(activity_write_kernel, dim3(nb), dim3(PA_T), 0, st, d_events, n_events, d_verdict, (const uint32_t *) d_off, d_out);
     tm.mark("write");
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, off + nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     ECAL_HIP_TRY(ctx, hipGetLastError());
-    if (tm.on) ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (ECAL_TRACE=load alone: the timer reads its events when it goes out of scope)
     return ECAL_OK;
 }
 

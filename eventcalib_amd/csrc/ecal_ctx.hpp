@@ -119,6 +119,8 @@ struct ecal_ctx {
     ecal_devbuf reassoc_records;   // ecal_solver_reassociate / _create_reassociated: the record arrays, the count, the totals
     ecal_devbuf activity_scratch;  // ecal_filter_events_dev: one verdict byte per event, per-block counts / offsets
     ecal_devbuf activity_maps;     // ecal_stream_remove_hot_pixels: the count map, the mask, the totals, the count
+    ecal_devbuf noise_scratch;     // ecal_noise_verdict_dev / ecal_denoise_events_dev: sort keys and indices, sorted stamps, the start table, verdict bytes, per-block counts / offsets
+    ecal_devbuf noise_results;     // ecal_stream_remove_noise: the totals, the count
     ecal_devbuf aedat4_tables;     // aedat4 ingest: the packets' inflated sizes, spans, located events, first slots, the counters
     ecal_devbuf aedat4_inflated;   // aedat4 ingest: the inflated packets, each in its span (padded to 16 bytes)
     ecal_devbuf aedat4_blocks;     // aedat4 ingest: per-block kept counts / offsets
@@ -229,6 +231,12 @@ struct ecal_load_timer {
         for (int i = 0; i < n; i++) (void) hipEventDestroy(ev[i]);
     }
 };
+// The ordered compaction both stream filters end in (ecal_activity.hip): the exclusive scan of the nb = ceil(n_events / 4096) per-block
+// kept counts d_cnt into d_off [nb + 1], activity_write_kernel — the events whose verdict byte is non-zero, their own 25 bytes each, in
+// input order into d_out — and *d_count = the total.  d_verdict: whole blocks of 4096 bytes, 16-byte aligned (the bytes behind
+// n_events are read and masked).  n_events > 0.  Marks "scan" and "write" on tm; does not synchronise.
+int ecal_compact_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_verdict, const uint32_t *d_cnt,
+                            uint32_t *d_off, uint8_t *d_out, uint32_t *d_count, ecal_load_timer &tm, hipStream_t st);
 // reference element order: the per-pixel bucket table of the hot-path slicer, built on first use (ecal_events.hip)
 int ecal_ensure_bucket_table(ecal_ctx *ctx, hipStream_t st);
 // tail scheduling (see ecal_ctx::tail_seen): slots of the stages' lists, and "may this call run lean?"

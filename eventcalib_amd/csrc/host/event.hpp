@@ -457,6 +457,21 @@ struct EventContainer {
         stream_ = filtered;
     }
     ecal_hot_pixel_info hotPixelInfo{};   // what the last removeHotPixels saw (events and pixels, removed and kept)
+    // The events without a recent neighbour event taken out of a file-backed container (ecal_stream_remove_noise: every event judged
+    // on the device from the stream alone, an order-preserving filter; opt null: the defaults on a 346 x 260 sensor): the stream is
+    // swapped for the filtered one.  firstTime() / lastTime() stay the loaded stream's.  Hot pixels first when both are wanted.
+    void removeNoise(const ecal_noise_options *opt = nullptr, ecal_filter_totals *totals = nullptr) {
+        if (!fromFile_ || !stream_) throw std::logic_error("EventContainer: removeNoise needs a file-backed container (loadFile and its kin)");
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        ecal_stream *filtered = nullptr;
+        const int rc = ecal_stream_remove_noise(ctx, stream_, opt, &filtered, &noiseTotals);
+        if (totals) *totals = noiseTotals;
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("removeNoise: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_stream_remove_noise: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        ecal_stream_destroy(stream_);
+        stream_ = filtered;
+    }
+    ecal_filter_totals noiseTotals{};     // what the last removeNoise saw (events, off the grid, removed, kept)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {

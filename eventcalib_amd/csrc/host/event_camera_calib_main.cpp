@@ -197,6 +197,45 @@ int main(int argc, char **argv) {
                 if (hotMask[p]) std::fprintf(f, "%zu %zu %u %u\n", p % (size_t) width, p / (size_t) width, hotCounts[p], hotCounts[plane + p]);
             std::fclose(f);
         }
+        // NoiseFilter (a key of this build, optional): 1 = the events without a recent neighbour event — background activity — are
+        // taken out of the loaded stream on the device (ecal_stream_remove_noise on Camera.width x Camera.height), behind the hot
+        // pixels when both keys are set; one line on stdout, the options and the totals in saveDir/NoiseFilter.txt.  The rule's
+        // numbers, all optional: NoiseFilter_Dt (0.005 s), NoiseFilter_Radius (1), NoiseFilter_MinSupport (1), NoiseFilter_Self (0).
+        // Absent or 0: nothing changes
+        int wantNoiseFilter = 0;
+        fsSettings["NoiseFilter"] >> wantNoiseFilter;
+        if (wantNoiseFilter) {
+            ecal_noise_options opt;
+            ecal_noise_default_options(&opt);
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            int radius = (int) opt.radius, minSupport = (int) opt.min_support, self = (int) opt.include_self;
+            fsSettings["NoiseFilter_Dt"] >> opt.dt;
+            fsSettings["NoiseFilter_Radius"] >> radius;
+            fsSettings["NoiseFilter_MinSupport"] >> minSupport;
+            fsSettings["NoiseFilter_Self"] >> self;
+            opt.radius = (uint32_t) radius;   // (a negative number: refused by the library)
+            opt.min_support = (uint32_t) std::max(0, minSupport);
+            opt.include_self = (uint32_t) self;
+            ecal_filter_totals nt;
+            try {
+                container->removeNoise(&opt, &nt);
+            } catch (const std::exception &e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
+            std::printf("noise filter: %llu of %llu events removed\n", (unsigned long long) nt.n_removed, (unsigned long long) nt.n_events);
+            std::FILE *f = std::fopen((std::string(argv[3]) + "/NoiseFilter.txt").c_str(), "w");
+            if (!f) {
+                std::fprintf(stderr, "cannot write %s/NoiseFilter.txt\n", argv[3]);
+                return 3;
+            }
+            std::fprintf(f, "width %u\nheight %u\nradius %u\nmin_support %u\ninclude_self %u\ndt %.17g\n", opt.width, opt.height, opt.radius,
+                         opt.min_support, opt.include_self, opt.dt);
+            std::fprintf(f, "n_events %llu\nn_off_grid %llu\nn_removed %llu\nn_kept %llu\n", (unsigned long long) nt.n_events,
+                         (unsigned long long) nt.n_off_grid, (unsigned long long) nt.n_removed, (unsigned long long) nt.n_kept);
+            std::fclose(f);
+        }
     }
     while (!es.isEnd()) {                                    // :154-163
         if (customEnd && es.current().timeStamp() >= endTimeSetting) break;

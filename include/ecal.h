@@ -1563,6 +1563,51 @@ int ecal_stream_remove_hot_pixels(ecal_ctx *ctx, const ecal_stream *in, const ec
                                   ecal_stream **out, uint8_t *mask_out /*or NULL*/, uint32_t *counts_out /*or NULL*/,
                                   ecal_hot_pixel_info *info);
 
+/* ---- noise filter: the stream without the events that have no recent neighbour event (background activity) ----
+ * Background activity is isolated events spread over the whole array, with no neighbour firing near them in time.  The classic
+ * filter for it, stated so that it is exact, sequentially defined and reproducible in parallel; opt-in (nothing else in this header
+ * calls it).  New functionality: the reference has no such filter.  eventcalib_amd/csrc/noise_filter.hpp restates everything that
+ * decides for host and device; design/19_noise_filter.md has the reasoning, where the defaults come from and what was measured.
+ * The defaults come from the project's clean synthetic streams: no default has met a real recording.
+ *
+ * The rule: a walk over the records in stream order with a per-pixel `last` stamp and a `seen` flag, both empty at the start.  The
+ *   pixel of a record and "on the grid" are the hot-pixel section's.  An off-grid event is kept, updates nothing and supports nothing.
+ *   For an on-grid event i at pixel (X, Y) with stamp t_i (the f64 at record offset 0):
+ *     support = the number of pixels q in the square |dx| <= radius, |dy| <= radius around (X, Y), clipped to the sensor — the own
+ *       pixel only when include_self —, with seen[q] set and (t_i - last[q]) <= dt true in IEEE f64 (a NaN on either side: false);
+ *     event i is kept iff support >= min_support;
+ *     then last[(X, Y)] = t_i and seen[(X, Y)] = 1, whether event i was kept or not.
+ *   Support is polarity-blind.  "Earlier" means earlier in the stream: events with equal stamps support one another in file order,
+ *   and in an unsorted stream the most recent earlier event at q BY INDEX counts.  The first events of a stream have nothing before
+ *   them and are removed.  A lone hot pixel's events are removed when include_self == 0, but a hot pixel supports its neighbours'
+ *   noise: remove hot pixels first, then run this filter.
+ * Options: width, height 1 .. 4096; radius 1 .. 3; min_support >= 1; include_self 0 or 1; reserved 0; dt >= 0 and not NaN (+inf is
+ *   allowed), in the stream's own time unit — every ingest of this library produces seconds.  Anything else: ECAL_ERR_INVALID, and
+ *   ecal_last_error names the field.  opt NULL: the defaults.  More than 2^32-1 events: ECAL_ERR_RANGE.  n_events == 0 is valid.
+ * ecal_noise_verdict_host: HOST arrays, no context, no device: the walk as it is stated.  verdict [n_events]: 1 keep, 0 remove;
+ *   totals may be NULL; n_events = n_removed + n_kept, the off-grid events are among the kept.
+ * The _dev calls take any device memory of the caller's, whatever its alignment: nothing behind n_events * 25 bytes of d_events is
+ *   loaded, nothing behind n_events verdict bytes or the kept records is stored.  They zero their outputs on `stream`, enqueue and do
+ *   not synchronise.  The verdict depends on the input alone: every event is judged independently from an index of the stream by
+ *   pixel (a stable radix sort), byte for byte what the walk gives.
+ * ecal_noise_verdict_dev: d_verdict [n_events] u8; d_totals may be NULL.
+ * ecal_denoise_events_dev: the kept records, their own 25 bytes each, in input order into d_out (room for n_events records, not
+ *   overlapping d_events: ECAL_ERR_INVALID): a time-sorted stream stays time-sorted.  *d_count = the records written.
+ * ecal_stream_remove_noise: a new stream (*out; `in` is untouched) on the context's stream; waits for it.  totals (HOST) may be NULL. */
+typedef struct ecal_noise_options {
+    uint32_t width, height, radius, min_support, include_self, reserved;
+    double dt;
+} ecal_noise_options;
+void ecal_noise_default_options(ecal_noise_options *opt); /* 346 x 260, radius 1, min_support 1, include_self 0, dt 0.005 */
+int ecal_noise_verdict_host(const uint8_t *events /*HOST*/, uint64_t n_events, const ecal_noise_options *opt, uint8_t *verdict /*HOST [n_events]*/,
+                            ecal_filter_totals *totals /*or NULL*/);
+int ecal_noise_verdict_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const ecal_noise_options *opt, uint8_t *d_verdict,
+                           ecal_filter_totals *d_totals /*or NULL*/, void *stream);
+int ecal_denoise_events_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const ecal_noise_options *opt,
+                            uint8_t *d_out /*room for n_events records, not overlapping*/, uint32_t *d_count, ecal_filter_totals *d_totals,
+                            void *stream);
+int ecal_stream_remove_noise(ecal_ctx *ctx, const ecal_stream *in, const ecal_noise_options *opt, ecal_stream **out, ecal_filter_totals *totals);
+
 #ifdef __cplusplus
 }
 #endif
