@@ -65,10 +65,21 @@ inline double val(const Jet &x) { return x.a; }
 // The fisheye camera of BASELINE configs[4] — NEW functionality, no reference counterpart (the reference's solver throws for
 // anything but the radial model, EventCalibSpline.cpp:97-99): Kannala-Brandt in the inverse form of unDistort — the pixel's
 // distorted angle theta_d = r goes to the ray angle theta = r * poly(r^2) (the same five coefficients), and the ray's x, y
-// are scaled by tan(theta) / r instead of by poly.  Written as unDistort is, over T; sqrt has no derivative at r = 0 (the
-// product's code takes the limit there; the tests stay away from the exact centre).
+// are scaled by tan(theta) / r instead of by poly.  Written as unDistort is, over T.  sqrt has no derivative at r = 0 and
+// tan(r poly) / r is 0 / 0 there, so close to the principal point the scale is taken from its Taylor series in r2,
+//   tan(r poly) / r = poly + poly^3 r2 / 3 + 2 poly^5 r2^2 / 15 + 17 poly^7 r2^3 / 315 + ...,
+// evaluated on T so that every derivative comes out of the same dual numbers.  Below r2 = 1e-10 (a pixel within ~4e-3 px
+// of the centre at fx = 360) the first dropped term is 0.054 poly^7 r2^3 < 1e-31 of the value and 0.16 poly^7 r2^2 < 2e-21
+// of d / d r2: far under the rounding of a double.  Above it the quotient is taken as written: its derivative cancels to
+// ~1e-16 / r, and enters the ray multiplied by x or y <= r.
+constexpr double kFisheyeSeriesR2 = 1e-10;
+
 template <typename T>
 T fisheye_scale(const T &r2, const T &poly) {
+    if (val(r2) < kFisheyeSeriesR2) {
+        const T p2 = poly * poly, p3 = p2 * poly, p5 = p3 * p2;
+        return poly + T(1.0 / 3.0) * p3 * r2 + T(2.0 / 15.0) * p5 * r2 * r2;
+    }
     const T r = sqrt_(r2);
     return tan_(r * poly) / r;
 }
