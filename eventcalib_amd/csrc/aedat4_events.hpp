@@ -16,6 +16,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "event_record.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define ECAL_A4_HD __host__ __device__ __forceinline__
@@ -270,18 +271,6 @@ ECAL_A4_HD uint8_t a4_classify(const A4Event &e, const A4Filter &f, double *t_ou
     return t >= f.start_time ? A4_CLASS_KEEP : A4_CLASS_BEFORE_START;
 }
 
-ECAL_A4_HD void a4_put64(uint8_t *d, uint64_t u) {
-    for (int b = 0; b < 8; b++) d[b] = (uint8_t) (u >> (8 * b));
-}
-inline void a4_pack_record(uint8_t rec[25], double t, uint32_t xi, uint32_t yi, uint8_t pol) {
-    const double x = (double) xi, y = (double) yi;
-    uint64_t u;
-    memcpy(&u, &t, 8); a4_put64(rec, u);
-    memcpy(&u, &x, 8); a4_put64(rec + 8, u);
-    memcpy(&u, &y, 8); a4_put64(rec + 16, u);
-    rec[24] = pol;
-}
-
 // the whole second at or below a stamp: the automatic time base
 inline int64_t a4_whole_second(int64_t t_us) {
     int64_t q = t_us / 1000000;
@@ -318,7 +307,7 @@ template <class PutRecord> struct A4Sink {
             case A4_CLASS_STOP: stopped = true; c.n_after_end++; break;
             default: {
                 uint8_t rec[25];
-                a4_pack_record(rec, t, x, y, e.on);
+                ecal::pack_record(rec, t, (double) x, (double) y, e.on);
                 put(rec);
                 c.n_events++;
             }

@@ -17,6 +17,7 @@
 #include <stddef.h>
 #include <string.h>
 #include <string>
+#include "event_record.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define ECAL_AEDAT_HD __host__ __device__ __forceinline__
@@ -105,19 +106,6 @@ ECAL_AEDAT_HD uint8_t aedat_classify(const AedatEvent &e, const AedatFilter &f, 
     return t >= f.start_time ? AEDAT_CLASS_KEEP : AEDAT_CLASS_BEFORE_START;
 }
 
-// the packed 25-byte record: f64 t, f64 x, f64 y, u8 polarity (little endian)
-ECAL_AEDAT_HD void aedat_put64(uint8_t *d, uint64_t u) {
-    for (int b = 0; b < 8; b++) d[b] = (uint8_t) (u >> (8 * b));
-}
-inline void aedat_pack_record(uint8_t rec[25], double t, uint32_t xi, uint32_t yi, uint8_t pol) {
-    const double x = (double) xi, y = (double) yi;
-    uint64_t u;
-    memcpy(&u, &t, 8); aedat_put64(rec, u);
-    memcpy(&u, &x, 8); aedat_put64(rec + 8, u);
-    memcpy(&u, &y, 8); aedat_put64(rec + 16, u);
-    rec[24] = pol;
-}
-
 // the counters of one decode (ecal_aedat_info's, without the header's)
 struct AedatCounts {
     uint64_t n_raw_events, n_events, n_invalid, n_outside, n_negative, n_before_start, n_after_end, n_packets, n_other_packets,
@@ -148,7 +136,7 @@ template <class PutRecord> struct AedatSink {
             case AEDAT_CLASS_STOP: stopped = true; c.n_after_end++; break;
             default: {
                 uint8_t rec[25];
-                aedat_pack_record(rec, t, x, y, e.pol);
+                ecal::pack_record(rec, t, (double) x, (double) y, e.pol);
                 put(rec);
                 c.n_events++;
             }

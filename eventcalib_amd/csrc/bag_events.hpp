@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
+#include "event_record.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define ECAL_BAG_HD __host__ __device__ __forceinline__
@@ -97,19 +98,6 @@ ECAL_BAG_HD uint8_t bag_classify(const BagEvent &e, const BagFilter &f, double *
     return t >= f.start_time ? BAG_CLASS_KEEP : BAG_CLASS_BEFORE_START;
 }
 
-// the packed 25-byte record: f64 t, f64 x, f64 y, u8 polarity (little endian)
-ECAL_BAG_HD void bag_put64(uint8_t *d, uint64_t u) {
-    for (int b = 0; b < 8; b++) d[b] = (uint8_t) (u >> (8 * b));
-}
-inline void bag_pack_record(uint8_t rec[25], double t, uint32_t xi, uint32_t yi, uint8_t pol) {
-    const double x = (double) xi, y = (double) yi;
-    uint64_t u;
-    memcpy(&u, &t, 8); bag_put64(rec, u);
-    memcpy(&u, &x, 8); bag_put64(rec + 8, u);
-    memcpy(&u, &y, 8); bag_put64(rec + 16, u);
-    rec[24] = pol;
-}
-
 // the counters of one decode (ecal_bag_info's)
 struct BagCounts {
     uint64_t n_raw_events, n_events, n_outside, n_negative, n_before_start, n_after_end, n_messages, n_other_messages, n_chunks,
@@ -141,7 +129,7 @@ template <class PutRecord> struct BagSink {
             case BAG_CLASS_STOP: stopped = true; c.n_after_end++; break;
             default: {
                 uint8_t rec[25];
-                bag_pack_record(rec, t, x, y, e.pol);
+                ecal::pack_record(rec, t, (double) x, (double) y, e.pol);
                 put(rec);
                 c.n_events++;
             }

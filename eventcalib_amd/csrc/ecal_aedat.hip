@@ -19,10 +19,10 @@
 //                                     are packed into LDS and copied out with aligned 32-bit stores; the totals
 // "The stream ends here" is the test `slot < first offender` in pass 5, as in the raw ingest.  The host sees the counters once,
 // behind pass 5 (the file forms of 2.0 once more behind pass 1: the record buffer's size is a count).
+// The table scan, the bisection, the clipped load and the tails of passes 3 and 5 are ingest_blocks.hpp's, shared with the other
+// ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <algorithm>
-#include <thread>
 #include <vector>
 #include <math.h>
 #include <fcntl.h>
@@ -30,6 +30,7 @@
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
+#include "ingest_blocks.hpp"
 #include "aedat_events.hpp"
 
 namespace ecal {
@@ -54,25 +55,6 @@ struct AedatWords {
     unsigned long long n_events, n_invalid, n_outside, n_negative, n_before_start;
     unsigned long long bad_table;    // 3.1: packets of the table that do not lie within n_bytes
 };
-
-// the 32-bit word at the 4-byte aligned offset a, bytes at or behind n_bytes as zeros: nothing behind n_bytes is read
-__device__ __forceinline__ uint32_t ae_ld32(const uint8_t *__restrict__ payload, uint64_t a, uint64_t n_bytes) {
-    if (a + 4u <= n_bytes) return *reinterpret_cast<const uint32_t *>(payload + a);
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 3; j++)
-        if (a + j < n_bytes) v |= (uint32_t) payload[a + j] << (8u * j);
-    return v;
-}
-
-// the last packet in [lo, hi] whose first slot is not behind s (first[lo] <= s): it is not empty and holds s when s < first[hi + 1]
-__device__ __forceinline__ uint32_t ae_find_packet(const unsigned long long *__restrict__ first, uint32_t lo, uint32_t hi, uint64_t s) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-        if (first[mid] <= s) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
 
 // what a block kernel is given of the payload
 struct AedatSource {
@@ -105,9 +87,9 @@ template <int FMT> struct AeSlots {
                 // the block's packets by bisection (the same for every thread), the thread's inside them
                 const uint64_t b0 = (uint64_t) blockIdx.x * AE_BLOCK;
                 const uint64_t b1 = b0 + AE_BLOCK < src.n_slots ? b0 + AE_BLOCK - 1u : src.n_slots - 1u;
-                const uint32_t p_lo = ae_find_packet(src.first, 0u, src.n_packets - 1u, b0);
-                const uint32_t p_hi = ae_find_packet(src.first, p_lo, src.n_packets - 1u, b1);
-                uint32_t p = ae_find_packet(src.first, p_lo, p_hi, s0);
+                const uint32_t p_lo = table_find(src.first, 0u, src.n_packets - 1u, b0);
+                const uint32_t p_hi = table_find(src.first, p_lo, src.n_packets - 1u, b1);
+                uint32_t p = table_find(src.first, p_lo, p_hi, s0);
                 uint64_t p_first = src.first[p], p_next = src.first[p + 1], p_off = src.packets[p].offset;
                 uint32_t p_ovf = (uint32_t) src.packets[p].ts_overflow;
 #pragma unroll
@@ -115,7 +97,7 @@ template <int FMT> struct AeSlots {
                     if (j < n) {
                         const uint64_t s = s0 + j;
                         if (s >= p_next) {   // (packets of no events in between are stepped over by the search)
-                            p = ae_find_packet(src.first, p + 1u, p_hi, s);
+                            p = table_find(src.first, p + 1u, p_hi, s);
                             p_first = src.first[p];
                             p_next = src.first[p + 1];
                             p_off = src.packets[p].offset;
@@ -129,7 +111,7 @@ template <int FMT> struct AeSlots {
                             const uint32_t sh = 8u * (uint32_t) (off & 3u);
                             const uint32_t w0 = *reinterpret_cast<const uint32_t *>(src.payload + al);
                             const uint32_t w1 = *reinterpret_cast<const uint32_t *>(src.payload + al + 4u);
-                            const uint32_t w2 = sh ? ae_ld32(src.payload, al + 8u, src.n_bytes) : 0u;
+                            const uint32_t w2 = sh ? load32_clipped(src.payload, al + 8u, src.n_bytes) : 0u;
                             a[j] = (uint32_t) ((((uint64_t) w1 << 32) | w0) >> sh);
                             ts[j] = (uint32_t) ((((uint64_t) w2 << 32) | w1) >> sh);
                         }
@@ -172,41 +154,17 @@ template <int FMT> struct AeSlots {
     }
 };
 
-// first[p] = n_events of the packets before p, first[n] = all of them: every thread a run of consecutive packets, the runs' totals
-// scanned in the workgroup.  One workgroup.
+// first[p] = n_events of the packets before p, first[n] = all of them (table_exscan_1024); the table checked against n_bytes.
+// One workgroup.
 __global__ __launch_bounds__(1024) void aedat_packet_scan_kernel(const AedatPacket *__restrict__ packets, uint32_t n, uint64_t n_bytes,
                                                                  unsigned long long *__restrict__ first, AedatWords *__restrict__ w) {
-    __shared__ unsigned long long s_wave[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t per = ((uint64_t) n + 1023u) / 1024u;
-    const uint64_t lo = (uint64_t) threadIdx.x * per, p0 = lo < n ? lo : n, p1 = p0 + per < n ? p0 + per : n;
-    unsigned long long mine = 0, bad = 0;
-    for (uint64_t p = p0; p < p1; p++) {
+    const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) packets[p].n_events; }, first);
+    if (threadIdx.x == 0) w->n_slots = tot;
+    // (a pass of its own, strided: the table is read once more than the scan needs; the scan's value_of runs twice an entry)
+    unsigned long long bad = 0;
+    for (uint64_t p = threadIdx.x; p < n; p += 1024u) {
         const uint64_t off = packets[p].offset, len = (uint64_t) packets[p].n_events * 8u;
-        mine += packets[p].n_events;
         if (off > n_bytes || len > n_bytes - off) bad++;
-    }
-    unsigned long long inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0;
-    for (int x = 0; x < 16; x++) {
-        if (x < wave) pre += s_wave[x];
-        tot += s_wave[x];
-    }
-    unsigned long long run = pre + inc - mine;
-    for (uint64_t p = p0; p < p1; p++) {
-        first[p] = run;
-        run += packets[p].n_events;
-    }
-    if (threadIdx.x == 0) {
-        first[n] = tot;
-        w->n_slots = tot;
     }
     if (bad) atomicAdd(&w->bad_table, bad);
 }
@@ -252,7 +210,6 @@ template <int FMT>
 __global__ __launch_bounds__(AE_T) void aedat_verdict_kernel(AedatSource src, AedatFilter flt, uint32_t *__restrict__ blk_keep,
                                                              AedatWords *__restrict__ w) {
     __shared__ unsigned long long s_scan[AE_T / 64];
-    __shared__ uint32_t s_red[AE_T / 64][2];
     const int tid = threadIdx.x;
     const AeSlots<FMT> mine(src, s_scan, true);
     uint32_t keep = 0, stop = 0xFFFFFFFFu;   // (stop: a slot within the block)
@@ -267,25 +224,7 @@ __global__ __launch_bounds__(AE_T) void aedat_verdict_kernel(AedatSource src, Ae
             if (c == AEDAT_CLASS_STOP && at < stop) stop = at;
         }
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        keep += __shfl_xor(keep, d, 64);
-        const uint32_t v = __shfl_xor(stop, d, 64);
-        stop = v < stop ? v : stop;
-    }
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = keep;
-        s_red[tid >> 6][1] = stop;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t kc = 0, sm = 0xFFFFFFFFu;
-        for (int x = 0; x < AE_T / 64; x++) {
-            kc += s_red[x][0];
-            sm = s_red[x][1] < sm ? s_red[x][1] : sm;
-        }
-        blk_keep[blockIdx.x] = kc;
-        if (sm != 0xFFFFFFFFu) atomicMin(&w->first_stop, (unsigned long long) blockIdx.x * AE_BLOCK + sm);
-    }
+    block_keep_and_stop<AE_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * AE_BLOCK; });
 }
 
 // the kept events below the first offender, packed in LDS and copied out; the totals
@@ -324,21 +263,14 @@ __global__ __launch_bounds__(AE_T) void aedat_write_kernel(AedatSource src, cons
     }
     uint32_t kex, eb, ktot, tb;
     block_exscan_pair<AE_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    for (int d = 32; d > 0; d >>= 1)
-        for (int i = 0; i < 4; i++) drop[i] += __shfl_xor(drop[i], d, 64);
-    if ((tid & 63) == 0)
-        for (int i = 0; i < 4; i++)
-            if (drop[i]) atomicAdd(&s_cnt[i], drop[i]);
+    block_add_drops<4>(drop, s_cnt);
     // at most AE_BLOCK kept events: one chunk of LDS holds them all
     uint32_t k = kex;
 #pragma unroll
     for (uint32_t j = 0; j < AE_PER; j++) {
         if (kept_mask >> j & 1u) {
-            uint8_t *rec = s_rec + k * 25u;
-            aedat_put64(rec, (uint64_t) __double_as_longlong(kt[j]));
-            aedat_put64(rec + 8, (uint64_t) __double_as_longlong((double) kx[j]));
-            aedat_put64(rec + 16, (uint64_t) __double_as_longlong((double) ky[j]));
-            rec[24] = (uint8_t) (FMT == AEDAT_FORMAT_31 ? (mine.a[j] >> 1) & 1u : (mine.a[j] >> 11) & 1u);
+            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j],
+                        (uint8_t) (FMT == AEDAT_FORMAT_31 ? (mine.a[j] >> 1) & 1u : (mine.a[j] >> 11) & 1u));
             k++;
         }
     }
@@ -347,25 +279,7 @@ __global__ __launch_bounds__(AE_T) void aedat_write_kernel(AedatSource src, cons
         atomicAdd(tid == 0 ? &w->n_invalid : tid == 1 ? &w->n_outside : tid == 2 ? &w->n_negative : &w->n_before_start,
                   (unsigned long long) s_cnt[tid]);
     if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    // copy-out of the block's records, clipped to the capacity: bytes up to the first 4-byte boundary of the destination, whole
-    // words, the bytes behind them
-    const uint64_t first = blk_koff[blockIdx.x], room = capacity > first ? capacity - first : 0;
-    const uint32_t n_out = (uint64_t) ktot < room ? ktot : (uint32_t) room;
-    if (n_out) {
-        uint8_t *dst = events + first * 25u;
-        const uint32_t nb = n_out * 25u;
-        uint32_t head = (uint32_t) ((4u - ((uintptr_t) dst & 3u)) & 3u);
-        head = head < nb ? head : nb;
-        const uint32_t nw = (nb - head) / 4u;
-        if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-        for (uint32_t j = (uint32_t) tid; j < nw; j += AE_T) {
-            const uint32_t q = head + 4u * j;
-            const uint32_t v = (uint32_t) s_rec[q] | ((uint32_t) s_rec[q + 1] << 8) | ((uint32_t) s_rec[q + 2] << 16) | ((uint32_t) s_rec[q + 3] << 24);
-            *reinterpret_cast<uint32_t *>(dst + q) = v;
-        }
-        const uint32_t tail0 = head + 4u * nw;
-        if (tail0 + (uint32_t) tid < nb) dst[tail0 + tid] = s_rec[tail0 + tid];
-    }
+    block_copy_out<AE_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
 }
 
 }  // namespace ecal
@@ -386,8 +300,6 @@ extern "C" uint32_t ecal_aedat_block_events(int format) {
 
 namespace {
 
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
 void aedat_info_from_counts(ecal_aedat_info &I, const AedatCounts &c) {
     I.n_raw_events = c.n_raw_events;
     I.n_packets = c.n_packets;
@@ -400,29 +312,9 @@ int aedat_check_args(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, 
         ctx->last_error = "aedat ingest: no format (ECAL_AEDAT_3_1 or ECAL_AEDAT_2_0)";
         return ECAL_ERR_INVALID;
     }
-    if (n_bytes && !d_payload) {
-        ctx->last_error = "aedat ingest: null payload";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_payload & 15u) {
-        ctx->last_error = "aedat ingest: the payload must be 16-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    if (format == ECAL_AEDAT_3_1) {
-        if (n_packets && !d_packets) {
-            ctx->last_error = "aedat ingest: null packet table";
-            return ECAL_ERR_INVALID;
-        }
-        if ((uintptr_t) d_packets & 7u) {
-            ctx->last_error = "aedat ingest: the packet table must be 8-byte aligned";
-            return ECAL_ERR_INVALID;
-        }
-        if (n_packets > 0x7FFFFFFFull) {
-            ctx->last_error = "aedat ingest: more than 2^31-1 packets";
-            return ECAL_ERR_RANGE;
-        }
-    }
-    return ECAL_OK;
+    int rc = ecal_ingest_check_buffer(ctx, "aedat ingest", d_payload, n_bytes, 16, "payload");
+    if (!rc && format == ECAL_AEDAT_3_1) rc = ecal_ingest_check_buffer(ctx, "aedat ingest", d_packets, n_packets, 8, "packet table", nullptr, "packets");
+    return rc;
 }
 
 int aedat_check_options(ecal_ctx *ctx, const ecal_aedat_options &o) {
@@ -430,12 +322,6 @@ int aedat_check_options(ecal_ctx *ctx, const ecal_aedat_options &o) {
         ctx->last_error = "aedat ingest: flip_x / flip_y need width / height";
         return ECAL_ERR_INVALID;
     }
-    return ECAL_OK;
-}
-
-int aedat_wipe_words(ecal_ctx *ctx, AedatWords *d_w, hipStream_t st) {
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_w, 0, sizeof(AedatWords), st));
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(&d_w->first_stop, 0xFF, sizeof(unsigned long long), st));
     return ECAL_OK;
 }
 
@@ -479,15 +365,11 @@ int aedat_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, cons
              *koff = (uint32_t *) (base + o_koff);
     AedatWords *d_w = (AedatWords *) (base + o_words);
     const AedatFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
-    if ((rc = aedat_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(AedatWords), &d_w->first_stop, st))) return rc;
     tm.mark("start");
     AedatSource src{d_payload, n_bytes, bound, d_packets, first, (uint32_t) n_packets, win};
     AedatWords W;
-    auto fetch = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
+    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
     uint32_t nb = nb_max;
     if (V31) {
         hipLaunchKernelGGL(aedat_packet_scan_kernel, dim3(1), dim3(1024), 0, st, d_packets, (uint32_t) n_packets, n_bytes, first, d_w);
@@ -526,20 +408,10 @@ int aedat_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, cons
         }
     }
     if (own_events) {
-        hipError_t e = hipMalloc((void **) &d_events, (size_t) capacity * 25 + 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("aedat ingest: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-        *own_events = d_events;
+        if ((rc = ecal_ingest_alloc_records(ctx, "aedat ingest", capacity, own_events))) return rc;
+        d_events = *own_events;
     }
-    auto fail = [&](int code) {
-        if (own_events && *own_events) {
-            (void) hipFree(*own_events);
-            *own_events = nullptr;
-        }
-        return code;
-    };
+    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     auto launched = [&]() -> int {
         ECAL_HIP_TRY(ctx, hipGetLastError());
         return ECAL_OK;
@@ -653,61 +525,25 @@ int aedat_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat_optio
     }
     I.header_bytes = header_bytes;
     I.format = format;
-    const bool trace = ctx->sw.load_trace;
     std::vector<AedatPacket> table;
     AedatCounts c;
     memset(&c, 0, sizeof(c));
-    int index_rc = ECAL_OK;
-    std::string index_error;
-    double index_ms = 0;
-    std::thread indexer;
+    ecal_ingest_index_fn index;   // (2.0 has no packets to index)
     if (format == ECAL_AEDAT_3_1)
-        indexer = std::thread([&]() {
-            const auto t0 = std::chrono::steady_clock::now();
-            index_rc = aedat_index_file(fd, header_bytes, (uint64_t) sb.st_size, o.source, table, c, path, &index_error);
-            index_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        });
-    const auto t0 = std::chrono::steady_clock::now();
-    uint8_t *d_payload = nullptr;
-    uint64_t n_bytes = 0;
-    rc = hipSetDevice(ctx->device) == hipSuccess ? ECAL_OK : ECAL_ERR_HIP;
-    if (rc) ctx->last_error = "aedat ingest: hipSetDevice failed";
-    else rc = ecal_upload_file(ctx, "aedat ingest", path, header_bytes, &d_payload, &n_bytes);
-    const double upload_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (indexer.joinable()) indexer.join();
-    close(fd);
-    if (!rc && index_rc) {
-        rc = index_rc;
-        ctx->last_error = index_error;
-    }
-    if (rc) {
-        if (d_payload) (void) hipFree(d_payload);
-        return rc;
-    }
+        index = [&](std::string *error, const void **tab, size_t *tab_bytes) {
+            const int index_rc = aedat_index_file(fd, header_bytes, (uint64_t) sb.st_size, o.source, table, c, path, error);
+            *tab = table.data();
+            *tab_bytes = table.size() * sizeof(AedatPacket);
+            return index_rc;
+        };
+    ecal_ingest_upload up;
+    if ((rc = ecal_ingest_upload_indexed(ctx, "aedat", "aedat ingest", "host packet index", path, fd, header_bytes, ECAL_INGEST_ANY_SIZE, index, &up))) return rc;
     aedat_info_from_counts(I, c);
-    if (trace) {
-        if (format == ECAL_AEDAT_3_1) fprintf(stderr, "ecal aedat ingest: %-24s %.3f ms\n", "host packet index", index_ms);
-        fprintf(stderr, "ecal aedat ingest: %-24s %.3f ms\n", "file read + upload", upload_ms);
-        fprintf(stderr, "ecal aedat ingest: %-24s %.3f ms\n", "index beside upload",
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    }
-    AedatPacket *d_packets = nullptr;
-    if (!table.empty()) {
-        hipError_t e = hipMalloc((void **) &d_packets, table.size() * sizeof(AedatPacket));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_packets, table.data(), table.size() * sizeof(AedatPacket), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("aedat ingest: ") + hipGetErrorString(e);
-            if (d_packets) (void) hipFree(d_packets);
-            (void) hipFree(d_payload);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
     const uint64_t trailing = I.n_trailing_bytes;
-    rc = aedat_ingest_any(ctx, format, d_payload, n_bytes, d_packets, table.size(), c.n_raw_events, o, nullptr, 0, d_events, I, ctx->stream);
+    rc = aedat_ingest_any(ctx, format, up.d_file, up.n_bytes, (const AedatPacket *) up.d_table, table.size(), c.n_raw_events, o, nullptr, 0, d_events, I,
+                          ctx->stream);
     if (format == ECAL_AEDAT_3_1) I.n_trailing_bytes = trailing;
-    (void) hipStreamSynchronize(ctx->stream);   // (the table's upload reads host memory that goes out of scope here)
-    if (d_packets) (void) hipFree(d_packets);
-    (void) hipFree(d_payload);
+    ecal_ingest_free_upload(ctx, &up);
     return rc;
 }
 
@@ -756,7 +592,7 @@ extern "C" int ecal_aedat_count_events_dev(ecal_ctx *ctx, const uint8_t *d_paylo
     const size_t o_words = up16((size_t) (v31 ? n_packets + 1 : 0) * 8);
     if ((rc = ecal_ensure(ctx, buf, o_words + sizeof(AedatWords)))) return rc;
     AedatWords *d_w = (AedatWords *) (buf.as<uint8_t>() + o_words);
-    if ((rc = aedat_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(AedatWords), &d_w->first_stop, st))) return rc;
     if (v31) {
         hipLaunchKernelGGL(aedat_packet_scan_kernel, dim3(1), dim3(1024), 0, st, reinterpret_cast<const AedatPacket *>(d_packets),
                            (uint32_t) n_packets, n_bytes, buf.as<unsigned long long>(), d_w);
@@ -766,8 +602,7 @@ extern "C" int ecal_aedat_count_events_dev(ecal_ctx *ctx, const uint8_t *d_paylo
     }
     ECAL_HIP_TRY(ctx, hipGetLastError());
     AedatWords W;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-    ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st))) return rc;
     if (v31 && W.bad_table) {
         ctx->last_error = "aedat ingest: " + std::to_string(W.bad_table) + " packets of the table do not lie within the payload";
         return ECAL_ERR_INVALID;
@@ -808,14 +643,7 @@ extern "C" int ecal_stream_create_from_aedat_file(ecal_ctx *ctx, const char *pat
     const int rc = aedat_file_to_events(ctx, path, opt, &d_events, I);
     if (info) *info = I;
     if (rc) return rc;
-    if (!d_events) {   // no events: a stream of none
-        hipError_t e = hipMalloc((void **) &d_events, 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("ecal_stream_create_from_aedat_file: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
-    return ecal_stream_adopt(ctx, d_events, I.n_events, out);
+    return ecal_stream_from_events(ctx, "ecal_stream_create_from_aedat_file", d_events, I.n_events, out);
 }
 
 extern "C" int ecal_aedat_to_bin_file(ecal_ctx *ctx, const char *aedat_path, const char *bin_path, const ecal_aedat_options *opt,
@@ -824,10 +652,7 @@ extern "C" int ecal_aedat_to_bin_file(ecal_ctx *ctx, const char *aedat_path, con
     uint8_t *d_events = nullptr;
     ecal_aedat_info I;
     memset(&I, 0, sizeof(I));
-    int rc = aedat_file_to_events(ctx, aedat_path, opt, &d_events, I);
+    const int rc = aedat_file_to_events(ctx, aedat_path, opt, &d_events, I);
     if (info) *info = I;
-    if (rc) return rc;
-    rc = ecal_write_records_file(ctx, "ecal_aedat_to_bin_file", d_events, I.n_events, bin_path);
-    if (d_events) (void) hipFree(d_events);
-    return rc;
+    return rc ? rc : ecal_ingest_records_to_bin(ctx, "ecal_aedat_to_bin_file", d_events, I.n_events, bin_path);
 }

@@ -18,10 +18,10 @@
 //        7. ecal_scan_blocks            the blocks' first kept index
 //        8. aedat4_write_kernel         classed again; the kept events below the first offender packed into LDS and copied out
 // Compression NONE skips 1 - 3 and locates in the file itself.
+// The table scans, the bisection, the clipped load and the tails of passes 6 and 8 are ingest_blocks.hpp's, shared with the other
+// ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <algorithm>
-#include <thread>
 #include <vector>
 #include <math.h>
 #include <fcntl.h>
@@ -29,6 +29,7 @@
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
+#include "ingest_blocks.hpp"
 #include "aedat4_events.hpp"
 
 namespace ecal {
@@ -167,41 +168,19 @@ __global__ __launch_bounds__(64) void aedat4_frame_kernel(const uint8_t *__restr
     }
 }
 
-// span[k] = the padded sizes of the packets before k, span[n] = all of them; the plain sum of the sizes.  One workgroup.
+// span[k] = the padded sizes of the packets before k, span[n] = all of them (table_exscan_1024); the plain sum of the sizes.
+// One workgroup.
 __global__ __launch_bounds__(1024) void aedat4_span_scan_kernel(const unsigned long long *__restrict__ sizes, uint32_t n,
                                                                 unsigned long long *__restrict__ span, A4Words *__restrict__ w) {
-    __shared__ unsigned long long s_wave[16], s_plain[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t per = ((uint64_t) n + 1023u) / 1024u;
-    const uint64_t lo = (uint64_t) threadIdx.x * per, p0 = lo < n ? lo : n, p1 = p0 + per < n ? p0 + per : n;
-    unsigned long long mine = 0, plain = 0;
-    for (uint64_t p = p0; p < p1; p++) {
-        mine += (sizes[p] + 15ull) & ~15ull;
-        plain += sizes[p];
-    }
-    unsigned long long inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
+    __shared__ unsigned long long s_plain[16];
+    unsigned long long plain = 0;
+    for (uint64_t p = threadIdx.x; p < n; p += 1024u) plain += sizes[p];
     for (int d = 32; d > 0; d >>= 1) plain += __shfl_xor(plain, d, 64);
-    if (lane == 63) s_wave[wave] = inc;
-    if (lane == 0) s_plain[wave] = plain;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0, ptot = 0;
-    for (int x = 0; x < 16; x++) {
-        if (x < wave) pre += s_wave[x];
-        tot += s_wave[x];
-        ptot += s_plain[x];
-    }
-    unsigned long long run = pre + inc - mine;
-    for (uint64_t p = p0; p < p1; p++) {
-        span[p] = run;
-        run += (sizes[p] + 15ull) & ~15ull;
-    }
+    if ((threadIdx.x & 63) == 0) s_plain[threadIdx.x >> 6] = plain;
+    const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (sizes[p] + 15ull) & ~15ull; }, span);   // (its barrier orders s_plain too)
     if (threadIdx.x == 0) {
-        span[n] = tot;
+        unsigned long long ptot = 0;
+        for (int x = 0; x < 16; x++) ptot += s_plain[x];
         w->span_total = tot;
         w->n_inflated = ptot;
     }
@@ -236,55 +215,11 @@ __global__ __launch_bounds__(256) void aedat4_locate_kernel(const uint8_t *__res
     located[k] = A4Packet{base + first, count, 0u};
 }
 
-// first[p] = the events of the packets before p, first[n] = all of them.  One workgroup.
+// first[p] = the events of the packets before p, first[n] = all of them (table_exscan_1024).  One workgroup.
 __global__ __launch_bounds__(1024) void aedat4_packet_scan_kernel(const A4Packet *__restrict__ located, uint32_t n, unsigned long long *__restrict__ first,
                                                                   A4Words *__restrict__ w) {
-    __shared__ unsigned long long s_wave[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t per = ((uint64_t) n + 1023u) / 1024u;
-    const uint64_t lo = (uint64_t) threadIdx.x * per, p0 = lo < n ? lo : n, p1 = p0 + per < n ? p0 + per : n;
-    unsigned long long mine = 0;
-    for (uint64_t p = p0; p < p1; p++) mine += located[p].n_bytes;
-    unsigned long long inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0;
-    for (int x = 0; x < 16; x++) {
-        if (x < wave) pre += s_wave[x];
-        tot += s_wave[x];
-    }
-    unsigned long long run = pre + inc - mine;
-    for (uint64_t p = p0; p < p1; p++) {
-        first[p] = run;
-        run += located[p].n_bytes;
-    }
-    if (threadIdx.x == 0) {
-        first[n] = tot;
-        w->n_slots = tot;
-    }
-}
-
-// the 32-bit word at the 4-byte aligned offset a, bytes at or behind n as zeros: nothing behind n is read
-__device__ __forceinline__ uint32_t a4_ld32(const uint8_t *__restrict__ src, uint64_t a, uint64_t n) {
-    if (a + 4u <= n) return *reinterpret_cast<const uint32_t *>(src + a);
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 3; j++)
-        if (a + j < n) v |= (uint32_t) src[a + j] << (8u * j);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t a4_find_packet(const unsigned long long *__restrict__ first, uint32_t lo, uint32_t hi, uint64_t s) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-        if (first[mid] <= s) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
+    const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) located[p].n_bytes; }, first);
+    if (threadIdx.x == 0) w->n_slots = tot;
 }
 
 struct A4Source {
@@ -308,16 +243,16 @@ struct A4Slots {
         if (!n) return;
         const uint64_t b0 = (uint64_t) blockIdx.x * A4_BLOCK;
         const uint64_t b1 = b0 + A4_BLOCK < s.n_slots ? b0 + A4_BLOCK - 1u : s.n_slots - 1u;
-        const uint32_t p_lo = a4_find_packet(s.first, 0u, s.n_packets - 1u, b0);
-        const uint32_t p_hi = a4_find_packet(s.first, p_lo, s.n_packets - 1u, b1);
-        uint32_t p = a4_find_packet(s.first, p_lo, p_hi, s0);
+        const uint32_t p_lo = table_find(s.first, 0u, s.n_packets - 1u, b0);
+        const uint32_t p_hi = table_find(s.first, p_lo, s.n_packets - 1u, b1);
+        uint32_t p = table_find(s.first, p_lo, p_hi, s0);
         uint64_t p_first = s.first[p], p_next = s.first[p + 1], p_off = s.located[p].offset;
 #pragma unroll
         for (uint32_t j = 0; j < A4_PER; j++) {
             if (j < n) {
                 const uint64_t slot = s0 + j;
                 if (slot >= p_next) {   // (packets of no events in between are stepped over by the search)
-                    p = a4_find_packet(s.first, p + 1u, p_hi, slot);
+                    p = table_find(s.first, p + 1u, p_hi, slot);
                     p_first = s.first[p];
                     p_next = s.first[p + 1];
                     p_off = s.located[p].offset;
@@ -330,7 +265,7 @@ struct A4Slots {
                     uint32_t v[5];
 #pragma unroll
                     for (uint32_t q = 0; q < 4; q++) v[q] = *reinterpret_cast<const uint32_t *>(s.src + al + 4u * q);
-                    v[4] = sh ? a4_ld32(s.src, al + 16u, s.n_bytes) : 0u;
+                    v[4] = sh ? load32_clipped(s.src, al + 16u, s.n_bytes) : 0u;
 #pragma unroll
                     for (uint32_t q = 0; q < 4; q++) w[j][q] = (uint32_t) ((((uint64_t) v[q + 1] << 32) | v[q]) >> sh);
                 }
@@ -341,7 +276,6 @@ struct A4Slots {
 };
 
 __global__ __launch_bounds__(A4_T) void aedat4_verdict_kernel(A4Source src, A4Filter flt, uint32_t *__restrict__ blk_keep, A4Words *__restrict__ w) {
-    __shared__ uint32_t s_red[A4_T / 64][2];
     const int tid = threadIdx.x;
     const A4Slots mine(src);
     uint32_t keep = 0, stop = 0xFFFFFFFFu;
@@ -356,25 +290,7 @@ __global__ __launch_bounds__(A4_T) void aedat4_verdict_kernel(A4Source src, A4Fi
             if (c == A4_CLASS_STOP && at < stop) stop = at;
         }
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        keep += __shfl_xor(keep, d, 64);
-        const uint32_t v = __shfl_xor(stop, d, 64);
-        stop = v < stop ? v : stop;
-    }
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = keep;
-        s_red[tid >> 6][1] = stop;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t kc = 0, sm = 0xFFFFFFFFu;
-        for (int x = 0; x < A4_T / 64; x++) {
-            kc += s_red[x][0];
-            sm = s_red[x][1] < sm ? s_red[x][1] : sm;
-        }
-        blk_keep[blockIdx.x] = kc;
-        if (sm != 0xFFFFFFFFu) atomicMin(&w->first_stop, (unsigned long long) blockIdx.x * A4_BLOCK + sm);
-    }
+    block_keep_and_stop<A4_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * A4_BLOCK; });
 }
 
 __global__ __launch_bounds__(A4_T) void aedat4_write_kernel(A4Source src, const uint32_t *__restrict__ blk_koff, A4Filter flt,
@@ -413,20 +329,12 @@ __global__ __launch_bounds__(A4_T) void aedat4_write_kernel(A4Source src, const 
     }
     uint32_t kex, eb, ktot, tb;
     block_exscan_pair<A4_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    for (int d = 32; d > 0; d >>= 1)
-        for (int i = 0; i < 3; i++) drop[i] += __shfl_xor(drop[i], d, 64);
-    if ((tid & 63) == 0)
-        for (int i = 0; i < 3; i++)
-            if (drop[i]) atomicAdd(&s_cnt[i], drop[i]);
+    block_add_drops<3>(drop, s_cnt);
     uint32_t k = kex;
 #pragma unroll
     for (uint32_t j = 0; j < A4_PER; j++) {
         if (kept_mask >> j & 1u) {
-            uint8_t *rec = s_rec + k * 25u;
-            a4_put64(rec, (uint64_t) __double_as_longlong(kt[j]));
-            a4_put64(rec + 8, (uint64_t) __double_as_longlong((double) kx[j]));
-            a4_put64(rec + 16, (uint64_t) __double_as_longlong((double) ky[j]));
-            rec[24] = kp[j];
+            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j], kp[j]);
             k++;
         }
     }
@@ -434,24 +342,7 @@ __global__ __launch_bounds__(A4_T) void aedat4_write_kernel(A4Source src, const 
     if (tid < 3 && s_cnt[tid])
         atomicAdd(tid == 0 ? &w->n_outside : tid == 1 ? &w->n_negative : &w->n_before_start, (unsigned long long) s_cnt[tid]);
     if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    // copy-out of the block's records, clipped to the capacity: bytes up to the first 4-byte boundary, whole words, the bytes behind
-    const uint64_t first = blk_koff[blockIdx.x], room = capacity > first ? capacity - first : 0;
-    const uint32_t n_out = (uint64_t) ktot < room ? ktot : (uint32_t) room;
-    if (n_out) {
-        uint8_t *dst = events + first * 25u;
-        const uint32_t nb = n_out * 25u;
-        uint32_t head = (uint32_t) ((4u - ((uintptr_t) dst & 3u)) & 3u);
-        head = head < nb ? head : nb;
-        const uint32_t nw = (nb - head) / 4u;
-        if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-        for (uint32_t j = (uint32_t) tid; j < nw; j += A4_T) {
-            const uint32_t q = head + 4u * j;
-            const uint32_t v = (uint32_t) s_rec[q] | ((uint32_t) s_rec[q + 1] << 8) | ((uint32_t) s_rec[q + 2] << 16) | ((uint32_t) s_rec[q + 3] << 24);
-            *reinterpret_cast<uint32_t *>(dst + q) = v;
-        }
-        const uint32_t tail0 = head + 4u * nw;
-        if (tail0 + (uint32_t) tid < nb) dst[tail0 + tid] = s_rec[tail0 + tid];
-    }
+    block_copy_out<A4_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
 }
 
 }  // namespace ecal
@@ -472,8 +363,6 @@ extern "C" uint32_t ecal_aedat4_block_events(void) { return A4_BLOCK; }
 
 namespace {
 
-size_t a4_up16(size_t v) { return (v + 15) / 16 * 16; }
-
 void a4_info_from_counts(ecal_aedat4_info &I, const A4Counts &c) {
     I.n_packets = c.n_packets;
     I.n_other_packets = c.n_other_packets;
@@ -489,27 +378,8 @@ int a4_check_args(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const 
         ctx->last_error = "AEDAT 4 ingest: the compression must be given: ECAL_AEDAT4_NONE or ECAL_AEDAT4_LZ4";
         return ECAL_ERR_INVALID;
     }
-    if (n_bytes && !d_file) {
-        ctx->last_error = "AEDAT 4 ingest: null file";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_file & 15u) {
-        ctx->last_error = "AEDAT 4 ingest: the file must be 16-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    if (n_packets && !d_packets) {
-        ctx->last_error = "AEDAT 4 ingest: null packet table";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_packets & 7u) {
-        ctx->last_error = "AEDAT 4 ingest: the packet table must be 8-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    if (n_packets > 0x7FFFFFFFull) {
-        ctx->last_error = "AEDAT 4 ingest: more than 2^31-1 packets";
-        return ECAL_ERR_RANGE;
-    }
-    return ECAL_OK;
+    const int rc = ecal_ingest_check_buffer(ctx, "AEDAT 4 ingest", d_file, n_bytes, 16, "file");
+    return rc ? rc : ecal_ingest_check_buffer(ctx, "AEDAT 4 ingest", d_packets, n_packets, 8, "packet table", nullptr, "packets");
 }
 
 int a4_check_options(ecal_ctx *ctx, const ecal_aedat4_options &o) {
@@ -535,8 +405,8 @@ int a4_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const A4Pa
     if (!n_packets) return ECAL_OK;
     const uint32_t n = (uint32_t) n_packets;
     ecal_load_timer tm("aedat4", ctx->sw.load_trace, st);
-    const size_t o_sizes = 0, o_span = o_sizes + a4_up16((size_t) n * 8), o_loc = o_span + a4_up16(((size_t) n + 1) * 8),
-                 o_first = o_loc + a4_up16((size_t) n * 16), o_words = o_first + a4_up16(((size_t) n + 1) * 8), total = o_words + sizeof(A4Words);
+    const size_t o_sizes = 0, o_span = o_sizes + up16((size_t) n * 8), o_loc = o_span + up16(((size_t) n + 1) * 8),
+                 o_first = o_loc + up16((size_t) n * 16), o_words = o_first + up16(((size_t) n + 1) * 8), total = o_words + sizeof(A4Words);
     int rc;
     if ((rc = ecal_ensure(ctx, ctx->aedat4_tables, total))) return rc;
     uint8_t *base = ctx->aedat4_tables.as<uint8_t>();
@@ -544,16 +414,11 @@ int a4_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const A4Pa
                        *first = (unsigned long long *) (base + o_first);
     A4Packet *located = (A4Packet *) (base + o_loc);
     A4Words *d_w = (A4Words *) (base + o_words);
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_w, 0, sizeof(A4Words), st));
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(&d_w->first_stop, 0xFF, sizeof(unsigned long long), st));
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(A4Words), &d_w->first_stop, st))) return rc;
     ECAL_HIP_TRY(ctx, hipMemsetAsync(&d_w->bad_packet, 0xFF, sizeof(unsigned long long), st));
     tm.mark("start");
     A4Words W;
-    auto fetch = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
+    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
     auto launched = [&]() -> int {
         ECAL_HIP_TRY(ctx, hipGetLastError());
         return ECAL_OK;
@@ -619,24 +484,14 @@ int a4_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const A4Pa
     if (n_count) *n_count = W.n_slots;
     if (count_only || !W.n_slots) return ECAL_OK;
     const uint32_t nb = (uint32_t) ((W.n_slots + A4_BLOCK - 1) / A4_BLOCK);
-    if ((rc = ecal_ensure(ctx, ctx->aedat4_blocks, 2 * a4_up16(((size_t) nb + 1) * 4)))) return rc;
-    uint32_t *keep = ctx->aedat4_blocks.as<uint32_t>(), *koff = keep + a4_up16(((size_t) nb + 1) * 4) / 4;
+    if ((rc = ecal_ensure(ctx, ctx->aedat4_blocks, 2 * up16(((size_t) nb + 1) * 4)))) return rc;
+    uint32_t *keep = ctx->aedat4_blocks.as<uint32_t>(), *koff = keep + up16(((size_t) nb + 1) * 4) / 4;
     if (own_events) {
         capacity = W.n_slots;
-        hipError_t e = hipMalloc((void **) &d_events, (size_t) capacity * 25 + 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("AEDAT 4 ingest: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-        *own_events = d_events;
+        if ((rc = ecal_ingest_alloc_records(ctx, "AEDAT 4 ingest", capacity, own_events))) return rc;
+        d_events = *own_events;
     }
-    auto fail = [&](int code) {
-        if (own_events && *own_events) {
-            (void) hipFree(*own_events);
-            *own_events = nullptr;
-        }
-        return code;
-    };
+    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     const A4Filter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
     const A4Source src{lz4 ? scratch : d_file, lz4 ? scratch_bytes : n_bytes, W.n_slots, located, first, n};
     hipLaunchKernelGGL(aedat4_verdict_kernel, dim3(nb), dim3(A4_T), 0, st, src, flt, keep, d_w);
@@ -704,66 +559,32 @@ int a4_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat4_options
         ctx->last_error = err + " (" + path + ")";
         return rc;
     }
-    const bool trace = ctx->sw.load_trace;
     std::vector<A4Packet> table;
     A4Counts c;
     memset(&c, 0, sizeof(c));
     c.compression = h.compression;
-    int index_rc = ECAL_OK;
-    std::string index_error;
-    double index_ms = 0;
-    std::thread indexer([&]() {
-        const auto t0 = std::chrono::steady_clock::now();
+    ecal_ingest_upload up;
+    rc = ecal_ingest_upload_indexed(ctx, "aedat4", "AEDAT 4 ingest", "host packet index", path, fd, 0, ECAL_INGEST_ANY_SIZE, [&](std::string *error, const void **tab, size_t *tab_bytes) {
         std::vector<A4ChainPacket> chain;
-        index_rc = a4_walk_chain([&](uint64_t pos, uint8_t *raw) { return a4_pread(fd, raw, 8, pos); }, h.packets_begin, end,
-                                 [&](const A4ChainPacket &p) { chain.push_back(p); }, &c.n_trailing_bytes, &index_error);
+        int index_rc = a4_walk_chain([&](uint64_t pos, uint8_t *raw) { return a4_pread(fd, raw, 8, pos); }, h.packets_begin, end,
+                                     [&](const A4ChainPacket &p) { chain.push_back(p); }, &c.n_trailing_bytes, error);
         if (!index_rc)
             index_rc = a4_choose_stream(chain, h.compression, o.stream_id, [&](uint64_t off, uint32_t nb, std::vector<uint8_t> &out) {
                 out.resize(nb);
                 return nb == 0 || a4_pread(fd, out.data(), nb, off);
-            }, table, c, &index_error);
-        if (index_rc) index_error += std::string(" (") + path + ")";
-        index_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    });
-    const auto t0 = std::chrono::steady_clock::now();
-    uint8_t *d_file = nullptr;
-    uint64_t n_bytes = 0;
-    rc = hipSetDevice(ctx->device) == hipSuccess ? ECAL_OK : ECAL_ERR_HIP;
-    if (rc) ctx->last_error = "AEDAT 4 ingest: hipSetDevice failed";
-    else rc = ecal_upload_file(ctx, "AEDAT 4 ingest", path, 0, &d_file, &n_bytes);
-    const double upload_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    indexer.join();
-    close(fd);
-    if (!rc && index_rc) {
-        rc = index_rc;
-        ctx->last_error = index_error;
-    }
-    if (rc) {
-        if (d_file) (void) hipFree(d_file);
-        return rc;
-    }
+            }, table, c, error);
+        if (index_rc) *error += std::string(" (") + path + ")";
+        *tab = table.data();
+        *tab_bytes = table.size() * sizeof(A4Packet);
+        return index_rc;
+    }, &up);
+    if (rc) return rc;
     a4_info_from_counts(I, c);
-    if (trace) {
-        fprintf(stderr, "ecal aedat4 ingest: %-24s %.3f ms\n", "host packet index", index_ms);
-        fprintf(stderr, "ecal aedat4 ingest: %-24s %.3f ms\n", "file read + upload", upload_ms);
-        fprintf(stderr, "ecal aedat4 ingest: %-24s %.3f ms\n", "index beside upload",
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    }
     if (o.auto_time_base) o.time_base = c.first_stamp_us;
     I.time_base = o.time_base;
-    A4Packet *d_packets = nullptr;
-    if (!table.empty()) {
-        hipError_t e = hipMalloc((void **) &d_packets, table.size() * sizeof(A4Packet));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_packets, table.data(), table.size() * sizeof(A4Packet), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("AEDAT 4 ingest: ") + hipGetErrorString(e);
-            if (d_packets) (void) hipFree(d_packets);
-            (void) hipFree(d_file);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
     ecal_aedat4_info K = I;
-    rc = a4_ingest(ctx, d_file, n_bytes, d_packets, table.size(), h.compression, o, nullptr, 0, d_events, false, nullptr, K, ctx->stream);
+    rc = a4_ingest(ctx, up.d_file, up.n_bytes, (const A4Packet *) up.d_table, table.size(), h.compression, o, nullptr, 0, d_events, false, nullptr, K,
+                   ctx->stream);
     I.n_raw_events = K.n_raw_events;
     I.n_events = K.n_events;
     I.n_outside = K.n_outside;
@@ -771,9 +592,7 @@ int a4_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat4_options
     I.n_before_start = K.n_before_start;
     I.n_after_end = K.n_after_end;
     I.n_inflated_bytes = K.n_inflated_bytes;
-    (void) hipStreamSynchronize(ctx->stream);   // (the table's upload reads host memory that goes out of scope here)
-    if (d_packets) (void) hipFree(d_packets);
-    (void) hipFree(d_file);
+    ecal_ingest_free_upload(ctx, &up);
     return rc;
 }
 
@@ -873,14 +692,7 @@ extern "C" int ecal_stream_create_from_aedat4_file(ecal_ctx *ctx, const char *pa
     const int rc = a4_file_to_events(ctx, path, opt, &d_events, I);
     if (info) *info = I;
     if (rc) return rc;
-    if (!d_events) {   // no events: a stream of none
-        hipError_t e = hipMalloc((void **) &d_events, 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("ecal_stream_create_from_aedat4_file: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
-    return ecal_stream_adopt(ctx, d_events, I.n_events, out);
+    return ecal_stream_from_events(ctx, "ecal_stream_create_from_aedat4_file", d_events, I.n_events, out);
 }
 
 extern "C" int ecal_aedat4_to_bin_file(ecal_ctx *ctx, const char *aedat4_path, const char *bin_path, const ecal_aedat4_options *opt,
@@ -890,10 +702,7 @@ extern "C" int ecal_aedat4_to_bin_file(ecal_ctx *ctx, const char *aedat4_path, c
     ecal_aedat4_info I;
     memset(&I, 0, sizeof(I));
     I.stream_id = -1;
-    int rc = a4_file_to_events(ctx, aedat4_path, opt, &d_events, I);
+    const int rc = a4_file_to_events(ctx, aedat4_path, opt, &d_events, I);
     if (info) *info = I;
-    if (rc) return rc;
-    rc = ecal_write_records_file(ctx, "ecal_aedat4_to_bin_file", d_events, I.n_events, bin_path);
-    if (d_events) (void) hipFree(d_events);
-    return rc;
+    return rc ? rc : ecal_ingest_records_to_bin(ctx, "ecal_aedat4_to_bin_file", d_events, I.n_events, bin_path);
 }

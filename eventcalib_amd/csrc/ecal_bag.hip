@@ -16,11 +16,10 @@
 //                               packed into LDS and copied out with aligned 32-bit stores; the totals
 // "The stream ends here" is the test `slot < first offender` in pass 4, as in the raw and AEDAT ingests.  The host sees the counters
 // once, behind pass 4 (ecal_events_from_bag_dev once more behind pass 1: the grid is a count of the table).
-// The table scan and the staging code are copies of ecal_aedat.hip's (13-byte records, four words a record): that file is untouched.
+// The table scan, the bisection, the clipped load and the tails of passes 2 and 4 are ingest_blocks.hpp's, shared with the other
+// ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
-#include <chrono>
 #include <algorithm>
-#include <thread>
 #include <vector>
 #include <math.h>
 #include <fcntl.h>
@@ -28,6 +27,7 @@
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
+#include "ingest_blocks.hpp"
 #include "bag_events.hpp"
 
 namespace ecal {
@@ -49,25 +49,6 @@ struct BagWords {
     unsigned long long n_events, n_outside, n_negative, n_before_start;
     unsigned long long bad_table;    // messages of the table that do not lie within n_bytes
 };
-
-// the 32-bit word at the 4-byte aligned offset a, bytes at or behind n_bytes as zeros: nothing behind n_bytes is read
-__device__ __forceinline__ uint32_t bg_ld32(const uint8_t *__restrict__ file, uint64_t a, uint64_t n_bytes) {
-    if (a + 4u <= n_bytes) return *reinterpret_cast<const uint32_t *>(file + a);
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 3; j++)
-        if (a + j < n_bytes) v |= (uint32_t) file[a + j] << (8u * j);
-    return v;
-}
-
-// the last message in [lo, hi] whose first slot is not behind s (first[lo] <= s): it is not empty and holds s when s < first[hi + 1]
-__device__ __forceinline__ uint32_t bg_find_message(const unsigned long long *__restrict__ first, uint32_t lo, uint32_t hi, uint64_t s) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-        if (first[mid] <= s) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
 
 // what a block kernel is given of the file
 struct BagSource {
@@ -93,16 +74,16 @@ struct BgSlots {
             // the block's messages by bisection (the same for every thread), the thread's inside them
             const uint64_t b0 = (uint64_t) blockIdx.x * BG_BLOCK;
             const uint64_t b1 = b0 + BG_BLOCK < src.n_slots ? b0 + BG_BLOCK - 1u : src.n_slots - 1u;
-            const uint32_t m_lo = bg_find_message(src.first, 0u, src.n_messages - 1u, b0);
-            const uint32_t m_hi = bg_find_message(src.first, m_lo, src.n_messages - 1u, b1);
-            uint32_t m = bg_find_message(src.first, m_lo, m_hi, s0);
+            const uint32_t m_lo = table_find(src.first, 0u, src.n_messages - 1u, b0);
+            const uint32_t m_hi = table_find(src.first, m_lo, src.n_messages - 1u, b1);
+            uint32_t m = table_find(src.first, m_lo, m_hi, s0);
             uint64_t m_first = src.first[m], m_next = src.first[m + 1], m_off = src.messages[m].offset;
 #pragma unroll
             for (uint32_t j = 0; j < BG_PER; j++) {
                 if (j < n) {
                     const uint64_t s = s0 + j;
                     if (s >= m_next) {   // (messages of no events in between are stepped over by the search)
-                        m = bg_find_message(src.first, m + 1u, m_hi, s);
+                        m = table_find(src.first, m + 1u, m_hi, s);
                         m_first = src.first[m];
                         m_next = src.first[m + 1];
                         m_off = src.messages[m].offset;
@@ -116,7 +97,7 @@ struct BgSlots {
                         const uint32_t w0 = *reinterpret_cast<const uint32_t *>(src.file + al);
                         const uint32_t w1 = *reinterpret_cast<const uint32_t *>(src.file + al + 4u);
                         const uint32_t w2 = *reinterpret_cast<const uint32_t *>(src.file + al + 8u);
-                        const uint32_t w3 = bg_ld32(src.file, al + 12u, src.n_bytes);
+                        const uint32_t w3 = load32_clipped(src.file, al + 12u, src.n_bytes);
                         const uint32_t sh = 8u * (uint32_t) (off & 3u);
                         xy[j] = (uint32_t) ((((uint64_t) w1 << 32) | w0) >> sh);
                         secs[j] = (uint32_t) ((((uint64_t) w2 << 32) | w1) >> sh);
@@ -130,48 +111,23 @@ struct BgSlots {
     __device__ __forceinline__ BagEvent event(uint32_t j) const { return bag_event(xy[j], secs[j], nsecs[j], pol[j]); }
 };
 
-// first[m] = n_events of the messages before m, first[n] = all of them: every thread a run of consecutive messages, the runs' totals
-// scanned in the workgroup.  One workgroup.
+// first[m] = n_events of the messages before m, first[n] = all of them (table_exscan_1024); the table checked against n_bytes.
+// One workgroup.
 __global__ __launch_bounds__(1024) void bag_message_scan_kernel(const BagMessage *__restrict__ messages, uint32_t n, uint64_t n_bytes,
                                                                 unsigned long long *__restrict__ first, BagWords *__restrict__ w) {
-    __shared__ unsigned long long s_wave[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t per = ((uint64_t) n + 1023u) / 1024u;
-    const uint64_t lo = (uint64_t) threadIdx.x * per, p0 = lo < n ? lo : n, p1 = p0 + per < n ? p0 + per : n;
-    unsigned long long mine = 0, bad = 0;
-    for (uint64_t p = p0; p < p1; p++) {
+    const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) messages[p].n_events; }, first);
+    if (threadIdx.x == 0) w->n_slots = tot;
+    // (a pass of its own, strided: the table is read once more than the scan needs; the scan's value_of runs twice an entry)
+    unsigned long long bad = 0;
+    for (uint64_t p = threadIdx.x; p < n; p += 1024u) {
         const uint64_t off = messages[p].offset, len = (uint64_t) messages[p].n_events * BAG_EVENT_BYTES;
-        mine += messages[p].n_events;
         if (off > n_bytes || len > n_bytes - off) bad++;
-    }
-    unsigned long long inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned long long pre = 0, tot = 0;
-    for (int x = 0; x < 16; x++) {
-        if (x < wave) pre += s_wave[x];
-        tot += s_wave[x];
-    }
-    unsigned long long run = pre + inc - mine;
-    for (uint64_t p = p0; p < p1; p++) {
-        first[p] = run;
-        run += messages[p].n_events;
-    }
-    if (threadIdx.x == 0) {
-        first[n] = tot;
-        w->n_slots = tot;
     }
     if (bad) atomicAdd(&w->bad_table, bad);
 }
 
 // the class of every slot, the kept events per block, the first slot that reaches end_time
 __global__ __launch_bounds__(BG_T) void bag_verdict_kernel(BagSource src, BagFilter flt, uint32_t *__restrict__ blk_keep, BagWords *__restrict__ w) {
-    __shared__ uint32_t s_red[BG_T / 64][2];
     const int tid = threadIdx.x;
     const BgSlots mine(src);
     uint32_t keep = 0, stop = 0xFFFFFFFFu;   // (stop: a slot within the block)
@@ -186,25 +142,7 @@ __global__ __launch_bounds__(BG_T) void bag_verdict_kernel(BagSource src, BagFil
             if (c == BAG_CLASS_STOP && at < stop) stop = at;
         }
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        keep += __shfl_xor(keep, d, 64);
-        const uint32_t v = __shfl_xor(stop, d, 64);
-        stop = v < stop ? v : stop;
-    }
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = keep;
-        s_red[tid >> 6][1] = stop;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t kc = 0, sm = 0xFFFFFFFFu;
-        for (int x = 0; x < BG_T / 64; x++) {
-            kc += s_red[x][0];
-            sm = s_red[x][1] < sm ? s_red[x][1] : sm;
-        }
-        blk_keep[blockIdx.x] = kc;
-        if (sm != 0xFFFFFFFFu) atomicMin(&w->first_stop, (unsigned long long) blockIdx.x * BG_BLOCK + sm);
-    }
+    block_keep_and_stop<BG_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * BG_BLOCK; });
 }
 
 // the kept events below the first offender, packed in LDS and copied out; the totals
@@ -241,21 +179,13 @@ __global__ __launch_bounds__(BG_T) void bag_write_kernel(BagSource src, const ui
     }
     uint32_t kex, eb, ktot, tb;
     block_exscan_pair<BG_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    for (int d = 32; d > 0; d >>= 1)
-        for (int i = 0; i < 3; i++) drop[i] += __shfl_xor(drop[i], d, 64);
-    if ((tid & 63) == 0)
-        for (int i = 0; i < 3; i++)
-            if (drop[i]) atomicAdd(&s_cnt[i], drop[i]);
+    block_add_drops<3>(drop, s_cnt);
     // at most BG_BLOCK kept events: one chunk of LDS holds them all
     uint32_t k = kex;
 #pragma unroll
     for (uint32_t j = 0; j < BG_PER; j++) {
         if (kept_mask >> j & 1u) {
-            uint8_t *rec = s_rec + k * 25u;
-            bag_put64(rec, (uint64_t) __double_as_longlong(kt[j]));
-            bag_put64(rec + 8, (uint64_t) __double_as_longlong((double) kx[j]));
-            bag_put64(rec + 16, (uint64_t) __double_as_longlong((double) ky[j]));
-            rec[24] = (uint8_t) (mine.pol[j] != 0u ? 1u : 0u);
+            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j], (uint8_t) (mine.pol[j] != 0u ? 1u : 0u));
             k++;
         }
     }
@@ -263,25 +193,7 @@ __global__ __launch_bounds__(BG_T) void bag_write_kernel(BagSource src, const ui
     if (tid < 3 && s_cnt[tid])
         atomicAdd(tid == 0 ? &w->n_outside : tid == 1 ? &w->n_negative : &w->n_before_start, (unsigned long long) s_cnt[tid]);
     if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    // copy-out of the block's records, clipped to the capacity: bytes up to the first 4-byte boundary of the destination, whole
-    // words, the bytes behind them
-    const uint64_t first = blk_koff[blockIdx.x], room = capacity > first ? capacity - first : 0;
-    const uint32_t n_out = (uint64_t) ktot < room ? ktot : (uint32_t) room;
-    if (n_out) {
-        uint8_t *dst = events + first * 25u;
-        const uint32_t nb = n_out * 25u;
-        uint32_t head = (uint32_t) ((4u - ((uintptr_t) dst & 3u)) & 3u);
-        head = head < nb ? head : nb;
-        const uint32_t nw = (nb - head) / 4u;
-        if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-        for (uint32_t j = (uint32_t) tid; j < nw; j += BG_T) {
-            const uint32_t q = head + 4u * j;
-            const uint32_t v = (uint32_t) s_rec[q] | ((uint32_t) s_rec[q + 1] << 8) | ((uint32_t) s_rec[q + 2] << 16) | ((uint32_t) s_rec[q + 3] << 24);
-            *reinterpret_cast<uint32_t *>(dst + q) = v;
-        }
-        const uint32_t tail0 = head + 4u * nw;
-        if (tail0 + (uint32_t) tid < nb) dst[tail0 + tid] = s_rec[tail0 + tid];
-    }
+    block_copy_out<BG_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
 }
 
 }  // namespace ecal
@@ -298,8 +210,6 @@ extern "C" void ecal_bag_default_options(ecal_bag_options *opt) {
 extern "C" uint32_t ecal_bag_block_events(void) { return BG_BLOCK; }
 
 namespace {
-
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 BagChoice bag_choice(const ecal_bag_options *o) {
     BagChoice ch;
@@ -321,27 +231,8 @@ void bag_info_from_counts(ecal_bag_info &I, const BagCounts &c) {
 }
 
 int bag_check_args(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const void *d_messages, uint64_t n_messages) {
-    if (n_bytes && !d_file) {
-        ctx->last_error = "bag ingest: null file";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_file & 15u) {
-        ctx->last_error = "bag ingest: the file's bytes must be 16-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    if (n_messages && !d_messages) {
-        ctx->last_error = "bag ingest: null message table";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_messages & 7u) {
-        ctx->last_error = "bag ingest: the message table must be 8-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    if (n_messages > 0x7FFFFFFFull) {
-        ctx->last_error = "bag ingest: more than 2^31-1 messages";
-        return ECAL_ERR_RANGE;
-    }
-    return ECAL_OK;
+    const int rc = ecal_ingest_check_buffer(ctx, "bag ingest", d_file, n_bytes, 16, "file", "file's bytes");
+    return rc ? rc : ecal_ingest_check_buffer(ctx, "bag ingest", d_messages, n_messages, 8, "message table", nullptr, "messages");
 }
 
 int bag_check_options(ecal_ctx *ctx, const ecal_bag_options &o) {
@@ -349,12 +240,6 @@ int bag_check_options(ecal_ctx *ctx, const ecal_bag_options &o) {
         ctx->last_error = "bag ingest: flip_x / flip_y need width / height";
         return ECAL_ERR_INVALID;
     }
-    return ECAL_OK;
-}
-
-int bag_wipe_words(ecal_ctx *ctx, BagWords *d_w, hipStream_t st) {
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_w, 0, sizeof(BagWords), st));
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(&d_w->first_stop, 0xFF, sizeof(unsigned long long), st));
     return ECAL_OK;
 }
 
@@ -387,15 +272,11 @@ int bag_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const Bag
     uint32_t *keep = (uint32_t *) (base + o_keep), *koff = (uint32_t *) (base + o_koff);
     BagWords *d_w = (BagWords *) (base + o_words);
     const BagFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
-    if ((rc = bag_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(BagWords), &d_w->first_stop, st))) return rc;
     tm.mark("start");
     BagSource src{d_file, n_bytes, bound, d_messages, first, (uint32_t) n_messages};
     BagWords W;
-    auto fetch = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
+    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
     uint32_t nb = nb_max;
     hipLaunchKernelGGL(bag_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, first, d_w);
     ECAL_HIP_TRY(ctx, hipGetLastError());
@@ -422,20 +303,10 @@ int bag_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const Bag
     if (!src.n_slots) return ECAL_OK;
     if (own_events) {
         capacity = src.n_slots;
-        hipError_t e = hipMalloc((void **) &d_events, (size_t) capacity * 25 + 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("bag ingest: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-        *own_events = d_events;
+        if ((rc = ecal_ingest_alloc_records(ctx, "bag ingest", capacity, own_events))) return rc;
+        d_events = *own_events;
     }
-    auto fail = [&](int code) {
-        if (own_events && *own_events) {
-            (void) hipFree(*own_events);
-            *own_events = nullptr;
-        }
-        return code;
-    };
+    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     auto launched = [&]() -> int {
         ECAL_HIP_TRY(ctx, hipGetLastError());
         return ECAL_OK;
@@ -529,69 +400,28 @@ int bag_file_to_events(ecal_ctx *ctx, const char *path, const ecal_bag_options *
             return ECAL_ERR_INVALID;
         }
     }
-    const bool trace = ctx->sw.load_trace;
     std::vector<BagMessage> table;
     BagCounts c;
     memset(&c, 0, sizeof(c));
-    int index_rc = ECAL_OK;
-    std::string index_error;
-    double index_ms = 0;
-    std::thread indexer([&]() {   // nothing of the context is touched on this thread: index_error takes the text
-        const auto t0 = std::chrono::steady_clock::now();
+    ecal_ingest_upload up;
+    rc = ecal_ingest_upload_indexed(ctx, "bag", "bag ingest", "host message index", path, fd, 0, (uint64_t) sb.st_size, [&](std::string *error, const void **tab, size_t *tab_bytes) {
         BagFileReader rd{fd, (uint64_t) sb.st_size};
         std::string err;
-        index_rc = bag_walk(rd, (uint64_t) sb.st_size, choice, c, [&](const BagMessage &m) { table.push_back(m); }, &err);
-        if (index_rc) index_error = "bag ingest: " + err + " (" + path + ")";
-        index_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    });
-    const auto t0 = std::chrono::steady_clock::now();
-    uint8_t *d_file = nullptr;
-    uint64_t n_bytes = 0;
-    rc = hipSetDevice(ctx->device) == hipSuccess ? ECAL_OK : ECAL_ERR_HIP;
-    if (rc) ctx->last_error = "bag ingest: hipSetDevice failed";
-    else rc = ecal_upload_file(ctx, "bag ingest", path, 0, &d_file, &n_bytes);
-    const double upload_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    indexer.join();
-    close(fd);
-    if (!rc && index_rc) {
-        rc = index_rc;
-        ctx->last_error = index_error;
-    }
-    if (!rc && n_bytes != (uint64_t) sb.st_size) {
-        rc = ECAL_ERR_INVALID;
-        ctx->last_error = std::string("bag ingest: the file changed while it was read (") + path + ")";
-    }
-    if (rc) {
-        if (d_file) (void) hipFree(d_file);
-        return rc;
-    }
+        const int index_rc = bag_walk(rd, (uint64_t) sb.st_size, choice, c, [&](const BagMessage &m) { table.push_back(m); }, &err);
+        if (index_rc) *error = "bag ingest: " + err + " (" + path + ")";
+        *tab = table.data();
+        *tab_bytes = table.size() * sizeof(BagMessage);
+        return index_rc;
+    }, &up);
+    if (rc) return rc;
     bag_info_from_counts(I, c);
     o.time_base = bag_time_base(o.auto_time_base, o.time_base, c);
     I.time_base = o.time_base;
-    if (trace) {
-        fprintf(stderr, "ecal bag ingest: %-24s %.3f ms\n", "host message index", index_ms);
-        fprintf(stderr, "ecal bag ingest: %-24s %.3f ms\n", "file read + upload", upload_ms);
-        fprintf(stderr, "ecal bag ingest: %-24s %.3f ms\n", "index beside upload",
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    }
-    BagMessage *d_messages = nullptr;
-    if (!table.empty()) {
-        hipError_t e = hipMalloc((void **) &d_messages, table.size() * sizeof(BagMessage));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_messages, table.data(), table.size() * sizeof(BagMessage), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("bag ingest: ") + hipGetErrorString(e);
-            if (d_messages) (void) hipFree(d_messages);
-            (void) hipFree(d_file);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
     const ecal_bag_info walked = I;
-    rc = bag_ingest(ctx, d_file, n_bytes, d_messages, table.size(), c.n_raw_events, o, nullptr, 0, d_events, I, ctx->stream);
+    rc = bag_ingest(ctx, up.d_file, up.n_bytes, (const BagMessage *) up.d_table, table.size(), c.n_raw_events, o, nullptr, 0, d_events, I, ctx->stream);
     I.n_messages = walked.n_messages;
     I.n_raw_events = walked.n_raw_events;
-    (void) hipStreamSynchronize(ctx->stream);   // (the table's upload reads host memory that goes out of scope here)
-    if (d_messages) (void) hipFree(d_messages);
-    (void) hipFree(d_file);
+    ecal_ingest_free_upload(ctx, &up);
     return rc;
 }
 
@@ -625,13 +455,12 @@ extern "C" int ecal_bag_count_events_dev(ecal_ctx *ctx, const uint8_t *d_file, u
     const size_t o_words = up16((size_t) (n_messages + 1) * 8);
     if ((rc = ecal_ensure(ctx, buf, o_words + sizeof(BagWords)))) return rc;
     BagWords *d_w = (BagWords *) (buf.as<uint8_t>() + o_words);
-    if ((rc = bag_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(BagWords), &d_w->first_stop, st))) return rc;
     hipLaunchKernelGGL(bag_message_scan_kernel, dim3(1), dim3(1024), 0, st, reinterpret_cast<const BagMessage *>(d_messages), (uint32_t) n_messages,
                        n_bytes, buf.as<unsigned long long>(), d_w);
     ECAL_HIP_TRY(ctx, hipGetLastError());
     BagWords W;
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-    ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if ((rc = ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st))) return rc;
     if (W.bad_table) {
         ctx->last_error = "bag ingest: " + std::to_string(W.bad_table) + " messages of the table do not lie within the file";
         return ECAL_ERR_INVALID;
@@ -679,14 +508,7 @@ extern "C" int ecal_stream_create_from_bag_file(ecal_ctx *ctx, const char *path,
     const int rc = bag_file_to_events(ctx, path, opt, &d_events, I);
     if (info) *info = I;
     if (rc) return rc;
-    if (!d_events) {   // no events: a stream of none
-        hipError_t e = hipMalloc((void **) &d_events, 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("ecal_stream_create_from_bag_file: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
-    return ecal_stream_adopt(ctx, d_events, I.n_events, out);
+    return ecal_stream_from_events(ctx, "ecal_stream_create_from_bag_file", d_events, I.n_events, out);
 }
 
 extern "C" int ecal_bag_to_bin_file(ecal_ctx *ctx, const char *bag_path, const char *bin_path, const ecal_bag_options *opt, ecal_bag_info *info) {
@@ -694,10 +516,7 @@ extern "C" int ecal_bag_to_bin_file(ecal_ctx *ctx, const char *bag_path, const c
     uint8_t *d_events = nullptr;
     ecal_bag_info I;
     memset(&I, 0, sizeof(I));
-    int rc = bag_file_to_events(ctx, bag_path, opt, &d_events, I);
+    const int rc = bag_file_to_events(ctx, bag_path, opt, &d_events, I);
     if (info) *info = I;
-    if (rc) return rc;
-    rc = ecal_write_records_file(ctx, "ecal_bag_to_bin_file", d_events, I.n_events, bin_path);
-    if (d_events) (void) hipFree(d_events);
-    return rc;
+    return rc ? rc : ecal_ingest_records_to_bin(ctx, "ecal_bag_to_bin_file", d_events, I.n_events, bin_path);
 }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <string>
 #include <vector>
+#include <functional>
 #include <new>
 #include <stdio.h>
 #include <stdlib.h>
@@ -205,6 +206,39 @@ int ecal_stream_adopt(ecal_ctx *ctx, uint8_t *d_events, uint64_t n_events, ecal_
 int ecal_upload_file(ecal_ctx *ctx, const char *who, const char *path, uint64_t file_offset, uint8_t **d_out, uint64_t *n_bytes_out);
 // n_events packed records on the device into the file bin_path, through pinned staging, a chunk at a time (ecal_text.hip)
 int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path);
+// ---- what the ingests' host sides share (ecal_ingest_common.hip); `who` opens the error texts ("bag ingest") -------------------------
+inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+// An argument of a device form: "<who>: null <what>" when n != 0 and ptr is null, "<who>: the <what> must be <align>-byte aligned"
+// (what_aligned, when given, stands for what there), "<who>: more than 2^31-1 <plural>" when plural is given and n is above that.
+int ecal_ingest_check_buffer(ecal_ctx *ctx, const char *who, const void *ptr, uint64_t n, uint32_t align, const char *what,
+                             const char *what_aligned = nullptr, const char *plural = nullptr);
+// an ingest's counters in front of its first kernel: zeros, and all ones in *d_none (the minimum no slot has lowered: first_stop)
+int ecal_ingest_wipe_words(ecal_ctx *ctx, void *d_words, size_t bytes, unsigned long long *d_none, hipStream_t st);
+// ... and on the host, behind everything enqueued on st so far
+int ecal_ingest_fetch_words(ecal_ctx *ctx, void *words, const void *d_words, size_t bytes, hipStream_t st);
+// The record buffer an ingest allocates for its caller: *own = room for n records (the caller's to hipFree).  ecal_ingest_drop_records
+// frees it again on the way out of a failed ingest (own or *own may be null) and hands `code` through.
+int ecal_ingest_alloc_records(ecal_ctx *ctx, const char *who, uint64_t n, uint8_t **own);
+int ecal_ingest_drop_records(uint8_t **own, int code);
+// The middle of a file form: index(&error, &table, &table_bytes) — the format's walk over the open file, on a thread of its own, which
+// touches nothing of the context (null: no index, no table) — beside the upload of the file's bytes from file_offset on; fd is closed;
+// the two outcomes merged (the upload's error first); "ecal <tag> ingest:" lines for the index (index_label), the upload and both
+// together under ECAL_TRACE=load; the table uploaded on ctx->stream.  expect_bytes (ECAL_INGEST_ANY_SIZE: not asked): what the upload
+// must have read, else "<who>: the file changed while it was read (<path>)" in front of the trace lines and the table's upload.  On success the caller ends with ecal_ingest_free_upload, which
+// waits for the stream first (the table's upload reads the index's host memory); on an error nothing is left to free.
+struct ecal_ingest_upload {
+    uint8_t *d_file = nullptr;
+    uint64_t n_bytes = 0;
+    void *d_table = nullptr;
+};
+typedef std::function<int(std::string *error, const void **table, size_t *table_bytes)> ecal_ingest_index_fn;
+constexpr uint64_t ECAL_INGEST_ANY_SIZE = ~0ull;
+int ecal_ingest_upload_indexed(ecal_ctx *ctx, const char *tag, const char *who, const char *index_label, const char *path, int fd,
+                               uint64_t file_offset, uint64_t expect_bytes, const ecal_ingest_index_fn &index, ecal_ingest_upload *up);
+void ecal_ingest_free_upload(ecal_ctx *ctx, ecal_ingest_upload *up);
+// a file form's records as a stream (d_events null: no events, a stream of none), or written to bin_path and freed
+int ecal_stream_from_events(ecal_ctx *ctx, const char *who, uint8_t *d_events, uint64_t n_events, ecal_stream **out);
+int ecal_ingest_records_to_bin(ecal_ctx *ctx, const char *who, uint8_t *d_events, uint64_t n_events, const char *bin_path);
 // ECAL_TRACE=load: device time of an ingest's phases, "ecal <what> ingest: <phase> <ms>" lines on stderr when it goes out of scope
 struct ecal_load_timer {
     const char *what;

@@ -18,6 +18,8 @@
 // "The stream ends here" is the test `raw index < first offender` in pass 6: an event behind the offender may be counted as kept by
 // pass 4 — that only moves offsets of blocks that pass 6 writes nothing for.
 // The host sees the counters once, behind pass 6 (the file forms once more behind pass 1: the record buffer's size is a count).
+// The tails of passes 4 and 6 (kept count and first offender, drop counters, copy-out) are ingest_blocks.hpp's, shared with the other
+// ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <algorithm>
@@ -27,6 +29,7 @@
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
+#include "ingest_blocks.hpp"
 #include "raw_events.hpp"
 
 namespace ecal {
@@ -202,8 +205,6 @@ __global__ __launch_bounds__(RW_T) void raw_verdict_kernel(const uint8_t *__rest
                                                            RawFilter flt, uint32_t *__restrict__ blk_keep, RawWords *__restrict__ w) {
     __shared__ typename F::Summary s_wave[RW_T / 64];
     __shared__ unsigned long long s_scan[RW_T / 64];
-    __shared__ uint32_t s_red[RW_T / 64][2];
-    const int tid = threadIdx.x;
     const RwWords<F> mine(payload, n_words);
     typename F::Summary ex, total;
     rw_block_exscan<F, RW_T>(mine.summary(), s_wave, &ex, &total);
@@ -217,25 +218,7 @@ __global__ __launch_bounds__(RW_T) void raw_verdict_kernel(const uint8_t *__rest
         if (c == RAW_CLASS_STOP && at < stop) stop = at;
         at++;
     });
-    for (int d = 32; d > 0; d >>= 1) {
-        keep += __shfl_xor(keep, d, 64);
-        const uint32_t v = __shfl_xor(stop, d, 64);
-        stop = v < stop ? v : stop;
-    }
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = keep;
-        s_red[tid >> 6][1] = stop;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t kc = 0, sm = 0xFFFFFFFFu;
-        for (int x = 0; x < RW_T / 64; x++) {
-            kc += s_red[x][0];
-            sm = s_red[x][1] < sm ? s_red[x][1] : sm;
-        }
-        blk_keep[blockIdx.x] = kc;
-        if (sm != 0xFFFFFFFFu) atomicMin(&w->first_stop, (unsigned long long) blk_off[blockIdx.x] + sm);
-    }
+    block_keep_and_stop<RW_T>(keep, stop, blk_keep, &w->first_stop, [&] { return blk_off[blockIdx.x]; });
 }
 
 // the kept events below the first offender, packed in LDS a chunk at a time and copied out; the totals
@@ -275,11 +258,7 @@ __global__ __launch_bounds__(RW_T) void raw_write_kernel(const uint8_t *__restri
     });
     uint32_t kex, ktot;
     block_exscan_pair<RW_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    for (int d = 32; d > 0; d >>= 1)
-        for (int i = 0; i < 4; i++) drop[i] += __shfl_xor(drop[i], d, 64);
-    if ((tid & 63) == 0)
-        for (int i = 0; i < 4; i++)
-            if (drop[i]) atomicAdd(&s_cnt[i], drop[i]);
+    block_add_drops<4>(drop, s_cnt);
     __syncthreads();
     if (tid < 4 && s_cnt[tid])
         atomicAdd(tid == 0 ? &w->n_no_state : tid == 1 ? &w->n_outside : tid == 2 ? &w->n_negative : &w->n_before_start,
@@ -293,39 +272,14 @@ __global__ __launch_bounds__(RW_T) void raw_write_kernel(const uint8_t *__restri
                 if (r++ < lim) {
                     double t;
                     if (raw_classify(e, flt, &t) == RAW_CLASS_KEEP) {
-                        if (k >= c0 && k < c0 + RW_CHUNK) {
-                            uint8_t *rec = s_rec + (k - c0) * 25u;
-                            raw_put64(rec, (uint64_t) __double_as_longlong(t));
-                            raw_put64(rec + 8, (uint64_t) __double_as_longlong((double) e.x));
-                            raw_put64(rec + 16, (uint64_t) __double_as_longlong((double) e.y));
-                            rec[24] = e.pol;
-                        }
+                        if (k >= c0 && k < c0 + RW_CHUNK) pack_record(s_rec + (k - c0) * 25u, t, (double) e.x, (double) e.y, e.pol);
                         k++;
                     }
                 }
             });
         }
         __syncthreads();
-        // copy-out of the chunk's records, clipped to the capacity: bytes up to the first 4-byte boundary of the destination,
-        // whole words, the bytes behind them
-        const uint64_t first = at0 + c0, room = capacity > first ? capacity - first : 0;
-        const uint32_t n_chunk = ktot - c0 < RW_CHUNK ? ktot - c0 : RW_CHUNK;
-        const uint32_t n_out = (uint64_t) n_chunk < room ? n_chunk : (uint32_t) room;
-        if (n_out) {
-            uint8_t *dst = events + first * 25u;
-            const uint32_t nb = n_out * 25u;
-            uint32_t head = (uint32_t) ((4u - ((uintptr_t) dst & 3u)) & 3u);
-            head = head < nb ? head : nb;
-            const uint32_t nw = (nb - head) / 4u;
-            if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-            for (uint32_t j = (uint32_t) tid; j < nw; j += RW_T) {
-                const uint32_t q = head + 4u * j;
-                const uint32_t v = (uint32_t) s_rec[q] | ((uint32_t) s_rec[q + 1] << 8) | ((uint32_t) s_rec[q + 2] << 16) | ((uint32_t) s_rec[q + 3] << 24);
-                *reinterpret_cast<uint32_t *>(dst + q) = v;
-            }
-            const uint32_t tail0 = head + 4u * nw;
-            if (tail0 + (uint32_t) tid < nb) dst[tail0 + tid] = s_rec[tail0 + tid];
-        }
+        block_copy_out<RW_T>(s_rec, ktot - c0 < RW_CHUNK ? ktot - c0 : RW_CHUNK, events, at0 + c0, capacity);
         __syncthreads();
     }
 }
@@ -347,22 +301,12 @@ extern "C" uint32_t ecal_raw_block_words(int format) {
 
 namespace {
 
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
 int raw_check_args(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, int format) {
     if (format != ECAL_RAW_EVT2 && format != ECAL_RAW_EVT3) {
         ctx->last_error = "raw ingest: no format (ECAL_RAW_EVT2 or ECAL_RAW_EVT3)";
         return ECAL_ERR_INVALID;
     }
-    if (n_bytes && !d_payload) {
-        ctx->last_error = "raw ingest: null payload";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_payload & 15u) {
-        ctx->last_error = "raw ingest: the payload must be 16-byte aligned";
-        return ECAL_ERR_INVALID;
-    }
-    return ECAL_OK;
+    return ecal_ingest_check_buffer(ctx, "raw ingest", d_payload, n_bytes, 16, "payload");
 }
 
 int raw_block_count(ecal_ctx *ctx, uint64_t n_words, uint32_t block_words, uint32_t *nb) {
@@ -372,12 +316,6 @@ int raw_block_count(ecal_ctx *ctx, uint64_t n_words, uint32_t block_words, uint3
         return ECAL_ERR_RANGE;
     }
     *nb = (uint32_t) nb64;
-    return ECAL_OK;
-}
-
-int raw_wipe_words(ecal_ctx *ctx, RawWords *d_w, hipStream_t st) {
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_w, 0, sizeof(RawWords), st));
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(&d_w->first_stop, 0xFF, sizeof(unsigned long long), st));
     return ECAL_OK;
 }
 
@@ -391,7 +329,7 @@ template <class F> int raw_count(ecal_ctx *ctx, const uint8_t *d_payload, uint64
     ecal_devbuf words;
     if ((rc = ecal_ensure(ctx, words, sizeof(RawWords)))) return rc;
     RawWords *d_w = words.as<RawWords>();
-    if ((rc = raw_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(RawWords), &d_w->first_stop, st))) return rc;
     hipLaunchKernelGGL(raw_summary_kernel<F>, dim3(nb), dim3(RW_T), 0, st, d_payload, n_words, (typename F::Summary *) nullptr,
                        (uint32_t *) nullptr, d_w);
     ECAL_HIP_TRY(ctx, hipGetLastError());
@@ -429,7 +367,7 @@ int raw_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const 
              *koff = (uint32_t *) (base + o_koff);
     RawWords *d_w = (RawWords *) (base + o_words);
     const RawFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time};
-    if ((rc = raw_wipe_words(ctx, d_w, st))) return rc;
+    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(RawWords), &d_w->first_stop, st))) return rc;
     tm.mark("start");
     hipLaunchKernelGGL(raw_summary_kernel<F>, dim3(nb), dim3(RW_T), 0, st, d_payload, n_words, blk_sum, cnt, d_w);
     ECAL_HIP_TRY(ctx, hipGetLastError());
@@ -439,11 +377,7 @@ int raw_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const 
     ECAL_HIP_TRY(ctx, hipGetLastError());
     tm.mark("block scans");
     RawWords W;
-    auto fetch = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
+    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
     if (own_events) {   // the one count a size needs
         if ((rc = fetch())) return rc;
         if (W.n_raw > 0xFFFFFFFFull) {
@@ -452,20 +386,10 @@ int raw_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const 
             return ECAL_ERR_RANGE;
         }
         capacity = W.n_raw;
-        hipError_t e = hipMalloc((void **) &d_events, (size_t) capacity * 25 + 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("raw ingest: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-        *own_events = d_events;
+        if ((rc = ecal_ingest_alloc_records(ctx, "raw ingest", capacity, own_events))) return rc;
+        d_events = *own_events;
     }
-    auto fail = [&](int code) {
-        if (own_events && *own_events) {
-            (void) hipFree(*own_events);
-            *own_events = nullptr;
-        }
-        return code;
-    };
+    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     auto launched = [&]() -> int {
         ECAL_HIP_TRY(ctx, hipGetLastError());
         return ECAL_OK;
@@ -607,14 +531,7 @@ extern "C" int ecal_stream_create_from_raw_file(ecal_ctx *ctx, const char *path,
     const int rc = raw_file_to_events(ctx, path, opt, &d_events, I);
     if (info) *info = I;
     if (rc) return rc;
-    if (!d_events) {   // no words: a stream of no events
-        hipError_t e = hipMalloc((void **) &d_events, 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("ecal_stream_create_from_raw_file: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
-    return ecal_stream_adopt(ctx, d_events, I.n_events, out);
+    return ecal_stream_from_events(ctx, "ecal_stream_create_from_raw_file", d_events, I.n_events, out);
 }
 
 extern "C" int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const char *bin_path, const ecal_raw_options *opt,
@@ -623,10 +540,7 @@ extern "C" int ecal_raw_to_bin_file(ecal_ctx *ctx, const char *raw_path, const c
     uint8_t *d_events = nullptr;
     ecal_raw_info I;
     memset(&I, 0, sizeof(I));
-    int rc = raw_file_to_events(ctx, raw_path, opt, &d_events, I);
+    const int rc = raw_file_to_events(ctx, raw_path, opt, &d_events, I);
     if (info) *info = I;
-    if (rc) return rc;
-    rc = ecal_write_records_file(ctx, "ecal_raw_to_bin_file", d_events, I.n_events, bin_path);
-    if (d_events) (void) hipFree(d_events);
-    return rc;
+    return rc ? rc : ecal_ingest_records_to_bin(ctx, "ecal_raw_to_bin_file", d_events, I.n_events, bin_path);
 }

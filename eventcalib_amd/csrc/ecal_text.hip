@@ -20,6 +20,8 @@
 // pass 5 and counted by pass 6 — that only moves offsets of lines that pass 7 drops anyway.
 // The host sees the counters once, behind pass 7.  Only when the list of pass 4 is not empty it parses those lines (text and
 // line table come down for that), patches the arrays with one small kernel and runs passes 5 - 7 again.
+// The tail of pass 5 (kept count and first offender) and the copy-out of pass 7 are ingest_blocks.hpp's, shared with the other ingests;
+// the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <algorithm>
@@ -32,6 +34,8 @@
 #include "ecal_ctx.hpp"
 #include "block_utils.hpp"
 #include "text_events.hpp"
+#include "event_record.hpp"
+#include "ingest_blocks.hpp"
 
 namespace ecal {
 
@@ -211,7 +215,6 @@ __device__ __forceinline__ int64_t tx_base(const ecal_text_options &o, const Tex
 __global__ __launch_bounds__(TX_T) void text_verdict_kernel(const int64_t *__restrict__ stamp, const uint8_t *__restrict__ status,
                                                             uint64_t n_lines, ecal_text_options o, uint8_t *__restrict__ cls,
                                                             uint32_t *__restrict__ block_cnt, TextWords *__restrict__ w) {
-    __shared__ uint32_t s_red[TX_T / 64][2];
     const int tid = threadIdx.x;
     const uint64_t k = (uint64_t) blockIdx.x * TX_T + tid;
     const int64_t base = tx_base(o, w, stamp);
@@ -227,31 +230,8 @@ __global__ __launch_bounds__(TX_T) void text_verdict_kernel(const int64_t *__res
         }
         cls[k] = c;
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        keep += __shfl_xor(keep, d, 64);
-        const uint32_t v = __shfl_xor(stop, d, 64);
-        stop = v < stop ? v : stop;
-    }
-    if ((tid & 63) == 0) {
-        s_red[tid >> 6][0] = keep;
-        s_red[tid >> 6][1] = stop;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t kc = 0, sm = 0xFFFFFFFFu;
-        for (int x = 0; x < TX_T / 64; x++) {
-            kc += s_red[x][0];
-            sm = s_red[x][1] < sm ? s_red[x][1] : sm;
-        }
-        block_cnt[blockIdx.x] = kc;
-        if (sm != 0xFFFFFFFFu) atomicMin(&w->first_stop, (unsigned long long) sm);
-        if (blockIdx.x == 0) w->base = base;
-    }
-}
-
-__device__ __forceinline__ void tx_put64(uint8_t *d, uint64_t u) {
-#pragma unroll
-    for (int b = 0; b < 8; b++) d[b] = (uint8_t) (u >> (8 * b));
+    block_keep_and_stop<TX_T>(keep, stop, block_cnt, &w->first_stop, [] { return 0ull; });   // (stop is a line index, not one within the block)
+    if (blockIdx.x == 0 && tid == 0) w->base = base;
 }
 
 // the kept lines below the first offender, packed in LDS and copied out; the duplicated last record; the totals
@@ -281,10 +261,7 @@ __global__ __launch_bounds__(TX_T) void text_write_kernel(const uint8_t *__restr
     if (keep) {
         double t;
         (void) text_classify(stamp[k], base, o.time_magnitude, o.start_time, o.has_end_time, o.end_time, &t);
-        tx_put64(rec, (uint64_t) __double_as_longlong(t));
-        tx_put64(rec + 8, (uint64_t) __double_as_longlong(x[k]));
-        tx_put64(rec + 16, (uint64_t) __double_as_longlong(y[k]));
-        rec[24] = pol[k];
+        pack_record(rec, t, x[k], y[k], pol[k]);
 #pragma unroll
         for (int b = 0; b < 25; b++) s_rec[ex * 25u + b] = rec[b];
     }
@@ -318,24 +295,7 @@ __global__ __launch_bounds__(TX_T) void text_write_kernel(const uint8_t *__restr
         for (int q = 0; q < TX_T / 64; q++) v += s_cnt[q][tid];
         if (v) atomicAdd(tid == 0 ? &w->n_negative : tid == 1 ? &w->n_after_end : &w->n_before_start, (unsigned long long) v);
     }
-    // copy-out of the block's records, clipped to the capacity: bytes up to the first 4-byte boundary of the destination, whole
-    // words, the bytes behind them
-    const uint64_t room = capacity > at0 ? capacity - at0 : 0;
-    const uint32_t n_out = (uint64_t) tot < room ? tot : (uint32_t) room;
-    if (!n_out) return;
-    uint8_t *dst = events + at0 * 25u;
-    const uint32_t nb = n_out * 25u;
-    uint32_t head = (uint32_t) ((4u - ((uintptr_t) dst & 3u)) & 3u);
-    head = head < nb ? head : nb;
-    const uint32_t nw = (nb - head) / 4u;
-    if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-    for (uint32_t j = (uint32_t) tid; j < nw; j += TX_T) {
-        const uint32_t q = head + 4u * j;
-        const uint32_t v = (uint32_t) s_rec[q] | ((uint32_t) s_rec[q + 1] << 8) | ((uint32_t) s_rec[q + 2] << 16) | ((uint32_t) s_rec[q + 3] << 24);
-        *reinterpret_cast<uint32_t *>(dst + q) = v;
-    }
-    const uint32_t tail0 = head + 4u * nw;
-    if (tail0 + (uint32_t) tid < nb) dst[tail0 + tid] = s_rec[tail0 + tid];
+    block_copy_out<TX_T>(s_rec, tot, events, at0, capacity);
 }
 
 }  // namespace ecal
@@ -487,20 +447,10 @@ int text_ingest(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const ec
                        base + o_status,              base + o_cls};
     if (own_events) {
         capacity = n_lines + 1;
-        hipError_t e = hipMalloc((void **) &d_events, (size_t) capacity * 25 + 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("text ingest: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-        *own_events = d_events;
+        if ((rc = ecal_ingest_alloc_records(ctx, "text ingest", capacity, own_events))) return rc;
+        d_events = *own_events;
     }
-    auto fail = [&](int code) {
-        if (own_events && *own_events) {
-            (void) hipFree(*own_events);
-            *own_events = nullptr;
-        }
-        return code;
-    };
+    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     uint32_t *idx_cnt = idx.as<uint32_t>(), *idx_off = idx_cnt + nb_idx;
     if ((rc = ecal_scan_blocks(ctx, idx_cnt, nb_idx, idx_off, st))) return fail(rc);
     hipLaunchKernelGGL(text_offsets_kernel, dim3(nb_idx), dim3(TX_T), 0, st, d_text, n_bytes, n_bytes - 1, (const uint32_t *) idx_off, n_lines,
@@ -512,11 +462,7 @@ int text_ingest(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const ec
     if ((rc = text_filter_passes(ctx, d_text, n_bytes, n_lines, o, A, d_events, capacity, d_w, st))) return fail(rc);
     tm.mark("verdict, scan, write");
     TextWords W;
-    auto fetch = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&W, d_w, sizeof(W), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
+    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
     if ((rc = fetch())) return fail(rc);
     I.n_host_lines = W.n_host;
     if (W.n_host) {
@@ -548,18 +494,6 @@ int text_ingest(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, const ec
     if (I.n_events > capacity) {
         ctx->last_error = "text ingest: " + std::to_string(I.n_events) + " records, more than the capacity";
         return fail(ECAL_ERR_RANGE);
-    }
-    return ECAL_OK;
-}
-
-int text_check_args(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes) {
-    if (n_bytes && !d_text) {
-        ctx->last_error = "text ingest: null text";
-        return ECAL_ERR_INVALID;
-    }
-    if ((uintptr_t) d_text & 15u) {
-        ctx->last_error = "text ingest: the text must be 16-byte aligned";
-        return ECAL_ERR_INVALID;
     }
     return ECAL_OK;
 }
@@ -693,7 +627,7 @@ int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_eve
 
 extern "C" int ecal_text_count_lines_dev(ecal_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t *n_lines, void *stream) {
     if (!ctx || !n_lines) return ECAL_ERR_INVALID;
-    int rc = text_check_args(ctx, d_text, n_bytes);
+    int rc = ecal_ingest_check_buffer(ctx, "text ingest", d_text, n_bytes, 16, "text");
     if (rc) return rc;
     *n_lines = 0;
     if (!n_bytes) return ECAL_OK;
@@ -711,7 +645,7 @@ extern "C" int ecal_events_from_text_dev(ecal_ctx *ctx, const uint8_t *d_text, u
                                          uint8_t *d_events, uint64_t capacity, ecal_text_info *info, void *stream) {
     const ecal_range range__(ctx, "ecal_events_from_text");
     if (!ctx) return ECAL_ERR_INVALID;
-    const int rc = text_check_args(ctx, d_text, n_bytes);
+    const int rc = ecal_ingest_check_buffer(ctx, "text ingest", d_text, n_bytes, 16, "text");
     if (rc) return rc;
     if (capacity && !d_events) {
         ctx->last_error = "text ingest: null record buffer";
@@ -736,14 +670,7 @@ extern "C" int ecal_stream_create_from_text_file(ecal_ctx *ctx, const char *path
         ctx->last_error = "more than 2^32-1 events in one stream";
         return ECAL_ERR_RANGE;
     }
-    if (!d_events) {   // an empty file: a stream of no events
-        hipError_t e = hipMalloc((void **) &d_events, 16);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("ecal_stream_create_from_text_file: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-        }
-    }
-    return ecal_stream_adopt(ctx, d_events, I.n_events, out);
+    return ecal_stream_from_events(ctx, "ecal_stream_create_from_text_file", d_events, I.n_events, out);
 }
 
 extern "C" int ecal_text_to_bin_file(ecal_ctx *ctx, const char *txt_path, const char *bin_path, const ecal_text_options *opt,
@@ -752,10 +679,7 @@ extern "C" int ecal_text_to_bin_file(ecal_ctx *ctx, const char *txt_path, const 
     uint8_t *d_events = nullptr;
     ecal_text_info I;
     memset(&I, 0, sizeof(I));
-    int rc = text_file_to_events(ctx, txt_path, opt, &d_events, &I);
+    const int rc = text_file_to_events(ctx, txt_path, opt, &d_events, &I);
     if (info) *info = I;
-    if (rc) return rc;
-    rc = ecal_write_records_file(ctx, "ecal_text_to_bin_file", d_events, I.n_events, bin_path);
-    if (d_events) (void) hipFree(d_events);
-    return rc;
+    return rc ? rc : ecal_ingest_records_to_bin(ctx, "ecal_text_to_bin_file", d_events, I.n_events, bin_path);
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
+#include "event_record.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define ECAL_RAW_HD __host__ __device__ __forceinline__   // (not inlined, a summary passed by reference lives in scratch memory)
@@ -183,19 +184,6 @@ ECAL_RAW_HD uint8_t raw_classify(const RawEvent &e, const RawFilter &f, double *
     return t >= f.start_time ? RAW_CLASS_KEEP : RAW_CLASS_BEFORE_START;
 }
 
-// the packed 25-byte record: f64 t, f64 x, f64 y, u8 polarity (little endian)
-ECAL_RAW_HD void raw_put64(uint8_t *d, uint64_t u) {
-    for (int b = 0; b < 8; b++) d[b] = (uint8_t) (u >> (8 * b));
-}
-inline void raw_pack_record(uint8_t rec[25], double t, const RawEvent &e) {
-    const double x = (double) e.x, y = (double) e.y;
-    uint64_t u;
-    memcpy(&u, &t, 8); raw_put64(rec, u);
-    memcpy(&u, &x, 8); raw_put64(rec + 8, u);
-    memcpy(&u, &y, 8); raw_put64(rec + 16, u);
-    rec[24] = e.pol;
-}
-
 ECAL_RAW_HD uint32_t raw_load_word(const uint8_t *p, uint16_t) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8); }
 ECAL_RAW_HD uint32_t raw_load_word(const uint8_t *p, uint32_t) {
     return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24);
@@ -251,7 +239,7 @@ template <class PutRecord> struct RawSink {
             case RAW_CLASS_STOP: stopped = true; c.n_after_end++; break;
             default: {
                 uint8_t rec[25];
-                raw_pack_record(rec, t, e);
+                ecal::pack_record(rec, t, (double) e.x, (double) e.y, e.pol);
                 put(rec);
                 c.n_events++;
             }
