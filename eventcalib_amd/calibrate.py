@@ -157,11 +157,28 @@ def remove_noise(ctx, events, width=346, height=260, **options):
     return ctx.remove_noise(events, width=width, height=height, **options)
 
 
+def undistort_events(ctx, events, params, model=capi.CAMERA_RADIAL, out_k=None, opt=None, **options):
+    """The events as the ideal pinhole camera behind the solved one would have seen them: (events, info).  params: the solved
+    intrinsics fx fy cx cy k1..k5 (out["intrinsics"] of calibrate_stream: the INVERSE model, so a point is a closed-form polynomial);
+    model: capi.CAMERA_RADIAL or capi.CAMERA_FISHEYE; out_k: fx' fy' cx' cy' of the ideal camera (None: the solved fx fy cx cy, as
+    the reference's K_ * Xc).  options (capi.undistort_options): mode "subpixel" (default: a record carries u', v') or "pixel" (the
+    canvas pixel, std::round of u' + off_x, v' + off_y; events outside out_width x out_height go), sensor=(width, height) for the
+    reference's canvas.  Invalid events (the polynomial not positive, a fisheye angle past a right angle, NaN) are removed; a kept
+    record keeps its stamp and polarity byte; the order stays.  info: the options in force and the totals (n_events, n_invalid,
+    n_outside, n_kept).  The rule is include/ecal.h's ("undistortion"), every operation one IEEE f64 operation."""
+    cam = capi.undistort_camera(params, model, out_k=out_k)
+    o = opt if opt is not None else capi.undistort_options(**options)
+    out, tot = ctx.undistort_events(cam, events, o)
+    info = o.as_dict()
+    info.update({k: int(tot[k]) for k in capi.UNDISTORT_TOTALS.names})
+    return out, info
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
-                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None):
+                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -200,7 +217,11 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     the events that have no recent neighbour event (remove_noise below, on a width x height sensor) — after the hot pixels when both
     are on, since a hot pixel supports its neighbours' noise — and runs everything on the filtered stream; a stage of its own,
     `noise_filter`; out["noise_filter"] is the options in force and the filter's totals.  The defaults come from the clean synthetic
-    streams and have not met a real recording (design/19_noise_filter.md)."""
+    streams and have not met a real recording (design/19_noise_filter.md).
+    undistort (opt-in; None or False: nothing changes): True or a dict of options (undistort_events above: mode, sensor, out_width,
+    out_height, off_x, off_y, out_k) applies the solved camera to the stream the calibration ran on — a stage of its own,
+    `undistort`; out["undistorted_events"] is the uint8 CUDA tensor of the kept records, out["undistort"] the options in force and
+    the totals (design/20_undistort.md)."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -434,6 +455,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
                      "final_cost": float(summ.final_cost), "seconds": float(summ.seconds),
                      "jacobian_evaluations": int(summ.jacobian_evaluations), "unknowns": int(9 + 6 * seg_cp_off[-1])}
     out["intrinsics"] = x[:9].copy()
+    if undistort is not None and undistort is not False:
+        out["undistorted_events"], out["undistort"] = undistort_events(ctx, events, x[:9], model,
+                                                                       **(dict(undistort) if isinstance(undistort, dict) else {}))
+        mark("undistort")
     # updateMap (:253-317): keyframe poses re-read from the optimised splines
     n_cp = seg_cp_off[-1]
     q_all, t_all = x[9:9 + 4 * n_cp].reshape(n_cp, 4), x[9 + 4 * n_cp:].reshape(n_cp, 3)

@@ -17,7 +17,7 @@ EXPORTED_SYMBOLS = [
     "ecal_comm_unique_id", "ecal_comm_init", "ecal_comm_destroy", "ecal_comm_size", "ecal_comm_rank", "ecal_comm_allreduce_sum_dev", "ecal_comm_allreduce",
     "ecal_circle_radius_threshold", "ecal_extract_batch_dev", "ecal_extract_batch_ordered_dev", "ecal_extract_batch_exact_dev", "ecal_cluster_order_list_dev", "ecal_set_median_ties", "ecal_set_tail_mode", "ecal_get_tail_mode", "ecal_calibrate_fisheye_views", "ecal_set_profile_ranges",
     "ecal_get_median_ties", "ecal_detect_fused_dev", "ecal_cluster_order_dev", "ecal_cluster_order",
-    "ecal_stream_create", "ecal_stream_destroy", "ecal_stream_size", "ecal_stream_data", "ecal_detect_batch", "ecal_copy_dev",
+    "ecal_stream_create", "ecal_stream_destroy", "ecal_stream_size", "ecal_stream_data", "ecal_stream_to_bin_file", "ecal_detect_batch", "ecal_copy_dev",
     "ecal_grid_order_dev", "ecal_grid_order", "ecal_associate_dev", "ecal_associate", "ecal_pin_host", "ecal_unpin_host",
     "ecal_detect_stream_tiled", "ecal_gather_features_dev", "ecal_detect_pass", "ecal_detect_keyframes", "ecal_detect_keyframes_sharded", "ecal_detect_keyframes_cap_hint", "ecal_detect_keyframes_cap_hint_dev", "ecal_stream_create_from_file", "ecal_stream_times", "ecal_rectify_batch_dev", "ecal_rectify_batch",
     "ecal_solver_create", "ecal_solver_destroy", "ecal_solver_param_size", "ecal_solver_normal_size",
@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
     "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
     "ecal_noise_default_options", "ecal_noise_verdict_host", "ecal_noise_verdict_dev", "ecal_denoise_events_dev", "ecal_stream_remove_noise",
+    "ecal_undistort_camera_from_params", "ecal_undistort_reference_canvas", "ecal_undistort_camera_error", "ecal_undistort_options_error", "ecal_undistort_round_half_away", "ecal_undistort_points_host", "ecal_undistort_points_dev", "ecal_undistort_events_dev", "ecal_stream_undistort", "ecal_undistorted_frames_dev", "ecal_stream_undistorted_frames",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -422,6 +423,115 @@ def noise_verdict_host(events, **options):
     if st != 0:
         raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_noise_verdict_host (" + NOISE_OPTIONS_RULE + ")")
     return verdict, tot[0]
+
+
+CAMERA_RADIAL, CAMERA_FISHEYE = 0, 1          # ECAL_CAMERA_RADIAL / _FISHEYE
+UNDISTORT_SUBPIXEL, UNDISTORT_PIXEL = 0, 1    # ECAL_UNDISTORT_SUBPIXEL / _PIXEL
+UNDISTORT_TOTALS = np.dtype([("n_events", np.uint64), ("n_invalid", np.uint64), ("n_outside", np.uint64), ("n_kept", np.uint64)])
+UNDISTORT_FRAME_TOTALS = np.dtype([("n_pos", np.uint32), ("n_neg", np.uint32), ("n_invalid", np.uint32), ("n_outside", np.uint32)])
+
+
+class UndistortCamera(ctypes.Structure):
+    """ecal_undistort_camera (include/ecal.h, undistortion)."""
+    _fields_ = [("model", ctypes.c_int), ("reserved", ctypes.c_int), ("intr", ctypes.c_double * 9), ("out_k", ctypes.c_double * 4)]
+
+
+class UndistortOptions(ctypes.Structure):
+    """ecal_undistort_options (include/ecal.h, undistortion)."""
+    _fields_ = [("mode", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"mode": int(self.mode), "out_width": int(self.out_width), "out_height": int(self.out_height),
+                "off_x": float(self.off_x), "off_y": float(self.off_y)}
+
+
+def undistort_camera(params, model=CAMERA_RADIAL, out_k=None, reserved=0):
+    """ecal_undistort_camera from the head of the solver's parameter vector (fx fy cx cy k1..k5; ecal_undistort_camera_from_params:
+    out_k = fx fy cx cy, as the reference's K_ * Xc) or with another ideal camera out_k = (fx', fy', cx', cy').  An UndistortCamera
+    is handed through."""
+    if isinstance(params, UndistortCamera):
+        return params
+    L = load_library()
+    L.ecal_undistort_camera_from_params.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(UndistortCamera)]
+    L.ecal_undistort_camera_from_params.restype = None
+    p = np.ascontiguousarray(np.asarray(params, np.float64).ravel()[:9])
+    if p.size != 9:
+        raise ValueError("fx fy cx cy k1..k5: nine numbers")
+    cam = UndistortCamera()
+    L.ecal_undistort_camera_from_params(int(model), p.ctypes.data, ctypes.byref(cam))
+    if out_k is not None:
+        cam.out_k[:] = [float(v) for v in out_k]
+    cam.reserved = int(reserved)
+    return cam
+
+
+def undistort_reference_canvas(width, height):
+    """ecal_undistort_reference_canvas: PIXEL options with the reference's canvas, round(1.2 * size), and offsets, size * 0.1"""
+    L = load_library()
+    L.ecal_undistort_reference_canvas.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(UndistortOptions)]
+    L.ecal_undistort_reference_canvas.restype = None
+    o = UndistortOptions()
+    L.ecal_undistort_reference_canvas(int(width), int(height), ctypes.byref(o))
+    return o
+
+
+def undistort_options(mode=None, out_width=None, out_height=None, off_x=None, off_y=None, reserved=None, sensor=None):
+    """ecal_undistort_options: SUBPIXEL by default; sensor=(width, height) starts from the reference canvas (PIXEL); "pixel" /
+    "subpixel" or the number for mode.  An UndistortOptions is handed through."""
+    if isinstance(mode, UndistortOptions):
+        return mode
+    o = undistort_reference_canvas(*sensor) if sensor is not None else UndistortOptions()
+    if mode is not None:
+        o.mode = {"subpixel": UNDISTORT_SUBPIXEL, "pixel": UNDISTORT_PIXEL}[mode.lower()] if isinstance(mode, str) else int(mode)
+    for name, value in (("out_width", out_width), ("out_height", out_height), ("reserved", reserved)):
+        if value is not None:
+            setattr(o, name, int(value))
+    if off_x is not None:
+        o.off_x = float(off_x)
+    if off_y is not None:
+        o.off_y = float(off_y)
+    return o
+
+
+def undistort_camera_error(cam):
+    """ecal_undistort_camera_error: None, or the text that names the refused field"""
+    L = load_library()
+    L.ecal_undistort_camera_error.argtypes, L.ecal_undistort_camera_error.restype = [ctypes.POINTER(UndistortCamera)], ctypes.c_char_p
+    r = L.ecal_undistort_camera_error(ctypes.byref(cam))
+    return r.decode() if r else None
+
+
+def undistort_options_error(opt):
+    """ecal_undistort_options_error: None, or the text that names the refused field"""
+    L = load_library()
+    L.ecal_undistort_options_error.argtypes, L.ecal_undistort_options_error.restype = [ctypes.POINTER(UndistortOptions)], ctypes.c_char_p
+    r = L.ecal_undistort_options_error(ctypes.byref(opt))
+    return r.decode() if r else None
+
+
+def undistort_round_half_away(a):
+    """ecal_undistort_round_half_away: std::round as the library spells it"""
+    L = load_library()
+    L.ecal_undistort_round_half_away.argtypes, L.ecal_undistort_round_half_away.restype = [ctypes.c_double], ctypes.c_double
+    return float(L.ecal_undistort_round_half_away(float(a)))
+
+
+def undistort_points_host(cam, uv):
+    """ecal_undistort_points_host (host arrays; no context, no device): uv [n, 2] -> (out [n, 2] float64 with 0, 0 where invalid,
+    flag uint8 [n]: 0 valid, 1 invalid).  cam: an UndistortCamera (undistort_camera)."""
+    L = load_library()
+    L.ecal_undistort_points_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    L.ecal_undistort_points_host.restype = ctypes.c_int
+    uv = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
+    n = uv.shape[0]
+    out = np.zeros((n, 2), np.float64)
+    flag = np.zeros(n, np.uint8)
+    st = L.ecal_undistort_points_host(ctypes.byref(cam), uv.ctypes.data if n else None, n, out.ctypes.data if n else None,
+                                      flag.ctypes.data if n else None)
+    if st != 0:
+        raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_undistort_points_host: " + (undistort_camera_error(cam) or "null pointer"))
+    return out, flag
 
 
 def _ptr(a):
@@ -1418,6 +1528,120 @@ class Context:
             L.ecal_stream_destroy(h_in)
         out, _, _ = self._stream_records(h_out)
         return out, {k: int(tot[0][k]) for k in FILTER_TOTALS.names}
+
+    # ---- undistortion (ecal_undistort_points_dev, ecal_undistort_events_dev, the frames and the stream calls) ----
+    def undistort_points_dev(self, cam, d_events, n_events, d_uv, d_flag, stream=0):
+        """ecal_undistort_points_dev: raw device pointers; d_uv [n_events][2] f64, d_flag [n_events] u8; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_undistort_points_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), vp, ctypes.c_uint64, vp, vp, vp]
+        L.ecal_undistort_points_dev.restype = ctypes.c_int
+        self._check(L.ecal_undistort_points_dev(self._h, ctypes.byref(cam), d_events, int(n_events), d_uv, d_flag, stream))
+
+    def undistort_events_dev(self, cam, opt, d_events, n_events, d_out, d_count, d_totals=None, stream=0):
+        """ecal_undistort_events_dev: raw device pointers; opt an UndistortOptions or None (SUBPIXEL), d_out room for n_events records
+        (not overlapping the events), d_count one u32, d_totals UNDISTORT_TOTALS or None; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_undistort_events_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp, ctypes.c_uint64, vp, vp, vp, vp]
+        L.ecal_undistort_events_dev.restype = ctypes.c_int
+        self._check(L.ecal_undistort_events_dev(self._h, ctypes.byref(cam), ctypes.byref(opt) if opt is not None else None, d_events,
+                                                int(n_events), d_out, d_count, d_totals, stream))
+
+    def undistorted_frames_dev(self, cam, opt, d_xy, pk, d_seg_off, d_seg_cnt, S, d_rgb, d_frame_totals=None, stream=0):
+        """ecal_undistorted_frames_dev: raw device pointers; pk a PackedPoints or None (doubles), d_rgb [S][out_height][out_width][3]
+        u8, d_frame_totals [S] UNDISTORT_FRAME_TOTALS or None; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_undistorted_frames_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp,
+                                                  ctypes.POINTER(PackedPoints), vp, vp, ctypes.c_uint32, vp, vp, vp]
+        L.ecal_undistorted_frames_dev.restype = ctypes.c_int
+        self._check(L.ecal_undistorted_frames_dev(self._h, ctypes.byref(cam), ctypes.byref(opt) if opt is not None else None, d_xy,
+                                                  ctypes.byref(pk) if pk is not None else None, d_seg_off, d_seg_cnt, int(S), d_rgb,
+                                                  d_frame_totals, stream))
+
+    def undistort_points(self, cam, events):
+        """The rule per record of a packed stream: (uv: float64 CUDA tensor [n, 2] with 0, 0 where invalid, flag: uint8 CUDA tensor
+        [n], 1 invalid).  RADIAL: bit for bit undistort_points_host."""
+        import torch
+        t, n = self._records_arg(events)
+        uv = torch.empty((n, 2), dtype=torch.float64, device=t.device)
+        flag = torch.empty(n, dtype=torch.uint8, device=t.device)
+        with torch.cuda.device(t.device):
+            self.undistort_points_dev(cam, t.data_ptr() if n else None, n, uv.data_ptr() if n else None, flag.data_ptr() if n else None,
+                                      torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        return uv, flag
+
+    def undistort_events(self, cam, events, opt=None, **options):
+        """The stream as the ideal pinhole camera would have seen it: (events: uint8 CUDA tensor [n_kept * 25] — stamps and polarity
+        bytes as they were, x and y replaced, the order kept —, totals: one UNDISTORT_TOTALS record).  opt an UndistortOptions, or
+        options for undistort_options (mode, out_width, out_height, off_x, off_y, sensor)."""
+        import torch
+        t, n = self._records_arg(events)
+        o = opt if opt is not None else undistort_options(**options)
+        out = torch.empty(n * 25, dtype=torch.uint8, device=t.device)
+        cnt = torch.empty(1, dtype=torch.int32, device=t.device)
+        tot = torch.empty(4, dtype=torch.int64, device=t.device)
+        with torch.cuda.device(t.device):
+            self.undistort_events_dev(cam, o, t.data_ptr() if n else None, n, out.data_ptr() if n else None, cnt.data_ptr(), tot.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        kept = int(cnt.item()) & 0xFFFFFFFF
+        return out[: kept * 25], tot.cpu().numpy().view(UNDISTORT_TOTALS)[0]
+
+    def _host_stream(self, events):
+        """an ecal_stream of the host records `events` (the C++ shim's way); the caller destroys it"""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
+        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
+        ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
+        assert ev.size % 25 == 0, "packed 25-byte event records"
+        h = vp()
+        self._check(L.ecal_stream_create(self._h, _ptr(ev) if ev.size else None, ev.size // 25, ctypes.byref(h)))
+        return h
+
+    def undistort_stream(self, cam, events, opt=None, **options):
+        """ecal_stream_undistort over an ecal_stream made of the host records `events` -> (events as a uint8 CUDA tensor, totals dict)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_undistort.argtypes = [vp, vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), ctypes.POINTER(vp), vp]
+        L.ecal_stream_undistort.restype = ctypes.c_int
+        o = opt if opt is not None else undistort_options(**options)
+        tot = np.zeros(1, UNDISTORT_TOTALS)
+        h_in, h_out = self._host_stream(events), vp()
+        try:
+            self._check(L.ecal_stream_undistort(self._h, h_in, ctypes.byref(cam), ctypes.byref(o), ctypes.byref(h_out), tot.ctypes.data))
+        finally:
+            L.ecal_stream_destroy(h_in)
+        out, _, _ = self._stream_records(h_out)
+        return out, {k: int(tot[0][k]) for k in UNDISTORT_TOTALS.names}
+
+    def undistorted_frames(self, cam, events, t0, t1, opt=None, **options):
+        """ecal_stream_undistorted_frames over an ecal_stream made of the host records `events`: EventFrame::undistortedImage for the
+        windows [t0[s], t1[s]] -> (rgb uint8 [S, out_height, out_width, 3], totals: UNDISTORT_FRAME_TOTALS [S]).  Options as
+        undistort_events'; the mode must be PIXEL (sensor=(width, height): the reference canvas)."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_undistorted_frames.argtypes = [vp, vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp, vp,
+                                                     ctypes.c_uint32, vp, vp]
+        L.ecal_stream_undistorted_frames.restype = ctypes.c_int
+        o = opt if opt is not None else undistort_options(**options)
+        t0 = np.ascontiguousarray(np.asarray(t0, np.float64).ravel())
+        t1 = np.ascontiguousarray(np.asarray(t1, np.float64).ravel())
+        S = t0.size
+        assert t1.size == S
+        ok = undistort_options_error(o) is None and o.mode == UNDISTORT_PIXEL
+        rgb = np.zeros((S, int(o.out_height), int(o.out_width), 3) if ok else (S, 1, 1, 3), np.uint8)
+        tot = np.zeros(S, UNDISTORT_FRAME_TOTALS)
+        h_in = self._host_stream(events)
+        try:
+            self._check(L.ecal_stream_undistorted_frames(self._h, h_in, ctypes.byref(cam), ctypes.byref(o), _ptr(t0) if S else None,
+                                                         _ptr(t1) if S else None, S, _ptr(rgb) if S else None, _ptr(tot) if S else None))
+        finally:
+            L.ecal_stream_destroy(h_in)
+        return rgb, tot
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

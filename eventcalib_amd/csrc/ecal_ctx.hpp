@@ -122,7 +122,11 @@ struct ecal_ctx {
     ecal_devbuf activity_maps;     // ecal_stream_remove_hot_pixels: the count map, the mask, the totals, the count
     ecal_devbuf noise_scratch;     // ecal_noise_verdict_dev / ecal_denoise_events_dev: sort keys and indices, sorted stamps, the start table, verdict bytes, per-block counts / offsets
     ecal_devbuf noise_results;     // ecal_stream_remove_noise: the totals, the count
-    ecal_devbuf aedat4_tables;     // aedat4 ingest: the packets' inflated sizes, spans, located events, first slots, the counters
+    ecal_devbuf undistort_scratch; // ecal_undistort_events_dev: one verdict byte per event, per-block counts / offsets
+    ecal_devbuf undistort_results; // ecal_stream_undistort: the totals, the count
+    ecal_devbuf undistort_bits;    // ecal_undistorted_frames_dev: the windows' presence bits when a canvas does not fit LDS
+    ecal_devbuf undistort_frames;  // ecal_stream_undistorted_frames: the pictures and the per-window totals before their download
+    ecal_devbuf aedat4_tables;    // aedat4 ingest: the packets' inflated sizes, spans, located events, first slots, the counters
     ecal_devbuf aedat4_inflated;   // aedat4 ingest: the inflated packets, each in its span (padded to 16 bytes)
     ecal_devbuf aedat4_blocks;     // aedat4 ingest: per-block kept counts / offsets
     ecal_devbuf ingest_ev[2];           // ecal_detect_stream_tiled: ping-pong event chunks

@@ -297,6 +297,13 @@ extern "C" void ecal_stream_destroy(ecal_stream *s) {
 
 extern "C" uint64_t ecal_stream_size(const ecal_stream *s) { return s ? s->n_events : 0; }
 
+extern "C" int ecal_stream_to_bin_file(ecal_ctx *ctx, const ecal_stream *s, const char *bin_path) {
+    if (!ctx || !s || !bin_path) return ECAL_ERR_INVALID;
+    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ECAL_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ecal_write_records_file(ctx, "ecal_stream_to_bin_file", s->d_events, s->n_events, bin_path);
+}
+
 namespace {
 struct Out {
     void *host;

@@ -472,6 +472,23 @@ struct EventContainer {
         stream_ = filtered;
     }
     ecal_filter_totals noiseTotals{};     // what the last removeNoise saw (events, off the grid, removed, kept)
+    // The events as the ideal pinhole camera behind `camera` (the solved intrinsics: ecal_undistort_camera_from_params) would have seen
+    // them, as a container of its own (ecal_stream_undistort; this one is untouched): invalid events are gone, in PIXEL mode those
+    // outside the canvas too; stamps, polarities and the order stay.  opt null: sub-pixel coordinates.
+    Ptr undistorted(const ecal_undistort_camera &camera, const ecal_undistort_options *opt = nullptr, ecal_undistort_totals *totals = nullptr) {
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        Ptr out = std::make_shared<EventContainer>();
+        out->cameraSize = cameraSize;
+        const int rc = ecal_stream_undistort(ctx, device(), &camera, opt, &out->stream_, &undistortTotals);
+        if (totals) *totals = undistortTotals;
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("undistorted: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_stream_undistort: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        out->fromFile_ = true;
+        if (ecal_stream_size(out->stream_) && ecal_stream_times(out->stream_, &out->devFirst_, &out->devLast_) != ECAL_OK)
+            throw std::runtime_error("ecal_stream_times");
+        return out;
+    }
+    ecal_undistort_totals undistortTotals{};   // what the last undistorted saw (events, invalid, outside, kept)
     size_t size() const { return fromFile_ ? (size_t) ecal_stream_size(stream_) : records.size() / Event::kRecordBytes; }
     double firstTime() const { return fromFile_ ? devFirst_ : Event::unpack(records.data()).timeStamp(); }
     double lastTime() const {
@@ -620,6 +637,27 @@ public:
     const std::vector<Vector2d> &negativeEvents() {
         ensure();
         return det_.negative;
+    }
+    // EventFrame::undistortedImage (EventFrame.cpp:38-60) for the camera's size of the container: the RGB bytes of the canvas
+    // round(1.2 * size) — ecal_undistort_reference_canvas; width and height through the pointers —, red where a positive point of
+    // the frame lands, green where a negative one does (painted over the red).  Points that are invalid or land outside the canvas
+    // are painted nowhere (the reference indexes out of bounds there).
+    std::vector<uint8_t> undistortedImage(const ecal_undistort_camera &camera, int *widthOut = nullptr, int *heightOut = nullptr,
+                                          ecal_undistort_frame_totals *totals = nullptr) {
+        ensure();
+        if (det_.positive.empty() || det_.negative.empty()) throw std::logic_error("Events in Frame was cleared.");
+        ecal_undistort_options opt;
+        ecal_undistort_reference_canvas((uint32_t) container_->cameraSize[0], (uint32_t) container_->cameraSize[1], &opt);
+        std::vector<uint8_t> rgb((size_t) opt.out_width * opt.out_height * 3);
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_undistorted_frames(ctx, container_->device(), &camera, &opt, &duration_.first, &duration_.second, 1, rgb.data(),
+                                                      totals);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("undistortedImage: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_undistorted_frames: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (widthOut) *widthOut = (int) opt.out_width;
+        if (heightOut) *heightOut = (int) opt.out_height;
+        return rgb;
     }
 
 protected:

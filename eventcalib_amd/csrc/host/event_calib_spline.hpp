@@ -126,10 +126,12 @@ public:
     EventCalibSpline(std::vector<Frame> frames, EventContainer::Ptr eventContainer, CirclePatternParameters::Ptr pattern, bool useSO3,
                      double motionTimeStep, const double K[4], const double distCoeffs[5], int maxIterations = 50,
                      bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false,
-                     int refineRounds = 0, double refineRingTol = 0.0 /* board units; <= 0: the Huber width */)
+                     int refineRounds = 0, double refineRingTol = 0.0 /* board units; <= 0: the Huber width */,
+                     bool keepEvents = false /* the container's device stream outlives the solve (the caller undistorts it) */)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
           fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations),
-          wantBoardImage_(wantBoardImage), refineRounds_(refineRounds > 0 ? refineRounds : 0), refineRingTol_(refineRingTol) {
+          wantBoardImage_(wantBoardImage), refineRounds_(refineRounds > 0 ? refineRounds : 0), refineRingTol_(refineRingTol),
+          keepEvents_(keepEvents) {
         if (reportOptions) {
             report_.options = *reportOptions;
             wantReport_ = true;
@@ -275,7 +277,7 @@ private:
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_create_from_stream: ") + ecal_last_error(ctx));
         (void) n_events;
         const bool keepStream = wantBoardImage_ || refineRounds_ > 0;   // the board image and the refinement read the stream once more
-        if (!keepStream) eventContainer_->release();  // eventContainer_->container.clear() (:194)
+        if (!keepStream && !keepEvents_) eventContainer_->release();  // eventContainer_->container.clear() (:194)
         summary_.residuals = ecal_solver_num_residuals(solver);
         if (summary_.residuals == 0) {
             ecal_solver_destroy(solver);
@@ -350,7 +352,7 @@ private:
                 throw std::runtime_error(std::string("ecal_solver_board_image: ") + ecal_last_error(ctx));
             }
         }
-        if (keepStream) eventContainer_->release();
+        if (keepStream && !keepEvents_) eventContainer_->release();
         ecal_solver_destroy(solver);
         if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_solver_solve: ") + ecal_last_error(ctx));
         std::copy(x.begin(), x.begin() + 9, intrinsics_);
@@ -397,6 +399,7 @@ private:
     bool wantBoardImage_ = false;
     int refineRounds_ = 0;
     double refineRingTol_ = 0.0;
+    bool keepEvents_ = false;
     std::vector<RefineRound> refine_;
 };
 

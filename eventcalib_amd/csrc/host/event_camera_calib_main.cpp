@@ -369,8 +369,19 @@ int main(int argc, char **argv) {
     fsSettings["RefineRounds"] >> refineRounds;
     double refineRingTol = 0.0;
     fsSettings["RefineRingTol"] >> refineRingTol;
+    // UndistortedEvents / UndistortedEvents_Pixel / UndistortedImages (keys of this build, optional): the solved camera applied to
+    // the stream the calibration ran on (include/ecal.h, "undistortion").  UndistortedEvents: 1 writes saveDir/events_undistorted.bin,
+    // the records with sub-pixel coordinates — with UndistortedEvents_Pixel: 1 the pixels of the reference's canvas (round(1.2 * size),
+    // events outside it dropped).  UndistortedImages: 1 writes EventFrame::undistortedImage of every accepted keyframe to
+    // saveDir/undistortedImage/<std::to_string(timeStamp)>_undistorted.png (the folder and names visulization_eventCalib.cpp:85-93
+    // reads).  Either writes saveDir/Undistorted.txt.  Absent or 0: nothing changes
+    int wantUndistortedEvents = 0, wantUndistortedPixel = 0, wantUndistortedImages = 0;
+    fsSettings["UndistortedEvents"] >> wantUndistortedEvents;
+    fsSettings["UndistortedEvents_Pixel"] >> wantUndistortedPixel;
+    fsSettings["UndistortedImages"] >> wantUndistortedImages;
+    const bool wantUndistort = wantUndistortedEvents || wantUndistortedImages;
     EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
-                            wantBoardImage != 0, refineRounds, refineRingTol);
+                            wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort);
     const double *x = spline.intrinsics();
     std::printf("refined %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g residuals %zu iterations %d splines %zu\n", x[0], x[1], x[2], x[3],
                 x[4], x[5], x[6], x[7], x[8], spline.summary().residuals, spline.summary().iterations, spline.splineNum());
@@ -396,6 +407,80 @@ int main(int argc, char **argv) {
                 written++;
         }
         std::printf("images %zu\n", written);
+    }
+    if (wantUndistort) {
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        ecal_undistort_camera cam;
+        ecal_undistort_camera_from_params(cs->useFisheye ? ECAL_CAMERA_FISHEYE : ECAL_CAMERA_RADIAL, x, &cam);
+        ecal_undistort_options canvas;
+        ecal_undistort_reference_canvas((uint32_t) width, (uint32_t) height, &canvas);
+        std::FILE *f = std::fopen((std::string(argv[3]) + "/Undistorted.txt").c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "cannot write %s/Undistorted.txt\n", argv[3]);
+            return 3;
+        }
+        std::fprintf(f, "model %d\nintrinsics %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\nout_k %.17g %.17g %.17g %.17g\n", cam.model,
+                     x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cam.out_k[0], cam.out_k[1], cam.out_k[2], cam.out_k[3]);
+        try {
+            if (wantUndistortedEvents) {
+                ecal_undistort_options opt = canvas;
+                if (!wantUndistortedPixel) std::memset(&opt, 0, sizeof(opt));   // ECAL_UNDISTORT_SUBPIXEL
+                ecal_undistort_totals t;
+                EventContainer::Ptr und = container->undistorted(cam, &opt, &t);
+                const std::string bin = std::string(argv[3]) + "/events_undistorted.bin";
+                if (ecal_stream_to_bin_file(ctx, und->device(), bin.c_str()) != ECAL_OK) {
+                    std::fprintf(stderr, "%s\n", ecal_last_error(ctx));
+                    std::fclose(f);
+                    return 3;
+                }
+                std::fprintf(f, "events mode %u out_width %u out_height %u off_x %.17g off_y %.17g\n", opt.mode, opt.out_width, opt.out_height,
+                             opt.off_x, opt.off_y);
+                std::fprintf(f, "events n_events %llu n_invalid %llu n_outside %llu n_kept %llu\n", (unsigned long long) t.n_events,
+                             (unsigned long long) t.n_invalid, (unsigned long long) t.n_outside, (unsigned long long) t.n_kept);
+                std::printf("undistorted events %llu of %llu kept\n", (unsigned long long) t.n_kept, (unsigned long long) t.n_events);
+            }
+            if (wantUndistortedImages) {
+                const std::string dir = std::string(argv[3]) + "/undistortedImage";
+                std::error_code ec;
+                std::filesystem::remove_all(dir, ec);
+                std::filesystem::create_directories(dir, ec);
+                const std::vector<size_t> &acc = res.acceptedFrames;
+                const size_t pic = (size_t) canvas.out_width * canvas.out_height * 3, batchFrames = 64;
+                std::vector<uint8_t> rgb, one(pic);
+                unsigned long long sums[4] = {0, 0, 0, 0};
+                size_t written = 0;
+                for (size_t at = 0; at < acc.size(); at += batchFrames) {
+                    const size_t S = std::min(batchFrames, acc.size() - at);
+                    std::vector<double> t0(S), t1(S);
+                    std::vector<ecal_undistort_frame_totals> ft(S);
+                    for (size_t k = 0; k < S; k++) {
+                        t0[k] = kfs[acc[at + k]].duration.first;
+                        t1[k] = kfs[acc[at + k]].duration.second;
+                    }
+                    rgb.resize(S * pic);
+                    const int rc = ecal_stream_undistorted_frames(ctx, container->device(), &cam, &canvas, t0.data(), t1.data(), (uint32_t) S, rgb.data(),
+                                                                  ft.data());
+                    if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_stream_undistorted_frames: ") + ecal_last_error(ctx));
+                    for (size_t k = 0; k < S; k++) {
+                        one.assign(rgb.begin() + k * pic, rgb.begin() + (k + 1) * pic);
+                        if (ecal_host::write_png_rgb(dir + "/" + std::to_string(kfs[acc[at + k]].timeStamp) + "_undistorted.png", (int) canvas.out_width,
+                                                     (int) canvas.out_height, one))
+                            written++;
+                        sums[0] += ft[k].n_pos, sums[1] += ft[k].n_neg, sums[2] += ft[k].n_invalid, sums[3] += ft[k].n_outside;
+                    }
+                }
+                std::fprintf(f, "images %zu out_width %u out_height %u off_x %.17g off_y %.17g\n", written, canvas.out_width, canvas.out_height,
+                             canvas.off_x, canvas.off_y);
+                std::fprintf(f, "images n_pos %llu n_neg %llu n_invalid %llu n_outside %llu\n", sums[0], sums[1], sums[2], sums[3]);
+                std::printf("undistorted images %zu\n", written);
+            }
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            std::fclose(f);
+            return 4;
+        }
+        std::fclose(f);
+        container->release();
     }
     if (wantReport && spline.report().valid) {
         const EventCalibSpline::Report &rp = spline.report();

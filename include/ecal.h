@@ -354,6 +354,8 @@ void ecal_stream_destroy(ecal_stream *s);
 uint64_t ecal_stream_size(const ecal_stream *s);
 /* DEVICE pointer of the packed records (what the _dev entry points take as d_events) */
 const uint8_t *ecal_stream_data(const ecal_stream *s);
+/* the records of the stream as a .bin file (the reference's image: packed 25-byte records), through pinned staging; waits */
+int ecal_stream_to_bin_file(ecal_ctx *ctx, const ecal_stream *s, const char *bin_path);
 /* device-to-device copy on `stream` (optionally followed by a stream synchronise) */
 int ecal_copy_dev(ecal_ctx *ctx, void *d_dst, const void *d_src, size_t bytes, void *stream, int sync);
 int ecal_detect_batch(ecal_ctx *ctx, const ecal_stream *es, const double *t0, const double *t1, uint32_t S,
@@ -1607,6 +1609,90 @@ int ecal_denoise_events_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_e
                             uint8_t *d_out /*room for n_events records, not overlapping*/, uint32_t *d_count, ecal_filter_totals *d_totals,
                             void *stream);
 int ecal_stream_remove_noise(ecal_ctx *ctx, const ecal_stream *in, const ecal_noise_options *opt, ecal_stream **out, ecal_filter_totals *totals);
+
+/* ---- undistortion: the events, and event frames, of the ideal pinhole camera behind the solved one ----
+ * Applies the camera the solver found.  Its intrinsics (fx fy cx cy k1..k5, the head of the solver's parameter vector) are the INVERSE
+ * model — pixel to ideal ray is a closed-form polynomial —, so nothing is iterated.  The reference's PinholeCamera::undistortPoint
+ * (core/sensor/src/PinholeCamera.cpp:97-126) and EventFrame::undistortedImage (event/src/EventFrame.cpp:38-60) are what this stands
+ * for; Eigen's K.inverse() is NOT reproduced bit for bit: the rule below is this project's own statement, and parity with the
+ * reference is unpinned here.  eventcalib_amd/csrc/undistort_point.hpp restates the rule for host and device;
+ * design/20_undistort.md has the reasoning and what was measured.  Opt-in: nothing else in this header calls it.
+ *
+ * The rule, for a pixel (u, v).  Every operation is ONE IEEE f64 operation, rounded on its own: no FMA, a division is a division.
+ *     x = (u - cx) / fx;   y = (v - cy) / fy
+ *     r2 = x*x + y*y;  r4 = r2*r2;  r6 = r4*r2;  r8 = r6*r2;  r10 = r8*r2
+ *     poly = ((((1 + k1*r2) + k2*r4) + k3*r6) + k4*r8) + k5*r10
+ *     RADIAL :  c = poly;                                              valid iff poly > 0
+ *     FISHEYE:  r2 > 1e-16: r = sqrt(r2), th = r*poly, c = tan(th)/r;  valid iff th >= 0 && th < 1.5707963267948966
+ *               else       : c = poly;                                 valid iff poly > 0
+ *     u' = fx' * (x*c) + cx';   v' = fy' * (y*c) + cy';                valid also needs u', v' finite
+ *   A NaN anywhere makes the point invalid (every comparison above is false on a NaN).  tan is the one operation that is not
+ *   correctly rounded: host and device agree to a few ulp of it there, bit for bit everywhere else.
+ * The camera: ECAL_ERR_INVALID, and ecal_last_error (ecal_undistort_camera_error without a context) names the field, when fx, fy,
+ *   fx' or fy' is not finite or is <= 0, a k is not finite, reserved != 0, or the model is neither of the two.
+ * The options.  SUBPIXEL: a kept record carries u', v'.  PIXEL: X = round_half_away(u' + off_x), Y = round_half_away(v' + off_y) —
+ *   std::round: trunc(a) + (|a - trunc(a)| >= 0.5) * sign(a), not rint and not floor(a + 0.5) —; the event is kept iff
+ *   0 <= X < out_width && 0 <= Y < out_height, and its record carries X, Y as f64.  out_width, out_height 1 .. 8192, finite offsets,
+ *   reserved 0 (PIXEL); an unknown mode or a non-zero reserved word: ECAL_ERR_INVALID, the field named.  opt NULL: SUBPIXEL.
+ *   ecal_undistort_reference_canvas: the reference's (EventFrame.cpp:39,48-49): out = round(1.2 * size), off = size * 0.1 as f64
+ *   products: 346 x 260 -> 415 x 312, off 34.6, 26.0.
+ * The stream form: an invalid event is removed, in PIXEL mode one outside the canvas too.  A kept record keeps its stamp's 8 bytes and
+ *   its polarity byte, whatever their values; the order of the stream is kept.  n_events = n_invalid + n_outside + n_kept.
+ * ecal_undistort_points_host: HOST arrays, no context, no device.  uv [n][2] -> out [n][2] (0, 0 where invalid), flag [n]: 0 valid,
+ *   1 invalid.
+ * ecal_undistort_points_dev: the same per record of a packed stream (x, y at byte offsets 8 and 16 of each 25-byte record).
+ * ecal_undistort_events_dev: ecal_filter_events_dev's contract — any alignment of d_events, nothing read behind n_events * 25 bytes,
+ *   nothing stored behind the kept records, d_out has room for n_events records and does not overlap d_events (ECAL_ERR_INVALID), the
+ *   call zeroes its outputs on `stream`, enqueues and does not synchronise; n_events == 0 is valid; more than 2^32-1 events is
+ *   ECAL_ERR_RANGE.  d_totals may be NULL.
+ * ecal_stream_undistort: a new stream (*out; `in` is untouched) on the context's stream; waits for it.  totals (HOST) may be NULL.
+ * ecal_undistorted_frames_dev: EventFrame::undistortedImage for S windows at once, from the slicer's outputs (segment 2s the
+ *   positive, 2s + 1 the negative points of window s, the pixels present in both already erased); pk NULL: every segment is doubles,
+ *   else a segment is read in the form it has.  Requires opt->mode == ECAL_UNDISTORT_PIXEL.  A canvas pixel of window s is (0,255,0)
+ *   if any valid negative point of the window rounds onto it, else (255,0,0) if any valid positive point does, else (0,0,0): the
+ *   reference's red, then green painted over it, in RGB byte order.  Points that are invalid or land outside the canvas are counted and
+ *   painted nowhere (the reference indexes out of bounds there).  d_frame_totals [S] (or NULL): n_pos / n_neg the painted points of
+ *   either polarity; the four add up to the window's points.  Does not synchronise.
+ * ecal_stream_undistorted_frames: window bounds, the slicer and the frames for S windows [t0[s], t1[s]] on context scratch; rgb and
+ *   totals are HOST arrays; waits. */
+#define ECAL_UNDISTORT_SUBPIXEL 0
+#define ECAL_UNDISTORT_PIXEL 1
+typedef struct ecal_undistort_camera {
+    int model;         /* ECAL_CAMERA_RADIAL | ECAL_CAMERA_FISHEYE */
+    int reserved;      /* 0 */
+    double intr[9];    /* fx fy cx cy k1..k5: the solver's parameter head */
+    double out_k[4];   /* fx' fy' cx' cy' of the ideal pinhole camera the result is expressed in */
+} ecal_undistort_camera;
+typedef struct ecal_undistort_options {
+    uint32_t mode;             /* ECAL_UNDISTORT_SUBPIXEL 0 | ECAL_UNDISTORT_PIXEL 1 */
+    uint32_t out_width, out_height;   /* PIXEL: the canvas, 1 .. 8192 */
+    uint32_t reserved;
+    double off_x, off_y;       /* PIXEL: added before rounding */
+} ecal_undistort_options;
+typedef struct ecal_undistort_totals { uint64_t n_events, n_invalid, n_outside, n_kept; } ecal_undistort_totals;
+typedef struct ecal_undistort_frame_totals { uint32_t n_pos, n_neg, n_invalid, n_outside; } ecal_undistort_frame_totals;
+void ecal_undistort_camera_from_params(int model, const double *params9, ecal_undistort_camera *cam); /* out_k = intr[0..3], as the reference's K_ * Xc */
+void ecal_undistort_reference_canvas(uint32_t width, uint32_t height, ecal_undistort_options *opt);
+/* NULL: fine; else the text that names the refused field (a static string) */
+const char *ecal_undistort_camera_error(const ecal_undistort_camera *cam);
+const char *ecal_undistort_options_error(const ecal_undistort_options *opt);
+double ecal_undistort_round_half_away(double a);
+int ecal_undistort_points_host(const ecal_undistort_camera *cam, const double *uv /*HOST [n][2]*/, uint64_t n, double *out /*HOST [n][2]*/,
+                               uint8_t *flag /*HOST [n]*/);
+int ecal_undistort_points_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, const uint8_t *d_events, uint64_t n_events,
+                              double *d_uv /*[n][2]*/, uint8_t *d_flag /*[n]*/, void *stream);
+int ecal_undistort_events_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, const ecal_undistort_options *opt, const uint8_t *d_events,
+                              uint64_t n_events, uint8_t *d_out /*room for n_events records, not overlapping*/, uint32_t *d_count,
+                              ecal_undistort_totals *d_totals /*or NULL*/, void *stream);
+int ecal_stream_undistort(ecal_ctx *ctx, const ecal_stream *in, const ecal_undistort_camera *cam, const ecal_undistort_options *opt,
+                          ecal_stream **out, ecal_undistort_totals *totals /*or NULL*/);
+int ecal_undistorted_frames_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, const ecal_undistort_options *opt, const double *d_xy,
+                                const ecal_packed_points *pk /*or NULL*/, const uint32_t *d_seg_off /*[2S]*/, const uint32_t *d_seg_cnt /*[2S]*/,
+                                uint32_t S, uint8_t *d_rgb /*[S][out_height][out_width][3]*/,
+                                ecal_undistort_frame_totals *d_frame_totals /*[S], or NULL*/, void *stream);
+int ecal_stream_undistorted_frames(ecal_ctx *ctx, const ecal_stream *es, const ecal_undistort_camera *cam, const ecal_undistort_options *opt,
+                                   const double *t0, const double *t1, uint32_t S, uint8_t *rgb /*HOST*/,
+                                   ecal_undistort_frame_totals *totals /*HOST [S], or NULL*/);
 
 #ifdef __cplusplus
 }
