@@ -135,6 +135,45 @@ def load_events_bag(ctx, path, **options):
     return events, t_first, t_last
 
 
+def load_events_arrays(ctx, t, x, y, p, **options):
+    """Events held as four columns of one length (numpy arrays of any of the array ingest's types, any strides — a structured array's
+    fields are taken where they lie) -> (events, t_first, t_last) as calibrate_stream takes them: the columns uploaded as they are
+    (13 bytes an event for int64 / uint16 / uint16 / uint8, not 25) and packed on the device (capi.Context.stream_from_arrays), in
+    time order.  options: capi.fields_options' (time_magnitude — None: 1e-6 for integer stamps, 1.0 for float stamps —, time_base,
+    auto_time_base, width, height, flip_x, flip_y, start_time, end_time)."""
+    events, _info, t_first, t_last = ctx.stream_from_arrays(t, x, y, p, **options)
+    return events, t_first, t_last
+
+
+def load_events_npy(ctx, path, fields=None, columns=None, **options):
+    """A .npy file of events — a 1-D structured array with fields t|ts|time|timestamp, x, y, p|pol|polarity (or the names given as
+    fields = {"t": name, ...}), or a plain (N, 4) array whose columns are `columns` ("txyp") — -> (events, t_first, t_last): the header
+    read on the host, the payload uploaded and decoded in place on the device (capi.Context.stream_from_npy_file), in time order.
+    options as load_events_arrays."""
+    events, _info, t_first, t_last = ctx.stream_from_npy_file(path, fields=fields, columns=columns, **options)
+    return events, t_first, t_last
+
+
+def load_events_npz(ctx, path, **options):
+    """A .npz archive with members t|ts|timestamp, x, y and p|pol|polarity, opened with numpy (the C layer reads no zip) and taken
+    through load_events_arrays."""
+    import numpy as np
+    with np.load(path) as z:
+        cols = []
+        for names in (("t", "ts", "timestamp"), ("x",), ("y",), ("p", "pol", "polarity")):
+            hits = [k for k in z.files if k.lower() in names]
+            if len(hits) != 1:
+                raise ValueError("%s: %s member for %s (members: %s)" % (path, "no" if not hits else "more than one", names[0], ", ".join(z.files)))
+            cols.append(np.asarray(z[hits[0]]).reshape(-1))
+    return load_events_arrays(ctx, *cols, **options)
+
+
+def save_events_npy(ctx, events, path):
+    """Packed records (a CUDA or CPU uint8 tensor, a numpy array, bytes) as a .npy file of the packed dtype
+    [('t','<f8'),('x','<f8'),('y','<f8'),('p','u1')]: np.load returns the records, load_events_npy reads them back."""
+    ctx.stream_to_npy(events, path)
+
+
 def remove_hot_pixels(ctx, events, width=346, height=260, extra_mask=None, **options):
     """The events without those of hot pixels — pixels that fire whatever the scene does: (events, info) as
     capi.Context.remove_hot_pixels returns them.  A per-pixel count of the whole stream on the GPU, the rule on the host (a pixel

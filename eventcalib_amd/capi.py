@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "ecal_aedat_default_options", "ecal_aedat_block_events", "ecal_aedat_parse_header", "ecal_aedat_index_packets", "ecal_aedat_count_events_dev", "ecal_events_from_aedat_dev", "ecal_stream_create_from_aedat_file", "ecal_aedat_to_bin_file",
     "ecal_aedat4_default_options", "ecal_aedat4_block_events", "ecal_aedat4_parse_header", "ecal_aedat4_index_packets", "ecal_aedat4_count_events_dev", "ecal_events_from_aedat4_dev", "ecal_stream_create_from_aedat4_file", "ecal_aedat4_to_bin_file",
     "ecal_bag_default_options", "ecal_bag_block_events", "ecal_bag_index_messages", "ecal_bag_count_events_dev", "ecal_events_from_bag_dev", "ecal_stream_create_from_bag_file", "ecal_bag_to_bin_file",
+    "ecal_fields_default_options", "ecal_to_fields_default_options", "ecal_npy_default_options", "ecal_fields_block_events", "ecal_events_from_fields_host", "ecal_events_from_fields_dev", "ecal_stream_create_from_fields", "ecal_events_to_fields_host", "ecal_events_to_fields_dev", "ecal_npy_parse_header", "ecal_stream_create_from_npy_file", "ecal_npy_to_bin_file", "ecal_stream_to_npy_file",
     "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
     "ecal_noise_default_options", "ecal_noise_verdict_host", "ecal_noise_verdict_dev", "ecal_denoise_events_dev", "ecal_stream_remove_noise",
     "ecal_undistort_camera_from_params", "ecal_undistort_reference_canvas", "ecal_undistort_camera_error", "ecal_undistort_options_error", "ecal_undistort_round_half_away", "ecal_undistort_points_host", "ecal_undistort_points_dev", "ecal_undistort_events_dev", "ecal_stream_undistort", "ecal_undistorted_frames_dev", "ecal_stream_undistorted_frames",
@@ -202,6 +203,89 @@ class BagMessage(ctypes.Structure):
 
 
 BAG_MESSAGE_DTYPE = np.dtype([("offset_of_first_event", "<u8"), ("n_events", "<u4"), ("reserved", "<u4")])
+
+
+class Field(ctypes.Structure):
+    """ecal_field (include/ecal.h, array ingest): element i at ptr + i * stride."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("stride", ctypes.c_int64), ("type", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class FieldsOptions(ctypes.Structure):
+    """ecal_fields_options (include/ecal.h, array ingest)."""
+    _fields_ = [("time_magnitude", ctypes.c_double), ("time_base", ctypes.c_int64), ("auto_time_base", ctypes.c_int),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("flip_x", ctypes.c_int), ("flip_y", ctypes.c_int),
+                ("start_time", ctypes.c_double), ("has_end_time", ctypes.c_int), ("end_time", ctypes.c_double)]
+
+
+class FieldsInfo(ctypes.Structure):
+    """ecal_fields_info (include/ecal.h, array ingest)."""
+    _fields_ = [("n_raw_events", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("n_outside", ctypes.c_uint64),
+                ("n_negative", ctypes.c_uint64), ("n_before_start", ctypes.c_uint64), ("n_after_end", ctypes.c_uint64),
+                ("time_base", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class ToFieldsOptions(ctypes.Structure):
+    """ecal_to_fields_options (include/ecal.h, array ingest)."""
+    _fields_ = [("ticks_per_second", ctypes.c_double), ("time_base", ctypes.c_int64), ("polarity_signed", ctypes.c_int)]
+
+
+class ToFieldsInfo(ctypes.Structure):
+    """ecal_to_fields_info (include/ecal.h, array ingest)."""
+    _fields_ = [("n_events", ctypes.c_uint64), ("n_unrepresentable", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class NpyField(ctypes.Structure):
+    """ecal_npy_field (include/ecal.h, array ingest)."""
+    _fields_ = [("offset", ctypes.c_uint64), ("type", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class NpyLayout(ctypes.Structure):
+    """ecal_npy_layout (include/ecal.h, array ingest)."""
+    _fields_ = [("data_offset", ctypes.c_uint64), ("n_events", ctypes.c_uint64), ("item_stride", ctypes.c_uint64), ("field", NpyField * 4),
+                ("version_major", ctypes.c_uint32), ("version_minor", ctypes.c_uint32)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("data_offset", "n_events", "item_stride", "version_major", "version_minor")}
+        d["fields"] = {name: (int(self.field[k].offset), FIELD_TYPE_NAMES[self.field[k].type] if self.field[k].type < 9 else None)
+                       for k, name in enumerate("txyp")}
+        return d
+
+
+class NpyOptions(ctypes.Structure):
+    """ecal_npy_options (include/ecal.h, array ingest).  The names are byte strings that must outlive the call (npy_options keeps them
+    on the object)."""
+    _fields_ = [("fields", FieldsOptions), ("t_name", ctypes.c_char_p), ("x_name", ctypes.c_char_p), ("y_name", ctypes.c_char_p),
+                ("p_name", ctypes.c_char_p), ("columns", ctypes.c_char_p)]
+
+
+# ECAL_FIELD_*: the code of a numpy dtype (bool is U8), and the numpy dtype of a code
+FIELD_TYPE_NAMES = ("U8", "I8", "U16", "I16", "U32", "I32", "I64", "F32", "F64")
+FIELD_DTYPES = (np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.int64, np.float32, np.float64)
+
+
+def field_type(dtype):
+    """the ECAL_FIELD_* code of a numpy dtype (or of a torch dtype); ValueError for one that is not a column type"""
+    if not isinstance(dtype, (np.dtype, type, str)):   # a torch dtype
+        name = str(dtype).replace("torch.", "")
+        dtype = {"bool": "bool", "float": "float32", "double": "float64", "half": "float16", "long": "int64", "int": "int32", "short": "int16"}.get(name, name)
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError("dtype %s is not a column type of the array ingest" % (dtype,))
+    if dt == np.bool_:
+        return 0
+    if dt.byteorder == ">":
+        raise ValueError("big-endian dtype %s: the array ingest reads little-endian columns" % dt)
+    for code, d in enumerate(FIELD_DTYPES):
+        if dt == np.dtype(d):
+            return code
+    raise ValueError("dtype %s is not a column type of the array ingest (U8, I8, U16, I16, U32, I32, I64, F32, F64 are)" % dt)
 
 
 import weakref
@@ -532,6 +616,146 @@ def undistort_points_host(cam, uv):
     if st != 0:
         raise EcalError(st, L.ecal_strerror(st).decode() + ": ecal_undistort_points_host: " + (undistort_camera_error(cam) or "null pointer"))
     return out, flag
+
+
+def fields_options(time_magnitude=None, time_base=None, auto_time_base=False, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
+                   end_time=None):
+    """ecal_fields_options from ecal_fields_default_options (time_magnitude 1e-6, time_base 0, no size, no flips, start_time 0, no end
+    time); None leaves a default."""
+    L = load_library()
+    L.ecal_fields_default_options.argtypes, L.ecal_fields_default_options.restype = [ctypes.POINTER(FieldsOptions)], None
+    o = FieldsOptions()
+    L.ecal_fields_default_options(ctypes.byref(o))
+    if time_magnitude is not None:
+        o.time_magnitude = float(time_magnitude)
+    if time_base is not None:
+        o.time_base = int(time_base)
+    o.auto_time_base = 1 if auto_time_base else 0
+    o.width, o.height, o.flip_x, o.flip_y = int(width), int(height), 1 if flip_x else 0, 1 if flip_y else 0
+    if start_time is not None:
+        o.start_time = float(start_time)
+    if end_time is not None:
+        o.has_end_time, o.end_time = 1, float(end_time)
+    return o
+
+
+def to_fields_options(ticks_per_second=None, time_base=None, polarity_signed=False):
+    """ecal_to_fields_options from ecal_to_fields_default_options (1e6 ticks a second, base 0, polarity 0 / 1)."""
+    L = load_library()
+    L.ecal_to_fields_default_options.argtypes, L.ecal_to_fields_default_options.restype = [ctypes.POINTER(ToFieldsOptions)], None
+    o = ToFieldsOptions()
+    L.ecal_to_fields_default_options(ctypes.byref(o))
+    if ticks_per_second is not None:
+        o.ticks_per_second = float(ticks_per_second)
+    if time_base is not None:
+        o.time_base = int(time_base)
+    o.polarity_signed = 1 if polarity_signed else 0
+    return o
+
+
+def npy_options(fields=None, columns=None, **options):
+    """ecal_npy_options: fields = {"t": name, "x": ..., "y": ..., "p": ...} overrides the aliases of a structured file, columns the
+    order of an (N, 4) array ("txyp"); the other options are fields_options'."""
+    o = NpyOptions()
+    o.fields = fields_options(**options)
+    keep = []
+    for k in "txyp":
+        name = (fields or {}).get(k)
+        if name:
+            keep.append(name.encode())
+            setattr(o, k + "_name", keep[-1])
+    if columns:
+        keep.append(columns.encode())
+        o.columns = keep[-1]
+    o._keep = keep
+    return o
+
+
+def _host_column(a):
+    """a 1-D numpy array as it lies in memory (any stride) -> (array kept alive, Field)"""
+    a = np.asarray(a)
+    if a.ndim != 1:
+        raise ValueError("a column is a 1-D array")
+    if a.dtype == np.uint64:
+        if a.size and int(a.max()) >= 1 << 63:
+            raise ValueError("uint64 stamps beyond 2^63-1 are not taken")
+        a = a.view(np.int64)
+    if a.size > 1 and a.strides[0] < a.dtype.itemsize:   # (a reversed or a broadcast view)
+        a = np.ascontiguousarray(a)
+    return a, Field(a.ctypes.data if a.size else None, a.strides[0] if a.size > 1 else a.dtype.itemsize, field_type(a.dtype), 0)
+
+
+def _default_magnitude(options, stamp_dtype_code):
+    if options.get("time_magnitude") is None:
+        options = dict(options, time_magnitude=1.0 if stamp_dtype_code >= 7 else 1e-6)
+    return options
+
+
+def events_from_fields_host(t, x, y, p, capacity=None, **options):
+    """ecal_events_from_fields_host: the walk of the array ingest in plain C over numpy columns (any strides: a structured array's
+    fields are taken where they lie) -> (packed records as a uint8 array [n_events * 25], info dict).  No context, no device.
+    time_magnitude None: 1e-6 for integer stamps, 1.0 for float stamps.  A refusal raises EcalError with the library's text."""
+    L = load_library()
+    L.ecal_events_from_fields_host.argtypes = [ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.POINTER(FieldsInfo), ctypes.c_char_p, ctypes.c_uint64]
+    L.ecal_events_from_fields_host.restype = ctypes.c_int
+    cols = [_host_column(a) for a in (t, x, y, p)]
+    n = cols[0][0].size
+    if any(c[0].size != n for c in cols):
+        raise ValueError("the four columns must have one length")
+    f = (Field * 4)(*[c[1] for c in cols])
+    o = fields_options(**_default_magnitude(options, f[0].type))
+    cap = n if capacity is None else int(capacity)
+    out = np.zeros(cap * 25, np.uint8)
+    info = FieldsInfo()
+    err = ctypes.create_string_buffer(512)
+    st = L.ecal_events_from_fields_host(f, n, ctypes.byref(o), out.ctypes.data if cap else None, cap, ctypes.byref(info), err, 512)
+    if st != 0:
+        e = EcalError(st, err.value.decode())
+        e.info = info.as_dict()
+        raise e
+    return out[: int(info.n_events) * 25], info.as_dict()
+
+
+def events_to_fields_host(events, t=np.float64, xy=np.float64, p=np.uint8, **options):
+    """ecal_events_to_fields_host: packed records (bytes or a numpy uint8 array) -> ({"t", "x", "y", "p"} numpy arrays of the asked
+    dtypes, info dict).  Not representable events raise EcalError (status -6) with .info["n_unrepresentable"]."""
+    L = load_library()
+    L.ecal_events_to_fields_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Field), ctypes.POINTER(ToFieldsOptions),
+                                             ctypes.POINTER(ToFieldsInfo), ctypes.c_char_p, ctypes.c_uint64]
+    L.ecal_events_to_fields_host.restype = ctypes.c_int
+    rec = np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else np.ascontiguousarray(events, np.uint8).ravel()
+    n = rec.size // 25
+    out = {"t": np.zeros(n, t), "x": np.zeros(n, xy), "y": np.zeros(n, xy), "p": np.zeros(n, p)}
+    f = (Field * 4)(*[_host_column(out[k])[1] for k in "txyp"])
+    o = to_fields_options(**options)
+    info = ToFieldsInfo()
+    err = ctypes.create_string_buffer(512)
+    st = L.ecal_events_to_fields_host(rec.ctypes.data if n else None, n, f, ctypes.byref(o), ctypes.byref(info), err, 512)
+    if st != 0:
+        e = EcalError(st, err.value.decode())
+        e.info = info.as_dict()
+        raise e
+    return out, info.as_dict()
+
+
+def npy_parse_header(data, file_bytes=None, fields=None, columns=None):
+    """ecal_npy_parse_header over the front of a .npy file (bytes or a numpy uint8 array; file_bytes None: `data` is the whole file)
+    -> layout dict: data_offset, n_events, item_stride, version_major / _minor, fields {"t": (offset, type name), ...}.  A refusal
+    raises EcalError with the library's text."""
+    L = load_library()
+    L.ecal_npy_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(NpyOptions),
+                                        ctypes.POINTER(NpyLayout), ctypes.c_char_p, ctypes.c_uint64]
+    L.ecal_npy_parse_header.restype = ctypes.c_int
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).ravel()
+    o = npy_options(fields=fields, columns=columns)
+    lay = NpyLayout()
+    err = ctypes.create_string_buffer(512)
+    st = L.ecal_npy_parse_header(None, a.ctypes.data if a.size else None, a.size, 0 if file_bytes is None else int(file_bytes), ctypes.byref(o),
+                                 ctypes.byref(lay), err, 512)
+    if st != 0:
+        raise EcalError(st, err.value.decode())
+    return lay.as_dict()
 
 
 def _ptr(a):
@@ -1330,6 +1554,204 @@ class Context:
             self._text_fail(st, info)
         events, t_first, t_last = self._stream_records(h)
         return events, info.as_dict(), t_first, t_last
+
+    # ---- array ingest: columns packed into records in HBM, records unpacked into columns, .npy files (ecal_events_from_fields_dev, ...) ----
+    def fields_block_events(self):
+        """ecal_fields_block_events: events per block of the array ingest's kernels."""
+        self._L.ecal_fields_block_events.argtypes, self._L.ecal_fields_block_events.restype = [], ctypes.c_uint32
+        return int(self._L.ecal_fields_block_events())
+
+    def _device_column(self, a):
+        """a column (a numpy array, or a torch tensor on any device; a CUDA tensor is taken where it is, a 1-D strided view included)
+        -> (tensor kept alive, Field over device memory, length)"""
+        import torch
+        if isinstance(a, torch.Tensor):
+            if a.dim() != 1:
+                raise ValueError("a column is a 1-D array")
+            if a.is_cuda and (a.numel() < 2 or a.stride(0) >= 1):
+                n = a.numel()
+                return a, Field(a.data_ptr() if n else None, (a.stride(0) if n > 1 else 1) * a.element_size(), field_type(a.dtype), 0), n
+            a = a.cpu().contiguous().numpy()
+        h, f = _host_column(a)
+        h = np.ascontiguousarray(h)      # (a strided host column goes up as a copy of its own: events_from_structured keeps the items)
+        t = torch.from_numpy(h.view(np.uint8).copy()).to("cuda:%d" % self.device) if h.size else torch.zeros(0, dtype=torch.uint8, device="cuda:%d" % self.device)
+        return t, Field(t.data_ptr() if h.size else None, h.dtype.itemsize, f.type, 0), h.size
+
+    def events_from_fields_dev(self, fields, n, options, d_events, capacity, stream=0):
+        """ecal_events_from_fields_dev, raw: fields = (Field * 4) over device memory -> info dict; raises with .info on a refusal"""
+        L = self._L
+        L.ecal_events_from_fields_dev.argtypes = [ctypes.c_void_p, ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.c_void_p,
+                                                  ctypes.c_uint64, ctypes.POINTER(FieldsInfo), ctypes.c_void_p]
+        L.ecal_events_from_fields_dev.restype = ctypes.c_int
+        info = FieldsInfo()
+        st = L.ecal_events_from_fields_dev(self._h, fields, n, ctypes.byref(options), d_events, capacity, ctypes.byref(info), stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def events_from_arrays(self, t, x, y, p, capacity=None, **options):
+        """ecal_events_from_fields_dev: four columns (numpy arrays or torch tensors of one length; a CUDA tensor is taken where it
+        is, 1-D strided views included; a numpy uint64 stamp array is checked below 2^63 and viewed as int64) -> (packed 25-byte
+        records in input order as a uint8 CUDA tensor [n_events * 25], info dict).  options: fields_options'; time_magnitude None:
+        1e-6 for integer stamps, 1.0 for float stamps.  capacity None: the input's length (always enough); a smaller one raises
+        EcalError with status -6 and .info["n_events"] = the count needed."""
+        import torch
+        cols = [self._device_column(a) for a in (t, x, y, p)]
+        n = cols[0][2]
+        if any(c[2] != n for c in cols):
+            raise ValueError("the four columns must have one length")
+        f = (Field * 4)(*[c[1] for c in cols])
+        o = fields_options(**_default_magnitude(options, f[0].type))
+        cap = n if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device="cuda:%d" % self.device)
+        info = self.events_from_fields_dev(f, n, o, out.data_ptr(), cap, torch.cuda.current_stream().cuda_stream)
+        return out[: info["n_events"] * 25], info
+
+    @staticmethod
+    def _structured_roles(dtype, fields=None):
+        alias = {"t": ("t", "ts", "time", "timestamp"), "x": ("x",), "y": ("y",), "p": ("p", "pol", "polarity")}
+        roles = {}
+        for k in "txyp":
+            want = (fields or {}).get(k)
+            hits = [name for name in dtype.names if (name == want if want else name.lower() in alias[k])]
+            if len(hits) != 1:
+                raise ValueError("structured array: %s field for %s (names: %s)" % ("no" if not hits else "more than one", k, ", ".join(dtype.names)))
+            roles[k] = hits[0]
+        return roles
+
+    def events_from_structured(self, arr, fields=None, capacity=None, **options):
+        """a 1-D structured numpy array (packed or aligned, 13-, 14-, 16-byte items alike) uploaded once, as it lies, and packed on the
+        device with the fields pointing into the items.  Names are matched without case — t|ts|time|timestamp, x, y, p|pol|polarity
+        — or given as fields = {"t": name, ...}.  -> (records as a uint8 CUDA tensor, info dict)"""
+        import torch
+        arr = np.ascontiguousarray(arr)
+        if arr.ndim != 1 or arr.dtype.names is None:
+            raise ValueError("a 1-D structured array")
+        roles = self._structured_roles(arr.dtype, fields)
+        n = arr.size
+        d = torch.from_numpy(arr.view(np.uint8).copy()).to("cuda:%d" % self.device) if n else torch.zeros(0, dtype=torch.uint8, device="cuda:%d" % self.device)
+        f = (Field * 4)()
+        for k, role in enumerate("txyp"):
+            dt, off = arr.dtype.fields[roles[role]][:2]
+            if dt == np.uint64:
+                if n and int(arr[roles[role]].max()) >= 1 << 63:
+                    raise ValueError("uint64 stamps beyond 2^63-1 are not taken")
+                dt = np.dtype(np.int64)
+            f[k] = Field(d.data_ptr() + off if n else None, arr.dtype.itemsize, field_type(dt), 0)
+        o = fields_options(**_default_magnitude(options, f[0].type))
+        cap = n if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device="cuda:%d" % self.device)
+        info = self.events_from_fields_dev(f, n, o, out.data_ptr(), cap, torch.cuda.current_stream().cuda_stream)
+        return out[: info["n_events"] * 25], info
+
+    def stream_from_arrays(self, t, x, y, p, **options):
+        """ecal_stream_create_from_fields: HOST columns (numpy arrays, any strides) uploaded as they lie and packed on the device, the
+        records copied into a uint8 CUDA tensor (time order: the stream sorts when the input is not)
+        -> (events, info dict, t_first, t_last).  auto_time_base=True: the base is element 0's stamp."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_fields.argtypes = [vp, ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.POINTER(vp),
+                                                     ctypes.POINTER(FieldsInfo)]
+        L.ecal_stream_create_from_fields.restype = ctypes.c_int
+        cols = [_host_column(a) for a in (t, x, y, p)]
+        n = cols[0][0].size
+        if any(c[0].size != n for c in cols):
+            raise ValueError("the four columns must have one length")
+        f = (Field * 4)(*[c[1] for c in cols])
+        o = fields_options(**_default_magnitude(options, f[0].type))
+        info = FieldsInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_fields(self._h, f, n, ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    def events_to_fields_dev(self, d_events, n, fields, options, stream=0):
+        """ecal_events_to_fields_dev, raw: fields = (Field * 4) over device memory -> info dict; raises with .info on a refusal"""
+        L = self._L
+        L.ecal_events_to_fields_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Field), ctypes.POINTER(ToFieldsOptions),
+                                                ctypes.POINTER(ToFieldsInfo), ctypes.c_void_p]
+        L.ecal_events_to_fields_dev.restype = ctypes.c_int
+        info = ToFieldsInfo()
+        st = L.ecal_events_to_fields_dev(self._h, d_events, n, fields, ctypes.byref(options), ctypes.byref(info), stream)
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def events_to_arrays(self, events, t=np.float64, xy=np.float64, p=np.uint8, **options):
+        """ecal_events_to_fields_dev: packed records (a torch uint8 tensor on any device, a numpy array, bytes) -> a dict of CUDA
+        tensors "t", "x", "y", "p" of the asked numpy dtypes (bool for p: a torch.bool tensor).  options: ticks_per_second (1e6),
+        time_base, polarity_signed.  Events that are not representable raise EcalError with status -6 and
+        .info["n_unrepresentable"]."""
+        import torch
+        rec, n = self._records_arg(events)
+        out, f = {}, (Field * 4)()
+        for k, (name, dt) in enumerate((("t", t), ("x", xy), ("y", xy), ("p", p))):
+            dt = np.dtype(dt)
+            raw = torch.zeros(n * dt.itemsize, dtype=torch.uint8, device=rec.device)
+            out[name] = raw.view(getattr(torch, "bool" if dt == np.bool_ else dt.name))
+            f[k] = Field(raw.data_ptr() if n else None, dt.itemsize, field_type(dt), 0)
+        self.events_to_fields_dev(rec.data_ptr() if n else None, n, f, to_fields_options(**options), torch.cuda.current_stream(rec.device).cuda_stream)
+        return out
+
+    @staticmethod
+    def _npy_magnitude(path, fields, columns, options):
+        """time_magnitude None: by the stamp's type in the file's header, as events_from_arrays does (a file the parser refuses is
+        left to the library call, which says why)"""
+        if options.get("time_magnitude") is None:
+            try:
+                with open(path, "rb") as f:
+                    head = f.read(1 << 20)
+                lay = npy_parse_header(head, file_bytes=os.path.getsize(path), fields=fields, columns=columns)
+                options = dict(options, time_magnitude=1.0 if lay["fields"]["t"][1] in ("F32", "F64") else 1e-6)
+            except (OSError, EcalError):
+                pass
+        return options
+
+    def npy_to_bin(self, npy_path, bin_path, fields=None, columns=None, **options):
+        """ecal_npy_to_bin_file: the records of the .npy file (file order, no sort) as a .bin of the reference's layout -> info dict.
+        options: fields_options'; time_magnitude None: 1e-6 for integer stamps, 1.0 for float stamps."""
+        L = self._L
+        options = self._npy_magnitude(npy_path, fields, columns, options)
+        L.ecal_npy_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(NpyOptions), ctypes.POINTER(FieldsInfo)]
+        L.ecal_npy_to_bin_file.restype = ctypes.c_int
+        o = npy_options(fields=fields, columns=columns, **options)
+        info = FieldsInfo()
+        st = L.ecal_npy_to_bin_file(self._h, os.fsencode(npy_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        return info.as_dict()
+
+    def stream_from_npy_file(self, path, fields=None, columns=None, **options):
+        """ecal_stream_create_from_npy_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the file
+        is not) -> (events, info dict, t_first, t_last).  options as npy_to_bin."""
+        L = self._L
+        options = self._npy_magnitude(path, fields, columns, options)
+        vp = ctypes.c_void_p
+        L.ecal_stream_create_from_npy_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(NpyOptions), ctypes.POINTER(vp), ctypes.POINTER(FieldsInfo)]
+        L.ecal_stream_create_from_npy_file.restype = ctypes.c_int
+        o = npy_options(fields=fields, columns=columns, **options)
+        info = FieldsInfo()
+        h = vp()
+        st = L.ecal_stream_create_from_npy_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._text_fail(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
+
+    def stream_to_npy(self, events, npy_path):
+        """ecal_stream_to_npy_file: packed records (time-sorted by the stream when they are not) as a .npy of the packed dtype
+        [('t','<f8'),('x','<f8'),('y','<f8'),('p','u1')] — numpy's header and the records' bytes as they are."""
+        import torch
+        L = self._L
+        L.ecal_stream_to_npy_file.argtypes, L.ecal_stream_to_npy_file.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p], ctypes.c_int
+        h = self._host_stream(events.cpu().numpy() if isinstance(events, torch.Tensor) else
+                              np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else events)
+        try:
+            self._check(L.ecal_stream_to_npy_file(self._h, h, os.fsencode(npy_path)))
+        finally:
+            L.ecal_stream_destroy(h)
 
     # ---- pixel activity / hot pixels (ecal_pixel_activity_dev, ecal_filter_events_dev and the chain) ----
     def _records_arg(self, events):

@@ -208,8 +208,10 @@ int ecal_stream_adopt(ecal_ctx *ctx, uint8_t *d_events, uint64_t n_events, ecal_
 // chunks read by a few threads into pinned buffers of their own, every chunk's upload enqueued as soon as it is read.  `who`
 // opens the error texts.  (ecal_text.hip; the text ingest and the raw ingest)
 int ecal_upload_file(ecal_ctx *ctx, const char *who, const char *path, uint64_t file_offset, uint8_t **d_out, uint64_t *n_bytes_out);
-// n_events packed records on the device into the file bin_path, through pinned staging, a chunk at a time (ecal_text.hip)
-int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path);
+// n_events packed records on the device into the file bin_path, through pinned staging, a chunk at a time (ecal_text.hip); `prefix`
+// (may be null): bytes written in front of them (the .npy header of ecal_stream_to_npy_file)
+int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path,
+                            const std::string *prefix = nullptr);
 // ---- what the ingests' host sides share (ecal_ingest_common.hip); `who` opens the error texts ("bag ingest") -------------------------
 inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 // An argument of a device form: "<who>: null <what>" when n != 0 and ptr is null, "<who>: the <what> must be <align>-byte aligned"

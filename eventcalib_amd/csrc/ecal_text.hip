@@ -586,11 +586,21 @@ int ecal_upload_file(ecal_ctx *ctx, const char *who, const char *path, uint64_t 
     return ECAL_OK;
 }
 
-int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path) {
+int ecal_write_records_file(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const char *bin_path,
+                            const std::string *prefix) {
     const int fd = open(bin_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) {
         ctx->last_error = std::string(who) + ": cannot write " + bin_path;
         return ECAL_ERR_INVALID;
+    }
+    for (size_t put = 0; prefix && put < prefix->size();) {
+        const ssize_t wr = write(fd, prefix->data() + put, prefix->size() - put);
+        if (wr <= 0) {
+            close(fd);
+            ctx->last_error = std::string(who) + ": write failed for " + bin_path;
+            return ECAL_ERR_INVALID;
+        }
+        put += (size_t) wr;
     }
     // the records come down through pinned staging, a chunk at a time
     const uint64_t bytes = n_events * 25;

@@ -23,6 +23,7 @@
 #include "../aedat_events.hpp"
 #include "../aedat4_events.hpp"
 #include "../bag_events.hpp"
+#include "../fields_events.hpp"
 #include "dbscan.h"
 
 namespace opengv2 {
@@ -305,6 +306,55 @@ public:
         if (info) *info = I;
         return (long long) I.n_events;
     }
+    // A .npy file of events (a 1-D structured array or an (N, 4) array; include/ecal.h, "array ingest") -> .bin beside it, on one host
+    // thread: the header parser and the plain walk of fields_events.hpp, the records in file order.  The baseline of npy2binDevice,
+    // and its check: both write the same bytes.  opt null: the defaults (1e-6 s a tick, base 0, no bounds, no flips).
+    static long long npy2bin(const std::string &npyFilePath, const ecal_npy_options *opt = nullptr, ecal_fields_info *info = nullptr) {
+        std::ifstream is(npyFilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + npyFilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("npy2bin: cannot read " + npyFilePath);
+        ecal_npy_options o;
+        if (opt) o = *opt; else ecal_npy_default_options(&o);
+        ecal_fields::NpyChoice choice;
+        const char *names[4] = {o.t_name, o.x_name, o.y_name, o.p_name};
+        for (int k = 0; k < 4; k++)
+            if (names[k]) choice.name[k] = names[k];
+        if (o.columns) choice.columns = o.columns;
+        ecal_fields::NpyLayout L;
+        std::string err;
+        if (ecal_fields::npy_parse_header(bytes.data(), bytes.size(), 0, choice, L, &err))
+            throw std::invalid_argument("npy2bin: " + err + " (" + npyFilePath + ")");
+        ecal_fields::Field f[4];
+        for (int k = 0; k < 4; k++) f[k] = ecal_fields::Field{bytes.data() + L.data_offset + L.field[k].offset, (int64_t) L.item_stride, L.field[k].type, 0u};
+        if (o.fields.auto_time_base) o.fields.time_base = ecal_fields::fd_auto_time_base(f[0], L.n_events);
+        const ecal_fields::FieldsFilter flt{o.fields.time_magnitude, o.fields.time_base, o.fields.width, o.fields.height, o.fields.start_time,
+                                            o.fields.has_end_time, o.fields.end_time, o.fields.flip_x, o.fields.flip_y};
+        if (ecal_fields::fd_check_filter(flt, f[0].type, &err)) throw std::invalid_argument("npy2bin: " + err);
+        ecal_fields::FieldsCounts c;
+        std::vector<uint8_t> out;
+        ecal_fields::fd_walk(f, L.n_events, flt, c, [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); });
+        const auto dot = npyFilePath.find_last_of('.');
+        std::ofstream os(npyFilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info) *info = ecal_fields_info{c.n_raw_events, c.n_events, c.n_outside, c.n_negative, c.n_before_start, c.n_after_end, flt.time_base};
+        return (long long) c.n_events;
+    }
+    // npy2bin on the device (ecal_npy_to_bin_file: the header on the host, the payload uploaded and decoded in HBM): the same
+    // arguments, the same output file name, the same bytes in it, the same returned count
+    static long long npy2binDevice(const std::string &npyFilePath, const ecal_npy_options *opt = nullptr, ecal_fields_info *info = nullptr) {
+        const auto dot = npyFilePath.find_last_of('.');
+        ecal_fields_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_npy_to_bin_file(ctx, npyFilePath.c_str(), (npyFilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("npy2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_npy_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // txt2bin's arguments as ecal_text_options (LLONG_MIN: no base / no end, as there)
     static ecal_text_options textOptions(double timeMagnitude, long long timeBase_in, long long endTime_in) {
         ecal_text_options opt;
@@ -440,6 +490,32 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_bag_info bagInfo{};     // what the last loadBagFile saw (messages, chunks, drops, the time base in force)
+    // The same from events held as four columns in host memory (ecal_stream_create_from_fields: f[4] = t, x, y, p, element i at
+    // ptr + i * stride, any of the nine ECAL_FIELD_* types): uploaded as they lie and packed on the device.  opt null: the defaults.
+    void loadArrays(const ecal_field f[4], uint64_t n, const ecal_fields_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_fields(ctx, f, n, opt, &stream_, &fieldsInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadArrays: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_fields: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    // ... and from a .npy file of events (ecal_stream_create_from_npy_file): the header on the host, the payload decoded on the device.
+    void loadNpyFile(const std::string &npyFilePath, const ecal_npy_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_npy_file(ctx, npyFilePath.c_str(), opt, &stream_, &fieldsInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadNpyFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_npy_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_fields_info fieldsInfo{};   // what the last loadArrays / loadNpyFile saw (drops, the time base in force)
     // The events of hot pixels taken out of a file-backed container (ecal_stream_remove_hot_pixels: a per-pixel count, the rule, an
     // order-preserving filter; opt null: the defaults on a 346 x 260 sensor): the stream is swapped for the filtered one.
     // firstTime() / lastTime() stay the loaded stream's.  maskOut [height * width] / countsOut [2][height][width]: may be null.

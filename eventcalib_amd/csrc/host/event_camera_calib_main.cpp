@@ -4,7 +4,7 @@
 // eventcalib_amd/unit_test_eventCameraCalib next to libecal.so; run by tests/test_gpu_shims.py and bench.py's end_to_end leg.
 //   usage: unit_test_eventCameraCalib settings.yaml events.bin saveDir [batch]     (the reference's argv, eventCameraCalib.cpp:105-110;
 //   with batch, an events path ending in .txt is a text file of "stamp x y polarity" lines, converted on the device; one ending in
-//   .raw, .aedat, .aedat4 or .bag a camera's or recorder's own file, decoded on the device)
+//   .raw, .aedat, .aedat4 or .bag a camera's or recorder's own file, .npy events as numpy saves them, decoded on the device)
 // "batch": rectifyFeatures of all keyframes in one device pass (ecal_rectify_keyframes) instead of one CirclesEventFrame per
 // keyframe, the file read in one piece, and a "stage <name> <seconds>" line per stage of the chain (bench.py's end_to_end leg).
 #include <chrono>
@@ -155,6 +155,31 @@ int main(int argc, char **argv) {
                 return 4;
             }
             std::printf("bag_time_base %lld\n", (long long) container->bagInfo.time_base);   // nanoseconds: t = 0 of this run
+        } else if (eventsPath.size() >= 4 && eventsPath.compare(eventsPath.size() - 4, 4, ".npy") == 0) {
+            // events as numpy saves them — a 1-D structured array with fields t|ts|time|timestamp, x, y, p|pol|polarity, or an (N, 4)
+            // array — decoded on the device.  Keys of this build, all optional: Npy_TimeMagnitude (seconds per tick, 1e-6; 1 for
+            // stamps in seconds), Npy_TimeBase (ticks, 0), Npy_Columns (of an (N, 4) array, "txyp"), Npy_FlipX / Npy_FlipY (0).
+            // Events outside Camera.width x Camera.height are dropped.
+            ecal_npy_options opt;
+            ecal_npy_default_options(&opt);
+            std::string npyColumns;
+            if (!fsSettings["Npy_TimeMagnitude"].isNone()) fsSettings["Npy_TimeMagnitude"] >> opt.fields.time_magnitude;
+            if (!fsSettings["Npy_TimeBase"].isNone()) opt.fields.time_base = std::strtoll(((std::string) fsSettings["Npy_TimeBase"]).c_str(), nullptr, 10);
+            if (!fsSettings["Npy_Columns"].isNone()) npyColumns = (std::string) fsSettings["Npy_Columns"];
+            opt.columns = npyColumns.c_str();
+            if (!fsSettings["Npy_FlipX"].isNone()) opt.fields.flip_x = (int) fsSettings["Npy_FlipX"] ? 1 : 0;
+            if (!fsSettings["Npy_FlipY"].isNone()) opt.fields.flip_y = (int) fsSettings["Npy_FlipY"] ? 1 : 0;
+            opt.fields.width = (uint32_t) width;
+            opt.fields.height = (uint32_t) height;
+            opt.fields.start_time = startTime;
+            opt.fields.has_end_time = customEnd ? 1 : 0;
+            opt.fields.end_time = endTimeSetting;
+            try {
+                container->loadNpyFile(eventsPath, &opt);
+            } catch (const std::exception &e) {   // (a big-endian file, an object dtype, a missing field, a payload cut short: said plainly)
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
         } else {
             container->loadFile(argv[2], startTime, customEnd, endTimeSetting);
         }

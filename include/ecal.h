@@ -1514,6 +1514,144 @@ int ecal_events_from_bag_dev(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_by
 int ecal_stream_create_from_bag_file(ecal_ctx *ctx, const char *path, const ecal_bag_options *opt, ecal_stream **out, ecal_bag_info *info);
 int ecal_bag_to_bin_file(ecal_ctx *ctx, const char *bag_path, const char *bin_path, const ecal_bag_options *opt, ecal_bag_info *info);
 
+/* ---- array ingest: events held as columns (arrays, .npy files) packed into records in HBM, and records unpacked into columns ----
+ * For events that are in memory already as t, x, y, p — from np.load, h5py, a vendor library's structured array, a torch pipeline —
+ * and for the way back out.  New functionality: the reference reads its own .bin and text only.
+ * eventcalib_amd/csrc/fields_events.hpp restates everything that decides for the kernels, the host entry points and the CPU test;
+ * design/21_array_ingest.md has the reasoning.
+ *
+ * A field (ecal_field) is a column: element i lives at ptr + i * stride; stride is at least the type's size (else
+ *   ECAL_ERR_INVALID).  NO alignment of ptr or stride is assumed: packed structured items of 13 or 14 bytes are the normal case.  The
+ *   device loads touch only the 4-byte aligned words that hold at least one byte of an element i < n.  Types, little-endian:
+ *   ECAL_FIELD_U8, I8, U16, I16, U32, I32, I64, F32, F64 (bool is U8).  t takes U32, I32, I64, F32 or F64; x, y and p take any of the
+ *   nine.  A type that its field does not take is ECAL_ERR_INVALID with the field's name in the error text.
+ * Conversion of event i, in input order:
+ *   integer stamp: t = (double)((int64) ti - time_base) * time_magnitude (one integer subtraction, one conversion, one multiplication,
+ *     no contraction: the other ingests' rule).  Float stamp: t = (double) tf * time_magnitude; time_base must be 0 (else
+ *     ECAL_ERR_INVALID); with time_magnitude == 1.0 an F64 stamp passes bit for bit.
+ *   x, y = the double of the value; float values are kept as they are (a sub-pixel stream can come back in).
+ *   The polarity byte of the record is value > 0: 0 / 1, bool and -1 / +1 alike; NaN gives 0.
+ * Filter — the bag ingest's, in its order:  with width / height non-zero an event with !(x >= 0 && x < width) or
+ *   !(y >= 0 && y < height) is dropped (n_outside; a NaN coordinate is outside).  flip_x / flip_y give x = (double)(width - 1) - x /
+ *   y = (double)(height - 1) - y, applied BEHIND the bounds test; they need width / height non-zero (else ECAL_ERR_INVALID).  Then
+ *   !(t >= 0) is dropped (n_negative; a NaN stamp lands here); then with has_end_time the first event with t >= end_time ends the
+ *   stream: it and every event behind it count as n_after_end and as nothing else; then kept if t >= start_time (else
+ *   n_before_start).  n_events + n_outside + n_negative + n_before_start + n_after_end = n_raw_events, always.
+ * ecal_fields_default_options: time_magnitude 1e-6, time_base 0, auto_time_base 0, no size, no flips, start_time 0, no end time.
+ * Automatic time base (options.auto_time_base != 0; the host walk, the stream form and the file forms): the base is element 0's stamp
+ *   for an integer stamp, 0 for a float stamp and for no events; info.time_base = the base in force.  The _dev form takes an explicit
+ *   base only: auto_time_base != 0 there is ECAL_ERR_INVALID, as in the bag ingest.
+ *
+ * ecal_events_from_fields_host: the walk in plain C over HOST fields, no context, no device — the statement the kernels are held to.
+ *   events (HOST, room for `capacity` records; more kept events than that: ECAL_ERR_RANGE with info->n_events = the count needed, the
+ *   first `capacity` written).  err / err_cap (may be NULL / 0): the error text.
+ * ecal_fields_block_events: events per block of the kernels — a fact for tests that place block boundaries.
+ * ecal_events_from_fields_dev: f[4] = t, x, y, p over DEVICE memory, n events, into d_events (DEVICE, room for `capacity` records, input
+ *   order, not sorted; any alignment; nothing behind capacity * 25 bytes is stored).  info (HOST) is filled on ECAL_OK and on
+ *   ECAL_ERR_RANGE (capacity too small: info->n_events = the count needed).  n > 2^32-1: ECAL_ERR_RANGE.  n == 0 is valid.  An
+ *   output that overlaps a field's bytes is ECAL_ERR_INVALID naming the field.  Enqueues on `stream` and waits for it.
+ * ecal_stream_create_from_fields: HOST fields; the bytes the columns cover go up through pinned staging (13 bytes an event for the
+ *   common layout, not 25; columns that share an item, as a structured array's, go up once) and are packed on the device; then the
+ *   stream is brought into time order if it is not (ecal_stream_create's rule).  info may be NULL.
+ * The reverse.  ecal_events_to_fields_dev: n records (DEVICE, any alignment) into out[4] = t, x, y, p over DEVICE memory (strides and
+ *   alignment as above; only the elements' own bytes are stored).  F64 is a copy, F32 rounds to nearest.  An integer stamp is
+ *   time_base + llrint(t * ticks_per_second): one multiplication, ties to even, one addition (default 1e6, base 0).  Integer x / y
+ *   need an integral value within the type's range.  p is 0 / 1; with polarity_signed -1 / +1, and an unsigned type is then
+ *   ECAL_ERR_INVALID.  Anything not representable (a non-finite stamp to an integer type included) is counted in
+ *   info->n_unrepresentable and the call returns ECAL_ERR_RANGE; the output is then undefined.  An output that overlaps the records
+ *   is ECAL_ERR_INVALID.  Waits for `stream`.  ecal_events_to_fields_host: the same over HOST memory, no context.
+ * .npy files (`.npz` is not read here: Python opens it with numpy and comes in through the arrays).
+ * ecal_npy_parse_header: HOST; ctx may be NULL.  bytes / n_bytes: the front of the file, the whole header at least; file_bytes: the
+ *   file's size (0: n_bytes is the whole file).  Reads the magic \x93NUMPY, versions 1.0, 2.0 and 3.0 and the header dict as numpy
+ *   writes it.  Accepted: a 1-D structured descr — a list of ('name', '<code') pairs, '|V<n>' padding entries and fields of other
+ *   names stepped over — whose names are matched without case, t|ts|time|timestamp, x, y, p|pol|polarity, or exactly the names the
+ *   options give; and a 2-D plain C-order array (N, 4) of one stamp type whose columns follow options.columns (default "txyp").
+ *   Refused by name (ECAL_ERR_INVALID, the text in err and in ecal_last_error): big-endian codes, sub-array fields, object dtypes,
+ *   fortran_order: True on 2-D data, a missing or duplicate field, a type its field does not take, and a payload shorter than the
+ *   shape says (both sizes in the text).
+ * ecal_stream_create_from_npy_file: the header on the host, the payload through pinned buffers into HBM from the data offset on, the
+ *   fields pointing into the uploaded bytes, decoded in place; then time order as above.  ecal_npy_to_bin_file: the same records in
+ *   file order, no sort, as a .bin.
+ * ecal_stream_to_npy_file: a 25-byte record is exactly an item of the packed dtype [('t','<f8'),('x','<f8'),('y','<f8'),('p','u1')]:
+ *   the file is a version 1.0 header and the stream's bytes as they are. */
+enum {
+    ECAL_FIELD_U8 = 0, ECAL_FIELD_I8 = 1, ECAL_FIELD_U16 = 2, ECAL_FIELD_I16 = 3, ECAL_FIELD_U32 = 4, ECAL_FIELD_I32 = 5,
+    ECAL_FIELD_I64 = 6, ECAL_FIELD_F32 = 7, ECAL_FIELD_F64 = 8
+};
+typedef struct ecal_field {
+    const void *ptr;
+    int64_t stride;          /* bytes from one element to the next */
+    uint32_t type;           /* ECAL_FIELD_* */
+    uint32_t reserved;       /* 0 */
+} ecal_field;
+typedef struct ecal_fields_options {
+    double time_magnitude;   /* seconds per tick */
+    int64_t time_base;       /* ticks; 0 for a float stamp */
+    int auto_time_base;      /* the base is element 0's stamp (not in the _dev form) */
+    uint32_t width, height;  /* 0: no bound */
+    int flip_x, flip_y;      /* need width / height */
+    double start_time;       /* seconds */
+    int has_end_time;
+    double end_time;         /* seconds */
+} ecal_fields_options;
+typedef struct ecal_fields_info {
+    uint64_t n_raw_events;   /* events before any drop */
+    uint64_t n_events;       /* records written, or needed */
+    uint64_t n_outside;
+    uint64_t n_negative;
+    uint64_t n_before_start;
+    uint64_t n_after_end;
+    int64_t time_base;       /* the base in force */
+} ecal_fields_info;
+typedef struct ecal_to_fields_options {
+    double ticks_per_second;
+    int64_t time_base;       /* ticks, added to an integer stamp */
+    int polarity_signed;     /* -1 / +1 instead of 0 / 1 */
+} ecal_to_fields_options;
+typedef struct ecal_to_fields_info {
+    uint64_t n_events;
+    uint64_t n_unrepresentable;
+} ecal_to_fields_info;
+typedef struct ecal_npy_field {
+    uint64_t offset;         /* of the field inside an item */
+    uint32_t type;           /* ECAL_FIELD_* */
+    uint32_t reserved;
+} ecal_npy_field;
+typedef struct ecal_npy_layout {
+    uint64_t data_offset;    /* of element 0, from byte 0 of the file */
+    uint64_t n_events;
+    uint64_t item_stride;    /* bytes from one event to the next */
+    ecal_npy_field field[4]; /* t, x, y, p */
+    uint32_t version_major, version_minor;
+} ecal_npy_layout;
+typedef struct ecal_npy_options {
+    ecal_fields_options fields;
+    const char *t_name;      /* NULL or "": the aliases */
+    const char *x_name;
+    const char *y_name;
+    const char *p_name;
+    const char *columns;     /* of an (N, 4) array; NULL or "": "txyp" */
+} ecal_npy_options;
+void ecal_fields_default_options(ecal_fields_options *opt);
+void ecal_to_fields_default_options(ecal_to_fields_options *opt);
+void ecal_npy_default_options(ecal_npy_options *opt);
+uint32_t ecal_fields_block_events(void);
+int ecal_events_from_fields_host(const ecal_field f[4] /*t x y p*/, uint64_t n, const ecal_fields_options *opt, uint8_t *events,
+                                 uint64_t capacity, ecal_fields_info *info, char *err, uint64_t err_cap);
+int ecal_events_from_fields_dev(ecal_ctx *ctx, const ecal_field f[4] /*t x y p*/, uint64_t n, const ecal_fields_options *opt,
+                                uint8_t *d_events /*room for capacity records*/, uint64_t capacity, ecal_fields_info *info, void *stream);
+int ecal_stream_create_from_fields(ecal_ctx *ctx, const ecal_field f[4] /*HOST*/, uint64_t n, const ecal_fields_options *opt,
+                                   ecal_stream **out, ecal_fields_info *info);
+int ecal_events_to_fields_host(const uint8_t *events, uint64_t n, const ecal_field out[4], const ecal_to_fields_options *opt,
+                               ecal_to_fields_info *info, char *err, uint64_t err_cap);
+int ecal_events_to_fields_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n, const ecal_field out[4] /*t x y p*/,
+                              const ecal_to_fields_options *opt, ecal_to_fields_info *info, void *stream);
+int ecal_npy_parse_header(ecal_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t file_bytes, const ecal_npy_options *opt,
+                          ecal_npy_layout *layout, char *err, uint64_t err_cap);
+int ecal_stream_create_from_npy_file(ecal_ctx *ctx, const char *path, const ecal_npy_options *opt, ecal_stream **out, ecal_fields_info *info);
+int ecal_npy_to_bin_file(ecal_ctx *ctx, const char *npy_path, const char *bin_path, const ecal_npy_options *opt, ecal_fields_info *info);
+int ecal_stream_to_npy_file(ecal_ctx *ctx, const ecal_stream *s, const char *npy_path);
+
 /* ---- pixel activity / hot pixels: a per-pixel count map, a mask, the stream without the masked pixels' events ----
  * A hot pixel fires events whatever the scene does.  Three stages, each callable on its own, and one call that chains them; all of
  * it opt-in (nothing else in this header calls it).  New functionality: the reference has no such filter.
