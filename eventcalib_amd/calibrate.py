@@ -213,11 +213,79 @@ def undistort_events(ctx, events, params, model=capi.CAMERA_RADIAL, out_k=None, 
     return out, info
 
 
+def _image_options(width, height, channels, method, options):
+    options = dict(options)
+    if "canvas" in options:   # "reference": the reference's canvas, round(1.2 * size) with offsets round(size * 0.1)
+        canvas = options.pop("canvas")
+        if canvas not in (None, "sensor", "reference"):
+            raise ValueError('canvas: "sensor" or "reference"')
+        options["reference_canvas"] = canvas == "reference"
+    ref = bool(options.pop("reference_canvas", False))
+    o = capi.image_options(sensor=(width, height), reference_canvas=ref)
+    # (the reference canvas brings the reference's method, channels and normalize with it: the caller's words come after)
+    if ref and "normalize" not in options:
+        options["normalize"] = 1 if method in ("reference", capi.IMAGE_REFERENCE) else 0
+    return _image_options_apply(o, method, channels, options)
+
+
+def _image_options_apply(o, method, channels, options):
+    if method is not None:
+        o.method = {"reference": capi.IMAGE_REFERENCE, "bilinear": capi.IMAGE_BILINEAR}[method.lower()] if isinstance(method, str) else int(method)
+    if channels is not None:
+        o.channels = int(channels)
+    for name in ("out_width", "out_height", "normalize", "reserved"):
+        if name in options:
+            setattr(o, name, int(options.pop(name)))
+    for name in ("off_x", "off_y"):
+        if name in options:
+            setattr(o, name, float(options.pop(name)))
+    if options:
+        raise TypeError("unknown image option(s): " + ", ".join(sorted(options)))
+    return o
+
+
+def undistort_images(ctx, images, params, model=capi.CAMERA_RADIAL, method="reference", out_k=None, opt=None, **options):
+    """Pictures taken through the solved lens — intensity frames, accumulated event images, activity maps — on the ideal pinhole
+    camera's canvas: uint8 (H, W), (H, W, C) or (N, H, W, C) with C = 1 or 3 -> the same rank on the canvas.  params, model, out_k as
+    undistort_events'.  method "reference": the reference's PinholeCamera::undistortImage, every canvas pixel the inverse-squared-
+    distance average of the source pixels carried within 2 px of it (it blurs, and leaves holes where the lens stretches the
+    picture); "bilinear": the forward projection's rectification maps and a bilinear sample of the source (cv::remap's way).
+    options: canvas="sensor" (default: the sensor's own size, no offsets) or "reference" (round(1.2 * size), offsets
+    round(size * 0.1)), out_width, out_height, off_x, off_y, normalize (min-max of every frame to 0 .. 255; default 1 for "reference" on
+    the reference canvas, else 0); or opt, a capi.ImageOptions.  The rules are include/ecal.h's ("image undistortion").  A plan is
+    built per call: for many batches through one camera keep ctx.image_plan(...) and call its apply / apply_dev."""
+    a = np.asarray(images)
+    if a.ndim not in (2, 3, 4):
+        raise ValueError("images: (H, W), (H, W, C) or (N, H, W, C)")
+    height, width = (a.shape[0], a.shape[1]) if a.ndim < 4 else (a.shape[1], a.shape[2])
+    channels = 1 if a.ndim == 2 else a.shape[-1]
+    cam = capi.undistort_camera(params, model, out_k=out_k)
+    o = opt if opt is not None else _image_options(width, height, channels, method, options)
+    with ctx.image_plan(cam, width, height, o) as plan:
+        return plan.apply(a)
+
+
+def undistort_maps(ctx, params, model=capi.CAMERA_RADIAL, width=346, height=260, out_k=None, opt=None, **options):
+    """The rectification maps of the solved camera, cv::initUndistortRectifyMap's CV_32FC1 convention for the new camera out_k shifted
+    by the offsets: {"map_x", "map_y": float32 (out_height, out_width) — the sensor position each canvas pixel samples, -1 where the
+    forward projection has none —, "valid": uint8, "info": the options in force, r_lim, truncated, n_invalid, n_not_converged}.
+    cv2.remap(image, map_x, map_y, cv2.INTER_LINEAR) takes them as they are.  options as undistort_images' (canvas, out_width,
+    out_height, off_x, off_y)."""
+    cam = capi.undistort_camera(params, model, out_k=out_k)
+    o = opt if opt is not None else _image_options(int(width), int(height), 1, "bilinear", options)
+    with ctx.image_plan(cam, int(width), int(height), o) as plan:
+        mx, my, valid = plan.maps()
+        return {"map_x": mx, "map_y": my, "valid": valid, "info": plan.info}
+
+
+_undistort_maps = undistort_maps   # (calibrate_stream has an argument of that name)
+
+
 def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, frame_event_num_threshold=4000, piece_num=30,
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
-                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None):
+                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None, undistort_maps=None):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -260,7 +328,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     undistort (opt-in; None or False: nothing changes): True or a dict of options (undistort_events above: mode, sensor, out_width,
     out_height, off_x, off_y, out_k) applies the solved camera to the stream the calibration ran on — a stage of its own,
     `undistort`; out["undistorted_events"] is the uint8 CUDA tensor of the kept records, out["undistort"] the options in force and
-    the totals (design/20_undistort.md)."""
+    the totals (design/20_undistort.md).
+    undistort_maps (opt-in; None or False: nothing changes): True or a dict of options (undistort_maps above: canvas, out_width,
+    out_height, off_x, off_y, out_k) builds the solved camera's rectification maps for the width x height sensor — a stage of its
+    own, `undistort_maps`; out["undistort_maps"] holds map_x, map_y, valid and info (design/22_image_undistort.md)."""
     if flags is None:
         flags = EXAMPLE_FLAGS_FISHEYE if fisheye else EXAMPLE_FLAGS
     model = 1 if fisheye else 0
@@ -498,6 +569,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
         out["undistorted_events"], out["undistort"] = undistort_events(ctx, events, x[:9], model,
                                                                        **(dict(undistort) if isinstance(undistort, dict) else {}))
         mark("undistort")
+    if undistort_maps is not None and undistort_maps is not False:
+        out["undistort_maps"] = _undistort_maps(ctx, x[:9], model, int(width), int(height),
+                                                **(dict(undistort_maps) if isinstance(undistort_maps, dict) else {}))
+        mark("undistort_maps")
     # updateMap (:253-317): keyframe poses re-read from the optimised splines
     n_cp = seg_cp_off[-1]
     q_all, t_all = x[9:9 + 4 * n_cp].reshape(n_cp, 4), x[9 + 4 * n_cp:].reshape(n_cp, 3)

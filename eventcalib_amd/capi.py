@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "ecal_hot_pixel_default_options", "ecal_pixel_activity_dev", "ecal_hot_pixel_mask", "ecal_filter_events_dev", "ecal_stream_remove_hot_pixels",
     "ecal_noise_default_options", "ecal_noise_verdict_host", "ecal_noise_verdict_dev", "ecal_denoise_events_dev", "ecal_stream_remove_noise",
     "ecal_undistort_camera_from_params", "ecal_undistort_reference_canvas", "ecal_undistort_camera_error", "ecal_undistort_options_error", "ecal_undistort_round_half_away", "ecal_undistort_points_host", "ecal_undistort_points_dev", "ecal_undistort_events_dev", "ecal_stream_undistort", "ecal_undistorted_frames_dev", "ecal_stream_undistorted_frames",
+    "ecal_image_reference_options", "ecal_image_options_error", "ecal_camera_monotone_radius", "ecal_distort_points_host", "ecal_distort_points_dev", "ecal_undistort_image_host", "ecal_image_table_host", "ecal_image_maps_host", "ecal_image_plan_create", "ecal_image_plan_destroy", "ecal_image_plan_info", "ecal_image_plan_maps_dev", "ecal_image_plan_maps", "ecal_image_plan_table", "ecal_undistort_images_dev", "ecal_undistort_images",
     "ecal_calib_default_options", "ecal_calib_view_blocks_dev", "ecal_pnp_batch_dev", "ecal_pnp_batch", "ecal_pose_gates", "ecal_calibrate_views", "ecal_spline_fit", "ecal_spline_eval", "ecal_spline_so3_refine",
 ]
 
@@ -618,6 +619,310 @@ def undistort_points_host(cam, uv):
     return out, flag
 
 
+IMAGE_REFERENCE, IMAGE_BILINEAR = 0, 1              # ECAL_IMAGE_REFERENCE / _BILINEAR
+DISTORT_INVALID, DISTORT_NOT_CONVERGED = 1, 2       # ECAL_DISTORT_INVALID / _NOT_CONVERGED
+
+
+class ImageOptions(ctypes.Structure):
+    """ecal_image_options (include/ecal.h, image undistortion)."""
+    _fields_ = [("method", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32),
+                ("normalize", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"method": int(self.method), "channels": int(self.channels), "out_width": int(self.out_width), "out_height": int(self.out_height),
+                "normalize": int(self.normalize), "off_x": float(self.off_x), "off_y": float(self.off_y)}
+
+
+class ImageInfo(ctypes.Structure):
+    """ecal_image_info (include/ecal.h, image undistortion)."""
+    _fields_ = [("opt", ImageOptions), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("n_invalid_sources", ctypes.c_uint64),
+                ("n_empty", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("max_neighbours", ctypes.c_uint32), ("truncated", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint64), ("r_lim", ctypes.c_double), ("n_invalid", ctypes.c_uint64), ("n_not_converged", ctypes.c_uint64)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_[1:]}
+        d["options"] = self.opt.as_dict()
+        return d
+
+
+def image_reference_options(width, height):
+    """ecal_image_reference_options: the reference's canvas, round(1.2 * size) with offsets round(size * 0.1), 3 channels, normalize 1,
+    REFERENCE"""
+    L = load_library()
+    L.ecal_image_reference_options.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions)]
+    L.ecal_image_reference_options.restype = None
+    o = ImageOptions()
+    L.ecal_image_reference_options(int(width), int(height), ctypes.byref(o))
+    return o
+
+
+def image_options(method=None, channels=None, out_width=None, out_height=None, normalize=None, off_x=None, off_y=None, reserved=None,
+                  sensor=None, reference_canvas=False):
+    """ecal_image_options.  sensor=(width, height): the canvas is the sensor's own (BILINEAR, normalize 0, no offsets), or with
+    reference_canvas=True the reference's (REFERENCE, 3 channels, normalize 1); "reference" / "bilinear" or the number for method.
+    An ImageOptions is handed through."""
+    if isinstance(method, ImageOptions):
+        return method
+    if sensor is not None and reference_canvas:
+        o = image_reference_options(*sensor)
+    else:
+        o = ImageOptions(IMAGE_BILINEAR, 1, 0, 0, 0, 0, 0.0, 0.0)
+        if sensor is not None:
+            o.out_width, o.out_height = int(sensor[0]), int(sensor[1])
+    if method is not None:
+        o.method = {"reference": IMAGE_REFERENCE, "bilinear": IMAGE_BILINEAR}[method.lower()] if isinstance(method, str) else int(method)
+    for name, value in (("channels", channels), ("out_width", out_width), ("out_height", out_height), ("normalize", normalize), ("reserved", reserved)):
+        if value is not None:
+            setattr(o, name, int(value))
+    if off_x is not None:
+        o.off_x = float(off_x)
+    if off_y is not None:
+        o.off_y = float(off_y)
+    return o
+
+
+def image_options_error(opt):
+    """ecal_image_options_error: None, or the text that names the refused field"""
+    L = load_library()
+    L.ecal_image_options_error.argtypes, L.ecal_image_options_error.restype = [ctypes.POINTER(ImageOptions)], ctypes.c_char_p
+    r = L.ecal_image_options_error(ctypes.byref(opt) if opt is not None else None)
+    return r.decode() if r else None
+
+
+def _image_sensor_error(width, height):
+    if not 1 <= int(width) <= 8192:
+        return "width from 1 to 8192"
+    if not 1 <= int(height) <= 8192:
+        return "height from 1 to 8192"
+    return None
+
+
+def _image_host_fail(L, st, who, cam, width, height, opt):
+    why = undistort_camera_error(cam) or _image_sensor_error(width, height) or (image_options_error(opt) if opt is not None else None)
+    raise EcalError(st, L.ecal_strerror(st).decode() + ": " + who + ": " + (why or "null pointer or the wrong method"))
+
+
+def camera_monotone_radius(cam, width, height):
+    """ecal_camera_monotone_radius -> (r_lim, truncated): the normalised sensor radius up to which the forward projection inverts"""
+    L = load_library()
+    L.ecal_camera_monotone_radius.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_uint32)]
+    L.ecal_camera_monotone_radius.restype = ctypes.c_int
+    r, t = ctypes.c_double(0.0), ctypes.c_uint32(0)
+    st = L.ecal_camera_monotone_radius(ctypes.byref(cam), max(0, int(width)), max(0, int(height)), ctypes.byref(r), ctypes.byref(t))
+    if st != 0:
+        _image_host_fail(L, st, "ecal_camera_monotone_radius", cam, width, height, None)
+    return float(r.value), int(t.value)
+
+
+def distort_points_host(cam, width, height, uv):
+    """ecal_distort_points_host (host arrays; no context, no device): uv [n, 2] of the ideal camera -> (out [n, 2] float64 sensor
+    pixels with 0, 0 where invalid, flag uint8 [n]: 0, DISTORT_INVALID or DISTORT_NOT_CONVERGED)."""
+    L = load_library()
+    L.ecal_distort_points_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_void_p]
+    L.ecal_distort_points_host.restype = ctypes.c_int
+    uv = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
+    n = uv.shape[0]
+    out = np.zeros((n, 2), np.float64)
+    flag = np.zeros(n, np.uint8)
+    st = L.ecal_distort_points_host(ctypes.byref(cam), max(0, int(width)), max(0, int(height)), uv.ctypes.data if n else None, n,
+                                    out.ctypes.data if n else None, flag.ctypes.data if n else None)
+    if st != 0:
+        _image_host_fail(L, st, "ecal_distort_points_host", cam, width, height, None)
+    return out, flag
+
+
+def _frames_arg(images, width, height, channels):
+    """uint8 [H, W], [H, W, C] or [N, H, W, C] -> ([N, H, W, C] contiguous, the rank it came with)"""
+    a = np.asarray(images)
+    if a.dtype != np.uint8:
+        raise ValueError("images must be uint8")
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    elif rank != 4:
+        raise ValueError("images: (H, W), (H, W, C) or (N, H, W, C)")
+    if a.shape[1:] != (int(height), int(width), int(channels)):
+        raise ValueError("images of %s do not match the sensor %d x %d with %d channel(s)" % (a.shape[1:], int(width), int(height), int(channels)))
+    return np.ascontiguousarray(a), rank
+
+
+def _frames_result(out, rank):
+    return out[0, :, :, 0] if rank == 2 else (out[0] if rank == 3 else out)
+
+
+def undistort_image_host(cam, width, height, image, opt=None, **options):
+    """ecal_undistort_image_host (host arrays; no context, no device): ONE frame uint8 [H, W] or [H, W, C] -> (picture uint8 of the same
+    rank on the canvas, minmax float32 [2], info dict).  opt an ImageOptions, or options for image_options."""
+    L = load_library()
+    L.ecal_undistort_image_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ImageInfo)]
+    L.ecal_undistort_image_host.restype = ctypes.c_int
+    o = opt if opt is not None else image_options(**options)
+    if image_options_error(o) or _image_sensor_error(width, height):
+        _image_host_fail(L, -1, "ecal_undistort_image_host", cam, width, height, o)
+    a, rank = _frames_arg(image, width, height, o.channels)
+    if rank == 4 or a.shape[0] != 1:
+        raise ValueError("one frame")
+    out = np.zeros((1, int(o.out_height), int(o.out_width), int(o.channels)), np.uint8)
+    mm = np.zeros(2, np.float32)
+    info = ImageInfo()
+    st = L.ecal_undistort_image_host(ctypes.byref(cam), int(width), int(height), ctypes.byref(o), a.ctypes.data, out.ctypes.data, mm.ctypes.data,
+                                     ctypes.byref(info))
+    if st != 0:
+        _image_host_fail(L, st, "ecal_undistort_image_host", cam, width, height, o)
+    return _frames_result(out, rank), mm, info.as_dict()
+
+
+def image_table_host(cam, width, height, opt=None, **options):
+    """ecal_image_table_host: the REFERENCE table of the host walk -> (off uint32 [canvas pixels + 1], idx uint32 [n], w float64 [n],
+    info dict)"""
+    L = load_library()
+    L.ecal_image_table_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ImageInfo)]
+    L.ecal_image_table_host.restype = ctypes.c_int
+    o = opt if opt is not None else image_options(**options)
+    if image_options_error(o) or _image_sensor_error(width, height):
+        _image_host_fail(L, -1, "ecal_image_table_host", cam, width, height, o)
+    off = np.zeros(int(o.out_width) * int(o.out_height) + 1, np.uint32)
+    cap = 13 * int(width) * int(height)   # a source neighbours at most 13 canvas pixels
+    idx, w = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+    info = ImageInfo()
+    st = L.ecal_image_table_host(ctypes.byref(cam), int(width), int(height), ctypes.byref(o), off.ctypes.data, idx.ctypes.data, w.ctypes.data, cap,
+                                 ctypes.byref(info))
+    if st != 0:
+        _image_host_fail(L, st, "ecal_image_table_host", cam, width, height, o)
+    n = int(info.n_entries)
+    return off, idx[:n].copy(), w[:n].copy(), info.as_dict()
+
+
+def image_maps_host(cam, width, height, opt=None, **options):
+    """ecal_image_maps_host: the BILINEAR maps of the host walk -> (map_x, map_y float32 [out_height, out_width], valid uint8, info dict)"""
+    L = load_library()
+    L.ecal_image_maps_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ImageInfo)]
+    L.ecal_image_maps_host.restype = ctypes.c_int
+    o = opt if opt is not None else image_options(**options)
+    if image_options_error(o) or _image_sensor_error(width, height):
+        _image_host_fail(L, -1, "ecal_image_maps_host", cam, width, height, o)
+    shape = (int(o.out_height), int(o.out_width))
+    mx, my, valid = np.zeros(shape, np.float32), np.zeros(shape, np.float32), np.zeros(shape, np.uint8)
+    info = ImageInfo()
+    st = L.ecal_image_maps_host(ctypes.byref(cam), int(width), int(height), ctypes.byref(o), mx.ctypes.data, my.ctypes.data, valid.ctypes.data,
+                                ctypes.byref(info))
+    if st != 0:
+        _image_host_fail(L, st, "ecal_image_maps_host", cam, width, height, o)
+    return mx, my, valid, info.as_dict()
+
+
+class ImagePlan:
+    """An ecal_image_plan of a Context (Context.image_plan): the method's tables on the device for one camera, sensor and canvas."""
+
+    def __init__(self, ctx, cam, width, height, opt):
+        L = ctx._L
+        vp = ctypes.c_void_p
+        L.ecal_image_plan_create.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
+                                             ctypes.POINTER(vp)]
+        L.ecal_image_plan_create.restype = ctypes.c_int
+        L.ecal_image_plan_destroy.argtypes, L.ecal_image_plan_destroy.restype = [vp], None
+        L.ecal_image_plan_info.argtypes, L.ecal_image_plan_info.restype = [vp, ctypes.POINTER(ImageInfo)], ctypes.c_int
+        L.ecal_image_plan_maps.argtypes, L.ecal_image_plan_maps.restype = [vp, vp, vp, vp], ctypes.c_int
+        L.ecal_image_plan_maps_dev.argtypes, L.ecal_image_plan_maps_dev.restype = [vp, vp, vp, vp, vp], ctypes.c_int
+        L.ecal_image_plan_table.argtypes, L.ecal_image_plan_table.restype = [vp, vp, vp, vp], ctypes.c_int
+        L.ecal_undistort_images.argtypes, L.ecal_undistort_images.restype = [vp, vp, vp, ctypes.c_uint32, vp, vp], ctypes.c_int
+        L.ecal_undistort_images_dev.argtypes, L.ecal_undistort_images_dev.restype = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp], ctypes.c_int
+        self._ctx, self._L, self._h = ctx, L, None
+        self.width, self.height = int(width), int(height)
+        h = vp()
+        ctx._check(L.ecal_image_plan_create(ctx._h, ctypes.byref(cam), max(0, int(width)), max(0, int(height)), ctypes.byref(opt), ctypes.byref(h)))
+        self._h = h
+        info = ImageInfo()
+        ctx._check(L.ecal_image_plan_info(h, ctypes.byref(info)))
+        self._info = info
+        self.options = info.opt
+
+    @property
+    def info(self):
+        return self._info.as_dict()
+
+    def close(self):
+        if self._h is not None and self._ctx._h is not None:
+            self._L.ecal_image_plan_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _shape(self):
+        return int(self.options.out_height), int(self.options.out_width)
+
+    def maps(self):
+        """ecal_image_plan_maps -> (map_x, map_y float32 [out_height, out_width], valid uint8): cv::remap's CV_32FC1 maps (BILINEAR)"""
+        mx, my, valid = np.zeros(self._shape(), np.float32), np.zeros(self._shape(), np.float32), np.zeros(self._shape(), np.uint8)
+        self._ctx._check(self._L.ecal_image_plan_maps(self._h, mx.ctypes.data, my.ctypes.data, valid.ctypes.data))
+        return mx, my, valid
+
+    def maps_dev(self):
+        """ecal_image_plan_maps_dev -> (map_x, map_y float32 CUDA tensors [out_height, out_width], valid uint8 CUDA tensor)"""
+        import torch
+        dev = torch.device("cuda", self._ctx.device)
+        mx, my = torch.empty(self._shape(), dtype=torch.float32, device=dev), torch.empty(self._shape(), dtype=torch.float32, device=dev)
+        valid = torch.empty(self._shape(), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            self._ctx._check(self._L.ecal_image_plan_maps_dev(self._h, mx.data_ptr(), my.data_ptr(), valid.data_ptr(),
+                                                              torch.cuda.current_stream().cuda_stream))
+            torch.cuda.synchronize()
+        return mx, my, valid
+
+    def table(self):
+        """ecal_image_plan_table -> (off uint32 [canvas pixels + 1], idx uint32 [n_entries], w float64 [n_entries]) (REFERENCE)"""
+        n = int(self._info.n_entries)
+        off = np.zeros(self._shape()[0] * self._shape()[1] + 1, np.uint32)
+        idx, w = np.zeros(n, np.uint32), np.zeros(n, np.float64)
+        self._ctx._check(self._L.ecal_image_plan_table(self._h, off.ctypes.data, idx.ctypes.data if n else None, w.ctypes.data if n else None))
+        return off, idx, w
+
+    def apply(self, images, minmax=False):
+        """ecal_undistort_images: uint8 host frames [H, W], [H, W, C] or [N, H, W, C] -> the pictures, the same rank, on the canvas
+        (with minmax=True: also float32 [N, 2], every frame's min and max before the rounding)"""
+        a, rank = _frames_arg(images, self.width, self.height, self.options.channels)
+        n = a.shape[0]
+        out = np.zeros((n,) + self._shape() + (int(self.options.channels),), np.uint8)
+        mm = np.zeros((n, 2), np.float32)
+        self._ctx._check(self._L.ecal_undistort_images(self._ctx._h, self._h, a.ctypes.data if n else None, n, out.ctypes.data if n else None,
+                                                       mm.ctypes.data if minmax and n else None))
+        return (_frames_result(out, rank), mm) if minmax else _frames_result(out, rank)
+
+    def apply_dev(self, tensor, minmax=False):
+        """ecal_undistort_images_dev on a uint8 CUDA tensor [N, H, W, C] already on the device -> a uint8 CUDA tensor
+        [N, out_height, out_width, C] (with minmax=True: also a float32 CUDA tensor [N, 2]); waits for the result."""
+        import torch
+        C = int(self.options.channels)
+        if tensor.dtype != torch.uint8 or tensor.dim() != 4 or tuple(tensor.shape[1:]) != (self.height, self.width, C):
+            raise ValueError("a uint8 CUDA tensor [N, %d, %d, %d]" % (self.height, self.width, C))
+        t = tensor.contiguous()
+        n = t.shape[0]
+        out = torch.empty((n,) + self._shape() + (C,), dtype=torch.uint8, device=t.device)
+        mm = torch.empty((n, 2), dtype=torch.float32, device=t.device)
+        with torch.cuda.device(t.device):
+            self._ctx._check(self._L.ecal_undistort_images_dev(self._ctx._h, self._h, t.data_ptr() if n else None, n, out.data_ptr() if n else None,
+                                                               mm.data_ptr() if minmax and n else None, torch.cuda.current_stream().cuda_stream))
+            torch.cuda.synchronize()
+        return (out, mm) if minmax else out
+
+
 def fields_options(time_magnitude=None, time_base=None, auto_time_base=False, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
                    end_time=None):
     """ecal_fields_options from ecal_fields_default_options (time_magnitude 1e-6, time_base 0, no size, no flips, start_time 0, no end
@@ -783,6 +1088,8 @@ class Context:
 
     def close(self):
         self._calibrate_pipe = None   # (calibrate.calibrate_stream keeps its detection pipeline's arrays with the context)
+        for plan in list(getattr(self, "_image_plans", ())):   # (a plan belongs to its context and goes before it)
+            plan.close()
         if getattr(self, "_h", None):
             _live_contexts.discard(self)
             self._L.ecal_destroy(self._h)
@@ -2064,6 +2371,46 @@ class Context:
         finally:
             L.ecal_stream_destroy(h_in)
         return rgb, tot
+
+    # ---- image undistortion (ecal_image_plan_*, ecal_undistort_images*, ecal_distort_points_dev) ----
+    def image_plan(self, cam, width, height, opt=None, **options):
+        """ecal_image_plan_create -> an ImagePlan with .info, .maps(), .table(), .apply(images), .apply_dev(tensor), .close().  opt an
+        ImageOptions, or options for image_options (method, channels, out_width, out_height, normalize, off_x, off_y,
+        reference_canvas); without a canvas the sensor's own size is taken."""
+        import weakref
+        if opt is None:
+            options.setdefault("sensor", (width, height))
+            opt = image_options(**options)
+        plan = ImagePlan(self, cam, width, height, opt)
+        if not hasattr(self, "_image_plans"):
+            self._image_plans = weakref.WeakSet()
+        self._image_plans.add(plan)
+        return plan
+
+    def distort_points_dev(self, cam, width, height, d_uv, n, d_out, d_flag, stream=0):
+        """ecal_distort_points_dev: raw device pointers; d_uv and d_out [n][2] f64, d_flag [n] u8; no host synchronisation."""
+        L = self._L
+        vp = ctypes.c_void_p
+        L.ecal_distort_points_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]
+        L.ecal_distort_points_dev.restype = ctypes.c_int
+        self._check(L.ecal_distort_points_dev(self._h, ctypes.byref(cam), max(0, int(width)), max(0, int(height)), d_uv, int(n), d_out, d_flag, stream))
+
+    def distort_points(self, cam, width, height, uv):
+        """The forward projection on the device: uv [n, 2] of the ideal camera (a host array or a float64 CUDA tensor) -> (out: float64
+        CUDA tensor [n, 2] of sensor pixels with 0, 0 where invalid, flag: uint8 CUDA tensor [n]).  RADIAL: bit for bit
+        distort_points_host."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = uv if isinstance(uv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2)))
+        t = t.to(device=dev, dtype=torch.float64).reshape(-1, 2).contiguous()
+        n = t.shape[0]
+        out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        flag = torch.empty(n, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            self.distort_points_dev(cam, width, height, t.data_ptr() if n else None, n, out.data_ptr() if n else None,
+                                    flag.data_ptr() if n else None, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        return out, flag
 
     def slice_events_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                          d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, stream=0):

@@ -126,6 +126,9 @@ struct ecal_ctx {
     ecal_devbuf undistort_results; // ecal_stream_undistort: the totals, the count
     ecal_devbuf undistort_bits;    // ecal_undistorted_frames_dev: the windows' presence bits when a canvas does not fit LDS
     ecal_devbuf undistort_frames;  // ecal_stream_undistorted_frames: the pictures and the per-window totals before their download
+    ecal_devbuf image_scratch;     // ecal_image_plan_create: positions, sort keys and indices, the start table, per-block counts / offsets, the counters
+    ecal_devbuf image_values;      // ecal_undistort_images_dev: the frames' min / max bits, the workgroups' min / max pairs, the f32 values before their rounding to u8
+    ecal_devbuf image_io;          // ecal_undistort_images: the frames, the pictures and min / max around their transfers
     ecal_devbuf aedat4_tables;    // aedat4 ingest: the packets' inflated sizes, spans, located events, first slots, the counters
     ecal_devbuf aedat4_inflated;   // aedat4 ingest: the inflated packets, each in its span (padded to 16 bytes)
     ecal_devbuf aedat4_blocks;     // aedat4 ingest: per-block kept counts / offsets

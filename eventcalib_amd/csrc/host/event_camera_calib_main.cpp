@@ -16,6 +16,8 @@
 
 #include "event_calib_spline.hpp"
 #include "png_writer.hpp"
+#include "npy_writer.hpp"
+#include "pinhole_camera.hpp"
 
 int main(int argc, char **argv) {
     using namespace opengv2;
@@ -405,6 +407,14 @@ int main(int argc, char **argv) {
     fsSettings["UndistortedEvents_Pixel"] >> wantUndistortedPixel;
     fsSettings["UndistortedImages"] >> wantUndistortedImages;
     const bool wantUndistort = wantUndistortedEvents || wantUndistortedImages;
+    // UndistortMaps / UndistortMaps_Reference (keys of this build, optional): the solved camera's rectification maps (include/ecal.h,
+    // "image undistortion": cv::initUndistortRectifyMap's CV_32FC1 convention, ready for cv::remap).  UndistortMaps: 1 writes
+    // saveDir/undistort_map_x.npy and undistort_map_y.npy (f32 (out_height, out_width), numpy.load reads them) on the sensor's own canvas —
+    // with UndistortMaps_Reference: 1 on the reference's (round(1.2 * size), offsets round(size * 0.1)) — and saveDir/UndistortMaps.txt.
+    // Absent or 0: nothing changes
+    int wantUndistortMaps = 0, wantUndistortMapsReference = 0;
+    fsSettings["UndistortMaps"] >> wantUndistortMaps;
+    fsSettings["UndistortMaps_Reference"] >> wantUndistortMapsReference;
     EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
                             wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort);
     const double *x = spline.intrinsics();
@@ -506,6 +516,37 @@ int main(int argc, char **argv) {
         }
         std::fclose(f);
         container->release();
+    }
+    if (wantUndistortMaps) {
+        std::vector<float> mapX, mapY;
+        ecal_image_info info;
+        try {
+            PinholeCamera solved({(double) width, (double) height}, {x[0], 0.0, x[2], 0.0, x[1], x[3], 0.0, 0.0, 1.0},
+                                 std::vector<double>(x + 4, x + 9), cs->useFisheye);
+            info = solved.undistortMaps(mapX, mapY, wantUndistortMapsReference != 0);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 4;
+        }
+        const ecal_image_options &o = info.opt;
+        const std::string dir = argv[3];
+        std::FILE *f = std::fopen((dir + "/UndistortMaps.txt").c_str(), "w");
+        if (!f || !ecal_host::write_npy_f32(dir + "/undistort_map_x.npy", o.out_height, o.out_width, mapX.data()) ||
+            !ecal_host::write_npy_f32(dir + "/undistort_map_y.npy", o.out_height, o.out_width, mapY.data())) {
+            std::fprintf(stderr, "cannot write the undistortion maps under %s\n", argv[3]);
+            if (f) std::fclose(f);
+            return 3;
+        }
+        std::fprintf(f, "model %d\nintrinsics %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\nout_k %.17g %.17g %.17g %.17g\n",
+                     cs->useFisheye ? ECAL_CAMERA_FISHEYE : ECAL_CAMERA_RADIAL, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[0], x[1], x[2],
+                     x[3]);
+        std::fprintf(f, "options method %u channels %u out_width %u out_height %u normalize %u off_x %.17g off_y %.17g\n", o.method, o.channels,
+                     o.out_width, o.out_height, o.normalize, o.off_x, o.off_y);
+        std::fprintf(f, "info width %u height %u r_lim %.17g truncated %u n_invalid %llu n_not_converged %llu n_empty %llu bytes %llu\n", info.width,
+                     info.height, info.r_lim, info.truncated, (unsigned long long) info.n_invalid, (unsigned long long) info.n_not_converged,
+                     (unsigned long long) info.n_empty, (unsigned long long) info.bytes);
+        std::fclose(f);
+        std::printf("undistort maps %u x %u invalid %llu\n", o.out_width, o.out_height, (unsigned long long) info.n_invalid);
     }
     if (wantReport && spline.report().valid) {
         const EventCalibSpline::Report &rp = spline.report();

@@ -1832,6 +1832,124 @@ int ecal_stream_undistorted_frames(ecal_ctx *ctx, const ecal_stream *es, const e
                                    const double *t0, const double *t1, uint32_t S, uint8_t *rgb /*HOST*/,
                                    ecal_undistort_frame_totals *totals /*HOST [S], or NULL*/);
 
+/* ---- image undistortion: u8 frames on the ideal pinhole camera's canvas, rectification maps, the forward projection ----
+ * Applies the solved camera (ecal_undistort_camera, as above; ud_point is the rule of the "undistortion" section) to pictures taken
+ * through the same lens: batches of interleaved u8 frames [N][H][W][C], C = 1 or 3.  Two methods.  REFERENCE is the reference's
+ * PinholeCamera::undistortImage (core/sensor/src/PinholeCamera.cpp:128-214): every source pixel is carried to the canvas, and a canvas
+ * pixel is the inverse-squared-distance average of the carried pixels within 2 px of it.  BILINEAR goes the other way: the forward
+ * projection (ideal pixel -> sensor pixel) gives cv::initUndistortRectifyMap's CV_32FC1 maps for the new camera out_k shifted by the
+ * offsets, ready for cv::remap, and a canvas pixel is the bilinear sample of the source there.  OpenCV's own float paths (cv::Mat
+ * arithmetic, cv::normalize, cv::remap's fixed-point interpolation) are NOT reproduced bit for bit: parity unpinned, as for the other
+ * OpenCV calls.  eventcalib_amd/csrc/image_undistort.hpp restates the rules for host and device; design/22_image_undistort.md has the
+ * reasoning and what was measured.  Opt-in: nothing else in this header calls it.  Every operation below is ONE IEEE f64 or f32
+ * operation, rounded on its own: no FMA.  tan (ud_point) and atan (FISHEYE only) are the operations that are not correctly rounded.
+ *
+ * The options: method ECAL_IMAGE_REFERENCE | ECAL_IMAGE_BILINEAR, channels 1 | 3, out_width / out_height 1 .. 8192, normalize 0 | 1,
+ *   reserved 0, finite offsets; else ECAL_ERR_INVALID with the field named (ecal_image_options_error without a context; a NULL
+ *   options pointer is refused too).  The sensor: width, height 1 .. 8192.  ecal_image_reference_options: the reference's canvas
+ *   (PinholeCamera.cpp:132-135): out = round_half_away(1.2 * size), off = round_half_away(size * 0.1) — ROUNDED, unlike the event
+ *   frames' —, 3 channels, normalize 1, REFERENCE: 346 x 260 -> 415 x 312, off 35, 26.
+ *
+ * REFERENCE.  Source pixel idx = row * W + col stands at (cu, cv) = ud_point(cam, col, row) + (off_x, off_y); an invalid source pixel
+ *   takes part nowhere (n_invalid_sources), and so does one with floor(cu) outside -2 .. out_width + 1 or floor(cv) outside
+ *   -2 .. out_height + 1 (it neighbours nothing).  Canvas pixel (j, i) takes every source pixel with
+ *       dx = j - cu;  dy = i - cv;  d2 = dx*dx + dy*dy;   d2 < 4.0   (strict: nanoflann's radius result set, squared L2)
+ *       w = 1.0 / max(d2, 100 * DBL_EPSILON)
+ *   in the order ascending (floor(cv), floor(cu), idx) — the reference's is its kd-tree's traversal (sorted = false), which cannot
+ *   be pinned.  Per channel, over the neighbours in that order:  acc_f32 = acc_f32 + (float)(w * (double) v);  wsum_f64 = wsum_f64 + w;
+ *   then avg = (float)((double) acc * (1.0 / wsum)), and 0 for a pixel without a neighbour (n_empty).
+ * To u8, both methods.  normalize 1 is cv::normalize(NORM_MINMAX, 0 .. 255) over all channels and pixels of ONE frame, empty ones
+ *   included:  span = (double) max - (double) min;  scale = span > DBL_EPSILON ? 255.0 / span : 0.0;
+ *   out = (u8) rint((double) val * scale - (double) min * scale), ties to even.  normalize 0: out = (u8) round_half_away(val).  Both
+ *   saturate at 0 and 255.
+ *
+ * The forward projection.  With s = r*r, s2 = s*s, s3 = s2*s, s4 = s3*s, s5 = s4*s:
+ *       poly(s) = ((((1 + k1*s) + k2*s2) + k3*s3) + k4*s4) + k5*s5
+ *       dp(s)   = (((k1 + (2*k2)*s) + (3*k3)*s2) + (4*k4)*s3) + (5*k5)*s4
+ *       g(r)    = r * poly(r*r);      g'(r) = poly(s) + (2*s) * dp(s)
+ *   The limit r_lim, once per camera and sensor on the host (ecal_camera_monotone_radius): 1.05 x the largest of
+ *   sqrt(x*x + y*y), x = (u - cx) / fx, y = (v - cy) / fy over the four outer corners (-0.5 | W - 0.5, -0.5 | H - 0.5); g' is sampled at
+ *   (r_lim * m) / 4096, m = 1 .. 4096, and at the first sample with !(g' > 0) r_lim falls to the sample before it and truncated = 1.
+ *   A point (u', v') of the ideal camera:
+ *       xu = (u' - cx') / fx';  yu = (v' - cy') / fy';  rho2 = xu*xu + yu*yu
+ *       rho2 <= 1e-16: u = fx * (xu * 1) + cx,  v = fy * (yu * 1) + cy, valid, never flagged
+ *       else: rho = sqrt(rho2);  T = rho (RADIAL) | atan(rho) (FISHEYE);  valid iff T <= g(r_lim)
+ *             r = T * (r_lim / g(r_lim));  EIGHT times:  r = r - (g(r) - T) / g'(r);  r = r < 0 ? 0 : r;  r = r > r_lim ? r_lim : r
+ *             (the count is fixed: no early exit);  ECAL_DISTORT_NOT_CONVERGED iff |g(r) - T| * max(fx, fy) > 1e-9
+ *             u = fx * (xu * (r / rho)) + cx;  v = fy * (yu * (r / rho)) + cy
+ *   valid also needs u, v finite; a NaN anywhere makes the point invalid (the comparisons are false on it).  flag: 0,
+ *   ECAL_DISTORT_INVALID (out is 0, 0) or ECAL_DISTORT_NOT_CONVERGED (out is written all the same).
+ * BILINEAR.  map_x, map_y (f32 [out_height][out_width]) and valid (u8): for canvas pixel (X, Y), (u, v) = distort(X - off_x, Y - off_y),
+ *   map = ((float) u, (float) v), and (-1, -1) with valid 0 for an invalid point.  Per channel, in f32:
+ *       x0 = floorf(mx);  ax = mx - x0;  y0 = floorf(my);  ay = my - y0;   a tap off the sensor is 0
+ *       val = (s00*(1-ax) + s01*ax)*(1-ay) + (s10*(1-ax) + s11*ax)*ay      (s00 at (x0, y0), s01 at (x0+1, y0), s10 at (x0, y0+1))
+ *
+ * ecal_image_plan_create: builds the method's tables on the device, on the context's stream, and waits: REFERENCE the table of
+ *   (u32 idx, f64 w) entries in the stated order with a first-entry word per canvas pixel, BILINEAR the maps.  ecal_image_plan_info:
+ *   the options in force, the sensor, n_invalid_sources / n_empty (canvas pixels with no source; BILINEAR: the invalid ones) /
+ *   n_entries / max_neighbours, the device bytes held, and for BILINEAR r_lim, truncated, n_invalid, n_not_converged.  A plan belongs
+ *   to its context and must be destroyed before it.  ECAL_ERR_RANGE for what could hold more than 2^32-1 table entries (a source
+ *   neighbours at most 13 canvas pixels: no sensor of 8192 a side gets there).
+ * ecal_image_plan_maps_dev / _maps (HOST; waits): copy the maps out (any pointer may be NULL); ECAL_ERR_INVALID for a REFERENCE plan.
+ * ecal_image_plan_table (HOST; waits): off [canvas pixels + 1], idx / w [n_entries]; ECAL_ERR_INVALID for a BILINEAR plan.
+ * ecal_undistort_images_dev: d_src [N][H][W][C] -> d_dst [N][out_height][out_width][C]; d_minmax [N][2] f32 (or NULL): every frame's
+ *   min and max of val before the rounding.  Any alignment; enqueues on `stream` and does not synchronise; N == 0 is valid; more than
+ *   2^32-1 frames x canvas pixels, or more than 262140 frames, is ECAL_ERR_RANGE, before anything is launched.
+ * ecal_undistort_images: the same with HOST arrays on the context's stream; waits.
+ * ecal_undistort_image_host: ONE frame, HOST arrays, no context, no device: one sequential walk per method — the statement of the
+ *   rule.  minmax [2] and info may be NULL (info.bytes is 0).  ecal_image_table_host / ecal_image_maps_host: the table (entries behind
+ *   `capacity` are not written; info.n_entries says how many there are) and the maps of that walk.
+ * ecal_distort_points_host / _dev: uv [n][2] f64 of the ideal camera -> out [n][2] (0, 0 where invalid), flag [n]. */
+#define ECAL_IMAGE_REFERENCE 0
+#define ECAL_IMAGE_BILINEAR 1
+#define ECAL_DISTORT_INVALID 1
+#define ECAL_DISTORT_NOT_CONVERGED 2
+typedef struct ecal_image_options {
+    uint32_t method;           /* ECAL_IMAGE_REFERENCE 0 | ECAL_IMAGE_BILINEAR 1 */
+    uint32_t channels;         /* 1 | 3, interleaved u8 */
+    uint32_t out_width, out_height;   /* the canvas, 1 .. 8192 */
+    uint32_t normalize;        /* 1: min-max of every frame to 0 .. 255 */
+    uint32_t reserved;
+    double off_x, off_y;       /* canvas = ideal pixel + offset */
+} ecal_image_options;
+typedef struct ecal_image_info {
+    ecal_image_options opt;
+    uint32_t width, height;
+    uint64_t n_invalid_sources, n_empty, n_entries;
+    uint32_t max_neighbours, truncated;
+    uint64_t bytes;
+    double r_lim;
+    uint64_t n_invalid, n_not_converged;
+} ecal_image_info;
+typedef struct ecal_image_plan ecal_image_plan;
+void ecal_image_reference_options(uint32_t width, uint32_t height, ecal_image_options *opt);
+const char *ecal_image_options_error(const ecal_image_options *opt);   /* NULL: fine; else the refused field (a static string) */
+int ecal_camera_monotone_radius(const ecal_undistort_camera *cam, uint32_t width, uint32_t height, double *r_lim, uint32_t *truncated);
+int ecal_distort_points_host(const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const double *uv /*HOST [n][2]*/, uint64_t n,
+                             double *out /*HOST [n][2]*/, uint8_t *flag /*HOST [n]*/);
+int ecal_distort_points_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const double *d_uv /*[n][2]*/,
+                            uint64_t n, double *d_out /*[n][2]*/, uint8_t *d_flag /*[n]*/, void *stream);
+int ecal_undistort_image_host(const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const ecal_image_options *opt,
+                              const uint8_t *src /*HOST [H][W][C]*/, uint8_t *dst /*HOST [oh][ow][C]*/, float *minmax /*HOST [2], or NULL*/,
+                              ecal_image_info *info /*or NULL*/);
+int ecal_image_table_host(const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const ecal_image_options *opt,
+                          uint32_t *off /*HOST [oh * ow + 1]*/, uint32_t *idx /*HOST [capacity]*/, double *w /*HOST [capacity]*/, uint64_t capacity,
+                          ecal_image_info *info /*or NULL*/);
+int ecal_image_maps_host(const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const ecal_image_options *opt,
+                         float *map_x /*HOST [oh][ow]*/, float *map_y, uint8_t *valid /*or NULL*/, ecal_image_info *info /*or NULL*/);
+int ecal_image_plan_create(ecal_ctx *ctx, const ecal_undistort_camera *cam, uint32_t width, uint32_t height, const ecal_image_options *opt,
+                           ecal_image_plan **plan);
+void ecal_image_plan_destroy(ecal_image_plan *plan);
+int ecal_image_plan_info(const ecal_image_plan *plan, ecal_image_info *info);
+int ecal_image_plan_maps_dev(const ecal_image_plan *plan, float *d_map_x, float *d_map_y, uint8_t *d_valid, void *stream);
+int ecal_image_plan_maps(const ecal_image_plan *plan, float *map_x /*HOST*/, float *map_y /*HOST*/, uint8_t *valid /*HOST*/);
+int ecal_image_plan_table(const ecal_image_plan *plan, uint32_t *off /*HOST [oh * ow + 1]*/, uint32_t *idx /*HOST [n_entries]*/,
+                          double *w /*HOST [n_entries]*/);
+int ecal_undistort_images_dev(ecal_ctx *ctx, const ecal_image_plan *plan, const uint8_t *d_src /*[N][H][W][C]*/, uint32_t n_frames,
+                              uint8_t *d_dst /*[N][oh][ow][C]*/, float *d_minmax /*[N][2], or NULL*/, void *stream);
+int ecal_undistort_images(ecal_ctx *ctx, const ecal_image_plan *plan, const uint8_t *src /*HOST*/, uint32_t n_frames, uint8_t *dst /*HOST*/,
+                          float *minmax /*HOST [N][2], or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
