@@ -285,7 +285,8 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
                      frames_to_use=200, width=346.0, height=260.0, rows=9, cols=4, square=5.5, circle_radius=1.75,
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
-                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None, undistort_maps=None):
+                     refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None, undistort_maps=None,
+                     report_px=False):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -306,6 +307,9 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     spline's start) that tests/test_gpu_oracle_chain.py compares with the CPU oracle chain.
     report: also bin the residuals at the solution on the GPU (capi.Solver.report: per keyframe of the splines, per circle of
     the board, per 16-pixel cell of the sensor, histogram; board units) into out["report"] — a stage of its own, `report`.
+    report_px (opt-in, default False: nothing changes): the same report in PIXELS (capi.Solver.report_px: per residual the
+    first-order distance from the event to the projected rim; `rms_px`, `px_per_unit`, `n_degenerate` beside the families) into
+    out["report_px"] — a stage of its own, `report_px` (design/23_report_px.md).
     board_image: also carry EVERY event of the stream through the solution onto the board (capi.Solver.board_image: the
     motion-compensated image per polarity and the ring profile of every circle) into out["board_image"] — a stage of its own,
     `board_image`.
@@ -554,6 +558,10 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
         mark("lm_solve")
         out["report"] = solver.report(x, kf["time"][kf_idx], width=int(width), height=int(height))
         mark("report")
+    if report_px:
+        mark("lm_solve")
+        out["report_px"] = solver.report_px(x, kf["time"][kf_idx], width=int(width), height=int(height))
+        mark("report_px")
     if board_image:
         mark("lm_solve")
         out["board_image"] = solver.board_image(x, events)

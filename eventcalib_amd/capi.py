@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "ecal_associate_ranges_dev", "ecal_ref_nth_element_f64", "ecal_solver_create_from_stream", "ecal_rectify_keyframes", "ecal_solver_time_shard_cuts",
     "ecal_slice_events_packed_dev", "ecal_dbscan_batch_packed_dev", "ecal_extract_batch_packed_dev", "ecal_unpack_points_dev",
     "ecal_report_default_options", "ecal_solver_report_dev", "ecal_solver_report", "ecal_solver_num_landmarks",
+    "ecal_report_px_default_options", "ecal_solver_report_px_dev", "ecal_solver_report_px", "ecal_residuals_px_dev", "ecal_residuals_px",
     "ecal_board_image_default_options", "ecal_solver_board_image_dev", "ecal_solver_board_image", "ecal_solver_board_points_dev", "ecal_solver_board_points",
     "ecal_solver_reassociate_dev", "ecal_solver_reassociate", "ecal_solver_create_reassociated",
     "ecal_text_default_options", "ecal_events_from_text_dev", "ecal_text_count_lines_dev", "ecal_stream_create_from_text_file", "ecal_text_to_bin_file",
@@ -2646,6 +2647,8 @@ class ReportOptions(ctypes.Structure):
 BIN_STATS = np.dtype([("n", np.uint64), ("n_out", np.uint64), ("sum_r", np.float64), ("sum_r2", np.float64), ("sum_abs", np.float64),
                       ("max_abs", np.float64)])
 REPORT_TOTALS = np.dtype([("all", BIN_STATS), ("cost", np.float64)])
+# ecal_report_px_totals (the report in pixels)
+REPORT_PX_TOTALS = np.dtype([("all", BIN_STATS), ("n_degenerate", np.uint64), ("sum_px_per_unit", np.float64)])
 
 
 class BoardImageOptions(ctypes.Structure):
@@ -2688,6 +2691,16 @@ def _declare_solver(L):
     L.ecal_solver_report_dev.restype = i32
     L.ecal_solver_report.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp]
     L.ecal_solver_report.restype = i32
+    L.ecal_report_px_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
+    L.ecal_report_px_default_options.restype = None
+    L.ecal_solver_report_px_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.ecal_solver_report_px_dev.restype = i32
+    L.ecal_solver_report_px.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp]
+    L.ecal_solver_report_px.restype = i32
+    L.ecal_residuals_px_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.ecal_residuals_px_dev.restype = i32
+    L.ecal_residuals_px.argtypes = [vp, vp, vp, vp, vp]
+    L.ecal_residuals_px.restype = i32
     L.ecal_solver_num_landmarks.argtypes = [vp]
     L.ecal_solver_num_landmarks.restype = ctypes.c_uint32
     L.ecal_solver_create.argtypes = [vp, ctypes.POINTER(_SplineProblem), ctypes.POINTER(vp)]
@@ -2925,6 +2938,93 @@ class Solver:
         if hist is not None:
             out["hist"] = hist
             rng = o.hist_range if o.hist_range > 0 else 4.0 * self.huber_a
+            out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
+        return out
+
+    def residuals_px(self, params, with_gradient=False):
+        """ecal_residuals_px: the residuals in PIXELS, per record the first-order (Sampson) distance r / |d r / d (u, v)| from the
+        event to the projected rim (include/ecal.h, "report in pixels").  Returns (r_px [n_res], 0.0 where the record is
+        degenerate; grad [n_res, 2] = (d r / d u, d r / d v) or None; flag [n_res] uint8, 1 = degenerate)."""
+        p = np.ascontiguousarray(params, np.float64)
+        assert p.shape[0] == self.n_params
+        n = int(self.n_res)
+        r = np.zeros(max(n, 1))
+        g = np.zeros((max(n, 1), 2)) if with_gradient else None
+        f = np.zeros(max(n, 1), np.uint8)
+        self.ctx._check(self.ctx._L.ecal_residuals_px(self._h, _ptr(p), _ptr(r), _ptr(g) if with_gradient else None, _ptr(f)))
+        return r[:n], (g[:n] if with_gradient else None), f[:n]
+
+    def report_px_options(self, **options):
+        """ecal_report_px_default_options (346 x 260, 16 px cells, 64 bins, hist_range 4 px, outlier_thresh 1 px) with the given
+        ReportOptions members set."""
+        o = ReportOptions()
+        self.ctx._L.ecal_report_px_default_options(ctypes.byref(o))
+        for k, v in options.items():
+            if not hasattr(o, k):
+                raise TypeError("no report option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def report_px_dev(self, d_params, d_kf_time, n_keyframes, options, d_total, d_kf=None, d_lm=None, d_cell_n=None, d_cell_sum_r2=None,
+                      d_hist=None, stream=0):
+        """ecal_solver_report_px_dev: raw device pointers (None: that family is skipped), records laid out as BIN_STATS /
+        REPORT_PX_TOTALS; no host synchronisation."""
+        self.ctx._check(self.ctx._L.ecal_solver_report_px_dev(self._h, d_params, d_kf_time, int(n_keyframes),
+                                                              ctypes.byref(options) if options is not None else None, d_total, d_kf,
+                                                              d_lm, d_cell_n, d_cell_sum_r2, d_hist, stream))
+
+    def report_px(self, params, kf_time=None, families=("kf", "lm", "cells", "hist"), **options):
+        """ecal_solver_report_px: the residuals at `params` in PIXELS (residuals_px above) binned on the GPU.  Arguments and the
+        returned dict as report's — `totals` is one REPORT_PX_TOTALS record and there is no `cost` — plus `n_degenerate` (records
+        without a distance: in no bin), `px_per_unit` (the mean of 1 / |d r / d (u, v)|: how many pixels a board unit is in this
+        data; NaN without records) and `rms_px` (= `rms`)."""
+        p = np.ascontiguousarray(params, np.float64)
+        assert p.shape[0] == self.n_params
+        o = self.report_px_options(**options)
+        want = set(families)
+        if kf_time is None:
+            want.discard("kf")
+        kt = np.ascontiguousarray(kf_time, np.float64) if "kf" in want else None
+        total = np.zeros(1, REPORT_PX_TOTALS)
+        kf = np.zeros(kt.shape[0], BIN_STATS) if "kf" in want else None
+        lm = np.zeros(self.n_landmarks, BIN_STATS) if "lm" in want else None
+        cn = cs = hist = None
+        if "cells" in want and o.cell_px:
+            cy, cx = -(-o.height // o.cell_px), -(-o.width // o.cell_px)
+            cn, cs = np.zeros((cy, cx), np.uint64), np.zeros((cy, cx))
+        elif "cells" in want:
+            cn, cs = np.zeros((1, 1), np.uint64), np.zeros((1, 1))    # (the call refuses cell_px == 0)
+        if "hist" in want:
+            hist = np.zeros(max(int(o.hist_bins), 1), np.uint64)
+
+        def ptr(a):
+            return _ptr(a) if a is not None else None
+        self.ctx._check(self.ctx._L.ecal_solver_report_px(self._h, _ptr(p), ptr(kt), 0 if kt is None else kt.shape[0], ctypes.byref(o),
+                                                          _ptr(total), ptr(kf), ptr(lm), ptr(cn), ptr(cs), ptr(hist)))
+
+        def derived(out, name, b):
+            n = b["n"].astype(np.float64)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[name + "rms"] = np.sqrt(b["sum_r2"] / n)
+                out[name + "mean"] = b["sum_r"] / n
+                out[name + "outlier_frac"] = b["n_out"] / n
+        out = {"totals": total[0], "options": o, "n_degenerate": int(total[0]["n_degenerate"])}
+        derived(out, "", total["all"][0])
+        out["rms_px"] = out["rms"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["px_per_unit"] = float(total[0]["sum_px_per_unit"] / np.float64(total[0]["all"]["n"]))
+        if kf is not None:
+            out["kf"] = kf
+            derived(out, "kf_", kf)
+        if lm is not None:
+            out["lm"] = lm
+            derived(out, "lm_", lm)
+        if cn is not None:
+            out["cell_n"], out["cell_sum_r2"] = cn, cs
+            out["empty_cell_frac"] = float((cn == 0).mean())
+        if hist is not None:
+            out["hist"] = hist
+            rng = o.hist_range if o.hist_range > 0 else 4.0
             out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
         return out
 

@@ -79,6 +79,7 @@ struct ecal_solver {
     uint32_t last_solve[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ecal_debug_solver_last_solve: how the last ecal_solver_solve ran
     size_t report_lds = 0;   // ecal_solver_report_dev: the dynamic LDS its kernel has been allowed so far
     size_t board_lds = 0;    // ecal_solver_board_image_dev: the same
+    size_t report_px_lds = 0;   // ecal_solver_report_px_dev: the same
     size_t n_params() const { return 9 + 7 * (size_t) n_cp; }
     size_t n_accum() const { return ecal::ACC_HEAD + ecal::ACC_PER_CP * (size_t) n_cp; }
 };

@@ -51,6 +51,28 @@ public:
         }
     };
 
+    // The same report in PIXELS (ecal_solver_report_px) at the solution: per residual the first-order distance from the event to
+    // the projected rim of its circle, binned as above.  Filled when the constructor is given pixel report options; valid = false
+    // otherwise.
+    struct ReportPx {
+        bool valid = false;
+        ecal_report_options options{};
+        ecal_report_px_totals totals{};
+        std::vector<ecal_bin_stats> keyframes, landmarks;
+        uint32_t cells_x = 0, cells_y = 0;
+        std::vector<uint64_t> cell_n, hist;   // cell_n [cells_y][cells_x]
+        std::vector<double> cell_sum_r2;
+        double hist_range = 0, outlier_thresh = 0;   // pixels, as the call took them (a value <= 0 in options: the defaults)
+        double rmsPx() const { return Report::rms(totals.all); }
+        double pxPerUnit() const { return totals.all.n ? totals.sum_px_per_unit / (double) totals.all.n : 0.0; }
+        double outlierFraction() const { return totals.all.n ? (double) totals.all.n_out / (double) totals.all.n : 0.0; }
+        double emptyCellFraction() const {
+            size_t empty = 0;
+            for (uint64_t n : cell_n) empty += n == 0;
+            return cell_n.empty() ? 0.0 : (double) empty / (double) cell_n.size();
+        }
+    };
+
     // The board-frame event image (ecal_solver_board_image) at the solution: every event of the stream carried through the
     // refined camera and the spline pose at its own time stamp onto the board, with the call's default options (the landmarks'
     // bounding box padded by 3 radii, bin = radius / 8, 64 ring bins over +- radius).  Filled when the constructor is asked for
@@ -127,7 +149,8 @@ public:
                      double motionTimeStep, const double K[4], const double distCoeffs[5], int maxIterations = 50,
                      bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false,
                      int refineRounds = 0, double refineRingTol = 0.0 /* board units; <= 0: the Huber width */,
-                     bool keepEvents = false /* the container's device stream outlives the solve (the caller undistorts it) */)
+                     bool keepEvents = false /* the container's device stream outlives the solve (the caller undistorts it) */,
+                     const ecal_report_options *reportPxOptions = nullptr)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
           fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations),
           wantBoardImage_(wantBoardImage), refineRounds_(refineRounds > 0 ? refineRounds : 0), refineRingTol_(refineRingTol),
@@ -135,6 +158,10 @@ public:
         if (reportOptions) {
             report_.options = *reportOptions;
             wantReport_ = true;
+        }
+        if (reportPxOptions) {
+            reportPx_.options = *reportPxOptions;
+            wantReportPx_ = true;
         }
         if (frames_.size() <= 10) throw std::logic_error("too few frames in the map.");  // :26-28
         std::sort(frames_.begin(), frames_.end(), [](const Frame &a, const Frame &b) { return a.timeStamp < b.timeStamp; });
@@ -189,6 +216,7 @@ public:
     const std::vector<Frame> &frames() const { return frames_; }
     const Summary &summary() const { return summary_; }
     const Report &report() const { return report_; }
+    const ReportPx &reportPx() const { return reportPx_; }
     const BoardImage &boardImage() const { return boardImage_; }
     const std::vector<RefineRound> &refine() const { return refine_; }
     size_t splineNum() const { return segments_.size(); }
@@ -338,6 +366,29 @@ private:
                 throw std::runtime_error(std::string("ecal_solver_report: ") + ecal_last_error(ctx));
             }
         }
+        if (rc == ECAL_OK && wantReportPx_) {   // the same records, in pixels
+            ReportPx &r = reportPx_;
+            const ecal_report_options &o = r.options;
+            ecal_report_options def;
+            ecal_report_px_default_options(&def);
+            r.cells_x = o.cell_px ? (o.width + o.cell_px - 1) / o.cell_px : 0;
+            r.cells_y = o.cell_px ? (o.height + o.cell_px - 1) / o.cell_px : 0;
+            r.keyframes.assign(F, ecal_bin_stats{});
+            r.landmarks.assign(n_circ, ecal_bin_stats{});
+            r.cell_n.assign((size_t) r.cells_x * r.cells_y, 0);
+            r.cell_sum_r2.assign(r.cell_n.size(), 0.0);
+            r.hist.assign(o.hist_bins, 0);
+            r.hist_range = o.hist_range > 0 ? o.hist_range : def.hist_range;
+            r.outlier_thresh = o.outlier_thresh > 0 ? o.outlier_thresh : def.outlier_thresh;
+            rc = ecal_solver_report_px(solver, x.data(), kf_time.data(), F, &o, &r.totals, r.keyframes.data(), r.landmarks.data(),
+                                       r.cell_n.data(), r.cell_sum_r2.data(), r.hist.data());
+            r.valid = rc == ECAL_OK;
+            if (rc != ECAL_OK) {
+                ecal_solver_destroy(solver);
+                if (keepStream) eventContainer_->release();
+                throw std::runtime_error(std::string("ecal_solver_report_px: ") + ecal_last_error(ctx));
+            }
+        }
         if (rc == ECAL_OK && wantBoardImage_) {   // every event of the stream through the solution
             BoardImage &b = boardImage_;
             (void) ecal_board_image_default_options(solver, &b.options);
@@ -395,6 +446,8 @@ private:
     Summary summary_;
     Report report_;
     bool wantReport_ = false;
+    ReportPx reportPx_;
+    bool wantReportPx_ = false;
     BoardImage boardImage_;
     bool wantBoardImage_ = false;
     int refineRounds_ = 0;

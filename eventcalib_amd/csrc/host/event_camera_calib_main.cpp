@@ -385,6 +385,15 @@ int main(int argc, char **argv) {
     ecal_report_default_options(&reportOptions);
     reportOptions.width = (uint32_t) width;
     reportOptions.height = (uint32_t) height;
+    // CalibrationReportPixels (a key of this build, optional): 1 = the same report in PIXELS (ecal_solver_report_px: per residual the
+    // first-order distance from the event to the projected rim) written to saveDir/CalibrationReportPixels.txt, the layout of
+    // CalibrationReport.txt; absent or 0: nothing changes
+    int wantReportPx = 0;
+    fsSettings["CalibrationReportPixels"] >> wantReportPx;
+    ecal_report_options reportPxOptions;
+    ecal_report_px_default_options(&reportPxOptions);
+    reportPxOptions.width = (uint32_t) width;
+    reportPxOptions.height = (uint32_t) height;
     // BoardImage (a key of this build, optional): 1 = every event of the stream carried through the solution onto the board
     // (ecal_solver_board_image), written to saveDir/board_image.png and saveDir/BoardImage.txt; absent or 0: nothing changes
     int wantBoardImage = 0;
@@ -416,7 +425,7 @@ int main(int argc, char **argv) {
     fsSettings["UndistortMaps"] >> wantUndistortMaps;
     fsSettings["UndistortMaps_Reference"] >> wantUndistortMapsReference;
     EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
-                            wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort);
+                            wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort, wantReportPx ? &reportPxOptions : nullptr);
     const double *x = spline.intrinsics();
     std::printf("refined %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g residuals %zu iterations %d splines %zu\n", x[0], x[1], x[2], x[3],
                 x[4], x[5], x[6], x[7], x[8], spline.summary().residuals, spline.summary().iterations, spline.splineNum());
@@ -589,6 +598,50 @@ int main(int argc, char **argv) {
         std::fprintf(f, "\n");
         std::fclose(f);
         std::printf("report rms %.9g outliers %.6f empty_cells %.6f\n", Rp::rms(a), rp.outlierFraction(), rp.emptyCellFraction());
+    }
+    if (wantReportPx && spline.reportPx().valid) {
+        const EventCalibSpline::ReportPx &rp = spline.reportPx();
+        using Rp = EventCalibSpline::Report;
+        const ecal_bin_stats &a = rp.totals.all;
+        std::FILE *f = std::fopen((std::string(argv[3]) + "/CalibrationReportPixels.txt").c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "cannot write %s/CalibrationReportPixels.txt\n", argv[3]);
+            return 3;
+        }
+        auto line = [&](const char *tag, size_t id, const ecal_bin_stats &b) {
+            std::fprintf(f, "%s %zu n %llu n_out %llu rms %.9g mean %.9g mean_abs %.9g max_abs %.9g\n", tag, id, (unsigned long long) b.n,
+                         (unsigned long long) b.n_out, Rp::rms(b), b.n ? b.sum_r / (double) b.n : 0.0, b.n ? b.sum_abs / (double) b.n : 0.0,
+                         b.max_abs);
+        };
+        std::fprintf(f, "# residuals in pixels (first-order distance to the projected rim); px_per_unit %.9g; outlier: |r| > %.9g\n",
+                     rp.pxPerUnit(), rp.outlier_thresh);
+        std::fprintf(f, "totals n %llu n_out %llu sum_r %.17g sum_r2 %.17g sum_abs %.17g max_abs %.17g n_degenerate %llu sum_px_per_unit %.17g rms %.9g\n",
+                     (unsigned long long) a.n, (unsigned long long) a.n_out, a.sum_r, a.sum_r2, a.sum_abs, a.max_abs,
+                     (unsigned long long) rp.totals.n_degenerate, rp.totals.sum_px_per_unit, rp.rmsPx());
+        std::vector<size_t> order;
+        for (size_t k = 0; k < rp.keyframes.size(); k++)
+            if (rp.keyframes[k].n) order.push_back(k);
+        std::stable_sort(order.begin(), order.end(), [&](size_t i, size_t j) { return Rp::rms(rp.keyframes[i]) > Rp::rms(rp.keyframes[j]); });
+        std::fprintf(f, "worst_keyframes %zu of %zu\n", std::min<size_t>(10, order.size()), rp.keyframes.size());
+        for (size_t k = 0; k < order.size() && k < 10; k++) {
+            std::fprintf(f, "t %.6f ", spline.frames()[order[k]].timeStamp);
+            line("keyframe", order[k], rp.keyframes[order[k]]);
+        }
+        std::fprintf(f, "landmarks %zu\n", rp.landmarks.size());
+        for (size_t k = 0; k < rp.landmarks.size(); k++) line("landmark", k, rp.landmarks[k]);
+        std::fprintf(f, "coverage %u %u cell_px %u\n", rp.cells_y, rp.cells_x, rp.options.cell_px);
+        for (uint32_t y = 0; y < rp.cells_y; y++) {
+            for (uint32_t x2 = 0; x2 < rp.cells_x; x2++)
+                std::fprintf(f, x2 ? " %llu" : "%llu", (unsigned long long) rp.cell_n[(size_t) y * rp.cells_x + x2]);
+            std::fprintf(f, "\n");
+        }
+        std::fprintf(f, "empty_cells %.6f\n", rp.emptyCellFraction());
+        std::fprintf(f, "histogram %zu range %.9g\n", rp.hist.size(), rp.hist_range);
+        for (size_t k = 0; k < rp.hist.size(); k++) std::fprintf(f, k ? " %llu" : "%llu", (unsigned long long) rp.hist[k]);
+        std::fprintf(f, "\n");
+        std::fclose(f);
+        std::printf("report_px rms_px %.9g px_per_unit %.9g outliers %.6f degenerate %llu\n", rp.rmsPx(), rp.pxPerUnit(), rp.outlierFraction(),
+                    (unsigned long long) rp.totals.n_degenerate);
     }
     if (wantBoardImage && spline.boardImage().valid) {
         const EventCalibSpline::BoardImage &bi = spline.boardImage();

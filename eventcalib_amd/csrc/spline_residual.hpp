@@ -504,4 +504,126 @@ ECAL_HD void spline_pose_so3(const double b[4], const double (*q)[4], const doub
         for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
 }
 
+// ---- the residual and its gradient by the event's own pixel (the report in pixels, ecal_report_px.hip) ------------------------
+// r and g = (d r / d u, d r / d v): the lean pair behind the first-order (Sampson) distance r / |g| from the event to the projected
+// rim, in pixels (include/ecal.h, "report in pixels").  d r / d (u, v) is minus d r / d (cx, cy), columns 2 and 3 of the Jacobian
+// row: g = (gx * ifx, gy * ify) = (-J[2], -J[3]), with no robust loss.  The three functions below DUPLICATE the lines of
+// residual_core, spline_residual and spline_residual_so3 that lead to gx, gy, the same operations in the same order, for the reason
+// the board-point functions above do: the residual functions are not rewritten on top of them.  tests/cpp/check_residual_px.cpp
+// holds r and g to the originals bit for bit.
+template <bool FISHEYE = false>
+ECAL_HD double residual_core_px(const ResidualInput &in, const double *intr, double ux, double uy, double uz, double w,
+                                const double T[3], double g[2]) {
+    const double cx = intr[2], cy = intr[3];
+    const double ifx = in.ifx != 0.0 ? in.ifx : 1.0 / intr[0], ify = in.ify != 0.0 ? in.ify : 1.0 / intr[1];
+    const double x = (in.u - cx) * ifx, y = (in.v - cy) * ify;
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2, r8 = r6 * r2, r10 = r8 * r2;
+    const double poly = 1.0 + intr[4] * r2 + intr[5] * r4 + intr[6] * r6 + intr[7] * r8 + intr[8] * r10;
+    double c = poly, sec2 = 1.0;
+    if (FISHEYE) {
+        if (r2 > 1e-16) {
+            const double r = sqrt(r2), tn = tan(r * poly);
+            sec2 = 1.0 + tn * tn;
+            c = tn / r;
+        }
+    }
+    const double px = x * c, py = y * c, pz = 1.0;
+    const double cxp0 = uy * pz - uz * py, cxp1 = uz * px - ux * pz, cxp2 = ux * py - uy * px;
+    const double udp = ux * px + uy * py + uz * pz, udu = ux * ux + uy * uy + uz * uz;
+    const double Y0 = px + 2 * w * cxp0 + 2 * (ux * udp - px * udu);
+    const double Y1 = py + 2 * w * cxp1 + 2 * (uy * udp - py * udu);
+    const double Y2 = pz + 2 * w * cxp2 + 2 * (uz * udp - pz * udu);
+    const double iY2 = 1.0 / Y2;
+    const double s = -T[2] * iY2;
+    const double Xw0 = T[0] + s * Y0, Xw1 = T[1] + s * Y1, Xw2 = T[2] + s * Y2;
+    const double d0 = Xw0 - in.lmx, d1 = Xw1 - in.lmy, d2 = Xw2 - in.lmz;
+    const double dd = d0 * d0 + d1 * d1 + d2 * d2;
+    const double idist = res_rsqrt(dd);
+    const double dist = dd * idist;
+    const double res = dist - in.radius;
+
+    const double esc = idist;
+    const double e0 = d0 * esc, e1 = d1 * esc, e2 = d2 * esc;
+    const double eY = e0 * Y0 + e1 * Y1 + e2 * Y2;
+    const double k = s;
+    const double gY0 = k * e0, gY1 = k * e1, gY2 = k * e2 - k * eY * iY2;
+    const double udg = ux * gY0 + uy * gY1 + uz * gY2;
+    const double cxg0 = uy * gY2 - uz * gY1, cxg1 = uz * gY0 - ux * gY2;
+    const double gp0 = gY0 - 2 * w * cxg0 + 2 * (ux * udg - gY0 * udu);
+    const double gp1 = gY1 - 2 * w * cxg1 + 2 * (uy * udg - gY1 * udu);
+    double cp = intr[4] + 2 * intr[5] * r2 + 3 * intr[6] * r4 + 4 * intr[7] * r6 + 5 * intr[8] * r8;
+    if (FISHEYE) {
+        cp = r2 > 1e-8 ? (sec2 * (0.5 * poly + r2 * cp) - 0.5 * c) / r2 : cp + poly * poly * poly * (1.0 / 3.0);
+    }
+    const double gx = gp0 * (c + 2 * x * x * cp) + gp1 * (2 * x * y * cp);
+    const double gy = gp0 * (2 * x * y * cp) + gp1 * (c + 2 * y * y * cp);
+    g[0] = gx * ifx;
+    g[1] = gy * ify;
+    return res;
+}
+
+template <bool FISHEYE = false>
+ECAL_HD double spline_residual_px(const ResidualInput &in, const double *intr, const double (*q)[4], const double (*t)[3],
+                                  double g[2]) {
+    double vq[4] = {0, 0, 0, 0}, T[3] = {0, 0, 0};
+    for (int j = 0; j < 4; j++) {
+        for (int k = 0; k < 4; k++) vq[k] += in.b[j] * q[j][k];
+        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
+    }
+    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
+    const double ux = vq[0] * ivn, uy = vq[1] * ivn, uz = vq[2] * ivn, w = vq[3] * ivn;
+    return residual_core_px<FISHEYE>(in, intr, ux, uy, uz, w, T, g);
+}
+
+template <bool FISHEYE = false>
+ECAL_HD double spline_residual_px_so3(const ResidualInput &in, const double *intr, const double (*q)[4],
+                                      const double (*t)[3], double g[2]) {
+    double beta[3];
+    beta[2] = in.b[3];
+    beta[1] = beta[2] + in.b[2];
+    beta[0] = beta[1] + in.b[1];
+    double d[3][3], bd[3][3], Q[4] = {q[0][0], q[0][1], q[0][2], q[0][3]}, T[3] = {0, 0, 0};
+    for (int j = 1; j <= 3; j++) {
+        const double inv[4] = {-q[j - 1][0], -q[j - 1][1], -q[j - 1][2], q[j - 1][3]};
+        double rel[4], e[4], nq[4];
+        quat_mul(inv, q[j], rel);
+        so3_log(rel, d[j - 1]);
+        for (int k = 0; k < 3; k++) bd[j - 1][k] = beta[j - 1] * d[j - 1][k];
+        so3_exp(bd[j - 1], e);
+        quat_mul(Q, e, nq);
+        for (int k = 0; k < 4; k++) Q[k] = nq[k];
+    }
+    for (int j = 0; j < 4; j++)
+        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
+    return residual_core_px<FISHEYE>(in, intr, Q[0], Q[1], Q[2], Q[3], T, g);
+}
+
+// The first-order distance itself, operation by operation as include/ecal.h states it: g2 = gu * gu + gv * gv; the record is
+// DEGENERATE (true is returned, *r_px = *px_per_unit = 0) iff r or g2 is not finite or g2 > 0 is false; otherwise
+// *px_per_unit = 1 / sqrt(g2) and *r_px = r / sqrt(g2), square root and divisions correctly rounded.  No contraction: explicit
+// single operations on the device, and the host builds that call it are compiled with -ffp-contract=off.
+ECAL_HD bool residual_px_distance(double r, const double g[2], double *r_px, double *px_per_unit) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double g2 = __dadd_rn(__dmul_rn(g[0], g[0]), __dmul_rn(g[1], g[1]));
+#else
+    const double a = g[0] * g[0], b = g[1] * g[1];
+    const double g2 = a + b;
+#endif
+    const double big = 1.79769313486231570e308;
+    const bool ok = fabs(r) <= big && g2 > 0.0 && g2 <= big;   // (a NaN fails every comparison)
+    *r_px = 0.0;
+    *px_per_unit = 0.0;
+    if (!ok) return true;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double n = __dsqrt_rn(g2);
+    *px_per_unit = __ddiv_rn(1.0, n);
+    *r_px = __ddiv_rn(r, n);
+#else
+    const double n = sqrt(g2);
+    *px_per_unit = 1.0 / n;
+    *r_px = r / n;
+#endif
+    return false;
+}
+
 }  // namespace ecal

@@ -773,6 +773,45 @@ int ecal_solver_report(ecal_solver *s, const double *params, const double *kf_ti
                        const ecal_report_options *opt, ecal_report_totals *total, ecal_bin_stats *kf, ecal_bin_stats *lm,
                        uint64_t *cell_n, double *cell_sum_r2, uint64_t *hist);
 uint32_t ecal_solver_num_landmarks(const ecal_solver *s);
+/* ---- report in pixels ---------------------------------------------------------------------------------------------------------
+ * The same report with every statistic in PIXELS: per residual record the first-order (Sampson) distance from the event to the
+ * projected rim of its circle, r_px = r / |d r / d (u, v)|, signed like r.  It is defined wherever the residual is — it does not go
+ * through a forward projection, which exists only inside the solved polynomial's monotone radius — and it does not grow with depth
+ * or obliquity as the board-unit residual does.  For a residual record (pixel u, v, time, landmark) at `params`, operation by
+ * operation:
+ *   r        the raw residual of ecal_residuals
+ *   gu, gv   d r / d u, d r / d v = the negatives of columns 2 and 3 (cx, cy) of that record's Jacobian row; in residual_core's terms
+ *            (spline_residual.hpp) gu = gx * ifx, gv = gy * ify, with no robust loss
+ *   g2       gu * gu + gv * gv
+ *   degenerate  iff r or g2 is not finite or g2 > 0 is false: the record is counted in n_degenerate and enters no bin
+ *   r_px     r / sqrt(g2) otherwise, the division and the square root correctly rounded; px_per_unit = 1 / sqrt(g2)
+ * r, gu and gv are compiled the way the solver compiles its residual (contraction to FMA allowed); everything from g2 on, and
+ * everything that decides a bin, without contraction.
+ * ecal_solver_report_px[_dev]: arguments, families, NULL-skips-the-family rule, keyframe tie rule, limits and error codes of
+ * ecal_solver_report[_dev]; every statistic is of r_px and there is no cost.  Options: ecal_report_options with pixel defaults
+ * (ecal_report_px_default_options: 346 x 260, 16 px cells, 64 bins, hist_range = 4.0 px, outlier_thresh = 1.0 px — interface
+ * choices, not tolerances); a hist_range or outlier_thresh <= 0 passed in a call means these same two values.
+ * totals.sum_px_per_unit = the sum of 1 / sqrt(g2) over the non-degenerate records: its mean says how many pixels one board unit
+ * is in this data.  all.n + n_degenerate = the solver's residuals.  The call zeroes its outputs itself on `stream`; the _dev form
+ * takes device pointers and does not synchronise with the host; the host form stages through the context's scratch.
+ * ecal_residuals_px[_dev], the per-event form: r_px [n_res] (0.0 where the record is degenerate), grad [n_res][2] = (gu, gv)
+ * (optional), flag [n_res] (optional): 1 = degenerate, 0 otherwise. */
+typedef struct ecal_report_px_totals {
+    ecal_bin_stats all;
+    uint64_t n_degenerate;
+    double sum_px_per_unit;
+} ecal_report_px_totals;
+void ecal_report_px_default_options(ecal_report_options *opt);
+int ecal_solver_report_px_dev(ecal_solver *s, const double *d_params, const double *d_kf_time, uint32_t n_keyframes,
+                              const ecal_report_options *opt /*NULL: the pixel defaults*/, ecal_report_px_totals *d_total,
+                              ecal_bin_stats *d_kf, ecal_bin_stats *d_lm, uint64_t *d_cell_n, double *d_cell_sum_r2, uint64_t *d_hist,
+                              void *stream);
+int ecal_solver_report_px(ecal_solver *s, const double *params, const double *kf_time, uint32_t n_keyframes,
+                          const ecal_report_options *opt, ecal_report_px_totals *total, ecal_bin_stats *kf, ecal_bin_stats *lm,
+                          uint64_t *cell_n, double *cell_sum_r2, uint64_t *hist);
+int ecal_residuals_px_dev(ecal_solver *s, const double *d_params, double *d_r_px /*[n_res]*/, double *d_grad /*[n_res][2] or NULL*/,
+                          uint8_t *d_flag /*[n_res] or NULL*/, void *stream);
+int ecal_residuals_px(ecal_solver *s, const double *params, double *r_px, double *grad, uint8_t *flag);
 /* Board-frame event image (the motion-compensated image of the calibration): EVERY event of a stream — not only the ones the
  * association kept — carried through the intrinsics of `params` and the pose of the solver's spline at its own time stamp onto
  * the board plane z = 0 (the first half of the residual: inverse camera model, rotation, ray / plane intersection).  With a good
