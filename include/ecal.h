@@ -195,6 +195,11 @@ int ecal_unpack_points_dev(ecal_ctx *ctx, const ecal_packed_points *pk, const ui
  * mutual-nearest / midpoint path of :283-311 (the shipped example.yaml), fit_circle != 0 the knn_num-nearest
  * / algebraic CirclesEventFrame::fitCircle (:361-415) / double-direction path of :180-281 (knn_num <= 8).  Inputs are the outputs of ecal_slice_events_dev and ecal_dbscan_batch_dev with
  * S' = 2S segments (2s = positive, 2s+1 = negative polarity of window s).
+ * knn_num (fit_circle != 0, 1..8): the neighbour list of a representative holds its knn_num nearest representatives of the
+ *   other polarity in ascending squared distance, equal distances in ascending cluster index.  With FEWER kept clusters of
+ *   that polarity than knn_num the list ENDS at their number — each cluster appears once — and the two gates of :187-193
+ *   (d > 4 d0, d > 4 radius_threshold^2; a neighbour AT either bound stays) then cut it as usual.  (The reference there reads
+ *   on into whatever its reused result vectors held, :173-193 and :232-241; design/04_slicing_extraction.md, section 4f.)
  *
  * ecal_circle_radius_threshold: circleRadiusThreshold_ (CirclesEventFrame.cpp:16-33); pure host math.
  * ecal_extract_batch_dev, per window s (all outputs indexed like the points: window s owns the

@@ -106,8 +106,11 @@ size_t nearest(const Side &s, const Pt &q, double *d2_out) {
     return best;
 }
 
-// k nearest centres, ascending squared distance (ties: smaller index first — nanoflann unpinned)
-void knn(const Side &s, const Pt &q, size_t k, std::vector<size_t> &idx, std::vector<double> &d2) {
+// k nearest centres, ascending squared distance (ties: smaller index first — nanoflann unpinned).  Returns how many there
+// are: min(k, kept clusters), nanoflann's returned count.  idx / d2 end there — with fewer than k kept clusters the reference
+// reads on into whatever its reused n_idx / p_idx / out_dists_sqr vectors held (:173-193, :232-241), which nothing can pin;
+// the project's contract (include/ecal.h at knn_num, design/04_slicing_extraction.md) is that the list ends at that count.
+size_t knn(const Side &s, const Pt &q, size_t k, std::vector<size_t> &idx, std::vector<double> &d2) {
     std::vector<std::pair<double, size_t>> all;
     for (size_t i = 0; i < s.centres.size(); i++) {
         const Pt &c = s.pts[s.centres[i]];
@@ -115,12 +118,14 @@ void knn(const Side &s, const Pt &q, size_t k, std::vector<size_t> &idx, std::ve
         all.emplace_back(dx * dx + dy * dy, i);
     }
     std::stable_sort(all.begin(), all.end(), [](auto &a, auto &b) { return a.first < b.first; });
-    idx.assign(k, 0);
-    d2.assign(k, 0.0);
-    for (size_t i = 0; i < k && i < all.size(); i++) {
+    const size_t found = std::min(k, all.size());
+    idx.resize(found);
+    d2.resize(found);
+    for (size_t i = 0; i < found; i++) {
         idx[i] = all[i].second;
         d2[i] = all[i].first;
     }
+    return found;
 }
 
 struct Fit {
@@ -293,9 +298,8 @@ int oracle_extract_candidates_full(const double *pos_xy, uint32_t n_pos, const d
         std::vector<size_t> n_idx, p_idx;
         std::vector<double> d2;
         for (size_t pi = 0; pi < P.centres.size(); pi++) {
-            size_t real = K;
-            knn(N, P.pts[P.centres[pi]], K, n_idx, d2);
-            for (size_t oi = 0; oi < K; oi++)
+            size_t real = knn(N, P.pts[P.centres[pi]], K, n_idx, d2);
+            for (size_t oi = 0; oi < real; oi++)
                 if (d2[oi] > d2[0] * 4 || d2[oi] > gate) {
                     real = oi;
                     break;
@@ -307,9 +311,8 @@ int oracle_extract_candidates_full(const double *pos_xy, uint32_t n_pos, const d
             for (size_t j = 1; j < real; j++)
                 if (fits[j].err < fits[nmin].err) nmin = j;  // std::min_element: first minimum
             if (!(fits[nmin].err < 2 / fits[nmin].radius)) continue;
-            real = K;
-            knn(P, N.pts[N.centres[n_idx[nmin]]], K, p_idx, d2);
-            for (size_t oi = 0; oi < K; oi++)
+            real = knn(P, N.pts[N.centres[n_idx[nmin]]], K, p_idx, d2);
+            for (size_t oi = 0; oi < real; oi++)
                 if (d2[oi] > d2[0] * 4 || d2[oi] > gate) {
                     real = oi;
                     break;
