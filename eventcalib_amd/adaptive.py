@@ -34,10 +34,7 @@ def _nth_element_median(theta):
     """theta [n, rows]: what libstdc++'s std::nth_element leaves at position rows // 2 of every row — with NaNs among the
     angles (every comparison false) that is not the order statistic but whatever the library's loops leave there
     (EventCalibIni.cpp:78); the library's restatement is exported by libecal for exactly this (ecal_ref_nth_element_f64)."""
-    import ctypes
     L = capi.load_library()
-    L.ecal_ref_nth_element_f64.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
-    L.ecal_ref_nth_element_f64.restype = None
     out = np.empty(theta.shape[0])
     for i in range(theta.shape[0]):
         row = np.ascontiguousarray(theta[i], np.float64).copy()

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
 ]
 
 
+# ---- the mirror of include/ecal.h: its structs, callback types, record layouts (numpy dtypes) and constants, then PROTOTYPES ----
 class PackedPoints(ctypes.Structure):
     """ecal_packed_points: d_xy16 [cap_points] u32 (x | y << 16), d_seg_fmt [2S] u32 (0 doubles, 1 packed, 3 both)."""
     _fields_ = [("d_xy16", ctypes.c_void_p), ("d_seg_fmt", ctypes.c_void_p)]
@@ -290,6 +291,409 @@ def field_type(dtype):
     raise ValueError("dtype %s is not a column type of the array ingest (U8, I8, U16, I16, U32, I32, I64, F32, F64 are)" % dt)
 
 
+class HotPixelOptions(ctypes.Structure):
+    """ecal_hot_pixel_options (include/ecal.h, pixel activity / hot pixels)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("quantile_permille", ctypes.c_uint32),
+                ("min_count", ctypes.c_uint32), ("factor", ctypes.c_double)]
+
+
+class HotPixelInfo(ctypes.Structure):
+    """ecal_hot_pixel_info (include/ecal.h, pixel activity / hot pixels)."""
+    _fields_ = [("n_events", ctypes.c_uint64), ("n_off_grid", ctypes.c_uint64), ("n_removed", ctypes.c_uint64), ("n_kept", ctypes.c_uint64),
+                ("n_active_pixels", ctypes.c_uint32), ("n_hot_pixels", ctypes.c_uint32), ("n_masked_pixels", ctypes.c_uint32),
+                ("quantile_count", ctypes.c_uint32), ("max_count", ctypes.c_uint32), ("max_kept_count", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+# ecal_activity_totals / ecal_filter_totals as numpy records
+ACTIVITY_TOTALS = np.dtype([("n_events", np.uint64), ("n_on_grid", np.uint64), ("n_off_grid", np.uint64)])
+FILTER_TOTALS = np.dtype([("n_events", np.uint64), ("n_off_grid", np.uint64), ("n_removed", np.uint64), ("n_kept", np.uint64)])
+
+
+class NoiseOptions(ctypes.Structure):
+    """ecal_noise_options (include/ecal.h, noise filter)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32), ("min_support", ctypes.c_uint32),
+                ("include_self", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("dt", ctypes.c_double)]
+
+
+CAMERA_RADIAL, CAMERA_FISHEYE = 0, 1          # ECAL_CAMERA_RADIAL / _FISHEYE
+UNDISTORT_SUBPIXEL, UNDISTORT_PIXEL = 0, 1    # ECAL_UNDISTORT_SUBPIXEL / _PIXEL
+UNDISTORT_TOTALS = np.dtype([("n_events", np.uint64), ("n_invalid", np.uint64), ("n_outside", np.uint64), ("n_kept", np.uint64)])
+UNDISTORT_FRAME_TOTALS = np.dtype([("n_pos", np.uint32), ("n_neg", np.uint32), ("n_invalid", np.uint32), ("n_outside", np.uint32)])
+
+
+class UndistortCamera(ctypes.Structure):
+    """ecal_undistort_camera (include/ecal.h, undistortion)."""
+    _fields_ = [("model", ctypes.c_int), ("reserved", ctypes.c_int), ("intr", ctypes.c_double * 9), ("out_k", ctypes.c_double * 4)]
+
+
+class UndistortOptions(ctypes.Structure):
+    """ecal_undistort_options (include/ecal.h, undistortion)."""
+    _fields_ = [("mode", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"mode": int(self.mode), "out_width": int(self.out_width), "out_height": int(self.out_height),
+                "off_x": float(self.off_x), "off_y": float(self.off_y)}
+
+
+IMAGE_REFERENCE, IMAGE_BILINEAR = 0, 1              # ECAL_IMAGE_REFERENCE / _BILINEAR
+DISTORT_INVALID, DISTORT_NOT_CONVERGED = 1, 2       # ECAL_DISTORT_INVALID / _NOT_CONVERGED
+
+
+class ImageOptions(ctypes.Structure):
+    """ecal_image_options (include/ecal.h, image undistortion)."""
+    _fields_ = [("method", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32),
+                ("normalize", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"method": int(self.method), "channels": int(self.channels), "out_width": int(self.out_width), "out_height": int(self.out_height),
+                "normalize": int(self.normalize), "off_x": float(self.off_x), "off_y": float(self.off_y)}
+
+
+class ImageInfo(ctypes.Structure):
+    """ecal_image_info (include/ecal.h, image undistortion)."""
+    _fields_ = [("opt", ImageOptions), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("n_invalid_sources", ctypes.c_uint64),
+                ("n_empty", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("max_neighbours", ctypes.c_uint32), ("truncated", ctypes.c_uint32),
+                ("bytes", ctypes.c_uint64), ("r_lim", ctypes.c_double), ("n_invalid", ctypes.c_uint64), ("n_not_converged", ctypes.c_uint64)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_[1:]}
+        d["options"] = self.opt.as_dict()
+        return d
+
+
+class _SplineProblem(ctypes.Structure):
+    _fields_ = [("n_segments", ctypes.c_uint32), ("seg_cp_off", ctypes.c_void_p), ("knots", ctypes.c_void_p),
+                ("n_res", ctypes.c_uint64), ("obs", ctypes.c_void_p), ("time", ctypes.c_void_p),
+                ("lm_id", ctypes.c_void_p), ("seg_id", ctypes.c_void_p), ("n_landmarks", ctypes.c_uint32),
+                ("landmarks", ctypes.c_void_p), ("circle_radius", ctypes.c_double), ("huber_a", ctypes.c_double),
+                ("use_so3", ctypes.c_int), ("camera_model", ctypes.c_int)]
+
+
+ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
+
+
+class LmOptions(ctypes.Structure):
+    _fields_ = [("max_num_iterations", ctypes.c_int), ("function_tolerance", ctypes.c_double),
+                ("gradient_tolerance", ctypes.c_double), ("parameter_tolerance", ctypes.c_double),
+                ("initial_trust_region_radius", ctypes.c_double), ("max_trust_region_radius", ctypes.c_double),
+                ("min_relative_decrease", ctypes.c_double), ("min_lm_diagonal", ctypes.c_double),
+                ("max_lm_diagonal", ctypes.c_double), ("jacobi_scaling", ctypes.c_int),
+                ("allreduce", ALLREDUCE_FN), ("allreduce_user", ctypes.c_void_p),
+                ("distributed", ctypes.c_int), ("rank", ctypes.c_int), ("world_size", ctypes.c_int)]
+
+
+class LmSummary(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("successful_steps", ctypes.c_int), ("unsuccessful_steps", ctypes.c_int),
+                ("jacobian_evaluations", ctypes.c_int), ("cost_evaluations", ctypes.c_int),
+                ("termination", ctypes.c_int), ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
+                ("seconds", ctypes.c_double), ("seconds_evaluate", ctypes.c_double),
+                ("seconds_linear_solve", ctypes.c_double)]
+
+
+class ReportOptions(ctypes.Structure):
+    """ecal_report_options (include/ecal.h)."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("cell_px", ctypes.c_uint32), ("hist_bins", ctypes.c_uint32),
+                ("hist_range", ctypes.c_double), ("outlier_thresh", ctypes.c_double)]
+
+
+# ecal_bin_stats / ecal_report_totals as numpy records
+BIN_STATS = np.dtype([("n", np.uint64), ("n_out", np.uint64), ("sum_r", np.float64), ("sum_r2", np.float64), ("sum_abs", np.float64),
+                      ("max_abs", np.float64)])
+REPORT_TOTALS = np.dtype([("all", BIN_STATS), ("cost", np.float64)])
+# ecal_report_px_totals (the report in pixels)
+REPORT_PX_TOTALS = np.dtype([("all", BIN_STATS), ("n_degenerate", np.uint64), ("sum_px_per_unit", np.float64)])
+
+
+class BoardImageOptions(ctypes.Structure):
+    """ecal_board_image_options (include/ecal.h)."""
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("bin", ctypes.c_double), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("ring_bins", ctypes.c_uint32), ("ring_range", ctypes.c_double)]
+
+
+# ecal_board_image_totals / ecal_ring_stats as numpy records; the kernel's block and staging sizes (ECAL_BOARD_IMAGE_*)
+BOARD_IMAGE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
+                               ("n_outside_image", np.uint64), ("n_image", np.uint64, (2,)), ("n_ring", np.uint64)])
+RING_STATS = np.dtype([("n", np.uint64), ("sum_d", np.float64), ("sum_d2", np.float64)])
+BOARD_IMAGE_BLOCK, BOARD_IMAGE_CP_LDS = 4096, 16
+# ecal_reassociate_totals
+REASSOCIATE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
+                               ("n_off_ring", np.uint64), ("n_kept", np.uint64)])
+
+
+CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1 << 0, 1 << 1, 1 << 2
+CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6 = (1 << 3, 1 << 4, 1 << 5, 1 << 6,
+                                                                                      1 << 7, 1 << 8)
+CALIB_FIX_SKEW, CALIB_RECOMPUTE_EXTRINSIC = 1 << 9, 1 << 10
+CALIB_USE_INTRINSIC_GUESS = 1 << 11
+CALIB_BLOCK_DOUBLES = 272
+
+
+class CalibOptions(ctypes.Structure):
+    """ecal_calib_options (include/ecal.h)."""
+    _fields_ = [("model", ctypes.c_int), ("flags", ctypes.c_uint32), ("aspect_ratio", ctypes.c_double),
+                ("max_iter", ctypes.c_int), ("eps", ctypes.c_double), ("allreduce", ALLREDUCE_FN),
+                ("allreduce_user", ctypes.c_void_p)]
+
+
+class CalibResult(ctypes.Structure):
+    _fields_ = [("intr", ctypes.c_double * 12), ("rms", ctypes.c_double), ("iterations", ctypes.c_int),
+                ("jacobian_evaluations", ctypes.c_int), ("error_evaluations", ctypes.c_int), ("seconds", ctypes.c_double)]
+
+
+class DetectParams(ctypes.Structure):
+    """ecal_detect_params (include/ecal.h)."""
+    _fields_ = [("dbscan_eps", ctypes.c_double), ("dbscan_min_samples", ctypes.c_uint32), ("cluster_min_sample", ctypes.c_uint32),
+                ("need_clusters", ctypes.c_uint32), ("circle_radius_threshold", ctypes.c_double), ("fit_circle", ctypes.c_int),
+                ("knn_num", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cols", ctypes.c_uint32)]
+
+
+class IngestStats(ctypes.Structure):
+    _fields_ = [("chunks", ctypes.c_uint32), ("max_chunk_events", ctypes.c_uint64), ("bytes_uploaded", ctypes.c_uint64),
+                ("seconds", ctypes.c_double)]
+
+
+class AdaptiveParams(ctypes.Structure):
+    _fields_ = [("motion_time_step", ctypes.c_double), ("frame_event_num_threshold", ctypes.c_uint32), ("piece_num", ctypes.c_uint32),
+                ("start_time", ctypes.c_double), ("end_time", ctypes.c_double), ("max_passes", ctypes.c_uint32),
+                ("check_every", ctypes.c_uint32), ("gate_mode", ctypes.c_int), ("piece_first", ctypes.c_uint32),
+                ("piece_count", ctypes.c_uint32)]
+GATE_OWN_PIECE, GATE_SHARED_MAP = 0, 1
+
+
+class KeyframeFrame(ctypes.Structure):   # ecal_keyframe_frame
+    _fields_ = [("has", ctypes.c_int), ("time", ctypes.c_double), ("dir", ctypes.c_double * 64)]
+
+
+_FRAME_RECV = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(KeyframeFrame), ctypes.c_int)
+_FRAME_SEND = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(KeyframeFrame))
+
+
+class AdaptiveHandover(ctypes.Structure):   # ecal_adaptive_handover
+    _fields_ = [("recv", _FRAME_RECV), ("send", _FRAME_SEND), ("user", ctypes.c_void_p)]
+
+
+def _prototypes():
+    """name -> (restype, argtypes) of every symbol include/ecal.h declares, in the header's order of arguments: POINTER(Struct)
+    where the callers pass byref(struct), c_void_p for handles and for device and host buffers, c_char_p for paths and text.
+    tests/test_capi_prototypes.py holds the table against the header."""
+    vp, cp, i32, u32, u64, sz, f64 = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t,
+                                      ctypes.c_double)
+    P = ctypes.POINTER
+    u8 = ctypes.c_uint8
+    keyframes = [vp, vp, u64, P(AdaptiveParams), P(DetectParams), u32, u32, vp, vp, vp, vp, P(u32), P(u32), P(u64)]
+    return {
+        "ecal_abi_version": (i32, []),
+        "ecal_init": (i32, [i32, P(vp)]),
+        "ecal_destroy": (None, [vp]),
+        "ecal_strerror": (cp, [i32]),
+        "ecal_last_error": (cp, [vp]),
+        "ecal_sync": (i32, [vp]),
+        "ecal_dbscan_batch": (i32, [vp, vp, vp, u32, f64, u32, vp, vp]),
+        "ecal_dbscan_batch_dev": (i32, [vp, vp, vp, vp, u32, u32, u32, f64, u32, vp, vp, vp]),
+        "ecal_window_bounds_dev": (i32, [vp, vp, u64, vp, vp, u32, vp, vp, vp, vp]),
+        "ecal_check_sorted_dev": (i32, [vp, vp, u64, vp, vp]),
+        "ecal_sort_events_dev": (i32, [vp, vp, u64, vp, vp]),
+        "ecal_slice_events_dev": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "ecal_set_point_order": (i32, [vp, i32]),
+        "ecal_get_point_order": (i32, [vp]),
+        "ecal_ref_bucket_step": (u64, [i32]),
+        "ecal_ref_pixel_hash": (u64, [f64, f64]),
+        "ecal_comm_unique_id": (i32, [vp]),
+        "ecal_comm_init": (i32, [vp, vp, i32, i32]),
+        "ecal_comm_destroy": (i32, [vp]),
+        "ecal_comm_size": (i32, [vp]),
+        "ecal_comm_rank": (i32, [vp]),
+        "ecal_comm_allreduce_sum_dev": (i32, [vp, vp, sz, vp]),
+        "ecal_comm_allreduce": (i32, [vp, vp, sz, vp]),
+        "ecal_circle_radius_threshold": (f64, [f64, f64, i32, i32, i32, f64, f64]),
+        "ecal_extract_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f64, i32, u32, vp, vp, vp, vp, vp, vp]),
+        "ecal_extract_batch_ordered_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f64, i32, u32, vp, vp, vp, vp, vp, vp]),
+        "ecal_extract_batch_exact_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, f64, u32, u32, f64, i32, u32, vp, vp, vp, vp, vp, vp]),
+        "ecal_cluster_order_list_dev": (i32, [vp, vp, vp, vp, u32, f64, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "ecal_set_median_ties": (i32, [vp, i32]),
+        "ecal_set_tail_mode": (i32, [vp, i32]),
+        "ecal_get_tail_mode": (i32, [vp]),
+        "ecal_calibrate_fisheye_views": (i32, [vp, vp, u32, vp, u32, f64, f64, P(CalibOptions), P(CalibResult), vp, vp, vp, P(i32)]),
+        "ecal_set_profile_ranges": (i32, [vp, i32]),
+        "ecal_get_median_ties": (i32, [vp]),
+        "ecal_detect_fused_dev": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u32, u32, f64, u32, u32, u32, f64, i32, u32,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ecal_cluster_order_dev": (i32, [vp, vp, vp, vp, u32, f64, vp, vp, vp, vp, i32, vp]),
+        "ecal_cluster_order": (i32, [vp, vp, vp, u32, f64, vp, vp, vp, vp]),
+        "ecal_stream_create": (i32, [vp, vp, u64, P(vp)]),
+        "ecal_stream_destroy": (None, [vp]),
+        "ecal_stream_size": (u64, [vp]),
+        "ecal_stream_data": (vp, [vp]),
+        "ecal_stream_to_bin_file": (i32, [vp, vp, cp]),
+        "ecal_detect_batch": (i32, [vp, vp, vp, vp, u32, P(DetectParams), u32, vp]),
+        "ecal_copy_dev": (i32, [vp, vp, vp, sz, vp, i32]),
+        "ecal_grid_order_dev": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]),
+        "ecal_grid_order": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "ecal_associate_dev": (i32, [vp, vp, u64, vp, vp, u32, u32, f64, f64, f64, f64, vp, vp, vp, vp, vp]),
+        "ecal_associate": (i32, [vp, vp, vp, vp, u32, u32, f64, f64, f64, f64, u64, vp, vp, vp, P(u64)]),
+        "ecal_pin_host": (i32, [vp, vp, sz]),
+        "ecal_unpin_host": (i32, [vp, vp]),
+        "ecal_detect_stream_tiled": (i32, [vp, vp, u64, f64, f64, u32, P(DetectParams), u32, vp, vp, vp, P(u32), P(IngestStats)]),
+        "ecal_gather_features_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]),
+        "ecal_detect_pass": (i32, [vp, vp, u64, vp, vp, u32, P(DetectParams), u32, vp]),
+        "ecal_detect_keyframes": (i32, keyframes),
+        "ecal_detect_keyframes_sharded": (i32, keyframes + [P(AdaptiveHandover)]),
+        "ecal_detect_keyframes_cap_hint": (u64, [P(AdaptiveParams), u64]),
+        "ecal_detect_keyframes_cap_hint_dev": (u64, [vp, vp, u64, P(AdaptiveParams)]),
+        "ecal_stream_create_from_file": (i32, [vp, cp, f64, i32, f64, P(vp)]),
+        "ecal_stream_times": (i32, [vp, P(f64), P(f64)]),
+        "ecal_rectify_batch_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, P(RectifyParams), vp, vp, vp, vp]),
+        "ecal_rectify_batch": (i32, [vp, vp, vp, vp, vp, u32, vp, u32, vp, P(RectifyParams), vp, vp, vp]),
+        "ecal_solver_create": (i32, [vp, P(_SplineProblem), P(vp)]),
+        "ecal_solver_destroy": (None, [vp]),
+        "ecal_solver_param_size": (sz, [vp]),
+        "ecal_solver_normal_size": (sz, [vp]),
+        "ecal_solver_num_chunks": (u32, [vp]),
+        "ecal_solver_evaluate_dev": (i32, [vp, vp, i32, vp, vp]),
+        "ecal_solver_evaluate": (i32, [vp, vp, i32, vp]),
+        "ecal_residuals_dev": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ecal_residuals": (i32, [vp, vp, vp, vp, vp]),
+        "ecal_lm_default_options": (None, [P(LmOptions)]),
+        "ecal_solver_solve": (i32, [vp, vp, P(LmOptions), P(LmSummary)]),
+        "ecal_inverse_radial_distortion": (None, [vp, vp]),
+        "ecal_solver_create_dev": (i32, [vp, P(_SplineProblem), vp, vp, P(vp)]),
+        "ecal_solver_num_residuals": (u64, [vp]),
+        "ecal_associate_ranges_dev": (i32, [vp, vp, u64, vp, vp, u32, u32, vp, u32, f64, f64, vp, vp, vp, vp, vp, vp]),
+        "ecal_ref_nth_element_f64": (None, [vp, u32, u32]),
+        "ecal_solver_create_from_stream": (i32, [vp, vp, vp, vp, u32, u32, vp, u32, f64, f64, P(_SplineProblem), P(vp)]),
+        "ecal_rectify_keyframes": (i32, [vp, vp, vp, u32, P(DetectParams), vp, vp, P(RectifyParams), vp, vp, vp]),
+        "ecal_solver_time_shard_cuts": (i32, [vp, u32, i32, vp]),
+        "ecal_slice_events_packed_dev": (i32, [vp, vp, u64, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, P(PackedPoints), vp]),
+        "ecal_dbscan_batch_packed_dev": (i32, [vp, vp, vp, vp, u32, u32, u32, f64, u32, vp, vp, P(PackedPoints), vp]),
+        "ecal_extract_batch_packed_dev": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, f64, u32, u32, f64, i32, u32, vp, vp, vp, vp, vp,
+                                                P(PackedPoints), vp]),
+        "ecal_unpack_points_dev": (i32, [vp, P(PackedPoints), vp, vp, u32, vp, vp]),
+        "ecal_report_default_options": (None, [P(ReportOptions)]),
+        "ecal_solver_report_dev": (i32, [vp, vp, vp, u32, P(ReportOptions), vp, vp, vp, vp, vp, vp, vp]),
+        "ecal_solver_report": (i32, [vp, vp, vp, u32, P(ReportOptions), vp, vp, vp, vp, vp, vp]),
+        "ecal_solver_num_landmarks": (u32, [vp]),
+        "ecal_report_px_default_options": (None, [P(ReportOptions)]),
+        "ecal_solver_report_px_dev": (i32, [vp, vp, vp, u32, P(ReportOptions), vp, vp, vp, vp, vp, vp, vp]),
+        "ecal_solver_report_px": (i32, [vp, vp, vp, u32, P(ReportOptions), vp, vp, vp, vp, vp, vp]),
+        "ecal_residuals_px_dev": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ecal_residuals_px": (i32, [vp, vp, vp, vp, vp]),
+        "ecal_board_image_default_options": (i32, [vp, P(BoardImageOptions)]),
+        "ecal_solver_board_image_dev": (i32, [vp, vp, vp, u64, P(BoardImageOptions), vp, vp, vp, vp, vp]),
+        "ecal_solver_board_image": (i32, [vp, vp, vp, P(BoardImageOptions), vp, vp, vp, vp]),
+        "ecal_solver_board_points_dev": (i32, [vp, vp, vp, u64, vp, vp, vp]),
+        "ecal_solver_board_points": (i32, [vp, vp, vp, vp, vp]),
+        "ecal_solver_reassociate_dev": (i32, [vp, vp, vp, u64, f64, vp, vp, vp, vp, vp, vp, vp]),
+        "ecal_solver_reassociate": (i32, [vp, vp, vp, f64, u64, vp, vp, vp, vp, P(u64), vp]),
+        "ecal_solver_create_reassociated": (i32, [vp, vp, vp, f64, P(vp), vp]),
+        "ecal_text_default_options": (None, [P(TextOptions)]),
+        "ecal_events_from_text_dev": (i32, [vp, vp, u64, P(TextOptions), vp, u64, P(TextInfo), vp]),
+        "ecal_text_count_lines_dev": (i32, [vp, vp, u64, P(u64), vp]),
+        "ecal_stream_create_from_text_file": (i32, [vp, cp, P(TextOptions), P(vp), P(TextInfo)]),
+        "ecal_text_to_bin_file": (i32, [vp, cp, cp, P(TextOptions), P(TextInfo)]),
+        "ecal_raw_default_options": (None, [P(RawOptions)]),
+        "ecal_raw_block_words": (u32, [i32]),
+        "ecal_raw_count_events_dev": (i32, [vp, vp, u64, i32, P(u64), vp]),
+        "ecal_events_from_raw_dev": (i32, [vp, vp, u64, P(RawOptions), vp, u64, P(RawInfo), vp]),
+        "ecal_stream_create_from_raw_file": (i32, [vp, cp, P(RawOptions), P(vp), P(RawInfo)]),
+        "ecal_raw_to_bin_file": (i32, [vp, cp, cp, P(RawOptions), P(RawInfo)]),
+        "ecal_aedat_default_options": (None, [P(AedatOptions)]),
+        "ecal_aedat_block_events": (u32, [i32]),
+        "ecal_aedat_parse_header": (i32, [vp, cp, u64, P(i32), P(u64)]),
+        "ecal_aedat_index_packets": (i32, [vp, vp, u64, i32, vp, u64, P(u64), P(AedatInfo)]),
+        "ecal_aedat_count_events_dev": (i32, [vp, vp, u64, vp, u64, i32, P(u64), vp]),
+        "ecal_events_from_aedat_dev": (i32, [vp, vp, u64, vp, u64, P(AedatOptions), vp, u64, P(AedatInfo), vp]),
+        "ecal_stream_create_from_aedat_file": (i32, [vp, cp, P(AedatOptions), P(vp), P(AedatInfo)]),
+        "ecal_aedat_to_bin_file": (i32, [vp, cp, cp, P(AedatOptions), P(AedatInfo)]),
+        "ecal_aedat4_default_options": (None, [P(Aedat4Options)]),
+        "ecal_aedat4_block_events": (u32, []),
+        "ecal_aedat4_parse_header": (i32, [vp, cp, u64, u64, P(i32), P(u64), P(u64)]),
+        "ecal_aedat4_index_packets": (i32, [vp, vp, u64, i32, vp, u64, P(u64), P(Aedat4Info)]),
+        "ecal_aedat4_count_events_dev": (i32, [vp, vp, u64, vp, u64, P(Aedat4Options), P(u64), vp]),
+        "ecal_events_from_aedat4_dev": (i32, [vp, vp, u64, vp, u64, P(Aedat4Options), vp, u64, P(Aedat4Info), vp]),
+        "ecal_stream_create_from_aedat4_file": (i32, [vp, cp, P(Aedat4Options), P(vp), P(Aedat4Info)]),
+        "ecal_aedat4_to_bin_file": (i32, [vp, cp, cp, P(Aedat4Options), P(Aedat4Info)]),
+        "ecal_bag_default_options": (None, [P(BagOptions)]),
+        "ecal_bag_block_events": (u32, []),
+        "ecal_bag_index_messages": (i32, [vp, vp, u64, P(BagOptions), vp, u64, P(u64), P(BagInfo)]),
+        "ecal_bag_count_events_dev": (i32, [vp, vp, u64, vp, u64, P(u64), vp]),
+        "ecal_events_from_bag_dev": (i32, [vp, vp, u64, vp, u64, P(BagOptions), vp, u64, P(BagInfo), vp]),
+        "ecal_stream_create_from_bag_file": (i32, [vp, cp, P(BagOptions), P(vp), P(BagInfo)]),
+        "ecal_bag_to_bin_file": (i32, [vp, cp, cp, P(BagOptions), P(BagInfo)]),
+        "ecal_fields_default_options": (None, [P(FieldsOptions)]),
+        "ecal_to_fields_default_options": (None, [P(ToFieldsOptions)]),
+        "ecal_npy_default_options": (None, [P(NpyOptions)]),
+        "ecal_fields_block_events": (u32, []),
+        "ecal_events_from_fields_host": (i32, [P(Field), u64, P(FieldsOptions), vp, u64, P(FieldsInfo), cp, u64]),
+        "ecal_events_from_fields_dev": (i32, [vp, P(Field), u64, P(FieldsOptions), vp, u64, P(FieldsInfo), vp]),
+        "ecal_stream_create_from_fields": (i32, [vp, P(Field), u64, P(FieldsOptions), P(vp), P(FieldsInfo)]),
+        "ecal_events_to_fields_host": (i32, [vp, u64, P(Field), P(ToFieldsOptions), P(ToFieldsInfo), cp, u64]),
+        "ecal_events_to_fields_dev": (i32, [vp, vp, u64, P(Field), P(ToFieldsOptions), P(ToFieldsInfo), vp]),
+        "ecal_npy_parse_header": (i32, [vp, vp, u64, u64, P(NpyOptions), P(NpyLayout), cp, u64]),
+        "ecal_stream_create_from_npy_file": (i32, [vp, cp, P(NpyOptions), P(vp), P(FieldsInfo)]),
+        "ecal_npy_to_bin_file": (i32, [vp, cp, cp, P(NpyOptions), P(FieldsInfo)]),
+        "ecal_stream_to_npy_file": (i32, [vp, vp, cp]),
+        "ecal_hot_pixel_default_options": (None, [P(HotPixelOptions)]),
+        "ecal_pixel_activity_dev": (i32, [vp, vp, u64, u32, u32, vp, vp, vp]),
+        "ecal_hot_pixel_mask": (i32, [vp, P(HotPixelOptions), vp, vp, P(HotPixelInfo)]),
+        "ecal_filter_events_dev": (i32, [vp, vp, u64, vp, u32, u32, vp, vp, vp, vp]),
+        "ecal_stream_remove_hot_pixels": (i32, [vp, vp, P(HotPixelOptions), vp, P(vp), vp, vp, P(HotPixelInfo)]),
+        "ecal_noise_default_options": (None, [P(NoiseOptions)]),
+        "ecal_noise_verdict_host": (i32, [vp, u64, P(NoiseOptions), vp, vp]),
+        "ecal_noise_verdict_dev": (i32, [vp, vp, u64, P(NoiseOptions), vp, vp, vp]),
+        "ecal_denoise_events_dev": (i32, [vp, vp, u64, P(NoiseOptions), vp, vp, vp, vp]),
+        "ecal_stream_remove_noise": (i32, [vp, vp, P(NoiseOptions), P(vp), vp]),
+        "ecal_undistort_camera_from_params": (None, [i32, vp, P(UndistortCamera)]),
+        "ecal_undistort_reference_canvas": (None, [u32, u32, P(UndistortOptions)]),
+        "ecal_undistort_camera_error": (cp, [P(UndistortCamera)]),
+        "ecal_undistort_options_error": (cp, [P(UndistortOptions)]),
+        "ecal_undistort_round_half_away": (f64, [f64]),
+        "ecal_undistort_points_host": (i32, [P(UndistortCamera), vp, u64, vp, vp]),
+        "ecal_undistort_points_dev": (i32, [vp, P(UndistortCamera), vp, u64, vp, vp, vp]),
+        "ecal_undistort_events_dev": (i32, [vp, P(UndistortCamera), P(UndistortOptions), vp, u64, vp, vp, vp, vp]),
+        "ecal_stream_undistort": (i32, [vp, vp, P(UndistortCamera), P(UndistortOptions), P(vp), vp]),
+        "ecal_undistorted_frames_dev": (i32, [vp, P(UndistortCamera), P(UndistortOptions), vp, P(PackedPoints), vp, vp, u32, vp, vp, vp]),
+        "ecal_stream_undistorted_frames": (i32, [vp, vp, P(UndistortCamera), P(UndistortOptions), vp, vp, u32, vp, vp]),
+        "ecal_image_reference_options": (None, [u32, u32, P(ImageOptions)]),
+        "ecal_image_options_error": (cp, [P(ImageOptions)]),
+        "ecal_camera_monotone_radius": (i32, [P(UndistortCamera), u32, u32, P(f64), P(u32)]),
+        "ecal_distort_points_host": (i32, [P(UndistortCamera), u32, u32, vp, u64, vp, vp]),
+        "ecal_distort_points_dev": (i32, [vp, P(UndistortCamera), u32, u32, vp, u64, vp, vp, vp]),
+        "ecal_undistort_image_host": (i32, [P(UndistortCamera), u32, u32, P(ImageOptions), vp, vp, vp, P(ImageInfo)]),
+        "ecal_image_table_host": (i32, [P(UndistortCamera), u32, u32, P(ImageOptions), vp, vp, vp, u64, P(ImageInfo)]),
+        "ecal_image_maps_host": (i32, [P(UndistortCamera), u32, u32, P(ImageOptions), vp, vp, vp, P(ImageInfo)]),
+        "ecal_image_plan_create": (i32, [vp, P(UndistortCamera), u32, u32, P(ImageOptions), P(vp)]),
+        "ecal_image_plan_destroy": (None, [vp]),
+        "ecal_image_plan_info": (i32, [vp, P(ImageInfo)]),
+        "ecal_image_plan_maps_dev": (i32, [vp, vp, vp, vp, vp]),
+        "ecal_image_plan_maps": (i32, [vp, vp, vp, vp]),
+        "ecal_image_plan_table": (i32, [vp, vp, vp, vp]),
+        "ecal_undistort_images_dev": (i32, [vp, vp, vp, u32, vp, vp, vp]),
+        "ecal_undistort_images": (i32, [vp, vp, vp, u32, vp, vp]),
+        "ecal_calib_default_options": (None, [P(CalibOptions)]),
+        "ecal_calib_view_blocks_dev": (i32, [vp, vp, u32, vp, u32, i32, u32, f64, vp, vp, i32, vp, vp]),
+        "ecal_pnp_batch_dev": (i32, [vp, vp, u32, vp, vp, u32, i32, vp, f64, i32, i32, vp, vp, vp, vp, vp]),
+        "ecal_pnp_batch": (i32, [vp, vp, u32, vp, vp, u32, i32, vp, f64, i32, i32, vp, vp, vp, vp]),
+        "ecal_pose_gates": (i32, [u32, P(f64), P(f64), P(f64), P(u8), P(u8), f64, P(u32), P(u32), P(u32), P(u32)]),
+        "ecal_calibrate_views": (i32, [vp, vp, u32, vp, u32, f64, f64, P(CalibOptions), P(CalibResult), vp, vp, vp]),
+        "ecal_spline_fit": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "ecal_spline_eval": (i32, [vp, vp, u32, u32, vp, u32, vp]),
+        "ecal_spline_so3_refine": (i32, [vp, u32, vp, vp, vp, u32, i32, P(f64), P(f64), P(i32)]),
+    }
+
+
+PROTOTYPES = _prototypes()
+# the ecal_debug_* symbols the package calls (not in the public header: set where the library exports them)
+DEBUG_PROTOTYPES = {
+    "ecal_debug_reload_env": (ctypes.c_int, [ctypes.c_void_p]),
+    "ecal_debug_px_todo_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]),
+    "ecal_debug_tail_seen": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+}
+
+
 import weakref
 
 _live_contexts = weakref.WeakSet()
@@ -329,97 +733,27 @@ def load_library():
     except ImportError:
         pass
     L = ctypes.CDLL(p)
-    vp, u32, i32, f64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_double
-    L.ecal_abi_version.restype = i32
-    L.ecal_init.argtypes = [i32, ctypes.POINTER(vp)]
-    L.ecal_init.restype = i32
-    L.ecal_destroy.argtypes = [vp]
-    L.ecal_destroy.restype = None
-    L.ecal_strerror.argtypes = [i32]
-    L.ecal_strerror.restype = ctypes.c_char_p
-    L.ecal_last_error.argtypes = [vp]
-    L.ecal_last_error.restype = ctypes.c_char_p
-    L.ecal_sync.argtypes = [vp]
-    L.ecal_sync.restype = i32
-    L.ecal_dbscan_batch.argtypes = [vp, vp, vp, u32, f64, u32, vp, vp]
-    L.ecal_dbscan_batch.restype = i32
-    L.ecal_dbscan_batch_dev.argtypes = [vp, vp, vp, vp, u32, u32, u32, f64, u32, vp, vp, vp]
-    L.ecal_dbscan_batch_dev.restype = i32
-    u64 = ctypes.c_uint64
-    L.ecal_comm_unique_id.argtypes = [vp]
-    L.ecal_comm_unique_id.restype = i32
-    L.ecal_comm_init.argtypes = [vp, vp, i32, i32]
-    L.ecal_comm_init.restype = i32
-    L.ecal_comm_destroy.argtypes = [vp]
-    L.ecal_comm_destroy.restype = i32
-    L.ecal_comm_size.argtypes = [vp]
-    L.ecal_comm_size.restype = i32
-    L.ecal_comm_rank.argtypes = [vp]
-    L.ecal_comm_rank.restype = i32
-    L.ecal_comm_allreduce_sum_dev.argtypes = [vp, vp, ctypes.c_size_t, vp]
-    L.ecal_comm_allreduce_sum_dev.restype = i32
-    L.ecal_set_point_order.argtypes = [vp, i32]
-    L.ecal_set_point_order.restype = i32
-    L.ecal_get_point_order.argtypes = [vp]
-    L.ecal_get_point_order.restype = i32
-    L.ecal_ref_bucket_step.argtypes = [i32]
-    L.ecal_ref_bucket_step.restype = u64
-    L.ecal_ref_pixel_hash.argtypes = [f64, f64]
-    L.ecal_ref_pixel_hash.restype = u64
-    L.ecal_window_bounds_dev.argtypes = [vp, vp, u64, vp, vp, u32, vp, vp, vp, vp]
-    L.ecal_window_bounds_dev.restype = i32
-    L.ecal_check_sorted_dev.argtypes = [vp, vp, u64, vp, vp]
-    L.ecal_check_sorted_dev.restype = i32
-    L.ecal_slice_events_dev.argtypes = [vp, vp, u64, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp]
-    L.ecal_slice_events_dev.restype = i32
-    L.ecal_circle_radius_threshold.argtypes = [f64, f64, i32, i32, i32, f64, f64]
-    L.ecal_circle_radius_threshold.restype = f64
-    L.ecal_extract_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, f64, i32, u32, vp, vp, vp, vp, vp, vp]
-    L.ecal_extract_batch_dev.restype = i32
-    L.ecal_detect_fused_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp, u32, u32, u32, u32, f64, u32, u32, u32, f64, i32, u32,
-                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.ecal_detect_fused_dev.restype = i32
-    L.ecal_grid_order_dev.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
-    L.ecal_grid_order_dev.restype = i32
-    L.ecal_rectify_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(RectifyParams),
-                                         vp, vp, vp, vp]
-    L.ecal_rectify_batch_dev.restype = i32
-    L.ecal_associate_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, u32, u32, f64, f64, f64, f64, vp, vp, vp, vp, vp]
-    L.ecal_associate_dev.restype = i32
-    L.ecal_associate_ranges_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, u32, u32, vp, u32, f64, f64, vp, vp, vp, vp, vp, vp]
-    L.ecal_associate_ranges_dev.restype = i32
-    L.ecal_copy_dev.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, i32]
-    L.ecal_copy_dev.restype = i32
+    _apply_prototypes(L)
     _LIB = L
     return L
 
 
-class HotPixelOptions(ctypes.Structure):
-    """ecal_hot_pixel_options (include/ecal.h, pixel activity / hot pixels)."""
-    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("quantile_permille", ctypes.c_uint32),
-                ("min_count", ctypes.c_uint32), ("factor", ctypes.c_double)]
-
-
-class HotPixelInfo(ctypes.Structure):
-    """ecal_hot_pixel_info (include/ecal.h, pixel activity / hot pixels)."""
-    _fields_ = [("n_events", ctypes.c_uint64), ("n_off_grid", ctypes.c_uint64), ("n_removed", ctypes.c_uint64), ("n_kept", ctypes.c_uint64),
-                ("n_active_pixels", ctypes.c_uint32), ("n_hot_pixels", ctypes.c_uint32), ("n_masked_pixels", ctypes.c_uint32),
-                ("quantile_count", ctypes.c_uint32), ("max_count", ctypes.c_uint32), ("max_kept_count", ctypes.c_uint32)]
-
-    def as_dict(self):
-        return {name: int(getattr(self, name)) for name, _ in self._fields_}
-
-
-# ecal_activity_totals / ecal_filter_totals as numpy records
-ACTIVITY_TOTALS = np.dtype([("n_events", np.uint64), ("n_on_grid", np.uint64), ("n_off_grid", np.uint64)])
-FILTER_TOTALS = np.dtype([("n_events", np.uint64), ("n_off_grid", np.uint64), ("n_removed", np.uint64), ("n_kept", np.uint64)])
+def _apply_prototypes(L):
+    """the one place a prototype is set on the library handle: every public symbol (a missing one raises AttributeError), and
+    the debug symbols this build exports"""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    for name, (restype, argtypes) in DEBUG_PROTOTYPES.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
 
 
 def hot_pixel_options(width=None, height=None, quantile_permille=None, min_count=None, factor=None):
     """ecal_hot_pixel_options from ecal_hot_pixel_default_options (346 x 260, the 99 % quantile, 64 events, factor 8); None keeps
     the default."""
     L = load_library()
-    L.ecal_hot_pixel_default_options.argtypes, L.ecal_hot_pixel_default_options.restype = [ctypes.POINTER(HotPixelOptions)], None
     o = HotPixelOptions()
     L.ecal_hot_pixel_default_options(ctypes.byref(o))
     if width is not None:
@@ -440,9 +774,6 @@ def hot_pixel_mask(counts, extra_mask=None, **options):
     an optional extra_mask [H, W] (non-zero: remove whatever it counts) -> (mask [H, W] bool, info dict).  options:
     quantile_permille, min_count, factor; width and height come from the shape of counts."""
     L = load_library()
-    L.ecal_hot_pixel_mask.argtypes = [ctypes.c_void_p, ctypes.POINTER(HotPixelOptions), ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.POINTER(HotPixelInfo)]
-    L.ecal_hot_pixel_mask.restype = ctypes.c_int
     c = np.asarray(counts)
     if c.ndim != 3 or c.shape[0] != 2:
         raise ValueError("counts must be [2, H, W]")
@@ -466,17 +797,10 @@ def hot_pixel_mask(counts, extra_mask=None, **options):
     return mask.astype(bool), info.as_dict()
 
 
-class NoiseOptions(ctypes.Structure):
-    """ecal_noise_options (include/ecal.h, noise filter)."""
-    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32), ("min_support", ctypes.c_uint32),
-                ("include_self", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("dt", ctypes.c_double)]
-
-
 def noise_options(width=None, height=None, radius=None, min_support=None, include_self=None, dt=None, reserved=None):
     """ecal_noise_options from ecal_noise_default_options (346 x 260, radius 1, min_support 1, include_self 0, dt 0.005 in the stream's
     time unit); None keeps the default."""
     L = load_library()
-    L.ecal_noise_default_options.argtypes, L.ecal_noise_default_options.restype = [ctypes.POINTER(NoiseOptions)], None
     o = NoiseOptions()
     L.ecal_noise_default_options(ctypes.byref(o))
     for name, value in (("width", width), ("height", height), ("radius", radius), ("min_support", min_support),
@@ -496,8 +820,6 @@ def noise_verdict_host(events, **options):
     records -> (verdict uint8 [n]: 1 keep, 0 remove; totals: one FILTER_TOTALS record).  options: width, height, radius,
     min_support, include_self, dt."""
     L = load_library()
-    L.ecal_noise_verdict_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), ctypes.c_void_p, ctypes.c_void_p]
-    L.ecal_noise_verdict_host.restype = ctypes.c_int
     ev = np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else np.asarray(events, np.uint8).ravel()
     ev = np.ascontiguousarray(ev)
     assert ev.size % 25 == 0, "packed 25-byte event records"
@@ -511,27 +833,6 @@ def noise_verdict_host(events, **options):
     return verdict, tot[0]
 
 
-CAMERA_RADIAL, CAMERA_FISHEYE = 0, 1          # ECAL_CAMERA_RADIAL / _FISHEYE
-UNDISTORT_SUBPIXEL, UNDISTORT_PIXEL = 0, 1    # ECAL_UNDISTORT_SUBPIXEL / _PIXEL
-UNDISTORT_TOTALS = np.dtype([("n_events", np.uint64), ("n_invalid", np.uint64), ("n_outside", np.uint64), ("n_kept", np.uint64)])
-UNDISTORT_FRAME_TOTALS = np.dtype([("n_pos", np.uint32), ("n_neg", np.uint32), ("n_invalid", np.uint32), ("n_outside", np.uint32)])
-
-
-class UndistortCamera(ctypes.Structure):
-    """ecal_undistort_camera (include/ecal.h, undistortion)."""
-    _fields_ = [("model", ctypes.c_int), ("reserved", ctypes.c_int), ("intr", ctypes.c_double * 9), ("out_k", ctypes.c_double * 4)]
-
-
-class UndistortOptions(ctypes.Structure):
-    """ecal_undistort_options (include/ecal.h, undistortion)."""
-    _fields_ = [("mode", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
-                ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
-
-    def as_dict(self):
-        return {"mode": int(self.mode), "out_width": int(self.out_width), "out_height": int(self.out_height),
-                "off_x": float(self.off_x), "off_y": float(self.off_y)}
-
-
 def undistort_camera(params, model=CAMERA_RADIAL, out_k=None, reserved=0):
     """ecal_undistort_camera from the head of the solver's parameter vector (fx fy cx cy k1..k5; ecal_undistort_camera_from_params:
     out_k = fx fy cx cy, as the reference's K_ * Xc) or with another ideal camera out_k = (fx', fy', cx', cy').  An UndistortCamera
@@ -539,8 +840,6 @@ def undistort_camera(params, model=CAMERA_RADIAL, out_k=None, reserved=0):
     if isinstance(params, UndistortCamera):
         return params
     L = load_library()
-    L.ecal_undistort_camera_from_params.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(UndistortCamera)]
-    L.ecal_undistort_camera_from_params.restype = None
     p = np.ascontiguousarray(np.asarray(params, np.float64).ravel()[:9])
     if p.size != 9:
         raise ValueError("fx fy cx cy k1..k5: nine numbers")
@@ -555,8 +854,6 @@ def undistort_camera(params, model=CAMERA_RADIAL, out_k=None, reserved=0):
 def undistort_reference_canvas(width, height):
     """ecal_undistort_reference_canvas: PIXEL options with the reference's canvas, round(1.2 * size), and offsets, size * 0.1"""
     L = load_library()
-    L.ecal_undistort_reference_canvas.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(UndistortOptions)]
-    L.ecal_undistort_reference_canvas.restype = None
     o = UndistortOptions()
     L.ecal_undistort_reference_canvas(int(width), int(height), ctypes.byref(o))
     return o
@@ -583,7 +880,6 @@ def undistort_options(mode=None, out_width=None, out_height=None, off_x=None, of
 def undistort_camera_error(cam):
     """ecal_undistort_camera_error: None, or the text that names the refused field"""
     L = load_library()
-    L.ecal_undistort_camera_error.argtypes, L.ecal_undistort_camera_error.restype = [ctypes.POINTER(UndistortCamera)], ctypes.c_char_p
     r = L.ecal_undistort_camera_error(ctypes.byref(cam))
     return r.decode() if r else None
 
@@ -591,7 +887,6 @@ def undistort_camera_error(cam):
 def undistort_options_error(opt):
     """ecal_undistort_options_error: None, or the text that names the refused field"""
     L = load_library()
-    L.ecal_undistort_options_error.argtypes, L.ecal_undistort_options_error.restype = [ctypes.POINTER(UndistortOptions)], ctypes.c_char_p
     r = L.ecal_undistort_options_error(ctypes.byref(opt))
     return r.decode() if r else None
 
@@ -599,7 +894,6 @@ def undistort_options_error(opt):
 def undistort_round_half_away(a):
     """ecal_undistort_round_half_away: std::round as the library spells it"""
     L = load_library()
-    L.ecal_undistort_round_half_away.argtypes, L.ecal_undistort_round_half_away.restype = [ctypes.c_double], ctypes.c_double
     return float(L.ecal_undistort_round_half_away(float(a)))
 
 
@@ -607,8 +901,6 @@ def undistort_points_host(cam, uv):
     """ecal_undistort_points_host (host arrays; no context, no device): uv [n, 2] -> (out [n, 2] float64 with 0, 0 where invalid,
     flag uint8 [n]: 0 valid, 1 invalid).  cam: an UndistortCamera (undistort_camera)."""
     L = load_library()
-    L.ecal_undistort_points_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-    L.ecal_undistort_points_host.restype = ctypes.c_int
     uv = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
     n = uv.shape[0]
     out = np.zeros((n, 2), np.float64)
@@ -620,38 +912,10 @@ def undistort_points_host(cam, uv):
     return out, flag
 
 
-IMAGE_REFERENCE, IMAGE_BILINEAR = 0, 1              # ECAL_IMAGE_REFERENCE / _BILINEAR
-DISTORT_INVALID, DISTORT_NOT_CONVERGED = 1, 2       # ECAL_DISTORT_INVALID / _NOT_CONVERGED
-
-
-class ImageOptions(ctypes.Structure):
-    """ecal_image_options (include/ecal.h, image undistortion)."""
-    _fields_ = [("method", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32),
-                ("normalize", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("off_x", ctypes.c_double), ("off_y", ctypes.c_double)]
-
-    def as_dict(self):
-        return {"method": int(self.method), "channels": int(self.channels), "out_width": int(self.out_width), "out_height": int(self.out_height),
-                "normalize": int(self.normalize), "off_x": float(self.off_x), "off_y": float(self.off_y)}
-
-
-class ImageInfo(ctypes.Structure):
-    """ecal_image_info (include/ecal.h, image undistortion)."""
-    _fields_ = [("opt", ImageOptions), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("n_invalid_sources", ctypes.c_uint64),
-                ("n_empty", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("max_neighbours", ctypes.c_uint32), ("truncated", ctypes.c_uint32),
-                ("bytes", ctypes.c_uint64), ("r_lim", ctypes.c_double), ("n_invalid", ctypes.c_uint64), ("n_not_converged", ctypes.c_uint64)]
-
-    def as_dict(self):
-        d = {name: getattr(self, name) for name, _ in self._fields_[1:]}
-        d["options"] = self.opt.as_dict()
-        return d
-
-
 def image_reference_options(width, height):
     """ecal_image_reference_options: the reference's canvas, round(1.2 * size) with offsets round(size * 0.1), 3 channels, normalize 1,
     REFERENCE"""
     L = load_library()
-    L.ecal_image_reference_options.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions)]
-    L.ecal_image_reference_options.restype = None
     o = ImageOptions()
     L.ecal_image_reference_options(int(width), int(height), ctypes.byref(o))
     return o
@@ -685,7 +949,6 @@ def image_options(method=None, channels=None, out_width=None, out_height=None, n
 def image_options_error(opt):
     """ecal_image_options_error: None, or the text that names the refused field"""
     L = load_library()
-    L.ecal_image_options_error.argtypes, L.ecal_image_options_error.restype = [ctypes.POINTER(ImageOptions)], ctypes.c_char_p
     r = L.ecal_image_options_error(ctypes.byref(opt) if opt is not None else None)
     return r.decode() if r else None
 
@@ -706,9 +969,6 @@ def _image_host_fail(L, st, who, cam, width, height, opt):
 def camera_monotone_radius(cam, width, height):
     """ecal_camera_monotone_radius -> (r_lim, truncated): the normalised sensor radius up to which the forward projection inverts"""
     L = load_library()
-    L.ecal_camera_monotone_radius.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
-                                              ctypes.POINTER(ctypes.c_uint32)]
-    L.ecal_camera_monotone_radius.restype = ctypes.c_int
     r, t = ctypes.c_double(0.0), ctypes.c_uint32(0)
     st = L.ecal_camera_monotone_radius(ctypes.byref(cam), max(0, int(width)), max(0, int(height)), ctypes.byref(r), ctypes.byref(t))
     if st != 0:
@@ -720,9 +980,6 @@ def distort_points_host(cam, width, height, uv):
     """ecal_distort_points_host (host arrays; no context, no device): uv [n, 2] of the ideal camera -> (out [n, 2] float64 sensor
     pixels with 0, 0 where invalid, flag uint8 [n]: 0, DISTORT_INVALID or DISTORT_NOT_CONVERGED)."""
     L = load_library()
-    L.ecal_distort_points_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
-                                           ctypes.c_void_p, ctypes.c_void_p]
-    L.ecal_distort_points_host.restype = ctypes.c_int
     uv = np.ascontiguousarray(np.asarray(uv, np.float64).reshape(-1, 2))
     n = uv.shape[0]
     out = np.zeros((n, 2), np.float64)
@@ -759,9 +1016,6 @@ def undistort_image_host(cam, width, height, image, opt=None, **options):
     """ecal_undistort_image_host (host arrays; no context, no device): ONE frame uint8 [H, W] or [H, W, C] -> (picture uint8 of the same
     rank on the canvas, minmax float32 [2], info dict).  opt an ImageOptions, or options for image_options."""
     L = load_library()
-    L.ecal_undistort_image_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ImageInfo)]
-    L.ecal_undistort_image_host.restype = ctypes.c_int
     o = opt if opt is not None else image_options(**options)
     if image_options_error(o) or _image_sensor_error(width, height):
         _image_host_fail(L, -1, "ecal_undistort_image_host", cam, width, height, o)
@@ -782,9 +1036,6 @@ def image_table_host(cam, width, height, opt=None, **options):
     """ecal_image_table_host: the REFERENCE table of the host walk -> (off uint32 [canvas pixels + 1], idx uint32 [n], w float64 [n],
     info dict)"""
     L = load_library()
-    L.ecal_image_table_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ImageInfo)]
-    L.ecal_image_table_host.restype = ctypes.c_int
     o = opt if opt is not None else image_options(**options)
     if image_options_error(o) or _image_sensor_error(width, height):
         _image_host_fail(L, -1, "ecal_image_table_host", cam, width, height, o)
@@ -803,9 +1054,6 @@ def image_table_host(cam, width, height, opt=None, **options):
 def image_maps_host(cam, width, height, opt=None, **options):
     """ecal_image_maps_host: the BILINEAR maps of the host walk -> (map_x, map_y float32 [out_height, out_width], valid uint8, info dict)"""
     L = load_library()
-    L.ecal_image_maps_host.argtypes = [ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ImageInfo)]
-    L.ecal_image_maps_host.restype = ctypes.c_int
     o = opt if opt is not None else image_options(**options)
     if image_options_error(o) or _image_sensor_error(width, height):
         _image_host_fail(L, -1, "ecal_image_maps_host", cam, width, height, o)
@@ -825,16 +1073,6 @@ class ImagePlan:
     def __init__(self, ctx, cam, width, height, opt):
         L = ctx._L
         vp = ctypes.c_void_p
-        L.ecal_image_plan_create.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ImageOptions),
-                                             ctypes.POINTER(vp)]
-        L.ecal_image_plan_create.restype = ctypes.c_int
-        L.ecal_image_plan_destroy.argtypes, L.ecal_image_plan_destroy.restype = [vp], None
-        L.ecal_image_plan_info.argtypes, L.ecal_image_plan_info.restype = [vp, ctypes.POINTER(ImageInfo)], ctypes.c_int
-        L.ecal_image_plan_maps.argtypes, L.ecal_image_plan_maps.restype = [vp, vp, vp, vp], ctypes.c_int
-        L.ecal_image_plan_maps_dev.argtypes, L.ecal_image_plan_maps_dev.restype = [vp, vp, vp, vp, vp], ctypes.c_int
-        L.ecal_image_plan_table.argtypes, L.ecal_image_plan_table.restype = [vp, vp, vp, vp], ctypes.c_int
-        L.ecal_undistort_images.argtypes, L.ecal_undistort_images.restype = [vp, vp, vp, ctypes.c_uint32, vp, vp], ctypes.c_int
-        L.ecal_undistort_images_dev.argtypes, L.ecal_undistort_images_dev.restype = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp], ctypes.c_int
         self._ctx, self._L, self._h = ctx, L, None
         self.width, self.height = int(width), int(height)
         h = vp()
@@ -929,7 +1167,6 @@ def fields_options(time_magnitude=None, time_base=None, auto_time_base=False, wi
     """ecal_fields_options from ecal_fields_default_options (time_magnitude 1e-6, time_base 0, no size, no flips, start_time 0, no end
     time); None leaves a default."""
     L = load_library()
-    L.ecal_fields_default_options.argtypes, L.ecal_fields_default_options.restype = [ctypes.POINTER(FieldsOptions)], None
     o = FieldsOptions()
     L.ecal_fields_default_options(ctypes.byref(o))
     if time_magnitude is not None:
@@ -948,7 +1185,6 @@ def fields_options(time_magnitude=None, time_base=None, auto_time_base=False, wi
 def to_fields_options(ticks_per_second=None, time_base=None, polarity_signed=False):
     """ecal_to_fields_options from ecal_to_fields_default_options (1e6 ticks a second, base 0, polarity 0 / 1)."""
     L = load_library()
-    L.ecal_to_fields_default_options.argtypes, L.ecal_to_fields_default_options.restype = [ctypes.POINTER(ToFieldsOptions)], None
     o = ToFieldsOptions()
     L.ecal_to_fields_default_options(ctypes.byref(o))
     if ticks_per_second is not None:
@@ -1002,9 +1238,6 @@ def events_from_fields_host(t, x, y, p, capacity=None, **options):
     fields are taken where they lie) -> (packed records as a uint8 array [n_events * 25], info dict).  No context, no device.
     time_magnitude None: 1e-6 for integer stamps, 1.0 for float stamps.  A refusal raises EcalError with the library's text."""
     L = load_library()
-    L.ecal_events_from_fields_host.argtypes = [ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.c_void_p, ctypes.c_uint64,
-                                               ctypes.POINTER(FieldsInfo), ctypes.c_char_p, ctypes.c_uint64]
-    L.ecal_events_from_fields_host.restype = ctypes.c_int
     cols = [_host_column(a) for a in (t, x, y, p)]
     n = cols[0][0].size
     if any(c[0].size != n for c in cols):
@@ -1027,10 +1260,7 @@ def events_to_fields_host(events, t=np.float64, xy=np.float64, p=np.uint8, **opt
     """ecal_events_to_fields_host: packed records (bytes or a numpy uint8 array) -> ({"t", "x", "y", "p"} numpy arrays of the asked
     dtypes, info dict).  Not representable events raise EcalError (status -6) with .info["n_unrepresentable"]."""
     L = load_library()
-    L.ecal_events_to_fields_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Field), ctypes.POINTER(ToFieldsOptions),
-                                             ctypes.POINTER(ToFieldsInfo), ctypes.c_char_p, ctypes.c_uint64]
-    L.ecal_events_to_fields_host.restype = ctypes.c_int
-    rec = np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else np.ascontiguousarray(events, np.uint8).ravel()
+    rec = _u8_array(events)
     n = rec.size // 25
     out = {"t": np.zeros(n, t), "x": np.zeros(n, xy), "y": np.zeros(n, xy), "p": np.zeros(n, p)}
     f = (Field * 4)(*[_host_column(out[k])[1] for k in "txyp"])
@@ -1050,10 +1280,7 @@ def npy_parse_header(data, file_bytes=None, fields=None, columns=None):
     -> layout dict: data_offset, n_events, item_stride, version_major / _minor, fields {"t": (offset, type name), ...}.  A refusal
     raises EcalError with the library's text."""
     L = load_library()
-    L.ecal_npy_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(NpyOptions),
-                                        ctypes.POINTER(NpyLayout), ctypes.c_char_p, ctypes.c_uint64]
-    L.ecal_npy_parse_header.restype = ctypes.c_int
-    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).ravel()
+    a = _u8_array(data)
     o = npy_options(fields=fields, columns=columns)
     lay = NpyLayout()
     err = ctypes.create_string_buffer(512)
@@ -1066,6 +1293,11 @@ def npy_parse_header(data, file_bytes=None, fields=None, columns=None):
 
 def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
+
+
+def _u8_array(data):
+    """bytes, bytearray, memoryview (viewed in place) or anything numpy takes as uint8 -> a flat contiguous uint8 array"""
+    return np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).ravel()
 
 
 class Context:
@@ -1084,7 +1316,6 @@ class Context:
     def reload_env(self):
         """ecal_debug_reload_env: read the ECAL_* debug switches again (they are read once, at ecal_init)."""
         if getattr(self, "_h", None):
-            self._L.ecal_debug_reload_env.argtypes = [ctypes.c_void_p]
             self._check(self._L.ecal_debug_reload_env(self._h))
 
     def close(self):
@@ -1136,8 +1367,6 @@ class Context:
         on this context left on their to-do lists -> (first, second); second is None when no second pass ran (no segment of the
         call could need it, or the lean tail).  stream: the stream that call ran on (None: the context's own, dbscan_batch's)."""
         L = self._L
-        L.ecal_debug_px_todo_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
-        L.ecal_debug_px_todo_counts.restype = ctypes.c_int
         if stream is None:
             self.sync()
             stream = 0
@@ -1150,8 +1379,6 @@ class Context:
         of the slicing and of the DBSCAN stage takes, by what the stage's last call saw on its two lists -> {"slice": p, "dbscan": p},
         p = "lean" (both lists were empty), "semi" (the second was) or "tiered".  The caller has drained the stream of those calls."""
         L = self._L
-        L.ecal_debug_tail_seen.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
-        L.ecal_debug_tail_seen.restype = ctypes.c_int
         seen = (ctypes.c_uint32 * 16)()
         self._check(L.ecal_debug_tail_seen(self._h, seen))
 
@@ -1207,7 +1434,6 @@ class Context:
     def set_median_ties(self, mode):
         """What the composite entry points do at tied medians: "reference" (default) or "smaller_pid"."""
         code = {"reference": 0, "smaller_pid": 1, 0: 0, 1: 1}[mode]
-        self._L.ecal_set_median_ties.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self._L.ecal_set_median_ties(self._h, code))
 
     TAIL_AUTO, TAIL_TIERED, TAIL_LEAN = 0, 1, 2
@@ -1216,13 +1442,10 @@ class Context:
         """How the stage calls schedule their later size tiers (ecal_set_tail_mode): "auto" (default: one general tail launch per
         stage while the stage's to-do lists were empty at its previous call), "tiered" (every tier, every call), "lean"."""
         code = {"auto": 0, "tiered": 1, "lean": 2, 0: 0, 1: 1, 2: 2}[mode]
-        self._L.ecal_set_tail_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self._L.ecal_set_tail_mode(self._h, code))
 
     def get_tail_mode(self):
         """The mode in force as its number (TAIL_AUTO / TAIL_TIERED / TAIL_LEAN): set_tail_mode takes it back."""
-        self._L.ecal_get_tail_mode.argtypes = [ctypes.c_void_p]
-        self._L.ecal_get_tail_mode.restype = ctypes.c_int
         mode = self._L.ecal_get_tail_mode(self._h)
         if mode < 0:
             self._check(mode)
@@ -1230,7 +1453,6 @@ class Context:
 
     def set_profile_ranges(self, on=True):
         """roctx ranges around the stage entry points (ecal_set_profile_ranges) for `rocprofv3 --marker-trace --kernel-trace`."""
-        self._L.ecal_set_profile_ranges.argtypes = [ctypes.c_void_p, ctypes.c_int]
         self._check(self._L.ecal_set_profile_ranges(self._h, 1 if on else 0))
 
     def set_point_order(self, order):
@@ -1246,20 +1468,117 @@ class Context:
                                                    d_win_hi, d_win_base, stream))
 
     def sort_events_dev(self, d_events, n_events, d_sorted, stream=0):
-        self._L.ecal_sort_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        self._L.ecal_sort_events_dev.restype = ctypes.c_int
         self._check(self._L.ecal_sort_events_dev(self._h, d_events, int(n_events), d_sorted, stream))
 
     def check_sorted_dev(self, d_events, n_events, d_flag, stream=0):
         self._check(self._L.ecal_check_sorted_dev(self._h, d_events, int(n_events), d_flag, stream))
+
+    # ---- what the ingest families (text, raw, aedat, aedat4, bag, npy) share: each passes its symbol, options, info and table ----
+    def _fail_with_info(self, st, info):
+        """EcalError of an entry point, with the info struct it filled (first_bad_line, the needed n_events, ...) as .info"""
+        try:
+            self._check(st)
+        except EcalError as e:
+            e.info = info.as_dict()
+            raise
+
+    @staticmethod
+    def _bytes_tensor(data):
+        """bytes / numpy uint8 / torch uint8 (any device) as a CUDA uint8 tensor whose storage starts 16-byte aligned"""
+        import torch
+        if isinstance(data, torch.Tensor):
+            t = data.contiguous().view(torch.uint8).reshape(-1)
+        else:
+            a = _u8_array(data)
+            t = torch.from_numpy(a.copy()) if a.size else torch.zeros(0, dtype=torch.uint8)
+        t = t.cuda()
+        if t.numel() and t.data_ptr() % 16:    # (a view into a larger tensor: the kernels load 16 bytes at a time)
+            t = t.clone()
+        return t
+
+    @staticmethod
+    def _table_tensor(table, dtype, device):
+        """a packet / message table (a numpy array of `dtype`, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
+        import torch
+        if table is None:
+            return torch.zeros(0, dtype=torch.uint8, device=device), 0
+        if isinstance(table, torch.Tensor):
+            t = table.contiguous().view(torch.uint8).reshape(-1).to(device)
+        else:
+            a = np.ascontiguousarray(table, dtype)
+            t = torch.from_numpy(a.view(np.uint8).copy()).to(device) if a.size else torch.zeros(0, dtype=torch.uint8, device=device)
+        return t, t.numel() // 16
+
+    def _payload_args(self, data, table):
+        """the leading arguments of a _dev decoder: (payload tensor, table tensor or None, [d_payload, bytes] + [d_table, entries] when the
+        family has a table = (table, dtype))"""
+        t = self._bytes_tensor(data)
+        args = [t.data_ptr() if t.numel() else None, t.numel()]
+        if table is None:
+            return t, None, args
+        pk, n_pk = self._table_tensor(table[0], table[1], t.device)
+        return t, pk, args + [pk.data_ptr() if n_pk else None, n_pk]
+
+    def _count_dev(self, symbol, data, table, *extra):
+        """an ecal_X_count_*_dev call: the payload, the table when the family has one, the family's own arguments -> the count"""
+        import torch
+        t, pk, args = self._payload_args(data, table)     # (t and pk hold the device memory over the call)
+        n = ctypes.c_uint64()
+        self._check(getattr(self._L, symbol)(self._h, *args, *extra, ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
+        return int(n.value)
+
+    def _events_from(self, symbol, data, table, options, info, capacity, count):
+        """an ecal_events_from_X_dev call -> (records as a uint8 CUDA tensor [n_events * 25], info dict).  capacity None: count(payload
+        tensor, table tensor or None); a refusal raises with .info"""
+        import torch
+        t, pk, args = self._payload_args(data, table)
+        cap = count(t, pk) if capacity is None else int(capacity)
+        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
+        st = getattr(self._L, symbol)(self._h, *args, ctypes.byref(options), out.data_ptr(), cap, ctypes.byref(info),
+                                      torch.cuda.current_stream().cuda_stream)
+        if st != 0:
+            self._fail_with_info(st, info)
+        return out[: int(info.n_events) * 25], info.as_dict()
+
+    def _index_table(self, symbol, data, selector, dtype, info, capacity):
+        """an ecal_X_index_* call over host bytes -> (table as a numpy array of `dtype`, info dict).  selector: the family's own
+        argument (source, stream_id, byref(options)).  capacity None: counted first, where -6 only says that the table is needed"""
+        fn = getattr(self._L, symbol)
+        a = _u8_array(data)
+        ptr = a.ctypes.data if a.size else None
+        n = ctypes.c_uint64()
+        if capacity is None:
+            st = fn(self._h, ptr, a.size, selector, None, 0, ctypes.byref(n), ctypes.byref(info))
+            if st not in (0, -6):
+                self._fail_with_info(st, info)
+            capacity = int(n.value)
+        table = np.zeros(int(capacity), dtype)
+        st = fn(self._h, ptr, a.size, selector, table.ctypes.data if table.size else None, table.size, ctypes.byref(n), ctypes.byref(info))
+        if st != 0:
+            self._fail_with_info(st, info)
+        return table[: int(n.value)], info.as_dict()
+
+    def _to_bin(self, symbol, src, dst, options, info):
+        """an ecal_X_to_bin_file call -> info dict; a refusal raises with .info"""
+        st = getattr(self._L, symbol)(self._h, os.fsencode(src), os.fsencode(dst), ctypes.byref(options), ctypes.byref(info))
+        if st != 0:
+            self._fail_with_info(st, info)
+        return info.as_dict()
+
+    def _stream_from_file(self, symbol, path, options, info):
+        """an ecal_stream_create_from_X_file call, the stream's records copied out -> (events, info dict, t_first, t_last)"""
+        h = ctypes.c_void_p()
+        st = getattr(self._L, symbol)(self._h, os.fsencode(path), ctypes.byref(options), ctypes.byref(h), ctypes.byref(info))
+        if st != 0:
+            self._fail_with_info(st, info)
+        events, t_first, t_last = self._stream_records(h)
+        return events, info.as_dict(), t_first, t_last
 
     # ---- text ingest: "stamp x y polarity" lines parsed in HBM (ecal_events_from_text_dev and the file forms) ----
     def text_options(self, time_magnitude=1e-6, time_base=None, end_stamp=None, start_time=None, end_time=None, duplicate_last=True):
         """ecal_text_options from ecal_text_default_options: time_base None = the first record line's stamp, end_stamp None = no
         break, start_time None = -inf, end_time None = to the end, duplicate_last = the reference's repeated last record."""
         L = self._L
-        L.ecal_text_default_options.argtypes = [ctypes.POINTER(TextOptions)]
-        L.ecal_text_default_options.restype = None
         o = TextOptions()
         L.ecal_text_default_options(ctypes.byref(o))
         o.time_magnitude = float(time_magnitude)
@@ -1274,99 +1593,31 @@ class Context:
         o.duplicate_last = 1 if duplicate_last else 0
         return o
 
-    def _text_fail(self, st, info):
-        """EcalError of a text entry point, with the ecal_text_info it filled (first_bad_line, the needed n_events) as .info"""
-        try:
-            self._check(st)
-        except EcalError as e:
-            e.info = info.as_dict()
-            raise
-
-    @staticmethod
-    def _text_tensor(text):
-        """bytes / numpy uint8 / torch uint8 (any device) as a CUDA uint8 tensor whose storage starts 16-byte aligned"""
-        import torch
-        if isinstance(text, torch.Tensor):
-            t = text.contiguous().view(torch.uint8).reshape(-1)
-        else:
-            a = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8).ravel()
-            t = torch.from_numpy(a.copy()) if a.size else torch.zeros(0, dtype=torch.uint8)
-        t = t.cuda()
-        if t.numel() and t.data_ptr() % 16:    # (a view into a larger tensor: the kernels load 16 bytes at a time)
-            t = t.clone()
-        return t
-
     def text_count_lines(self, text):
         """ecal_text_count_lines_dev: the lines of the text (lines + 1 bounds the records)."""
-        import torch
-        L = self._L
-        L.ecal_text_count_lines_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
-        L.ecal_text_count_lines_dev.restype = ctypes.c_int
-        t = self._text_tensor(text)
-        n = ctypes.c_uint64()
-        self._check(L.ecal_text_count_lines_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(n),
-                                                torch.cuda.current_stream().cuda_stream))
-        return int(n.value)
+        return self._count_dev("ecal_text_count_lines_dev", text, None)
 
     def events_from_text(self, text, capacity=None, **options):
         """ecal_events_from_text_dev: text (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is parsed where it is)
         -> (packed 25-byte records in file order as a uint8 CUDA tensor [n_events * 25], info dict).  options: text_options'.
         capacity None: lines + 1 records (always enough); a smaller one raises EcalError with status -6 and .info["n_events"] =
         the count needed.  A malformed line raises EcalError with status -1 and .info["first_bad_line"]."""
-        import torch
-        L = self._L
-        L.ecal_events_from_text_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(TextOptions), ctypes.c_void_p,
-                                                ctypes.c_uint64, ctypes.POINTER(TextInfo), ctypes.c_void_p]
-        L.ecal_events_from_text_dev.restype = ctypes.c_int
-        o = self.text_options(**options)
-        t = self._text_tensor(text)
-        cap = self.text_count_lines(t) + 1 if capacity is None else int(capacity)
-        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
-        info = TextInfo()
-        st = L.ecal_events_from_text_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(o), out.data_ptr(), cap,
-                                         ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
-        if st != 0:
-            self._text_fail(st, info)
-        return out[: int(info.n_events) * 25], info.as_dict()
+        return self._events_from("ecal_events_from_text_dev", text, None, self.text_options(**options), TextInfo(), capacity,
+                                 lambda t, _: self.text_count_lines(t) + 1)
 
     def text_to_bin(self, txt_path, bin_path, **options):
         """ecal_text_to_bin_file: the .bin the reference's txt2bin tool writes from txt_path (file order, no sort) -> info dict."""
-        L = self._L
-        L.ecal_text_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(TextOptions), ctypes.POINTER(TextInfo)]
-        L.ecal_text_to_bin_file.restype = ctypes.c_int
-        o = self.text_options(**options)
-        info = TextInfo()
-        st = L.ecal_text_to_bin_file(self._h, os.fsencode(txt_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_text_to_bin_file", txt_path, bin_path, self.text_options(**options), TextInfo())
 
     def stream_from_text_file(self, path, **options):
         """ecal_stream_create_from_text_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
         file is not) -> (events, info dict, t_first, t_last)."""
-        import torch
-        L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(TextOptions), ctypes.POINTER(vp), ctypes.POINTER(TextInfo)]
-        L.ecal_stream_create_from_text_file.restype = ctypes.c_int
-        o = self.text_options(**options)
-        info = TextInfo()
-        h = vp()
-        st = L.ecal_stream_create_from_text_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_text_file", path, self.text_options(**options), TextInfo())
 
     def _stream_records(self, h):
         """the records of the ecal_stream h copied into a uint8 CUDA tensor, its first and last time; destroys the stream"""
         import torch
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
-        L.ecal_stream_data.argtypes, L.ecal_stream_data.restype = [vp], vp
-        L.ecal_stream_times.argtypes, L.ecal_stream_times.restype = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int
-        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
         try:
             n = int(L.ecal_stream_size(h))
             events = torch.empty(n * 25, dtype=torch.uint8, device="cuda:%d" % self.device)
@@ -1384,8 +1635,6 @@ class Context:
         """ecal_raw_options from ecal_raw_default_options: format "EVT2" / "EVT3" / None (from the file header), time_base in
         microseconds of the camera's clock, width / height 0 = no bound, start_time None = -inf, end_time None = to the end."""
         L = self._L
-        L.ecal_raw_default_options.argtypes = [ctypes.POINTER(RawOptions)]
-        L.ecal_raw_default_options.restype = None
         o = RawOptions()
         L.ecal_raw_default_options(ctypes.byref(o))
         o.format, o.time_base, o.width, o.height = raw_format(format), int(time_base), int(width), int(height)
@@ -1397,70 +1646,28 @@ class Context:
 
     def raw_block_words(self, format):
         """ecal_raw_block_words: words per decode block of this build."""
-        self._L.ecal_raw_block_words.argtypes, self._L.ecal_raw_block_words.restype = [ctypes.c_int], ctypes.c_uint32
         return int(self._L.ecal_raw_block_words(raw_format(format)))
 
     def raw_count_events(self, payload, format):
         """ecal_raw_count_events_dev: the events the payload's words emit before any drop (always a sufficient capacity)."""
-        import torch
-        L = self._L
-        L.ecal_raw_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
-                                                ctypes.c_void_p]
-        L.ecal_raw_count_events_dev.restype = ctypes.c_int
-        t = self._text_tensor(payload)
-        n = ctypes.c_uint64()
-        self._check(L.ecal_raw_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), raw_format(format), ctypes.byref(n),
-                                                torch.cuda.current_stream().cuda_stream))
-        return int(n.value)
+        return self._count_dev("ecal_raw_count_events_dev", payload, None, raw_format(format))
 
     def events_from_raw(self, payload, format, capacity=None, **options):
         """ecal_events_from_raw_dev: payload (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where it
         is; no file header) -> (packed 25-byte records in file order as a uint8 CUDA tensor [n_events * 25], info dict).  options:
         raw_options'.  capacity None: raw_count_events (always enough); a smaller one raises EcalError with status -6 and
         .info["n_events"] = the count needed."""
-        import torch
-        L = self._L
-        L.ecal_events_from_raw_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(RawOptions), ctypes.c_void_p,
-                                               ctypes.c_uint64, ctypes.POINTER(RawInfo), ctypes.c_void_p]
-        L.ecal_events_from_raw_dev.restype = ctypes.c_int
-        o = self.raw_options(format=format, **options)
-        t = self._text_tensor(payload)
-        cap = self.raw_count_events(t, format) if capacity is None else int(capacity)
-        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
-        info = RawInfo()
-        st = L.ecal_events_from_raw_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), ctypes.byref(o), out.data_ptr(), cap,
-                                        ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
-        if st != 0:
-            self._text_fail(st, info)
-        return out[: int(info.n_events) * 25], info.as_dict()
+        return self._events_from("ecal_events_from_raw_dev", payload, None, self.raw_options(format=format, **options), RawInfo(), capacity,
+                                 lambda t, _: self.raw_count_events(t, format))
 
     def raw_to_bin(self, raw_path, bin_path, **options):
         """ecal_raw_to_bin_file: the records of the .raw file (file order, no sort) as a .bin of the reference's layout -> info dict."""
-        L = self._L
-        L.ecal_raw_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(RawOptions), ctypes.POINTER(RawInfo)]
-        L.ecal_raw_to_bin_file.restype = ctypes.c_int
-        o = self.raw_options(**options)
-        info = RawInfo()
-        st = L.ecal_raw_to_bin_file(self._h, os.fsencode(raw_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_raw_to_bin_file", raw_path, bin_path, self.raw_options(**options), RawInfo())
 
     def stream_from_raw_file(self, path, **options):
         """ecal_stream_create_from_raw_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
         file is not) -> (events, info dict, t_first, t_last)."""
-        L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_raw_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(RawOptions), ctypes.POINTER(vp), ctypes.POINTER(RawInfo)]
-        L.ecal_stream_create_from_raw_file.restype = ctypes.c_int
-        o = self.raw_options(**options)
-        info = RawInfo()
-        h = vp()
-        st = L.ecal_stream_create_from_raw_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_raw_file", path, self.raw_options(**options), RawInfo())
 
     # ---- aedat ingest: iniVation AEDAT 3.1 / 2.0 payloads decoded in HBM (ecal_events_from_aedat_dev and the file forms) ----
     def aedat_options(self, format=None, source=-1, time_base=0, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
@@ -1469,8 +1676,6 @@ class Context:
         = only polarity packets of that eventSource (3.1 file forms and the indexer), time_base in microseconds of the camera's clock,
         width / height 0 = no bound, flip_x / flip_y need them, start_time None = -inf, end_time None = to the end."""
         L = self._L
-        L.ecal_aedat_default_options.argtypes = [ctypes.POINTER(AedatOptions)]
-        L.ecal_aedat_default_options.restype = None
         o = AedatOptions()
         L.ecal_aedat_default_options(ctypes.byref(o))
         o.format, o.source, o.time_base, o.width, o.height = aedat_format(format), int(source), int(time_base), int(width), int(height)
@@ -1483,14 +1688,11 @@ class Context:
 
     def aedat_block_events(self, format):
         """ecal_aedat_block_events: event slots / records per decode block of this build."""
-        self._L.ecal_aedat_block_events.argtypes, self._L.ecal_aedat_block_events.restype = [ctypes.c_int], ctypes.c_uint32
         return int(self._L.ecal_aedat_block_events(aedat_format(format)))
 
     def aedat_parse_header(self, data, format=None):
         """ecal_aedat_parse_header: the first bytes of a file -> (format number in force, header_bytes)."""
         L = self._L
-        L.ecal_aedat_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]
-        L.ecal_aedat_parse_header.restype = ctypes.c_int
         data = bytes(data)
         fmt, hb = ctypes.c_int(aedat_format(format)), ctypes.c_uint64()
         self._check(L.ecal_aedat_parse_header(self._h, data, len(data), ctypes.byref(fmt), ctypes.byref(hb)))
@@ -1500,100 +1702,28 @@ class Context:
         """ecal_aedat_index_packets over a 3.1 payload in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
         AEDAT_PACKET_DTYPE, info dict).  capacity None: counted first; a smaller one raises EcalError with status -6 and
         .info["n_packets"] = the count needed."""
-        L = self._L
-        L.ecal_aedat_index_packets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(AedatInfo)]
-        L.ecal_aedat_index_packets.restype = ctypes.c_int
-        a = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.ascontiguousarray(payload, np.uint8).ravel()
-        ptr = a.ctypes.data if a.size else None
-        n, info = ctypes.c_uint64(), AedatInfo()
-        if capacity is None:
-            st = L.ecal_aedat_index_packets(self._h, ptr, a.size, int(source), None, 0, ctypes.byref(n), ctypes.byref(info))
-            if st not in (0, -6):
-                self._text_fail(st, info)
-            capacity = int(n.value)
-        table = np.zeros(int(capacity), AEDAT_PACKET_DTYPE)
-        st = L.ecal_aedat_index_packets(self._h, ptr, a.size, int(source), table.ctypes.data if table.size else None, table.size,
-                                        ctypes.byref(n), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return table[: int(n.value)], info.as_dict()
-
-    def _aedat_table_tensor(self, packets, device):
-        """a packet table (numpy AEDAT_PACKET_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
-        import torch
-        if packets is None:
-            return torch.zeros(0, dtype=torch.uint8, device=device), 0
-        if isinstance(packets, torch.Tensor):
-            t = packets.contiguous().view(torch.uint8).reshape(-1).to(device)
-        else:
-            a = np.ascontiguousarray(packets, AEDAT_PACKET_DTYPE)
-            t = torch.from_numpy(a.view(np.uint8).copy()).to(device) if a.size else torch.zeros(0, dtype=torch.uint8, device=device)
-        return t, t.numel() // 16
+        return self._index_table("ecal_aedat_index_packets", payload, int(source), AEDAT_PACKET_DTYPE, AedatInfo(), capacity)
 
     def aedat_count_events(self, payload, format, packets=None):
         """ecal_aedat_count_events_dev: the events before any drop (always a sufficient capacity)."""
-        import torch
-        L = self._L
-        L.ecal_aedat_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
-                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
-        L.ecal_aedat_count_events_dev.restype = ctypes.c_int
-        t = self._text_tensor(payload)
-        pk, n_pk = self._aedat_table_tensor(packets, t.device)
-        n = ctypes.c_uint64()
-        self._check(L.ecal_aedat_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
-                                                  aedat_format(format), ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
-        return int(n.value)
+        return self._count_dev("ecal_aedat_count_events_dev", payload, (packets, AEDAT_PACKET_DTYPE), aedat_format(format))
 
     def events_from_aedat(self, payload, format, packets=None, capacity=None, **options):
         """ecal_events_from_aedat_dev: payload (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where it
         is; no file header) and, for "3.1", the packet table of aedat_index_packets -> (packed 25-byte records in file order as a
         uint8 CUDA tensor [n_events * 25], info dict).  options: aedat_options'.  capacity None: aedat_count_events (always enough); a
         smaller one raises EcalError with status -6 and .info["n_events"] = the count needed."""
-        import torch
-        L = self._L
-        L.ecal_events_from_aedat_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                 ctypes.POINTER(AedatOptions), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AedatInfo), ctypes.c_void_p]
-        L.ecal_events_from_aedat_dev.restype = ctypes.c_int
-        o = self.aedat_options(format=format, **options)
-        t = self._text_tensor(payload)
-        pk, n_pk = self._aedat_table_tensor(packets, t.device)
-        cap = self.aedat_count_events(t, format, pk) if capacity is None else int(capacity)
-        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
-        info = AedatInfo()
-        st = L.ecal_events_from_aedat_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
-                                          ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
-        if st != 0:
-            self._text_fail(st, info)
-        return out[: int(info.n_events) * 25], info.as_dict()
+        return self._events_from("ecal_events_from_aedat_dev", payload, (packets, AEDAT_PACKET_DTYPE), self.aedat_options(format=format, **options),
+                                 AedatInfo(), capacity, lambda t, pk: self.aedat_count_events(t, format, pk))
 
     def aedat_to_bin(self, aedat_path, bin_path, **options):
         """ecal_aedat_to_bin_file: the records of the .aedat file (file order, no sort) as a .bin of the reference's layout -> info dict."""
-        L = self._L
-        L.ecal_aedat_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(AedatOptions), ctypes.POINTER(AedatInfo)]
-        L.ecal_aedat_to_bin_file.restype = ctypes.c_int
-        o = self.aedat_options(**options)
-        info = AedatInfo()
-        st = L.ecal_aedat_to_bin_file(self._h, os.fsencode(aedat_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_aedat_to_bin_file", aedat_path, bin_path, self.aedat_options(**options), AedatInfo())
 
     def stream_from_aedat_file(self, path, **options):
         """ecal_stream_create_from_aedat_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
         file is not) -> (events, info dict, t_first, t_last)."""
-        L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_aedat_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(AedatOptions), ctypes.POINTER(vp), ctypes.POINTER(AedatInfo)]
-        L.ecal_stream_create_from_aedat_file.restype = ctypes.c_int
-        o = self.aedat_options(**options)
-        info = AedatInfo()
-        h = vp()
-        st = L.ecal_stream_create_from_aedat_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_aedat_file", path, self.aedat_options(**options), AedatInfo())
 
     # ---- aedat4 ingest: iniVation AEDAT 4 files (LZ4 packets) inflated and decoded in HBM (ecal_events_from_aedat4_dev and the file forms) ----
     def aedat4_options(self, compression=None, stream_id=-1, time_base=None, width=0, height=0, flip_x=False, flip_y=False,
@@ -1603,8 +1733,6 @@ class Context:
         only), else int64 microseconds of epoch time, width / height 0 = no upper bound, flip_x / flip_y need them, start_time None =
         -inf, end_time None = to the end, max_inflated_bytes None = the default."""
         L = self._L
-        L.ecal_aedat4_default_options.argtypes = [ctypes.POINTER(Aedat4Options)]
-        L.ecal_aedat4_default_options.restype = None
         o = Aedat4Options()
         L.ecal_aedat4_default_options(ctypes.byref(o))
         o.compression, o.stream_id, o.width, o.height = aedat4_compression(compression), int(stream_id), int(width), int(height)
@@ -1621,16 +1749,12 @@ class Context:
 
     def aedat4_block_events(self):
         """ecal_aedat4_block_events: event slots per decode block of this build."""
-        self._L.ecal_aedat4_block_events.argtypes, self._L.ecal_aedat4_block_events.restype = [], ctypes.c_uint32
         return int(self._L.ecal_aedat4_block_events())
 
     def aedat4_parse_header(self, data, file_bytes=None):
         """ecal_aedat4_parse_header: the first bytes of a file of file_bytes bytes (None: these are all of it) -> (compression,
         packets_begin, packets_end)."""
         L = self._L
-        L.ecal_aedat4_parse_header.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int),
-                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L.ecal_aedat4_parse_header.restype = ctypes.c_int
         data = bytes(data)
         c, b, e = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint64()
         self._check(L.ecal_aedat4_parse_header(self._h, data, len(data), len(data) if file_bytes is None else int(file_bytes), ctypes.byref(c),
@@ -1640,47 +1764,12 @@ class Context:
     def aedat4_index_packets(self, file_bytes, stream_id=-1, capacity=None):
         """ecal_aedat4_index_packets over a whole file in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
         AEDAT4_PACKET_DTYPE, info dict).  capacity None: counted first; a smaller one raises EcalError with status -6."""
-        L = self._L
-        L.ecal_aedat4_index_packets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Aedat4Info)]
-        L.ecal_aedat4_index_packets.restype = ctypes.c_int
-        a = np.frombuffer(file_bytes, np.uint8) if isinstance(file_bytes, (bytes, bytearray, memoryview)) else np.ascontiguousarray(file_bytes, np.uint8).ravel()
-        ptr = a.ctypes.data if a.size else None
-        n, info = ctypes.c_uint64(), Aedat4Info()
-        if capacity is None:
-            st = L.ecal_aedat4_index_packets(self._h, ptr, a.size, int(stream_id), None, 0, ctypes.byref(n), ctypes.byref(info))
-            if st not in (0, -6):
-                self._text_fail(st, info)
-            capacity = int(n.value)
-        table = np.zeros(int(capacity), AEDAT4_PACKET_DTYPE)
-        st = L.ecal_aedat4_index_packets(self._h, ptr, a.size, int(stream_id), table.ctypes.data if table.size else None, table.size,
-                                         ctypes.byref(n), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return table[: int(n.value)], info.as_dict()
-
-    def _aedat4_table_tensor(self, packets, device):
-        """a packet table (numpy AEDAT4_PACKET_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
-        import torch
-        if packets is not None and not isinstance(packets, torch.Tensor):
-            a = np.ascontiguousarray(packets, AEDAT4_PACKET_DTYPE)
-            packets = torch.from_numpy(a.view(np.uint8).copy()) if a.size else None
-        return self._aedat_table_tensor(packets, device)
+        return self._index_table("ecal_aedat4_index_packets", file_bytes, int(stream_id), AEDAT4_PACKET_DTYPE, Aedat4Info(), capacity)
 
     def aedat4_count_events(self, file_bytes, compression, packets, max_inflated_bytes=None):
         """ecal_aedat4_count_events_dev: the events before any drop (always a sufficient capacity)."""
-        import torch
-        L = self._L
-        L.ecal_aedat4_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                   ctypes.POINTER(Aedat4Options), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
-        L.ecal_aedat4_count_events_dev.restype = ctypes.c_int
-        t = self._text_tensor(file_bytes)
-        pk, n_pk = self._aedat4_table_tensor(packets, t.device)
         o = self.aedat4_options(compression=compression, max_inflated_bytes=max_inflated_bytes)
-        n = ctypes.c_uint64()
-        self._check(L.ecal_aedat4_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
-                                                   ctypes.byref(o), ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
-        return int(n.value)
+        return self._count_dev("ecal_aedat4_count_events_dev", file_bytes, (packets, AEDAT4_PACKET_DTYPE), ctypes.byref(o))
 
     def events_from_aedat4(self, file_bytes, compression, packets, capacity=None, time_base=0, **options):
         """ecal_events_from_aedat4_dev: the whole file (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded
@@ -1688,51 +1777,18 @@ class Context:
         [n_events * 25], info dict).  compression "none" / "lz4" is explicit, time_base too (microseconds, default 0).  options:
         aedat4_options'.  capacity None: aedat4_count_events (always enough); a smaller one raises EcalError with status -6 and
         .info["n_events"] = the count needed."""
-        import torch
-        L = self._L
-        L.ecal_events_from_aedat4_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                  ctypes.POINTER(Aedat4Options), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Aedat4Info),
-                                                  ctypes.c_void_p]
-        L.ecal_events_from_aedat4_dev.restype = ctypes.c_int
-        o = self.aedat4_options(compression=compression, time_base=time_base, **options)
-        t = self._text_tensor(file_bytes)
-        pk, n_pk = self._aedat4_table_tensor(packets, t.device)
-        cap = self.aedat4_count_events(t, compression, pk, options.get("max_inflated_bytes")) if capacity is None else int(capacity)
-        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
-        info = Aedat4Info()
-        st = L.ecal_events_from_aedat4_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), pk.data_ptr() if n_pk else None, n_pk,
-                                           ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
-        if st != 0:
-            self._text_fail(st, info)
-        return out[: int(info.n_events) * 25], info.as_dict()
+        return self._events_from("ecal_events_from_aedat4_dev", file_bytes, (packets, AEDAT4_PACKET_DTYPE),
+                                 self.aedat4_options(compression=compression, time_base=time_base, **options), Aedat4Info(), capacity,
+                                 lambda t, pk: self.aedat4_count_events(t, compression, pk, options.get("max_inflated_bytes")))
 
     def aedat4_to_bin(self, aedat4_path, bin_path, **options):
         """ecal_aedat4_to_bin_file: the records of the .aedat4 file (file order, no sort) as a .bin of the reference's layout -> info dict."""
-        L = self._L
-        L.ecal_aedat4_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Aedat4Options), ctypes.POINTER(Aedat4Info)]
-        L.ecal_aedat4_to_bin_file.restype = ctypes.c_int
-        o = self.aedat4_options(**options)
-        info = Aedat4Info()
-        st = L.ecal_aedat4_to_bin_file(self._h, os.fsencode(aedat4_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_aedat4_to_bin_file", aedat4_path, bin_path, self.aedat4_options(**options), Aedat4Info())
 
     def stream_from_aedat4_file(self, path, **options):
         """ecal_stream_create_from_aedat4_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the
         file is not) -> (events, info dict, t_first, t_last)."""
-        L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_aedat4_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(Aedat4Options), ctypes.POINTER(vp), ctypes.POINTER(Aedat4Info)]
-        L.ecal_stream_create_from_aedat4_file.restype = ctypes.c_int
-        o = self.aedat4_options(**options)
-        info = Aedat4Info()
-        h = vp()
-        st = L.ecal_stream_create_from_aedat4_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_aedat4_file", path, self.aedat4_options(**options), Aedat4Info())
 
     # ---- bag ingest: ROS 1 bags of dvs_msgs/EventArray messages decoded in HBM (ecal_events_from_bag_dev and the file forms) ----
     def bag_options(self, topic=None, type=None, time_base=None, width=0, height=0, flip_x=False, flip_y=False, start_time=None,
@@ -1741,8 +1797,6 @@ class Context:
         time_base None = automatic (the first event's whole seconds), else int64 nanoseconds of epoch time, width / height 0 = no
         bound, flip_x / flip_y need them, start_time None = -inf, end_time None = to the end."""
         L = self._L
-        L.ecal_bag_default_options.argtypes = [ctypes.POINTER(BagOptions)]
-        L.ecal_bag_default_options.restype = None
         o = BagOptions()
         L.ecal_bag_default_options(ctypes.byref(o))
         o.topic = os.fsencode(topic) if topic else None
@@ -1759,58 +1813,18 @@ class Context:
 
     def bag_block_events(self):
         """ecal_bag_block_events: event slots per decode block of this build."""
-        self._L.ecal_bag_block_events.argtypes, self._L.ecal_bag_block_events.restype = [], ctypes.c_uint32
         return int(self._L.ecal_bag_block_events())
 
     def bag_index_messages(self, data, topic=None, type=None, capacity=None):
         """ecal_bag_index_messages over a bag's bytes in host memory (bytes or a numpy uint8 array) -> (table as a numpy array of
         BAG_MESSAGE_DTYPE, info dict; info["first_stamp_ns"] is the automatic time base).  capacity None: counted first; a smaller
         one raises EcalError with status -6 and .info["n_messages"] = the count needed."""
-        L = self._L
-        L.ecal_bag_index_messages.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(BagOptions), ctypes.c_void_p,
-                                              ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(BagInfo)]
-        L.ecal_bag_index_messages.restype = ctypes.c_int
-        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).ravel()
-        ptr = a.ctypes.data if a.size else None
         o = self.bag_options(topic=topic, type=type)
-        n, info = ctypes.c_uint64(), BagInfo()
-        if capacity is None:
-            st = L.ecal_bag_index_messages(self._h, ptr, a.size, ctypes.byref(o), None, 0, ctypes.byref(n), ctypes.byref(info))
-            if st not in (0, -6):
-                self._text_fail(st, info)
-            capacity = int(n.value)
-        table = np.zeros(int(capacity), BAG_MESSAGE_DTYPE)
-        st = L.ecal_bag_index_messages(self._h, ptr, a.size, ctypes.byref(o), table.ctypes.data if table.size else None, table.size,
-                                       ctypes.byref(n), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return table[: int(n.value)], info.as_dict()
-
-    def _bag_table_tensor(self, messages, device):
-        """a message table (numpy BAG_MESSAGE_DTYPE, or a CUDA uint8 tensor of 16-byte entries) as (CUDA uint8 tensor, entries)"""
-        import torch
-        if messages is None:
-            return torch.zeros(0, dtype=torch.uint8, device=device), 0
-        if isinstance(messages, torch.Tensor):
-            t = messages.contiguous().view(torch.uint8).reshape(-1).to(device)
-        else:
-            a = np.ascontiguousarray(messages, BAG_MESSAGE_DTYPE)
-            t = torch.from_numpy(a.view(np.uint8).copy()).to(device) if a.size else torch.zeros(0, dtype=torch.uint8, device=device)
-        return t, t.numel() // 16
+        return self._index_table("ecal_bag_index_messages", data, ctypes.byref(o), BAG_MESSAGE_DTYPE, BagInfo(), capacity)
 
     def bag_count_events(self, data, messages):
         """ecal_bag_count_events_dev: the events before any drop (always a sufficient capacity)."""
-        import torch
-        L = self._L
-        L.ecal_bag_count_events_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
-        L.ecal_bag_count_events_dev.restype = ctypes.c_int
-        t = self._text_tensor(data)
-        mt, n_m = self._bag_table_tensor(messages, t.device)
-        n = ctypes.c_uint64()
-        self._check(L.ecal_bag_count_events_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), mt.data_ptr() if n_m else None, n_m,
-                                                ctypes.byref(n), torch.cuda.current_stream().cuda_stream))
-        return int(n.value)
+        return self._count_dev("ecal_bag_count_events_dev", data, (messages, BAG_MESSAGE_DTYPE))
 
     def events_from_bag(self, data, messages, capacity=None, **options):
         """ecal_events_from_bag_dev: the whole bag (bytes, a numpy uint8 array or a torch uint8 tensor; a CUDA tensor is decoded where
@@ -1818,55 +1832,21 @@ class Context:
         [n_events * 25], info dict).  options: bag_options' — the device form needs an explicit time_base (the indexer's
         first_stamp_ns is the automatic one); without one the library refuses the call.  capacity None: bag_count_events (always
         enough); a smaller one raises EcalError with status -6 and .info["n_events"] = the count needed."""
-        import torch
-        L = self._L
-        L.ecal_events_from_bag_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                               ctypes.POINTER(BagOptions), ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(BagInfo), ctypes.c_void_p]
-        L.ecal_events_from_bag_dev.restype = ctypes.c_int
-        o = self.bag_options(**options)
-        t = self._text_tensor(data)
-        mt, n_m = self._bag_table_tensor(messages, t.device)
-        cap = self.bag_count_events(t, mt) if capacity is None else int(capacity)
-        out = torch.empty(cap * 25 + 16, dtype=torch.uint8, device=t.device)
-        info = BagInfo()
-        st = L.ecal_events_from_bag_dev(self._h, t.data_ptr() if t.numel() else None, t.numel(), mt.data_ptr() if n_m else None, n_m,
-                                        ctypes.byref(o), out.data_ptr(), cap, ctypes.byref(info), torch.cuda.current_stream().cuda_stream)
-        if st != 0:
-            self._text_fail(st, info)
-        return out[: int(info.n_events) * 25], info.as_dict()
+        return self._events_from("ecal_events_from_bag_dev", data, (messages, BAG_MESSAGE_DTYPE), self.bag_options(**options), BagInfo(), capacity,
+                                 self.bag_count_events)
 
     def bag_to_bin(self, bag_path, bin_path, **options):
         """ecal_bag_to_bin_file: the records of the .bag file (file order, no sort) as a .bin of the reference's layout -> info dict."""
-        L = self._L
-        L.ecal_bag_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(BagOptions), ctypes.POINTER(BagInfo)]
-        L.ecal_bag_to_bin_file.restype = ctypes.c_int
-        o = self.bag_options(**options)
-        info = BagInfo()
-        st = L.ecal_bag_to_bin_file(self._h, os.fsencode(bag_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_bag_to_bin_file", bag_path, bin_path, self.bag_options(**options), BagInfo())
 
     def stream_from_bag_file(self, path, **options):
         """ecal_stream_create_from_bag_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the file
         is not) -> (events, info dict, t_first, t_last).  info["time_base"] is the base in force (nanoseconds)."""
-        L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_bag_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(BagOptions), ctypes.POINTER(vp), ctypes.POINTER(BagInfo)]
-        L.ecal_stream_create_from_bag_file.restype = ctypes.c_int
-        o = self.bag_options(**options)
-        info = BagInfo()
-        h = vp()
-        st = L.ecal_stream_create_from_bag_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_bag_file", path, self.bag_options(**options), BagInfo())
 
     # ---- array ingest: columns packed into records in HBM, records unpacked into columns, .npy files (ecal_events_from_fields_dev, ...) ----
     def fields_block_events(self):
         """ecal_fields_block_events: events per block of the array ingest's kernels."""
-        self._L.ecal_fields_block_events.argtypes, self._L.ecal_fields_block_events.restype = [], ctypes.c_uint32
         return int(self._L.ecal_fields_block_events())
 
     def _device_column(self, a):
@@ -1888,13 +1868,10 @@ class Context:
     def events_from_fields_dev(self, fields, n, options, d_events, capacity, stream=0):
         """ecal_events_from_fields_dev, raw: fields = (Field * 4) over device memory -> info dict; raises with .info on a refusal"""
         L = self._L
-        L.ecal_events_from_fields_dev.argtypes = [ctypes.c_void_p, ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.c_void_p,
-                                                  ctypes.c_uint64, ctypes.POINTER(FieldsInfo), ctypes.c_void_p]
-        L.ecal_events_from_fields_dev.restype = ctypes.c_int
         info = FieldsInfo()
         st = L.ecal_events_from_fields_dev(self._h, fields, n, ctypes.byref(options), d_events, capacity, ctypes.byref(info), stream)
         if st != 0:
-            self._text_fail(st, info)
+            self._fail_with_info(st, info)
         return info.as_dict()
 
     def events_from_arrays(self, t, x, y, p, capacity=None, **options):
@@ -1958,9 +1935,6 @@ class Context:
         -> (events, info dict, t_first, t_last).  auto_time_base=True: the base is element 0's stamp."""
         L = self._L
         vp = ctypes.c_void_p
-        L.ecal_stream_create_from_fields.argtypes = [vp, ctypes.POINTER(Field), ctypes.c_uint64, ctypes.POINTER(FieldsOptions), ctypes.POINTER(vp),
-                                                     ctypes.POINTER(FieldsInfo)]
-        L.ecal_stream_create_from_fields.restype = ctypes.c_int
         cols = [_host_column(a) for a in (t, x, y, p)]
         n = cols[0][0].size
         if any(c[0].size != n for c in cols):
@@ -1971,20 +1945,17 @@ class Context:
         h = vp()
         st = L.ecal_stream_create_from_fields(self._h, f, n, ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
         if st != 0:
-            self._text_fail(st, info)
+            self._fail_with_info(st, info)
         events, t_first, t_last = self._stream_records(h)
         return events, info.as_dict(), t_first, t_last
 
     def events_to_fields_dev(self, d_events, n, fields, options, stream=0):
         """ecal_events_to_fields_dev, raw: fields = (Field * 4) over device memory -> info dict; raises with .info on a refusal"""
         L = self._L
-        L.ecal_events_to_fields_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Field), ctypes.POINTER(ToFieldsOptions),
-                                                ctypes.POINTER(ToFieldsInfo), ctypes.c_void_p]
-        L.ecal_events_to_fields_dev.restype = ctypes.c_int
         info = ToFieldsInfo()
         st = L.ecal_events_to_fields_dev(self._h, d_events, n, fields, ctypes.byref(options), ctypes.byref(info), stream)
         if st != 0:
-            self._text_fail(st, info)
+            self._fail_with_info(st, info)
         return info.as_dict()
 
     def events_to_arrays(self, events, t=np.float64, xy=np.float64, p=np.uint8, **options):
@@ -2020,40 +1991,21 @@ class Context:
     def npy_to_bin(self, npy_path, bin_path, fields=None, columns=None, **options):
         """ecal_npy_to_bin_file: the records of the .npy file (file order, no sort) as a .bin of the reference's layout -> info dict.
         options: fields_options'; time_magnitude None: 1e-6 for integer stamps, 1.0 for float stamps."""
-        L = self._L
         options = self._npy_magnitude(npy_path, fields, columns, options)
-        L.ecal_npy_to_bin_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(NpyOptions), ctypes.POINTER(FieldsInfo)]
-        L.ecal_npy_to_bin_file.restype = ctypes.c_int
-        o = npy_options(fields=fields, columns=columns, **options)
-        info = FieldsInfo()
-        st = L.ecal_npy_to_bin_file(self._h, os.fsencode(npy_path), os.fsencode(bin_path), ctypes.byref(o), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        return info.as_dict()
+        return self._to_bin("ecal_npy_to_bin_file", npy_path, bin_path, npy_options(fields=fields, columns=columns, **options), FieldsInfo())
 
     def stream_from_npy_file(self, path, fields=None, columns=None, **options):
         """ecal_stream_create_from_npy_file, its records copied into a uint8 CUDA tensor (time order: the stream sorts when the file
         is not) -> (events, info dict, t_first, t_last).  options as npy_to_bin."""
-        L = self._L
         options = self._npy_magnitude(path, fields, columns, options)
-        vp = ctypes.c_void_p
-        L.ecal_stream_create_from_npy_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(NpyOptions), ctypes.POINTER(vp), ctypes.POINTER(FieldsInfo)]
-        L.ecal_stream_create_from_npy_file.restype = ctypes.c_int
-        o = npy_options(fields=fields, columns=columns, **options)
-        info = FieldsInfo()
-        h = vp()
-        st = L.ecal_stream_create_from_npy_file(self._h, os.fsencode(path), ctypes.byref(o), ctypes.byref(h), ctypes.byref(info))
-        if st != 0:
-            self._text_fail(st, info)
-        events, t_first, t_last = self._stream_records(h)
-        return events, info.as_dict(), t_first, t_last
+        return self._stream_from_file("ecal_stream_create_from_npy_file", path, npy_options(fields=fields, columns=columns, **options),
+                                      FieldsInfo())
 
     def stream_to_npy(self, events, npy_path):
         """ecal_stream_to_npy_file: packed records (time-sorted by the stream when they are not) as a .npy of the packed dtype
         [('t','<f8'),('x','<f8'),('y','<f8'),('p','u1')] — numpy's header and the records' bytes as they are."""
         import torch
         L = self._L
-        L.ecal_stream_to_npy_file.argtypes, L.ecal_stream_to_npy_file.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p], ctypes.c_int
         h = self._host_stream(events.cpu().numpy() if isinstance(events, torch.Tensor) else
                               np.frombuffer(events, np.uint8) if isinstance(events, (bytes, bytearray, memoryview)) else events)
         try:
@@ -2079,18 +2031,12 @@ class Context:
         """ecal_pixel_activity_dev: raw device pointers; d_counts [2][height][width] u32 and d_totals (ACTIVITY_TOTALS, or None) are
         zeroed by the call; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_pixel_activity_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
-        L.ecal_pixel_activity_dev.restype = ctypes.c_int
         self._check(L.ecal_pixel_activity_dev(self._h, d_events, int(n_events), int(width), int(height), d_counts, d_totals, stream))
 
     def filter_events_dev(self, d_events, n_events, d_mask, width, height, d_out, d_count, d_totals=None, stream=0):
         """ecal_filter_events_dev: raw device pointers; d_mask [height * width] u8 (non-zero: remove), d_out room for n_events
         records, d_count one u32, d_totals FILTER_TOTALS or None; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_filter_events_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp]
-        L.ecal_filter_events_dev.restype = ctypes.c_int
         self._check(L.ecal_filter_events_dev(self._h, d_events, int(n_events), d_mask, int(width), int(height), d_out, d_count, d_totals, stream))
 
     def pixel_activity(self, events, width, height):
@@ -2151,10 +2097,6 @@ class Context:
         uint8 CUDA tensor, info dict with `mask` and `counts`)."""
         L = self._L
         vp = ctypes.c_void_p
-        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
-        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
-        L.ecal_stream_remove_hot_pixels.argtypes = [vp, vp, ctypes.POINTER(HotPixelOptions), vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(HotPixelInfo)]
-        L.ecal_stream_remove_hot_pixels.restype = ctypes.c_int
         ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
         assert ev.size % 25 == 0, "packed 25-byte event records"
         o = hot_pixel_options(width=width, height=height, **options)
@@ -2182,18 +2124,12 @@ class Context:
         """ecal_noise_verdict_dev: raw device pointers; opt a NoiseOptions or None (the defaults), d_verdict [n_events] u8, d_totals
         FILTER_TOTALS or None; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_noise_verdict_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), vp, vp, vp]
-        L.ecal_noise_verdict_dev.restype = ctypes.c_int
         self._check(L.ecal_noise_verdict_dev(self._h, d_events, int(n_events), ctypes.byref(opt) if opt is not None else None, d_verdict, d_totals, stream))
 
     def denoise_events_dev(self, d_events, n_events, opt, d_out, d_count, d_totals=None, stream=0):
         """ecal_denoise_events_dev: raw device pointers; d_out room for n_events records (not overlapping the events), d_count one
         u32, d_totals FILTER_TOTALS or None; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_denoise_events_dev.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(NoiseOptions), vp, vp, vp, vp]
-        L.ecal_denoise_events_dev.restype = ctypes.c_int
         self._check(L.ecal_denoise_events_dev(self._h, d_events, int(n_events), ctypes.byref(opt) if opt is not None else None, d_out, d_count,
                                               d_totals, stream))
 
@@ -2242,10 +2178,6 @@ class Context:
         CUDA tensor, totals dict)."""
         L = self._L
         vp = ctypes.c_void_p
-        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
-        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
-        L.ecal_stream_remove_noise.argtypes = [vp, vp, ctypes.POINTER(NoiseOptions), ctypes.POINTER(vp), vp]
-        L.ecal_stream_remove_noise.restype = ctypes.c_int
         ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
         assert ev.size % 25 == 0, "packed 25-byte event records"
         o = noise_options(width=width, height=height, **options)
@@ -2263,18 +2195,12 @@ class Context:
     def undistort_points_dev(self, cam, d_events, n_events, d_uv, d_flag, stream=0):
         """ecal_undistort_points_dev: raw device pointers; d_uv [n_events][2] f64, d_flag [n_events] u8; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_undistort_points_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), vp, ctypes.c_uint64, vp, vp, vp]
-        L.ecal_undistort_points_dev.restype = ctypes.c_int
         self._check(L.ecal_undistort_points_dev(self._h, ctypes.byref(cam), d_events, int(n_events), d_uv, d_flag, stream))
 
     def undistort_events_dev(self, cam, opt, d_events, n_events, d_out, d_count, d_totals=None, stream=0):
         """ecal_undistort_events_dev: raw device pointers; opt an UndistortOptions or None (SUBPIXEL), d_out room for n_events records
         (not overlapping the events), d_count one u32, d_totals UNDISTORT_TOTALS or None; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_undistort_events_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp, ctypes.c_uint64, vp, vp, vp, vp]
-        L.ecal_undistort_events_dev.restype = ctypes.c_int
         self._check(L.ecal_undistort_events_dev(self._h, ctypes.byref(cam), ctypes.byref(opt) if opt is not None else None, d_events,
                                                 int(n_events), d_out, d_count, d_totals, stream))
 
@@ -2282,10 +2208,6 @@ class Context:
         """ecal_undistorted_frames_dev: raw device pointers; pk a PackedPoints or None (doubles), d_rgb [S][out_height][out_width][3]
         u8, d_frame_totals [S] UNDISTORT_FRAME_TOTALS or None; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_undistorted_frames_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp,
-                                                  ctypes.POINTER(PackedPoints), vp, vp, ctypes.c_uint32, vp, vp, vp]
-        L.ecal_undistorted_frames_dev.restype = ctypes.c_int
         self._check(L.ecal_undistorted_frames_dev(self._h, ctypes.byref(cam), ctypes.byref(opt) if opt is not None else None, d_xy,
                                                   ctypes.byref(pk) if pk is not None else None, d_seg_off, d_seg_cnt, int(S), d_rgb,
                                                   d_frame_totals, stream))
@@ -2324,8 +2246,6 @@ class Context:
         """an ecal_stream of the host records `events` (the C++ shim's way); the caller destroys it"""
         L = self._L
         vp = ctypes.c_void_p
-        L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
-        L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
         ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
         assert ev.size % 25 == 0, "packed 25-byte event records"
         h = vp()
@@ -2336,8 +2256,6 @@ class Context:
         """ecal_stream_undistort over an ecal_stream made of the host records `events` -> (events as a uint8 CUDA tensor, totals dict)."""
         L = self._L
         vp = ctypes.c_void_p
-        L.ecal_stream_undistort.argtypes = [vp, vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), ctypes.POINTER(vp), vp]
-        L.ecal_stream_undistort.restype = ctypes.c_int
         o = opt if opt is not None else undistort_options(**options)
         tot = np.zeros(1, UNDISTORT_TOTALS)
         h_in, h_out = self._host_stream(events), vp()
@@ -2353,10 +2271,6 @@ class Context:
         windows [t0[s], t1[s]] -> (rgb uint8 [S, out_height, out_width, 3], totals: UNDISTORT_FRAME_TOTALS [S]).  Options as
         undistort_events'; the mode must be PIXEL (sensor=(width, height): the reference canvas)."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_stream_undistorted_frames.argtypes = [vp, vp, ctypes.POINTER(UndistortCamera), ctypes.POINTER(UndistortOptions), vp, vp,
-                                                     ctypes.c_uint32, vp, vp]
-        L.ecal_stream_undistorted_frames.restype = ctypes.c_int
         o = opt if opt is not None else undistort_options(**options)
         t0 = np.ascontiguousarray(np.asarray(t0, np.float64).ravel())
         t1 = np.ascontiguousarray(np.asarray(t1, np.float64).ravel())
@@ -2391,9 +2305,6 @@ class Context:
     def distort_points_dev(self, cam, width, height, d_uv, n, d_out, d_flag, stream=0):
         """ecal_distort_points_dev: raw device pointers; d_uv and d_out [n][2] f64, d_flag [n] u8; no host synchronisation."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_distort_points_dev.argtypes = [vp, ctypes.POINTER(UndistortCamera), ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64, vp, vp, vp]
-        L.ecal_distort_points_dev.restype = ctypes.c_int
         self._check(L.ecal_distort_points_dev(self._h, ctypes.byref(cam), max(0, int(width)), max(0, int(height)), d_uv, int(n), d_out, d_flag, stream))
 
     def distort_points(self, cam, width, height, uv):
@@ -2423,10 +2334,6 @@ class Context:
     def slice_events_packed_dev(self, d_events, n_events, d_win_lo, d_win_hi, d_win_base, S, max_win_events, cap_points,
                                 d_xy, d_seg_off, d_seg_cnt, d_event_point, d_overflow, pk, stream=0):
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_slice_events_packed_dev.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp,
-                                                   ctypes.POINTER(PackedPoints), vp]
-        L.ecal_slice_events_packed_dev.restype = ctypes.c_int
         self._check(L.ecal_slice_events_packed_dev(self._h, d_events, int(n_events), d_win_lo, d_win_hi, d_win_base, int(S),
                                                    int(max_win_events), int(cap_points), d_xy, d_seg_off, d_seg_cnt, d_event_point,
                                                    d_overflow, ctypes.byref(pk) if pk is not None else None, stream))
@@ -2434,10 +2341,6 @@ class Context:
     def dbscan_batch_packed_dev(self, d_xy, d_seg_off, d_seg_cnt, S, n_points, max_seg_points, eps, minpts, d_labels, d_n_clusters,
                                 pk, stream=0):
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_dbscan_batch_packed_dev.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.c_double, u32, vp, vp,
-                                                   ctypes.POINTER(PackedPoints), vp]
-        L.ecal_dbscan_batch_packed_dev.restype = ctypes.c_int
         self._check(L.ecal_dbscan_batch_packed_dev(self._h, d_xy, d_seg_off, d_seg_cnt, int(S), int(n_points), int(max_seg_points),
                                                    float(eps), int(minpts), d_labels, d_n_clusters,
                                                    ctypes.byref(pk) if pk is not None else None, stream))
@@ -2447,10 +2350,6 @@ class Context:
                                  fit_circle=False, knn_num=3):
         """The extraction the context's median-ties setting asks for (exact by default), on packed points."""
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_extract_batch_packed_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_double, u32, u32, ctypes.c_double,
-                                                    ctypes.c_int, u32, vp, vp, vp, vp, vp, ctypes.POINTER(PackedPoints), vp]
-        L.ecal_extract_batch_packed_dev.restype = ctypes.c_int
         self._check(L.ecal_extract_batch_packed_dev(self._h, d_xy, d_seg_off, d_seg_cnt, d_labels, d_n_clusters, int(S), int(n_points),
                                                     float(eps), int(cluster_min), int(need_clusters), float(radius_threshold),
                                                     int(bool(fit_circle)), int(knn_num), d_win_info, d_cand_pair, d_cand_xyr,
@@ -2458,13 +2357,9 @@ class Context:
 
     def unpack_points_dev(self, pk, d_seg_off, d_seg_cnt, n_segments, d_xy, stream=0):
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_unpack_points_dev.argtypes = [vp, ctypes.POINTER(PackedPoints), vp, vp, ctypes.c_uint32, vp, vp]
-        L.ecal_unpack_points_dev.restype = ctypes.c_int
         self._check(L.ecal_unpack_points_dev(self._h, ctypes.byref(pk), d_seg_off, d_seg_cnt, int(n_segments), d_xy, stream))
 
     def get_median_ties(self):
-        self._L.ecal_get_median_ties.argtypes = [ctypes.c_void_p]
         return int(self._L.ecal_get_median_ties(self._h))
 
     # ---- grid ordering ----
@@ -2474,9 +2369,6 @@ class Context:
 
     def grid_order(self, cand_xyr, rows, cols):
         """ecal_grid_order, the host-buffer form for one candidate list: cand_xyr [n, 3] -> (order int32 [rows*cols], found)."""
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        self._L.ecal_grid_order.argtypes = [vp, vp, u32, u32, u32, vp, vp]
-        self._L.ecal_grid_order.restype = ctypes.c_int
         cand = np.ascontiguousarray(cand_xyr, np.float64).reshape(-1, 3)
         order = np.full(max(int(rows) * int(cols), 1), -1, np.int32)
         found = np.zeros(1, np.uint32)
@@ -2494,9 +2386,6 @@ class Context:
         """ecal_rectify_batch, the host-buffer form: keyframe f owns segments 2f and 2f + 1 of xy [n_points, 2] / kept_labels.
         Returns (feat_xyr [F, n, 3], feat_valid [F, n] u32, frame_info [F, 2] u32); no points at all go down as NULL arrays."""
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_rectify_batch.argtypes = [vp, vp, vp, vp, vp, u32, vp, u32, vp, ctypes.POINTER(RectifyParams), vp, vp, vp]
-        L.ecal_rectify_batch.restype = ctypes.c_int
         xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
         kept = np.ascontiguousarray(kept_labels, np.int32)
         off, cnt = np.ascontiguousarray(seg_off, np.uint32), np.ascontiguousarray(seg_cnt, np.uint32)
@@ -2542,10 +2431,6 @@ class Context:
                                   stream=0, fit_circle=False, knn_num=3):
         """extract_batch_dev with the reference's own pick at tied medians (d_cluster_order from cluster_order_dev)."""
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_extract_batch_ordered_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, ctypes.c_double, ctypes.c_int, u32,
-                                                     vp, vp, vp, vp, vp, vp]
-        L.ecal_extract_batch_ordered_dev.restype = ctypes.c_int
         self._check(L.ecal_extract_batch_ordered_dev(self._h, d_xy, d_seg_off, d_seg_cnt, d_labels, d_n_clusters, d_cluster_order, int(S),
                                                      int(n_points), int(cluster_min), int(need_clusters), float(radius_threshold),
                                                      int(bool(fit_circle)), int(knn_num), d_win_info, d_cand_pair, d_cand_xyr,
@@ -2556,10 +2441,6 @@ class Context:
                                 knn_num=3):
         """The exact extraction in one call: plain pass + member order of the tied clusters + re-extraction of their windows."""
         L = self._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_extract_batch_exact_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.c_double, u32, u32, ctypes.c_double,
-                                                   ctypes.c_int, u32, vp, vp, vp, vp, vp, vp]
-        L.ecal_extract_batch_exact_dev.restype = ctypes.c_int
         self._check(L.ecal_extract_batch_exact_dev(self._h, d_xy, d_seg_off, d_seg_cnt, d_labels, d_n_clusters, int(S), int(n_points),
                                                    float(eps), int(cluster_min), int(need_clusters), float(radius_threshold),
                                                    int(bool(fit_circle)), int(knn_num), d_win_info, d_cand_pair, d_cand_xyr,
@@ -2570,16 +2451,12 @@ class Context:
         """Position of every core point inside the reference's Clusters[label] (expandCluster's pop order); -1 for noise.
         only_tied_medians: False / True, or 2 = only the clusters the caller marked with -3 in d_order (ecal.h)."""
         L = self._L
-        vp = ctypes.c_void_p
-        L.ecal_cluster_order_dev.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_double, vp, vp, vp, vp, ctypes.c_int, vp]
-        L.ecal_cluster_order_dev.restype = ctypes.c_int
         self._check(L.ecal_cluster_order_dev(self._h, d_xy, d_seg_off, d_seg_cnt, int(S), float(eps), d_labels, d_n_clusters, d_order,
                                              d_status, int(only_tied_medians), stream))
 
     def cluster_order(self, xy, slice_off, eps, labels, n_clusters):
         """Host-buffer form of cluster_order_dev: returns (order [N] int32, status [S] uint32)."""
         L = self._L
-        vp = ctypes.c_void_p
         xy = np.ascontiguousarray(xy, np.float64)
         slice_off = np.ascontiguousarray(slice_off, np.uint32)
         labels = np.ascontiguousarray(labels, np.int32)
@@ -2587,8 +2464,6 @@ class Context:
         S = len(slice_off) - 1
         order = np.full(max(len(labels), 1), -9, np.int32)
         status = np.full(max(S, 1), 9, np.uint32)
-        L.ecal_cluster_order.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_double, vp, vp, vp, vp]
-        L.ecal_cluster_order.restype = ctypes.c_int
         self._check(L.ecal_cluster_order(self._h, _ptr(xy), _ptr(slice_off), S, float(eps), _ptr(labels), _ptr(n_clusters), _ptr(order),
                                          _ptr(status)))
         return order[:len(labels)], status[:S]
@@ -2607,132 +2482,11 @@ class Context:
 
 
 # ---- continuous-time calibration solve ----
-class _SplineProblem(ctypes.Structure):
-    _fields_ = [("n_segments", ctypes.c_uint32), ("seg_cp_off", ctypes.c_void_p), ("knots", ctypes.c_void_p),
-                ("n_res", ctypes.c_uint64), ("obs", ctypes.c_void_p), ("time", ctypes.c_void_p),
-                ("lm_id", ctypes.c_void_p), ("seg_id", ctypes.c_void_p), ("n_landmarks", ctypes.c_uint32),
-                ("landmarks", ctypes.c_void_p), ("circle_radius", ctypes.c_double), ("huber_a", ctypes.c_double),
-                ("use_so3", ctypes.c_int), ("camera_model", ctypes.c_int)]
-CAMERA_RADIAL, CAMERA_FISHEYE = 0, 1
-
-
-ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
-
-
-class LmOptions(ctypes.Structure):
-    _fields_ = [("max_num_iterations", ctypes.c_int), ("function_tolerance", ctypes.c_double),
-                ("gradient_tolerance", ctypes.c_double), ("parameter_tolerance", ctypes.c_double),
-                ("initial_trust_region_radius", ctypes.c_double), ("max_trust_region_radius", ctypes.c_double),
-                ("min_relative_decrease", ctypes.c_double), ("min_lm_diagonal", ctypes.c_double),
-                ("max_lm_diagonal", ctypes.c_double), ("jacobi_scaling", ctypes.c_int),
-                ("allreduce", ALLREDUCE_FN), ("allreduce_user", ctypes.c_void_p),
-                ("distributed", ctypes.c_int), ("rank", ctypes.c_int), ("world_size", ctypes.c_int)]
-
-
-class LmSummary(ctypes.Structure):
-    _fields_ = [("iterations", ctypes.c_int), ("successful_steps", ctypes.c_int), ("unsuccessful_steps", ctypes.c_int),
-                ("jacobian_evaluations", ctypes.c_int), ("cost_evaluations", ctypes.c_int),
-                ("termination", ctypes.c_int), ("initial_cost", ctypes.c_double), ("final_cost", ctypes.c_double),
-                ("seconds", ctypes.c_double), ("seconds_evaluate", ctypes.c_double),
-                ("seconds_linear_solve", ctypes.c_double)]
-
-
-class ReportOptions(ctypes.Structure):
-    """ecal_report_options (include/ecal.h)."""
-    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("cell_px", ctypes.c_uint32), ("hist_bins", ctypes.c_uint32),
-                ("hist_range", ctypes.c_double), ("outlier_thresh", ctypes.c_double)]
-
-
-# ecal_bin_stats / ecal_report_totals as numpy records
-BIN_STATS = np.dtype([("n", np.uint64), ("n_out", np.uint64), ("sum_r", np.float64), ("sum_r2", np.float64), ("sum_abs", np.float64),
-                      ("max_abs", np.float64)])
-REPORT_TOTALS = np.dtype([("all", BIN_STATS), ("cost", np.float64)])
-# ecal_report_px_totals (the report in pixels)
-REPORT_PX_TOTALS = np.dtype([("all", BIN_STATS), ("n_degenerate", np.uint64), ("sum_px_per_unit", np.float64)])
-
-
-class BoardImageOptions(ctypes.Structure):
-    """ecal_board_image_options (include/ecal.h)."""
-    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("bin", ctypes.c_double), ("width", ctypes.c_uint32),
-                ("height", ctypes.c_uint32), ("ring_bins", ctypes.c_uint32), ("ring_range", ctypes.c_double)]
-
-
-# ecal_board_image_totals / ecal_ring_stats as numpy records; the kernel's block and staging sizes (ECAL_BOARD_IMAGE_*)
-BOARD_IMAGE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
-                               ("n_outside_image", np.uint64), ("n_image", np.uint64, (2,)), ("n_ring", np.uint64)])
-RING_STATS = np.dtype([("n", np.uint64), ("sum_d", np.float64), ("sum_d2", np.float64)])
-BOARD_IMAGE_BLOCK, BOARD_IMAGE_CP_LDS = 4096, 16
-# ecal_reassociate_totals
-REASSOCIATE_TOTALS = np.dtype([("n_events", np.uint64), ("n_outside_time", np.uint64), ("n_behind", np.uint64),
-                               ("n_off_ring", np.uint64), ("n_kept", np.uint64)])
-
-
-def _declare_solver(L):
-    vp, i32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    L.ecal_board_image_default_options.argtypes = [vp, ctypes.POINTER(BoardImageOptions)]
-    L.ecal_board_image_default_options.restype = i32
-    L.ecal_solver_board_image_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(BoardImageOptions), vp, vp, vp, vp, vp]
-    L.ecal_solver_board_image_dev.restype = i32
-    L.ecal_solver_board_image.argtypes = [vp, vp, vp, ctypes.POINTER(BoardImageOptions), vp, vp, vp, vp]
-    L.ecal_solver_board_image.restype = i32
-    L.ecal_solver_board_points_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp]
-    L.ecal_solver_board_points_dev.restype = i32
-    L.ecal_solver_board_points.argtypes = [vp, vp, vp, vp, vp]
-    L.ecal_solver_board_points.restype = i32
-    L.ecal_solver_reassociate_dev.argtypes = [vp, vp, vp, ctypes.c_uint64, f64, vp, vp, vp, vp, vp, vp, vp]
-    L.ecal_solver_reassociate_dev.restype = i32
-    L.ecal_solver_reassociate.argtypes = [vp, vp, vp, f64, ctypes.c_uint64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64), vp]
-    L.ecal_solver_reassociate.restype = i32
-    L.ecal_solver_create_reassociated.argtypes = [vp, vp, vp, f64, ctypes.POINTER(vp), vp]
-    L.ecal_solver_create_reassociated.restype = i32
-    L.ecal_report_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
-    L.ecal_report_default_options.restype = None
-    L.ecal_solver_report_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
-    L.ecal_solver_report_dev.restype = i32
-    L.ecal_solver_report.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp]
-    L.ecal_solver_report.restype = i32
-    L.ecal_report_px_default_options.argtypes = [ctypes.POINTER(ReportOptions)]
-    L.ecal_report_px_default_options.restype = None
-    L.ecal_solver_report_px_dev.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp, vp]
-    L.ecal_solver_report_px_dev.restype = i32
-    L.ecal_solver_report_px.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.POINTER(ReportOptions), vp, vp, vp, vp, vp, vp]
-    L.ecal_solver_report_px.restype = i32
-    L.ecal_residuals_px_dev.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.ecal_residuals_px_dev.restype = i32
-    L.ecal_residuals_px.argtypes = [vp, vp, vp, vp, vp]
-    L.ecal_residuals_px.restype = i32
-    L.ecal_solver_num_landmarks.argtypes = [vp]
-    L.ecal_solver_num_landmarks.restype = ctypes.c_uint32
-    L.ecal_solver_create.argtypes = [vp, ctypes.POINTER(_SplineProblem), ctypes.POINTER(vp)]
-    L.ecal_solver_create.restype = i32
-    L.ecal_solver_create_dev.argtypes = [vp, ctypes.POINTER(_SplineProblem), vp, vp, ctypes.POINTER(vp)]
-    L.ecal_solver_create_dev.restype = i32
-    L.ecal_solver_num_residuals.argtypes = [vp]
-    L.ecal_solver_num_residuals.restype = ctypes.c_uint64
-    L.ecal_solver_destroy.argtypes = [vp]
-    L.ecal_solver_destroy.restype = None
-    for f in (L.ecal_solver_param_size, L.ecal_solver_normal_size):
-        f.argtypes = [vp]
-        f.restype = ctypes.c_size_t
-    L.ecal_solver_num_chunks.argtypes = [vp]
-    L.ecal_solver_num_chunks.restype = ctypes.c_uint32
-    L.ecal_solver_evaluate_dev.argtypes = [vp, vp, i32, vp, vp]
-    L.ecal_solver_evaluate_dev.restype = i32
-    L.ecal_solver_evaluate.argtypes = [vp, vp, i32, vp]
-    L.ecal_solver_evaluate.restype = i32
-    L.ecal_lm_default_options.argtypes = [ctypes.POINTER(LmOptions)]
-    L.ecal_lm_default_options.restype = None
-    L.ecal_solver_solve.argtypes = [vp, vp, ctypes.POINTER(LmOptions), ctypes.POINTER(LmSummary)]
-    L.ecal_solver_solve.restype = i32
-    L.ecal_inverse_radial_distortion.argtypes = [vp, vp]
-    L.ecal_inverse_radial_distortion.restype = None
 
 
 def time_shard_cuts(knots, n_cp, world_size):
     """ecal_solver_time_shard_cuts: the world_size - 1 cut times of a spline's time shards (LmOptions.distributed = 2)."""
     L = load_library()
-    L.ecal_solver_time_shard_cuts.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
-    L.ecal_solver_time_shard_cuts.restype = ctypes.c_int
     kn = np.ascontiguousarray(knots, np.float64)
     out = np.zeros(max(world_size - 1, 1))
     rc = L.ecal_solver_time_shard_cuts(kn.ctypes.data, int(n_cp), int(world_size), out.ctypes.data)
@@ -2746,8 +2500,6 @@ def pose_gates(Rsw, twb, time, pnp_ok, rect_ok, motion_time_step):
     results known for all frames.  Returns (accepted indices int64, discarded by checkPose, discarded by rectify)."""
     L = load_library()
     u8p, u32p, f64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
-    L.ecal_pose_gates.argtypes = [ctypes.c_uint32, f64p, f64p, f64p, u8p, u8p, ctypes.c_double, u32p, u32p, u32p, u32p]
-    L.ecal_pose_gates.restype = ctypes.c_int
     R = np.ascontiguousarray(Rsw, np.float64).reshape(-1, 9)
     K = R.shape[0]
     tw = np.ascontiguousarray(twb, np.float64).reshape(K, 3)
@@ -2766,11 +2518,19 @@ def pose_gates(Rsw, twb, time, pnp_ok, rect_ok, motion_time_step):
 
 def inverse_radial_distortion(k4):
     L = load_library()
-    _declare_solver(L)
     k = np.ascontiguousarray(k4, np.float64)
     b = np.zeros(5)
     L.ecal_inverse_radial_distortion(_ptr(k), _ptr(b))
     return b
+
+
+def _set_members(o, options, what):
+    """the options struct o with its members set from keyword arguments; a name it does not have is a TypeError"""
+    for k, v in options.items():
+        if not hasattr(o, k):
+            raise TypeError("no %s option %r" % (what, k))
+        setattr(o, k, v)
+    return o
 
 
 class Solver:
@@ -2786,7 +2546,6 @@ class Solver:
         dict then carries only seg_cp_off, knots, landmarks and the scalars."""
         self.ctx = ctx
         L = ctx._L
-        _declare_solver(L)
         keep = {}
 
         def arr(name, dt):
@@ -2858,8 +2617,6 @@ class Solver:
         p = np.ascontiguousarray(params, np.float64)
         assert p.shape[0] == self.n_params
         L = self.ctx._L
-        L.ecal_residuals.argtypes = [ctypes.c_void_p] * 5
-        L.ecal_residuals.restype = ctypes.c_int
         n = int(self.n_res)
         r = np.zeros(max(n, 1))
         J = np.zeros((max(n, 1), 33)) if with_jacobian else None
@@ -2874,34 +2631,31 @@ class Solver:
         """ecal_report_default_options with the given members (width, height, cell_px, hist_bins, hist_range, outlier_thresh) set."""
         o = ReportOptions()
         self.ctx._L.ecal_report_default_options(ctypes.byref(o))
-        for k, v in options.items():
-            if not hasattr(o, k):
-                raise TypeError("no report option %r" % k)
-            setattr(o, k, v)
-        return o
+        return _set_members(o, options, "report")
 
     def report_dev(self, d_params, d_kf_time, n_keyframes, options, d_total, d_kf=None, d_lm=None, d_cell_n=None, d_cell_sum_r2=None,
                    d_hist=None, stream=0):
         """ecal_solver_report_dev: raw device pointers (None: that family is skipped), records laid out as BIN_STATS /
         REPORT_TOTALS; no host synchronisation."""
-        self.ctx._check(self.ctx._L.ecal_solver_report_dev(self._h, d_params, d_kf_time, int(n_keyframes),
-                                                           ctypes.byref(options) if options is not None else None, d_total, d_kf, d_lm,
-                                                           d_cell_n, d_cell_sum_r2, d_hist, stream))
+        self._report_dev("ecal_solver_report_dev", d_params, d_kf_time, n_keyframes, options, d_total, d_kf, d_lm, d_cell_n, d_cell_sum_r2,
+                         d_hist, stream)
 
-    def report(self, params, kf_time=None, families=("kf", "lm", "cells", "hist"), **options):
-        """ecal_solver_report: the raw residuals at `params` binned on the GPU, in board units (the unit of circle_radius).
-        kf_time: ascending keyframe times (all segments); options: ReportOptions members.  Returns a dict: `totals` (one
-        REPORT_TOTALS record), `kf` [K] / `lm` [n_landmarks] (BIN_STATS), `cell_n` / `cell_sum_r2` [cells_y, cells_x], `hist`
-        [hist_bins] with `hist_edges`, and per family `<family>_rms`, `_mean`, `_outlier_frac` (NaN where a bin is empty);
-        `rms`, `mean`, `outlier_frac` of the totals, `cost` (= evaluate(params, False)[0]) and `empty_cell_frac`."""
+    def _report_dev(self, symbol, d_params, d_kf_time, n_keyframes, options, *outputs_and_stream):
+        """report_dev and report_px_dev: the two calls take the same arguments"""
+        self.ctx._check(getattr(self.ctx._L, symbol)(self._h, d_params, d_kf_time, int(n_keyframes),
+                                                     ctypes.byref(options) if options is not None else None, *outputs_and_stream))
+
+    def _report(self, totals_dtype, symbol, options_factory, default_range, params, kf_time, families, options):
+        """report and report_px: the families' arrays, the call, the derived figures -> the dict without the keys that only one of the two
+        has.  default_range: the histogram's half width where hist_range is not positive."""
         p = np.ascontiguousarray(params, np.float64)
         assert p.shape[0] == self.n_params
-        o = self.report_options(**options)
+        o = options_factory(**options)
         want = set(families)
         if kf_time is None:
             want.discard("kf")
         kt = np.ascontiguousarray(kf_time, np.float64) if "kf" in want else None
-        total = np.zeros(1, REPORT_TOTALS)
+        total = np.zeros(1, totals_dtype)
         kf = np.zeros(kt.shape[0], BIN_STATS) if "kf" in want else None
         lm = np.zeros(self.n_landmarks, BIN_STATS) if "lm" in want else None
         cn = cs = hist = None
@@ -2915,8 +2669,8 @@ class Solver:
 
         def ptr(a):
             return _ptr(a) if a is not None else None
-        self.ctx._check(self.ctx._L.ecal_solver_report(self._h, _ptr(p), ptr(kt), 0 if kt is None else kt.shape[0], ctypes.byref(o),
-                                                       _ptr(total), ptr(kf), ptr(lm), ptr(cn), ptr(cs), ptr(hist)))
+        self.ctx._check(getattr(self.ctx._L, symbol)(self._h, _ptr(p), ptr(kt), 0 if kt is None else kt.shape[0], ctypes.byref(o),
+                                                     _ptr(total), ptr(kf), ptr(lm), ptr(cn), ptr(cs), ptr(hist)))
 
         def derived(out, name, b):
             n = b["n"].astype(np.float64)
@@ -2924,7 +2678,7 @@ class Solver:
                 out[name + "rms"] = np.sqrt(b["sum_r2"] / n)
                 out[name + "mean"] = b["sum_r"] / n
                 out[name + "outlier_frac"] = b["n_out"] / n
-        out = {"totals": total[0], "cost": float(total[0]["cost"]), "options": o}
+        out = {"totals": total[0], "options": o}
         derived(out, "", total["all"][0])
         if kf is not None:
             out["kf"] = kf
@@ -2937,8 +2691,18 @@ class Solver:
             out["empty_cell_frac"] = float((cn == 0).mean())
         if hist is not None:
             out["hist"] = hist
-            rng = o.hist_range if o.hist_range > 0 else 4.0 * self.huber_a
+            rng = o.hist_range if o.hist_range > 0 else default_range
             out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
+        return out
+
+    def report(self, params, kf_time=None, families=("kf", "lm", "cells", "hist"), **options):
+        """ecal_solver_report: the raw residuals at `params` binned on the GPU, in board units (the unit of circle_radius).
+        kf_time: ascending keyframe times (all segments); options: ReportOptions members.  Returns a dict: `totals` (one
+        REPORT_TOTALS record), `kf` [K] / `lm` [n_landmarks] (BIN_STATS), `cell_n` / `cell_sum_r2` [cells_y, cells_x], `hist`
+        [hist_bins] with `hist_edges`, and per family `<family>_rms`, `_mean`, `_outlier_frac` (NaN where a bin is empty);
+        `rms`, `mean`, `outlier_frac` of the totals, `cost` (= evaluate(params, False)[0]) and `empty_cell_frac`."""
+        out = self._report(REPORT_TOTALS, "ecal_solver_report", self.report_options, 4.0 * self.huber_a, params, kf_time, families, options)
+        out["cost"] = float(out["totals"]["cost"])
         return out
 
     def residuals_px(self, params, with_gradient=False):
@@ -2959,73 +2723,26 @@ class Solver:
         ReportOptions members set."""
         o = ReportOptions()
         self.ctx._L.ecal_report_px_default_options(ctypes.byref(o))
-        for k, v in options.items():
-            if not hasattr(o, k):
-                raise TypeError("no report option %r" % k)
-            setattr(o, k, v)
-        return o
+        return _set_members(o, options, "report")
 
     def report_px_dev(self, d_params, d_kf_time, n_keyframes, options, d_total, d_kf=None, d_lm=None, d_cell_n=None, d_cell_sum_r2=None,
                       d_hist=None, stream=0):
         """ecal_solver_report_px_dev: raw device pointers (None: that family is skipped), records laid out as BIN_STATS /
         REPORT_PX_TOTALS; no host synchronisation."""
-        self.ctx._check(self.ctx._L.ecal_solver_report_px_dev(self._h, d_params, d_kf_time, int(n_keyframes),
-                                                              ctypes.byref(options) if options is not None else None, d_total, d_kf,
-                                                              d_lm, d_cell_n, d_cell_sum_r2, d_hist, stream))
+        self._report_dev("ecal_solver_report_px_dev", d_params, d_kf_time, n_keyframes, options, d_total, d_kf, d_lm, d_cell_n, d_cell_sum_r2,
+                         d_hist, stream)
 
     def report_px(self, params, kf_time=None, families=("kf", "lm", "cells", "hist"), **options):
         """ecal_solver_report_px: the residuals at `params` in PIXELS (residuals_px above) binned on the GPU.  Arguments and the
         returned dict as report's — `totals` is one REPORT_PX_TOTALS record and there is no `cost` — plus `n_degenerate` (records
         without a distance: in no bin), `px_per_unit` (the mean of 1 / |d r / d (u, v)|: how many pixels a board unit is in this
         data; NaN without records) and `rms_px` (= `rms`)."""
-        p = np.ascontiguousarray(params, np.float64)
-        assert p.shape[0] == self.n_params
-        o = self.report_px_options(**options)
-        want = set(families)
-        if kf_time is None:
-            want.discard("kf")
-        kt = np.ascontiguousarray(kf_time, np.float64) if "kf" in want else None
-        total = np.zeros(1, REPORT_PX_TOTALS)
-        kf = np.zeros(kt.shape[0], BIN_STATS) if "kf" in want else None
-        lm = np.zeros(self.n_landmarks, BIN_STATS) if "lm" in want else None
-        cn = cs = hist = None
-        if "cells" in want and o.cell_px:
-            cy, cx = -(-o.height // o.cell_px), -(-o.width // o.cell_px)
-            cn, cs = np.zeros((cy, cx), np.uint64), np.zeros((cy, cx))
-        elif "cells" in want:
-            cn, cs = np.zeros((1, 1), np.uint64), np.zeros((1, 1))    # (the call refuses cell_px == 0)
-        if "hist" in want:
-            hist = np.zeros(max(int(o.hist_bins), 1), np.uint64)
-
-        def ptr(a):
-            return _ptr(a) if a is not None else None
-        self.ctx._check(self.ctx._L.ecal_solver_report_px(self._h, _ptr(p), ptr(kt), 0 if kt is None else kt.shape[0], ctypes.byref(o),
-                                                          _ptr(total), ptr(kf), ptr(lm), ptr(cn), ptr(cs), ptr(hist)))
-
-        def derived(out, name, b):
-            n = b["n"].astype(np.float64)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                out[name + "rms"] = np.sqrt(b["sum_r2"] / n)
-                out[name + "mean"] = b["sum_r"] / n
-                out[name + "outlier_frac"] = b["n_out"] / n
-        out = {"totals": total[0], "options": o, "n_degenerate": int(total[0]["n_degenerate"])}
-        derived(out, "", total["all"][0])
+        out = self._report(REPORT_PX_TOTALS, "ecal_solver_report_px", self.report_px_options, 4.0, params, kf_time, families, options)
+        total = out["totals"]
+        out["n_degenerate"] = int(total["n_degenerate"])
         out["rms_px"] = out["rms"]
         with np.errstate(divide="ignore", invalid="ignore"):
-            out["px_per_unit"] = float(total[0]["sum_px_per_unit"] / np.float64(total[0]["all"]["n"]))
-        if kf is not None:
-            out["kf"] = kf
-            derived(out, "kf_", kf)
-        if lm is not None:
-            out["lm"] = lm
-            derived(out, "lm_", lm)
-        if cn is not None:
-            out["cell_n"], out["cell_sum_r2"] = cn, cs
-            out["empty_cell_frac"] = float((cn == 0).mean())
-        if hist is not None:
-            out["hist"] = hist
-            rng = o.hist_range if o.hist_range > 0 else 4.0
-            out["hist_edges"] = np.linspace(-rng, rng, hist.shape[0] + 1)
+            out["px_per_unit"] = float(total["sum_px_per_unit"] / np.float64(total["all"]["n"]))
         return out
 
     def board_image_options(self, **options):
@@ -3033,11 +2750,7 @@ class Solver:
         +- radius) with the given members (x0, y0, bin, width, height, ring_bins, ring_range) set."""
         o = BoardImageOptions()
         self.ctx._check(self.ctx._L.ecal_board_image_default_options(self._h, ctypes.byref(o)))
-        for k, v in options.items():
-            if not hasattr(o, k):
-                raise TypeError("no board image option %r" % k)
-            setattr(o, k, v)
-        return o
+        return _set_members(o, options, "board image")
 
     def _events_arg(self, events):
         """events of the board-image calls -> (device pointer, count, object to keep alive): an EventStream-like object with an
@@ -3124,10 +2837,6 @@ class Solver:
     def _with_stream(self, events, call):
         """call(ecal_stream handle) on an ecal_stream made of the host records `events` (any order: the stream sorts)"""
         L = self.ctx._L
-        L.ecal_stream_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
-        L.ecal_stream_create.restype = ctypes.c_int
-        L.ecal_stream_destroy.argtypes = [ctypes.c_void_p]
-        L.ecal_stream_destroy.restype = None
         ev = np.ascontiguousarray(np.asarray(events, np.uint8).ravel())
         assert ev.size % 25 == 0, "packed 25-byte event records"
         h = ctypes.c_void_p()
@@ -3321,37 +3030,6 @@ def make_allreduce_hook(ctx: Context, world_size):
 
 
 # ---- init calibration on calibration views ----
-CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1 << 0, 1 << 1, 1 << 2
-CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6 = (1 << 3, 1 << 4, 1 << 5, 1 << 6,
-                                                                                      1 << 7, 1 << 8)
-CALIB_FIX_SKEW, CALIB_RECOMPUTE_EXTRINSIC = 1 << 9, 1 << 10
-CALIB_USE_INTRINSIC_GUESS = 1 << 11
-CALIB_BLOCK_DOUBLES = 272
-
-
-class CalibOptions(ctypes.Structure):
-    """ecal_calib_options (include/ecal.h)."""
-    _fields_ = [("model", ctypes.c_int), ("flags", ctypes.c_uint32), ("aspect_ratio", ctypes.c_double),
-                ("max_iter", ctypes.c_int), ("eps", ctypes.c_double), ("allreduce", ALLREDUCE_FN),
-                ("allreduce_user", ctypes.c_void_p)]
-
-
-class CalibResult(ctypes.Structure):
-    _fields_ = [("intr", ctypes.c_double * 12), ("rms", ctypes.c_double), ("iterations", ctypes.c_int),
-                ("jacobian_evaluations", ctypes.c_int), ("error_evaluations", ctypes.c_int), ("seconds", ctypes.c_double)]
-
-
-def _declare_calib(L):
-    vp, i32, u32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_double
-    L.ecal_calib_default_options.argtypes = [ctypes.POINTER(CalibOptions)]
-    L.ecal_calib_default_options.restype = None
-    L.ecal_calib_view_blocks_dev.argtypes = [vp, vp, u32, vp, u32, i32, u32, f64, vp, vp, i32, vp, vp]
-    L.ecal_calib_view_blocks_dev.restype = i32
-    L.ecal_pnp_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp, f64, i32, i32, vp, vp, vp, vp, vp]
-    L.ecal_pnp_batch_dev.restype = i32
-    L.ecal_calibrate_views.argtypes = [vp, vp, u32, vp, u32, f64, f64, ctypes.POINTER(CalibOptions),
-                                       ctypes.POINTER(CalibResult), vp, vp, vp]
-    L.ecal_calibrate_views.restype = i32
 
 
 def calibrate_views(ctx: Context, obj, img, width, height, model=0, flags=0, aspect_ratio=1.0, max_iter=0, eps=0.0,
@@ -3359,7 +3037,6 @@ def calibrate_views(ctx: Context, obj, img, width, height, model=0, flags=0, asp
     """ecal_calibrate_views: obj [n][3], img [V][n][2] (this rank's views).  Returns a dict.  intr_guess [12] goes with
     CALIB_USE_INTRINSIC_GUESS in flags."""
     L = ctx._L
-    _declare_calib(L)
     obj = np.ascontiguousarray(obj, np.float64)
     img = np.ascontiguousarray(img, np.float64).reshape(-1, obj.shape[0], 2)
     V = img.shape[0]
@@ -3389,7 +3066,6 @@ def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspe
     first, the radial model's focal lengths as a guess when that fails).  Returns calibrate_views' dict + "start_used".
     intr_guess [12] goes with CALIB_USE_INTRINSIC_GUESS in flags (one run, start_used 2)."""
     L = ctx._L
-    _declare_calib(L)
     obj = np.ascontiguousarray(obj, np.float64)
     img = np.ascontiguousarray(img, np.float64).reshape(-1, obj.shape[0], 2)
     V = img.shape[0]
@@ -3407,10 +3083,6 @@ def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspe
             res.intr[j] = float(v)
     rv, tv, pe = np.zeros((V, 3)), np.zeros((V, 3)), np.zeros(V)
     used = ctypes.c_int(-1)
-    L.ecal_calibrate_fisheye_views.restype = ctypes.c_int
-    L.ecal_calibrate_fisheye_views.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
-                                               ctypes.c_double, ctypes.c_double, ctypes.POINTER(CalibOptions), ctypes.POINTER(CalibResult),
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
     ctx._check(L.ecal_calibrate_fisheye_views(ctx._h, _ptr(obj), obj.shape[0], _ptr(img) if V else None, V, float(width), float(height),
                                               ctypes.byref(opt), ctypes.byref(res), _ptr(rv) if V else None, _ptr(tv) if V else None,
                                               _ptr(pe) if V else None, ctypes.byref(used)))
@@ -3421,14 +3093,12 @@ def calibrate_fisheye_views(ctx: Context, obj, img, width, height, flags=0, aspe
 
 def calib_view_blocks_dev(ctx: Context, d_obj, n_pts, d_img, n_views, model, flags, aspect_ratio, d_intr, d_view_params,
                           with_jacobian, d_blocks, stream=0):
-    _declare_calib(ctx._L)
     ctx._check(ctx._L.ecal_calib_view_blocks_dev(ctx._h, d_obj, n_pts, d_img, n_views, model, flags, aspect_ratio, d_intr,
                                                  d_view_params, int(with_jacobian), d_blocks, stream))
 
 
 def pnp_batch_dev(ctx: Context, d_obj, n_pts, d_img, d_valid, n_frames, model, d_intr, reproj_thresh, rounds, refine_iters,
                   d_pose, d_inlier=None, d_err=None, d_ok=None, stream=0):
-    _declare_calib(ctx._L)
     ctx._check(ctx._L.ecal_pnp_batch_dev(ctx._h, d_obj, n_pts, d_img, d_valid, n_frames, model, d_intr, float(reproj_thresh),
                                          int(rounds), int(refine_iters), d_pose, d_inlier, d_err, d_ok, stream))
 
@@ -3437,9 +3107,6 @@ def pnp_batch(ctx: Context, obj, img, valid, model, intr, reproj_thresh, rounds,
     """ecal_pnp_batch, the host-buffer form of pnp_batch_dev: obj [n][3], img [F][n][2], valid [F][n] uint32 or None, intr [12].
     Returns {"pose" [F][6], "inlier" [F][n] uint32, "err" [F], "ok" [F] uint32}."""
     L = ctx._L
-    vp, i32, u32, f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_double
-    L.ecal_pnp_batch.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp, f64, i32, i32, vp, vp, vp, vp]
-    L.ecal_pnp_batch.restype = i32
     obj = np.ascontiguousarray(obj, np.float64)
     n = obj.shape[0]
     img = np.ascontiguousarray(img, np.float64).reshape(-1, n, 2)
@@ -3460,8 +3127,6 @@ def spline_fit(u, data, n_cp):
     u = np.ascontiguousarray(u, np.float64)
     data = np.ascontiguousarray(data, np.float64).reshape(len(u), -1)
     knots, cp = np.zeros(n_cp + 4), np.zeros((n_cp, data.shape[1]))
-    L.ecal_spline_fit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                  ctypes.c_void_p, ctypes.c_void_p]
     st = L.ecal_spline_fit(_ptr(u), _ptr(data), len(u), data.shape[1], n_cp, _ptr(knots), _ptr(cp))
     if st != 0:
         raise EcalError(st, L.ecal_strerror(st).decode())
@@ -3472,8 +3137,6 @@ def spline_eval(knots, cp, u):
     L = load_library()
     knots, cp, u = (np.ascontiguousarray(a, np.float64) for a in (knots, cp, u))
     out = np.zeros((len(u), cp.shape[1]))
-    L.ecal_spline_eval.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
-                                   ctypes.c_uint32, ctypes.c_void_p]
     st = L.ecal_spline_eval(_ptr(knots), _ptr(cp), cp.shape[0], cp.shape[1], _ptr(u), len(u), _ptr(out))
     if st != 0:
         raise EcalError(st, L.ecal_strerror(st).decode())
@@ -3487,9 +3150,6 @@ def spline_so3_refine(knots, cp_quat, sample_quat, u, max_iterations=0):
     cp = np.ascontiguousarray(cp_quat, np.float64).copy()
     sq = np.ascontiguousarray(sample_quat, np.float64)
     c0, c1, it = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int(0)
-    L.ecal_spline_so3_refine.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     st = L.ecal_spline_so3_refine(_ptr(knots), cp.shape[0], _ptr(cp), _ptr(sq), _ptr(u), len(u), int(max_iterations),
                                   ctypes.byref(c0), ctypes.byref(c1), ctypes.byref(it))
     if st != 0:
@@ -3498,16 +3158,6 @@ def spline_so3_refine(knots, cp_quat, sample_quat, u, max_iterations=0):
 
 
 # ---- double-buffered ingest ----
-class DetectParams(ctypes.Structure):
-    """ecal_detect_params (include/ecal.h)."""
-    _fields_ = [("dbscan_eps", ctypes.c_double), ("dbscan_min_samples", ctypes.c_uint32), ("cluster_min_sample", ctypes.c_uint32),
-                ("need_clusters", ctypes.c_uint32), ("circle_radius_threshold", ctypes.c_double), ("fit_circle", ctypes.c_int),
-                ("knn_num", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("cols", ctypes.c_uint32)]
-
-
-class IngestStats(ctypes.Structure):
-    _fields_ = [("chunks", ctypes.c_uint32), ("max_chunk_events", ctypes.c_uint64), ("bytes_uploaded", ctypes.c_uint64),
-                ("seconds", ctypes.c_double)]
 
 
 def detect_stream_tiled(ctx: Context, host_ptr, n_events, t_start, window_len, windows_per_chunk, max_windows, eps=4.0, minpts=2,
@@ -3515,10 +3165,7 @@ def detect_stream_tiled(ctx: Context, host_ptr, n_events, t_start, window_len, w
     """ecal_detect_stream_tiled over packed records at host address `host_ptr` (pinned for overlap).  Returns
     (win_info [S,4], grid_found [S], features [S, rows*cols, 3] or None, stats dict)."""
     L = ctx._L
-    vp, u32, f64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double
-    L.ecal_detect_stream_tiled.argtypes = [vp, vp, ctypes.c_uint64, f64, f64, u32, ctypes.POINTER(DetectParams), u32, vp, vp, vp,
-                                           ctypes.POINTER(u32), ctypes.POINTER(IngestStats)]
-    L.ecal_detect_stream_tiled.restype = ctypes.c_int
+    u32 = ctypes.c_uint32
     prm = DetectParams(float(eps), int(minpts), int(cluster_min), int(rows * cols), float(radius_threshold), 0, 3, int(rows), int(cols))
     info = np.zeros((max_windows, 4), np.uint32)
     found = np.zeros(max_windows, np.uint32)
@@ -3533,20 +3180,10 @@ def detect_stream_tiled(ctx: Context, host_ptr, n_events, t_start, window_len, w
                                                                       "bytes_uploaded": st.bytes_uploaded, "seconds": st.seconds}
 
 
-class AdaptiveParams(ctypes.Structure):
-    _fields_ = [("motion_time_step", ctypes.c_double), ("frame_event_num_threshold", ctypes.c_uint32), ("piece_num", ctypes.c_uint32),
-                ("start_time", ctypes.c_double), ("end_time", ctypes.c_double), ("max_passes", ctypes.c_uint32),
-                ("check_every", ctypes.c_uint32), ("gate_mode", ctypes.c_int), ("piece_first", ctypes.c_uint32),
-                ("piece_count", ctypes.c_uint32)]
-GATE_OWN_PIECE, GATE_SHARED_MAP = 0, 1
-
-
 def detect_keyframes_cap_hint(ctx: Context, n_events, motion_time_step, frame_event_num_threshold, piece_num, start_time, end_time,
                               piece_first=0, piece_count=0):
     """ecal_detect_keyframes_cap_hint: a cap_points that detect_keyframes_dev will usually find sufficient."""
     L = ctx._L
-    L.ecal_detect_keyframes_cap_hint.argtypes = [ctypes.POINTER(AdaptiveParams), ctypes.c_uint64]
-    L.ecal_detect_keyframes_cap_hint.restype = ctypes.c_uint64
     ap = AdaptiveParams(float(motion_time_step), int(frame_event_num_threshold), int(piece_num), float(start_time), float(end_time), 0, 0, 0,
                         int(piece_first), int(piece_count))
     return int(L.ecal_detect_keyframes_cap_hint(ctypes.byref(ap), int(n_events)))
@@ -3556,23 +3193,9 @@ def detect_keyframes_cap_hint_dev(ctx: Context, d_events, n_events, motion_time_
                                   end_time, piece_first=0, piece_count=0):
     """ecal_detect_keyframes_cap_hint_dev: the hint from the events of the resident stream inside [start_time, end_time]."""
     L = ctx._L
-    L.ecal_detect_keyframes_cap_hint_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(AdaptiveParams)]
-    L.ecal_detect_keyframes_cap_hint_dev.restype = ctypes.c_uint64
     ap = AdaptiveParams(float(motion_time_step), int(frame_event_num_threshold), int(piece_num), float(start_time), float(end_time), 0, 0, 0,
                         int(piece_first), int(piece_count))
     return int(L.ecal_detect_keyframes_cap_hint_dev(ctx._h, d_events, int(n_events), ctypes.byref(ap)))
-
-
-class KeyframeFrame(ctypes.Structure):   # ecal_keyframe_frame
-    _fields_ = [("has", ctypes.c_int), ("time", ctypes.c_double), ("dir", ctypes.c_double * 64)]
-
-
-_FRAME_RECV = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(KeyframeFrame), ctypes.c_int)
-_FRAME_SEND = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(KeyframeFrame))
-
-
-class AdaptiveHandover(ctypes.Structure):   # ecal_adaptive_handover
-    _fields_ = [("recv", _FRAME_RECV), ("send", _FRAME_SEND), ("user", ctypes.c_void_p)]
 
 
 def detect_keyframes_dev(ctx: Context, d_events, n_events, motion_time_step, frame_event_num_threshold, piece_num, start_time,
@@ -3586,10 +3209,7 @@ def detect_keyframes_dev(ctx: Context, d_events, n_events, motion_time_step, fra
     yet; only when wait is false) or (has, time, dir [2 rows]) = the frame behind the pieces before this subset, and send(has, time,
     dir) for the frame behind this subset's pieces."""
     L = ctx._L
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.ecal_detect_keyframes.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(AdaptiveParams), ctypes.POINTER(DetectParams), u32, u32,
-                                        vp, vp, vp, vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint64)]
-    L.ecal_detect_keyframes.restype = ctypes.c_int
+    u32 = ctypes.c_uint32
     ap = AdaptiveParams(float(motion_time_step), int(frame_event_num_threshold), int(piece_num), float(start_time), float(end_time),
                         int(max_passes), int(check_every), int(gate_mode), int(piece_first), int(piece_count))
     prm = DetectParams(float(eps), int(minpts), int(cluster_min), int(rows * cols), float(radius_threshold), 0, 3, int(rows), int(cols))
@@ -3628,8 +3248,6 @@ def detect_keyframes_dev(ctx: Context, d_events, n_events, motion_time_step, fra
                     errs.append(ex)
                     return -1
             ho = AdaptiveHandover(_FRAME_RECV(recv), _FRAME_SEND(send), None)
-            L.ecal_detect_keyframes_sharded.argtypes = L.ecal_detect_keyframes.argtypes + [ctypes.POINTER(AdaptiveHandover)]
-            L.ecal_detect_keyframes_sharded.restype = ctypes.c_int
             st = L.ecal_detect_keyframes_sharded(ctx._h, d_events, int(n_events), ctypes.byref(ap), ctypes.byref(prm), int(cap_points),
                                                  int(max_keyframes), _ptr(t), _ptr(d), _ptr(e), _ptr(f), ctypes.byref(nk), ctypes.byref(ps),
                                                  ctypes.byref(nw), ctypes.byref(ho))
@@ -3647,9 +3265,6 @@ def detect_pass(ctx: Context, d_events, n_events, t0, t1, cap_points, eps=4.0, m
                 radius_threshold=15.511363636363637):
     """ecal_detect_pass: packed [S, 3 + 3 rows cols] = status, ok, unique pixels, ordered circles of every window."""
     L = ctx._L
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.ecal_detect_pass.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, u32, ctypes.POINTER(DetectParams), u32, vp]
-    L.ecal_detect_pass.restype = ctypes.c_int
     t0 = np.ascontiguousarray(t0, np.float64)
     t1 = np.ascontiguousarray(t1, np.float64)
     S = t0.shape[0]

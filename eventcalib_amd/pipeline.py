@@ -167,19 +167,14 @@ class DetectPipeline:
 
     def gather_features(self, rows=9, cols=4):
         """Ordered circles [S, rows*cols, 3] of the last run() + order_grid() (NaN rows where no grid was found), on device."""
-        import ctypes
         st = torch.cuda.current_stream(self.dev).cuda_stream
         M = rows * cols
         if getattr(self, "_feat_cap", 0) < self.S * M:
             self.feat = torch.empty(self.S * M * 3, dtype=torch.float64, device=self.dev)
             self._feat_cap = self.S * M
-        L = self.ctx._L
-        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        L.ecal_gather_features_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]
-        L.ecal_gather_features_dev.restype = ctypes.c_int
-        self.ctx._check(L.ecal_gather_features_dev(self.ctx._h, self.win_info.data_ptr(), self.seg_off.data_ptr(),
-                                                   self.cand_xyr.data_ptr(), self.grid_order.data_ptr(), self.grid_found.data_ptr(),
-                                                   self.S, M, self.feat.data_ptr(), st))
+        self.ctx._check(self.ctx._L.ecal_gather_features_dev(self.ctx._h, self.win_info.data_ptr(), self.seg_off.data_ptr(),
+                                                             self.cand_xyr.data_ptr(), self.grid_order.data_ptr(), self.grid_found.data_ptr(),
+                                                             self.S, M, self.feat.data_ptr(), st))
         return self.feat[: self.S * M * 3].view(self.S, M, 3)
 
     def overflowed(self):

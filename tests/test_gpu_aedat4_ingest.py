@@ -82,8 +82,9 @@ def test_structures_have_the_library_sizes(ctx):
         _fields_ = [("o", capi.Aedat4Options), ("guard", ctypes.c_uint8 * 64)]
     g = Guarded()
     ctypes.memset(ctypes.byref(g), 0x5A, ctypes.sizeof(g))
-    ctx._L.ecal_aedat4_default_options.argtypes, ctx._L.ecal_aedat4_default_options.restype = [ctypes.c_void_p], None
-    ctx._L.ecal_aedat4_default_options(ctypes.byref(g))
+    raw = ctypes.CDLL(capi.lib_path())      # (a handle of the test's own: the shared one keeps its struct-pointer prototype)
+    raw.ecal_aedat4_default_options.argtypes, raw.ecal_aedat4_default_options.restype = [ctypes.c_void_p], None
+    raw.ecal_aedat4_default_options(ctypes.byref(g))
     assert bytes(g.guard) == b"\x5A" * 64 and g.o.stream_id == -1 and g.o.auto_time_base == 1 and g.o.start_time == -INF
     assert g.o.max_inflated_bytes == 1 << 34 and g.o.compression == capi.AEDAT4_LZ4
     assert ctypes.sizeof(capi.Aedat4Packet) == 16 == capi.AEDAT4_PACKET_DTYPE.itemsize and ctypes.sizeof(capi.Aedat4Info) == 14 * 8

@@ -106,8 +106,9 @@ def test_structures_have_the_library_sizes(ctx):
             _fields_ = [("o", cls), ("guard", ctypes.c_uint8 * 64)]
         g = Guarded()
         ctypes.memset(ctypes.byref(g), 0x5A, ctypes.sizeof(g))
-        getattr(ctx._L, fn).argtypes, getattr(ctx._L, fn).restype = [ctypes.c_void_p], None
-        getattr(ctx._L, fn)(ctypes.byref(g))
+        raw = ctypes.CDLL(capi.lib_path())      # (a handle of the test's own: the shared one keeps its struct-pointer prototypes)
+        getattr(raw, fn).argtypes, getattr(raw, fn).restype = [ctypes.c_void_p], None
+        getattr(raw, fn)(ctypes.byref(g))
         assert bytes(g.guard) == b"\x5A" * 64 and ctypes.sizeof(cls) == size, fn
     assert ctypes.sizeof(capi.Field) == 24 and ctypes.sizeof(capi.FieldsInfo) == 56
 

@@ -503,13 +503,7 @@ def test_longer_range_tables_agree_on_their_common_ranges(ranged):
 def host(gpu):
     ctx, torch = gpu
     L = ctx._L
-    vp, u32, u64, f64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
-    L.ecal_stream_create.argtypes = [vp, vp, u64, ctypes.POINTER(vp)]
-    L.ecal_stream_create.restype = ctypes.c_int
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_destroy.restype = None
-    L.ecal_associate.argtypes = [vp, vp, vp, vp, u32, u32, f64, f64, f64, f64, u64, vp, vp, vp, ctypes.POINTER(u64)]
-    L.ecal_associate.restype = ctypes.c_int
+    vp, u64 = ctypes.c_void_p, ctypes.c_uint64
     n = 5000
     t, x, y, kt, circ, ties = _stream(n, 130.5 + 227.0 * np.arange(23), 36, 55)
     rec = _records(t, x, y)
@@ -564,10 +558,7 @@ def test_host_forms_refuse_keyframe_times_that_are_not_strictly_ascending(host, 
     msg = L.ecal_last_error(ctx._h).decode()
     assert "ecal_associate" in msg and "strictly ascending" in msg and "keyframe %d)" % bad in msg
     # ecal_solver_create_from_stream checks the same table, after its ranges
-    vp, u32, f64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double
-    L.ecal_solver_create_from_stream.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32, f64, f64, ctypes.POINTER(capi._SplineProblem),
-                                                 ctypes.POINTER(vp)]
-    L.ecal_solver_create_from_stream.restype = ctypes.c_int
+    vp = ctypes.c_void_p
     layout = capi._SplineProblem(n_segments=1)
     kt = np.array(times, np.float64)
     ranges = np.array([host["t"][0], host["t"][-1]])

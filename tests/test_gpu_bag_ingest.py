@@ -65,8 +65,9 @@ def test_structures_have_the_library_sizes(ctx):
         _fields_ = [("o", capi.BagOptions), ("guard", ctypes.c_uint8 * 64)]
     g = Guarded()
     ctypes.memset(ctypes.byref(g), 0x5A, ctypes.sizeof(g))
-    ctx._L.ecal_bag_default_options.argtypes, ctx._L.ecal_bag_default_options.restype = [ctypes.c_void_p], None
-    ctx._L.ecal_bag_default_options(ctypes.byref(g))
+    raw = ctypes.CDLL(capi.lib_path())      # (a handle of the test's own: the shared one keeps its struct-pointer prototype)
+    raw.ecal_bag_default_options.argtypes, raw.ecal_bag_default_options.restype = [ctypes.c_void_p], None
+    raw.ecal_bag_default_options(ctypes.byref(g))
     assert bytes(g.guard) == b"\x5A" * 64 and g.o.auto_time_base == 1 and g.o.time_base == 0 and g.o.start_time == -INF and g.o.flip_x == 0
     assert not g.o.topic and not g.o.type and g.o.has_end_time == 0 and g.o.width == 0
     assert ctypes.sizeof(capi.BagMessage) == 16 == capi.BAG_MESSAGE_DTYPE.itemsize and ctypes.sizeof(capi.BagInfo) == 14 * 8
@@ -398,8 +399,6 @@ def synthetic():
 def load_bin(ctx, path):
     L = ctx._L
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_file.argtypes = [vp, ctypes.c_char_p, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.POINTER(vp)]
-    L.ecal_stream_create_from_file.restype = ctypes.c_int
     h = vp()
     assert L.ecal_stream_create_from_file(ctx._h, os.fsencode(path), -INF, 0, 0.0, ctypes.byref(h)) == 0
     return ctx._stream_records(h)

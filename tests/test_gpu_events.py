@@ -546,12 +546,6 @@ def test_unsorted_stream_is_sorted_like_the_multimap(env):
     # through the host-pointer entry point: the stream object holds the sorted records
     import ctypes
     L = ctx._L
-    L.ecal_stream_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]
-    L.ecal_stream_create.restype = ctypes.c_int
-    L.ecal_stream_data.argtypes = [ctypes.c_void_p]
-    L.ecal_stream_data.restype = ctypes.c_void_p
-    L.ecal_stream_destroy.argtypes = [ctypes.c_void_p]
-    L.ecal_copy_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]
     h = ctypes.c_void_p()
     assert L.ecal_stream_create(ctx._h, rec.ctypes.data, n, ctypes.byref(h)) == 0
     back = torch.empty(n * 25, dtype=torch.uint8, device="cuda")

@@ -381,8 +381,6 @@ def synthetic():
 def load_bin(ctx, path):
     L = ctx._L
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_file.argtypes = [vp, ctypes.c_char_p, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.POINTER(vp)]
-    L.ecal_stream_create_from_file.restype = ctypes.c_int
     h = vp()
     assert L.ecal_stream_create_from_file(ctx._h, os.fsencode(path), -INF, 0, 0.0, ctypes.byref(h)) == 0
     return ctx._stream_records(h)

@@ -17,16 +17,6 @@ pytestmark = pytest.mark.gpu
 def _from_file(ctx, torch, path, start, has_end, end):
     L = ctx._L
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_file.argtypes = [vp, ctypes.c_char_p, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.POINTER(vp)]
-    L.ecal_stream_create_from_file.restype = ctypes.c_int
-    L.ecal_stream_size.argtypes = [vp]
-    L.ecal_stream_size.restype = ctypes.c_uint64
-    L.ecal_stream_data.argtypes = [vp]
-    L.ecal_stream_data.restype = vp
-    L.ecal_stream_times.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    L.ecal_stream_times.restype = ctypes.c_int
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_destroy.restype = None
     h = vp()
     rc = L.ecal_stream_create_from_file(ctx._h, path.encode(), float(start), int(has_end), float(end), ctypes.byref(h))
     if rc != 0:

@@ -115,9 +115,7 @@ def _both_nth(a, nth):
     import ctypes
     import eventcalib_amd
     L, P = O.lib(), eventcalib_amd.load_library()
-    for f in (L.oracle_nth_element_f64, P.ecal_ref_nth_element_f64):
-        f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]
-        f.restype = None
+    L.oracle_nth_element_f64.argtypes, L.oracle_nth_element_f64.restype = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32], None
     x, y = np.array(a, np.float64), np.array(a, np.float64)
     L.oracle_nth_element_f64(x.ctypes.data, len(x), nth)
     P.ecal_ref_nth_element_f64(y.ctypes.data, len(y), nth)

@@ -186,12 +186,8 @@ def main():
     torch.cuda.empty_cache()
 
     vp = ctypes.c_void_p
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
 
     def from_file(fn, path):
-        fn.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(vp), vp]
-
         def run():
             h = vp()
             t0 = time.perf_counter()

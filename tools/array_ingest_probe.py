@@ -110,7 +110,7 @@ def probe(ctx, n, a):
     host_file = payload.cpu().numpy()
     table_np, _ = ctx.bag_index_messages(host_file)
     table = torch.from_numpy(table_np.view("u1").copy()).cuda()
-    mt, n_m = ctx._bag_table_tensor(table, payload.device)
+    mt, n_m = ctx._table_tensor(table, capi.BAG_MESSAGE_DTYPE, payload.device)
     bopt = ctx.bag_options(time_base=base * 1000)
     L = ctx._L
     bag_records = torch.empty(n * 25 + 16, dtype=torch.uint8, device="cuda")
@@ -120,7 +120,7 @@ def probe(ctx, n, a):
         rc = L.ecal_events_from_bag_dev(ctx._h, payload.data_ptr(), payload.numel(), mt.data_ptr(), n_m, ctypes.byref(bopt), bag_records.data_ptr(), n,
                                         ctypes.byref(info), stream)
         assert rc == 0 and info.n_events == n, (rc, info.n_events)
-    ctx.events_from_bag(payload, table, capacity=n, time_base=base * 1000)   # (declares the argument types; a first warm run)
+    ctx.events_from_bag(payload, table, capacity=n, time_base=base * 1000)   # (a first warm run)
     with Trace("bag") as tr:
         res["from_bag"] = stats(timed(bag, a.warmup, a.runs))
     res["from_bag"]["phases_ms"] = tr.medians(a.runs)
@@ -151,10 +151,6 @@ def probe(ctx, n, a):
 
     # ---- the stream forms (wall time): HOST columns, and the same events as a .npy of packed 13-byte items in /dev/shm
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_fields.argtypes = [vp, ctypes.POINTER(capi.Field), ctypes.c_uint64, ctypes.POINTER(capi.FieldsOptions), ctypes.POINTER(vp), vp]
-    L.ecal_stream_create_from_npy_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(capi.NpyOptions), ctypes.POINTER(vp), vp]
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
     hcols = [capi._host_column(c) for c in (t_us.cpu().numpy(), x16.cpu().numpy().view(np.uint16), y16.cpu().numpy().view(np.uint16), p8.cpu().numpy())]
     hf = (capi.Field * 4)(*[c[1] for c in hcols])
 

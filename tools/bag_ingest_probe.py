@@ -158,9 +158,6 @@ def probe(ctx, n, a, drv):
     del host, payload, table
     torch.cuda.empty_cache()
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_bag_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(vp), vp]
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
 
     def from_file():
         h = vp()

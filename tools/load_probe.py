@@ -12,8 +12,6 @@ ev.cpu().numpy().tofile(path)
 del ev
 ctx = eventcalib_amd.Context(0)
 L = ctx._L
-L.ecal_stream_create_from_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]
-L.ecal_stream_destroy.argtypes = [ctypes.c_void_p]
 for rep in range(3):
     h = ctypes.c_void_p()
     t = time.perf_counter()

@@ -122,12 +122,6 @@ def probe(ctx, n, a):
     # ---- yardstick 1: the library-owned stream calls, the parent commit's filter beside this one (wall time: both wait for the device)
     L = ctx._L
     vp = ctypes.c_void_p
-    L.ecal_stream_create.argtypes, L.ecal_stream_create.restype = [vp, vp, ctypes.c_uint64, ctypes.POINTER(vp)], ctypes.c_int
-    L.ecal_stream_destroy.argtypes, L.ecal_stream_destroy.restype = [vp], None
-    L.ecal_stream_remove_hot_pixels.argtypes = [vp, vp, ctypes.POINTER(capi.HotPixelOptions), vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(capi.HotPixelInfo)]
-    L.ecal_stream_remove_hot_pixels.restype = ctypes.c_int
-    L.ecal_stream_remove_noise.argtypes = [vp, vp, ctypes.POINTER(capi.NoiseOptions), ctypes.POINTER(vp), vp]
-    L.ecal_stream_remove_noise.restype = ctypes.c_int
     host = ev.cpu().numpy()
     h_in = vp()
     ctx._check(L.ecal_stream_create(ctx._h, host.ctypes.data, n, ctypes.byref(h_in)))

@@ -130,9 +130,6 @@ def probe(ctx, fmt, n, a, drv):
     del host, payload
     torch.cuda.empty_cache()
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_raw_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(vp), vp]
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
 
     def from_raw_file():
         h = vp()

@@ -6,7 +6,6 @@ from eventcalib_amd.pipeline import DetectPipeline
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 ctx = eventcalib_amd.Context(0)
 L = eventcalib_amd.load_library()
-L.ecal_debug_tail_seen.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 ev = SS.make_stream(n, device="cuda")
 pipe = DetectPipeline(ctx, want_event_point=False)
 t0, t1 = SS.tiled_windows(5.0, 5.0 + (n - 1) / 1e6)

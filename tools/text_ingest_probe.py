@@ -126,10 +126,6 @@ def main():
     del host, text
     torch.cuda.empty_cache()
     vp = ctypes.c_void_p
-    L.ecal_stream_create_from_text_file.argtypes = [vp, ctypes.c_char_p, vp, ctypes.POINTER(vp), vp]
-    L.ecal_stream_create_from_file.argtypes = [vp, ctypes.c_char_p, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.POINTER(vp)]
-    L.ecal_stream_destroy.argtypes = [vp]
-    L.ecal_stream_size.argtypes, L.ecal_stream_size.restype = [vp], ctypes.c_uint64
     opt = ctx.text_options(time_base=0)
 
     def from_text_file():
