@@ -115,15 +115,7 @@ __global__ __launch_bounds__(NE_T) void report_kernel(const ResRecord *__restric
         const ResRecord e = e_next;
         e_next = rec[ch.start + min(k + (uint32_t) NE_T, ch.count - 1u)];
         ResidualInput in;
-        in.u = e.u;
-        in.v = e.v;
-        in.lmx = landmarks[3 * (size_t) e.lm];
-        in.lmy = landmarks[3 * (size_t) e.lm + 1];
-        in.lmz = landmarks[3 * (size_t) e.lm + 2];
-        in.radius = radius;
-        in.ifx = ifx;
-        in.ify = ify;
-        spline_basis_inv(kn, ch.span, binv, e.t, in.b);
+        residual_input_fill(in, e, landmarks, radius, ifx, ify, kn, ch.span, binv);
         const double r = SO3 ? spline_residual_so3<FISHEYE>(in, pin, q, t, nullptr) : spline_residual<FISHEYE>(in, pin, q, t, nullptr);
         double hr = 0.0;
         (void) huber_scale(r, huber_a, &hr, inv_huber_a);

@@ -59,15 +59,7 @@ template <bool SO3, bool FISHEYE>
 __device__ __forceinline__ double record_residual_px(const ResRecord &e, const Chunk &ch, const ChunkPose &P, const double *landmarks,
                                                      double radius, double g[2]) {
     ResidualInput in;
-    in.u = e.u;
-    in.v = e.v;
-    in.lmx = landmarks[3 * (size_t) e.lm];
-    in.lmy = landmarks[3 * (size_t) e.lm + 1];
-    in.lmz = landmarks[3 * (size_t) e.lm + 2];
-    in.radius = radius;
-    in.ifx = P.ifx;
-    in.ify = P.ify;
-    spline_basis_inv(P.kn, ch.span, P.binv, e.t, in.b);
+    residual_input_fill(in, e, landmarks, radius, P.ifx, P.ify, P.kn, ch.span, P.binv);
     return SO3 ? spline_residual_px_so3<FISHEYE>(in, P.pin, P.q, P.t, g) : spline_residual_px<FISHEYE>(in, P.pin, P.q, P.t, g);
 }
 

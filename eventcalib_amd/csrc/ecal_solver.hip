@@ -131,7 +131,9 @@ __device__ __forceinline__ void ne_publish_progress(const NeProgress *__restrict
     }
 }
 
-// WITH_JAC = false: cost only (no rows, no LDS, no tiles) — its own, small instantiation (69 VGPRs against 233)
+// WITH_JAC = false: cost only (no rows, no LDS, no tiles) — its own, small instantiation: 66 / 107 / 142 / 168 registers over
+// quaternion radial / quaternion fisheye / SO3 radial / SO3 fisheye against 225 / 255 / 374 / 402 with the Jacobian (the SO3 ones
+// with 118 / 146 of them AGPRs; ROCm 7.2.0, no scratch)
 template <bool SO3, bool WITH_JAC, bool FISHEYE = false>
 __global__ __launch_bounds__(NE_T, SO3 ? 1 : 2) void normal_eq_kernel(const ResRecord *__restrict__ rec,
                                                          const Chunk *__restrict__ chunks,
@@ -155,6 +157,10 @@ __global__ __launch_bounds__(NE_T, SO3 ? 1 : 2) void normal_eq_kernel(const ResR
     const double *intr = params;
     const double *qall = params + 9;
     const double *tall = params + 9 + 4 * (size_t) n_cp_total;
+    // (this prologue is written out here, in residual_rows_kernel and in report_kernel: shared with ecal_report_px.hip's ChunkPose,
+    // as a struct or as a function, it moves those kernels.  The fill of ResidualInput below is residual_input_fill's, written out
+    // in this kernel alone: the call moves six of its eight instantiations — design/08_solver.md, "One copy of the residual's
+    // pieces")
     double q[4][4], t[4][3], pin[9], binv[6];
     for (int i = 0; i < 9; i++) pin[i] = intr[i];
     spline_span_inverses(kn, ch.span, binv);           // uniform over the chunk: 6 + 2 divisions per thread, not per residual
@@ -362,15 +368,7 @@ __global__ __launch_bounds__(NE_T) void residual_rows_kernel(const ResRecord *__
         const size_t at = (size_t) ch.start + k;
         const ResRecord e = rec[at];
         ResidualInput in;
-        in.u = e.u;
-        in.v = e.v;
-        in.lmx = landmarks[3 * (size_t) e.lm];
-        in.lmy = landmarks[3 * (size_t) e.lm + 1];
-        in.lmz = landmarks[3 * (size_t) e.lm + 2];
-        in.radius = radius;
-        in.ifx = ifx;
-        in.ify = ify;
-        spline_basis_inv(kn, ch.span, binv, e.t, in.b);
+        residual_input_fill(in, e, landmarks, radius, ifx, ify, kn, ch.span, binv);
         double J[RES_NJ];
         const double r = SO3 ? spline_residual_so3<FISHEYE>(in, pin, q, t, J_out ? J : nullptr)
                              : spline_residual<FISHEYE>(in, pin, q, t, J_out ? J : nullptr);

@@ -5,6 +5,7 @@
 #include <vector>
 #include "ecal_ctx.hpp"
 #include "arrow_layout.hpp"
+#include "spline_residual.hpp"   // (a unit that contracts the residual to FMA by pragma includes it first, under its pragma)
 
 namespace ecal {
 
@@ -83,3 +84,24 @@ struct ecal_solver {
     size_t n_params() const { return 9 + 7 * (size_t) n_cp; }
     size_t n_accum() const { return ecal::ACC_HEAD + ecal::ACC_PER_CP * (size_t) n_cp; }
 };
+
+#if defined(__HIPCC__)
+namespace ecal {
+// One record into the residual's input: pixel, landmark, radius, 1 / fx, 1 / fy and the basis values at the record's time (kn, span,
+// binv: the chunk's knots and span inverses).  The robust-loss fields stay with the caller.  Used by residual_rows_kernel,
+// report_kernel and both kernels of ecal_report_px.hip; normal_eq_kernel writes these lines out, because six of its eight
+// instantiations move with the call (design/08_solver.md, "One copy of the residual's pieces").
+__device__ __forceinline__ void residual_input_fill(ResidualInput &in, const ResRecord &e, const double *landmarks, double radius,
+                                                    double ifx, double ify, const double *kn, uint32_t span, const double binv[6]) {
+    in.u = e.u;
+    in.v = e.v;
+    in.lmx = landmarks[3 * (size_t) e.lm];
+    in.lmy = landmarks[3 * (size_t) e.lm + 1];
+    in.lmz = landmarks[3 * (size_t) e.lm + 2];
+    in.radius = radius;
+    in.ifx = ifx;
+    in.ify = ify;
+    spline_basis_inv(kn, span, binv, e.t, in.b);
+}
+}  // namespace ecal
+#endif

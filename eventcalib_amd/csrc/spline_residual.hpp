@@ -118,19 +118,34 @@ struct ResidualInput {
     double ifx, ify;      // 1 / fx, 1 / fy (the kernel hoists them out of its residual loop); 0 = compute here
 };
 
-// Shared tail of both rotation parameterisations: residual for the unit quaternion (ux,uy,uz,w) and translation T;
-// when J != nullptr fills J[0..8] (intrinsics), gq = d res / d (unit quaternion, ambient xyzw) and gT = d res / d T.
-template <bool FISHEYE = false>
-ECAL_HD double residual_core(const ResidualInput &in, const double *intr, double ux, double uy, double uz, double w,
-                             const double T[3], double *J, double gq[4], double gT[3]) {
+// ---- the pieces every consumer of the residual shares ----------------------------------------------------------------------------
+// One copy of each: the ray (pixel -> inverse camera model -> rotation by the pose -> depth of the hit on the plane z = 0), the way
+// back from d res / d Y to d res / d p, d c / d r2, and the two pose functions.  residual_core (the solver), residual_core_px (the
+// report in pixels) and spline_board_point (the board image, the re-association) are built on them.  Everything is force-inlined
+// on the device, and WHERE the pieces are cut is not free there: every unit with kernels contracts this header to FMA (the solver
+// by its flag, the other four by pragma), and which product of a sum goes into the FMA depends on what the compiler sees in one
+// function.  Before moving a cut, read how the kernels were shown not to move and which cuts changed a rounding:
+// design/08_solver.md, "One copy of the residual's pieces".  tests/cpp/residual_frozen.cpp pins the host values.
+
+// the ray's intermediates: everything the backward sweeps read again
+struct ResidualRay {
+    double ifx, ify, x, y, r2, r4, r6, r8, r10, poly, c, sec2;   // sec2 = d c / d poly
+    double px, py, cxp0, cxp1, cxp2, udp, udu, Y0, Y1, Y2, iY2, s;   // p = (px, py, 1); u x p; u.p; u.u; Y = R(q) p; 1 / Y_z; depth
+};
+
+// (ux, uy, uz, w) the unit quaternion, T the translation; ifx_in / ify_in = 1 / fx, 1 / fy (0: computed here)
+template <bool FISHEYE>
+ECAL_HD void residual_ray(double u, double v, const double *intr, double ifx_in, double ify_in, double ux, double uy, double uz, double w,
+                          const double T[3], ResidualRay &R) {
     const double cx = intr[2], cy = intr[3];
     // divisions are reciprocal + multiply: one rcp each for fx, fy (hoisted by the kernel), Y_z, |Xw - lm|
-    const double ifx = in.ifx != 0.0 ? in.ifx : 1.0 / intr[0], ify = in.ify != 0.0 ? in.ify : 1.0 / intr[1];
+    R.ifx = ifx_in != 0.0 ? ifx_in : 1.0 / intr[0];
+    R.ify = ify_in != 0.0 ? ify_in : 1.0 / intr[1];
     // undistorted ray
-    const double x = (in.u - cx) * ifx, y = (in.v - cy) * ify;
+    const double x = (u - cx) * R.ifx, y = (v - cy) * R.ify;
     const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2, r8 = r6 * r2, r10 = r8 * r2;
     const double poly = 1.0 + intr[4] * r2 + intr[5] * r4 + intr[6] * r6 + intr[7] * r8 + intr[8] * r10;
-    double c = poly, sec2 = 1.0;   // sec2 = d c / d poly
+    double c = poly, sec2 = 1.0;
     if (FISHEYE) {
         if (r2 > 1e-16) {
             const double r = sqrt(r2), tn = tan(r * poly);
@@ -146,13 +161,68 @@ ECAL_HD double residual_core(const ResidualInput &in, const double *intr, double
     const double Y1 = py + 2 * w * cxp1 + 2 * (uy * udp - py * udu);
     const double Y2 = pz + 2 * w * cxp2 + 2 * (uz * udp - pz * udu);
     const double iY2 = 1.0 / Y2;
-    const double s = -T[2] * iY2;  // depth
-    const double Xw0 = T[0] + s * Y0, Xw1 = T[1] + s * Y1, Xw2 = T[2] + s * Y2;
+    R.x = x, R.y = y, R.r2 = r2, R.r4 = r4, R.r6 = r6, R.r8 = r8, R.r10 = r10, R.poly = poly, R.c = c, R.sec2 = sec2;
+    R.px = px, R.py = py, R.cxp0 = cxp0, R.cxp1 = cxp1, R.cxp2 = cxp2, R.udp = udp, R.udu = udu;
+    R.Y0 = Y0, R.Y1 = Y1, R.Y2 = Y2, R.iY2 = iY2;
+    R.s = -T[2] * iY2;  // depth
+}
+
+// res = |Xw - lm| - radius with Xw = T + s Y; d = Xw - lm and 1 / |d| go to the backward sweep
+ECAL_HD double residual_distance(const ResidualInput &in, const ResidualRay &R, const double T[3], double d[3], double *idist_out) {
+    const double Xw0 = T[0] + R.s * R.Y0, Xw1 = T[1] + R.s * R.Y1, Xw2 = T[2] + R.s * R.Y2;
     const double d0 = Xw0 - in.lmx, d1 = Xw1 - in.lmy, d2 = Xw2 - in.lmz;
     const double dd = d0 * d0 + d1 * d1 + d2 * d2;
     const double idist = res_rsqrt(dd);
     const double dist = dd * idist;
-    const double res = dist - in.radius;
+    d[0] = d0, d[1] = d1, d[2] = d2, *idist_out = idist;
+    return dist - in.radius;
+}
+
+// d Y / d p = R(q) = I + 2 w [u]x + 2 (u u^T - (u.u) I);   g_p = R^T g_Y = g_Y - 2 w (u x g_Y) + 2 (u (u.g_Y) - g_Y (u.u))
+ECAL_HD void residual_ray_back(const ResidualRay &R, double ux, double uy, double uz, double w, double gY0, double gY1, double gY2,
+                               double *udg_out, double *gp0, double *gp1) {
+    const double udg = ux * gY0 + uy * gY1 + uz * gY2;
+    const double cxg0 = uy * gY2 - uz * gY1, cxg1 = uz * gY0 - ux * gY2;
+    *gp0 = gY0 - 2 * w * cxg0 + 2 * (ux * udg - gY0 * R.udu);
+    *gp1 = gY1 - 2 * w * cxg1 + 2 * (uy * udg - gY1 * R.udu);
+    *udg_out = udg;
+}
+
+// d c / d r2.  (Returned by value, and the two lines that form gx, gy from it stay in the callers: see the note above.)
+template <bool FISHEYE>
+ECAL_HD double residual_dc_dr2(const double *intr, const ResidualRay &R) {
+    double cp = intr[4] + 2 * intr[5] * R.r2 + 3 * intr[6] * R.r4 + 4 * intr[7] * R.r6 + 5 * intr[8] * R.r8;  // d poly / d r2
+    if (FISHEYE) {
+        // c = tan(r poly) / r:  dc/dr2 = (sec^2 (poly / 2 + r2 poly') - c / 2) / r2  ->  poly' + poly^3 / 3 at r = 0
+        cp = R.r2 > 1e-8 ? (R.sec2 * (0.5 * R.poly + R.r2 * cp) - 0.5 * R.c) / R.r2 : cp + R.poly * R.poly * R.poly * (1.0 / 3.0);
+    }
+    return cp;
+}
+
+// the pose of the quaternion spline at basis values b: Q = v / |v| with v = sum_j b_j q_j, T = sum_j b_j t_j.  Returns 1 / |v|
+// (the Jacobian of the normalisation needs it).
+ECAL_HD double spline_pose_quat(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
+    double vq[4] = {0, 0, 0, 0};
+    T[0] = T[1] = T[2] = 0;
+    for (int j = 0; j < 4; j++) {
+        for (int k = 0; k < 4; k++) vq[k] += b[j] * q[j][k];
+        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
+    }
+    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
+    for (int k = 0; k < 4; k++) Q[k] = vq[k] * ivn;
+    return ivn;
+}
+
+// Shared tail of both rotation parameterisations: residual for the unit quaternion (ux,uy,uz,w) and translation T;
+// when J != nullptr fills J[0..8] (intrinsics), gq = d res / d (unit quaternion, ambient xyzw) and gT = d res / d T.
+template <bool FISHEYE = false>
+ECAL_HD double residual_core(const ResidualInput &in, const double *intr, double ux, double uy, double uz, double w,
+                             const double T[3], double *J, double gq[4], double gT[3]) {
+    ResidualRay R;
+    residual_ray<FISHEYE>(in.u, in.v, intr, in.ifx, in.ify, ux, uy, uz, w, T, R);
+    const double x = R.x, y = R.y, c = R.c, px = R.px, py = R.py, pz = 1.0, Y0 = R.Y0, Y1 = R.Y1, Y2 = R.Y2, iY2 = R.iY2, s = R.s;
+    double d[3], idist;
+    const double res = residual_distance(in, R, T, d, &idist);
     if (!J) return res;
 
     double esc = idist;
@@ -161,7 +231,7 @@ ECAL_HD double residual_core(const ResidualInput &in, const double *intr, double
         *in.sc_out = sc;
         esc = idist * sc;
     }
-    const double e0 = d0 * esc, e1 = d1 * esc, e2 = d2 * esc;  // d res / d Xw (times sqrt(rho') under the robust loss)
+    const double e0 = d[0] * esc, e1 = d[1] * esc, e2 = d[2] * esc;  // d res / d Xw (times sqrt(rho') under the robust loss)
     const double eY = e0 * Y0 + e1 * Y1 + e2 * Y2;
     // Xw = T - T_z Y / Y_z
     gT[0] = e0;
@@ -169,36 +239,29 @@ ECAL_HD double residual_core(const ResidualInput &in, const double *intr, double
     gT[2] = e2 - eY * iY2;
     const double k = s;
     const double gY0 = k * e0, gY1 = k * e1, gY2 = k * e2 - k * eY * iY2;
-    // d Y / d p = R(q) = I + 2 w [u]x + 2 (u u^T - (u.u) I);   g_p = R^T g_Y = g_Y - 2 w (u x g_Y) + 2 (u (u.g_Y) - g_Y (u.u))
-    const double udg = ux * gY0 + uy * gY1 + uz * gY2;
-    const double cxg0 = uy * gY2 - uz * gY1, cxg1 = uz * gY0 - ux * gY2;
-    const double gp0 = gY0 - 2 * w * cxg0 + 2 * (ux * udg - gY0 * udu);
-    const double gp1 = gY1 - 2 * w * cxg1 + 2 * (uy * udg - gY1 * udu);
+    double udg, gp0, gp1;
+    residual_ray_back(R, ux, uy, uz, w, gY0, gY1, gY2, &udg, &gp0, &gp1);
     // intrinsics
-    double cp = intr[4] + 2 * intr[5] * r2 + 3 * intr[6] * r4 + 4 * intr[7] * r6 + 5 * intr[8] * r8;  // d poly / d r2
-    if (FISHEYE) {
-        // c = tan(r poly) / r:  dc/dr2 = (sec^2 (poly / 2 + r2 poly') - c / 2) / r2  ->  poly' + poly^3 / 3 at r = 0
-        cp = r2 > 1e-8 ? (sec2 * (0.5 * poly + r2 * cp) - 0.5 * c) / r2 : cp + poly * poly * poly * (1.0 / 3.0);
-    }
+    const double cp = residual_dc_dr2<FISHEYE>(intr, R);
     const double gx = gp0 * (c + 2 * x * x * cp) + gp1 * (2 * x * y * cp);
     const double gy = gp0 * (2 * x * y * cp) + gp1 * (c + 2 * y * y * cp);
-    J[0] = -gx * x * ifx;
-    J[1] = -gy * y * ify;
-    J[2] = -gx * ifx;
-    J[3] = -gy * ify;
-    const double gk = (gp0 * x + gp1 * y) * sec2;   // d c / d k_i = sec^2 r2^i (pinhole: sec2 = 1)
-    J[4] = gk * r2;
-    J[5] = gk * r4;
-    J[6] = gk * r6;
-    J[7] = gk * r8;
-    J[8] = gk * r10;
+    J[0] = -gx * x * R.ifx;
+    J[1] = -gy * y * R.ify;
+    J[2] = -gx * R.ifx;
+    J[3] = -gy * R.ify;
+    const double gk = (gp0 * x + gp1 * y) * R.sec2;   // d c / d k_i = sec^2 r2^i (pinhole: sec2 = 1)
+    J[4] = gk * R.r2;
+    J[5] = gk * R.r4;
+    J[6] = gk * R.r6;
+    J[7] = gk * R.r8;
+    J[8] = gk * R.r10;
     // unit quaternion: g_w = 2 (u x p).g_Y ;  g_u = 2 w (p x g_Y) + 2 ((u.p) g_Y + p (u.g_Y) - 2 u (p.g_Y))
     const double pdg = px * gY0 + py * gY1 + pz * gY2;
     const double pxg0 = py * gY2 - pz * gY1, pxg1 = pz * gY0 - px * gY2, pxg2 = px * gY1 - py * gY0;
-    gq[0] = 2 * w * pxg0 + 2 * (udp * gY0 + px * udg - 2 * ux * pdg);
-    gq[1] = 2 * w * pxg1 + 2 * (udp * gY1 + py * udg - 2 * uy * pdg);
-    gq[2] = 2 * w * pxg2 + 2 * (udp * gY2 + pz * udg - 2 * uz * pdg);
-    gq[3] = 2 * (cxp0 * gY0 + cxp1 * gY1 + cxp2 * gY2);
+    gq[0] = 2 * w * pxg0 + 2 * (R.udp * gY0 + px * udg - 2 * ux * pdg);
+    gq[1] = 2 * w * pxg1 + 2 * (R.udp * gY1 + py * udg - 2 * uy * pdg);
+    gq[2] = 2 * w * pxg2 + 2 * (R.udp * gY2 + pz * udg - 2 * uz * pdg);
+    gq[3] = 2 * (R.cxp0 * gY0 + R.cxp1 * gY1 + R.cxp2 * gY2);
     return res;
 }
 
@@ -208,13 +271,9 @@ template <bool FISHEYE = false>
 ECAL_HD double spline_residual(const ResidualInput &in, const double *intr, const double (*q)[4], const double (*t)[3],
                                double *J) {
     // pose at the event time
-    double vq[4] = {0, 0, 0, 0}, T[3] = {0, 0, 0};
-    for (int j = 0; j < 4; j++) {
-        for (int k = 0; k < 4; k++) vq[k] += in.b[j] * q[j][k];
-        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
-    }
-    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
-    const double ux = vq[0] * ivn, uy = vq[1] * ivn, uz = vq[2] * ivn, w = vq[3] * ivn;
+    double Q[4], T[3];
+    const double ivn = spline_pose_quat(in.b, q, t, Q, T);
+    const double ux = Q[0], uy = Q[1], uz = Q[2], w = Q[3];
     double gq[4], gT[3];
     const double res = residual_core<FISHEYE>(in, intr, ux, uy, uz, w, T, J, gq, gT);
     if (!J) return res;
@@ -347,16 +406,16 @@ ECAL_HD void so3_exp(const double phi[3], double q[4]) {
     q[3] = re;
 }
 
-// q[4][4]: SO3 control points as unit quaternions (x y z w); in.b = the four N values (the cumulative basis is
-// formed here).  J layout as spline_residual, rotation columns = delta of r_cp_j <- r_cp_j * exp(delta).
-template <bool FISHEYE = false>
-ECAL_HD double spline_residual_so3(const ResidualInput &in, const double *intr, const double (*q)[4],
-                                   const double (*t)[3], double *J) {
-    double beta[3];
-    beta[2] = in.b[3];
-    beta[1] = beta[2] + in.b[2];
-    beta[0] = beta[1] + in.b[1];
-    double d[3][3], bd[3][3], Q[4] = {q[0][0], q[0][1], q[0][2], q[0][3]}, T[3] = {0, 0, 0};
+// the pose of the cumulative SO3 spline at basis values b (the four N values; the cumulative basis beta is formed here):
+// Q = q_0 (x) Exp(beta_1 d_1) (x) Exp(beta_2 d_2) (x) Exp(beta_3 d_3), T = sum_j b_j t_j.  beta, d and bd[j] = beta_j d_j are
+// handed out for spline_residual_so3's backward sweep.
+ECAL_HD void spline_product_so3(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3], double beta[3],
+                                double d[3][3], double bd[3][3]) {
+    beta[2] = b[3];
+    beta[1] = beta[2] + b[2];
+    beta[0] = beta[1] + b[1];
+    for (int k = 0; k < 4; k++) Q[k] = q[0][k];
+    T[0] = T[1] = T[2] = 0;
     for (int j = 1; j <= 3; j++) {
         const double inv[4] = {-q[j - 1][0], -q[j - 1][1], -q[j - 1][2], q[j - 1][3]};
         double rel[4], e[4], nq[4];
@@ -368,7 +427,20 @@ ECAL_HD double spline_residual_so3(const ResidualInput &in, const double *intr, 
         for (int k = 0; k < 4; k++) Q[k] = nq[k];
     }
     for (int j = 0; j < 4; j++)
-        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
+        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
+}
+ECAL_HD void spline_pose_so3(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
+    double beta[3], d[3][3], bd[3][3];
+    spline_product_so3(b, q, t, Q, T, beta, d, bd);
+}
+
+// q[4][4]: SO3 control points as unit quaternions (x y z w); in.b = the four N values.
+// J layout as spline_residual, rotation columns = delta of r_cp_j <- r_cp_j * exp(delta).
+template <bool FISHEYE = false>
+ECAL_HD double spline_residual_so3(const ResidualInput &in, const double *intr, const double (*q)[4],
+                                   const double (*t)[3], double *J) {
+    double beta[3], d[3][3], bd[3][3], Q[4], T[3];
+    spline_product_so3(in.b, q, t, Q, T, beta, d, bd);
     double gq[4], gT[3];
     const double res = residual_core<FISHEYE>(in, intr, Q[0], Q[1], Q[2], Q[3], T, J, gq, gT);
     if (!J) return res;
@@ -434,167 +506,60 @@ ECAL_HD void quaternion_plus(const double q[4], const double d[3], double out[4]
     out[3] = dq[3] * q[3] - dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2];
 }
 
-// ---- the board point of a pixel (the board-frame event image, ecal_board_image.hip) ------------------------------------------
-// The first half of the residual on its own: pixel -> inverse camera model -> rotation by the pose -> intersection with the
-// plane z = 0.  The three functions below DUPLICATE lines of residual_core, spline_residual and spline_residual_so3 on purpose,
-// the same operations in the same order: the residual functions are not rewritten on top of them, because the code generation
-// of normal_eq_kernel (227 VGPRs) must not move.  tests/cpp/check_board_point.cpp holds the copies to the originals bit for bit.
-
-// residual_core up to Xw.  ifx / ify = 1 / fx, 1 / fy (0: computed here).  false: the ray does not meet the plane in front of
-// the camera — the depth s = -T_z / Y_z is not finite or not positive; Xw is then not meaningful.
+// ---- the board point of a pixel (the board-frame event image, ecal_board_image.hip; ecal_reassociate.hip) ---------------------
+// The first half of the residual on its own: residual_ray, then Xw = T + s Y.  ifx / ify = 1 / fx, 1 / fy (0: computed here).
+// false: the ray does not meet the plane in front of the camera — the depth s = -T_z / Y_z is not finite or not positive; Xw is
+// then not meaningful.  With the pose from spline_pose_quat / spline_pose_so3.
 template <bool FISHEYE = false>
 ECAL_HD bool spline_board_point(double u, double v, const double *intr, double ifx_in, double ify_in, double ux, double uy, double uz,
                                 double w, const double T[3], double Xw[2]) {
-    const double cx = intr[2], cy = intr[3];
-    const double ifx = ifx_in != 0.0 ? ifx_in : 1.0 / intr[0], ify = ify_in != 0.0 ? ify_in : 1.0 / intr[1];
-    const double x = (u - cx) * ifx, y = (v - cy) * ify;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2, r8 = r6 * r2, r10 = r8 * r2;
-    const double poly = 1.0 + intr[4] * r2 + intr[5] * r4 + intr[6] * r6 + intr[7] * r8 + intr[8] * r10;
-    double c = poly;
-    if (FISHEYE) {
-        if (r2 > 1e-16) {
-            const double r = sqrt(r2), tn = tan(r * poly);
-            c = tn / r;
-        }
-    }
-    const double px = x * c, py = y * c, pz = 1.0;
-    const double cxp0 = uy * pz - uz * py, cxp1 = uz * px - ux * pz, cxp2 = ux * py - uy * px;
-    const double udp = ux * px + uy * py + uz * pz, udu = ux * ux + uy * uy + uz * uz;
-    const double Y0 = px + 2 * w * cxp0 + 2 * (ux * udp - px * udu);
-    const double Y1 = py + 2 * w * cxp1 + 2 * (uy * udp - py * udu);
-    const double Y2 = pz + 2 * w * cxp2 + 2 * (uz * udp - pz * udu);
-    const double iY2 = 1.0 / Y2;
-    const double s = -T[2] * iY2;
-    Xw[0] = T[0] + s * Y0;
-    Xw[1] = T[1] + s * Y1;
-    return s > 0.0 && s <= 1.79769313486231570e308;   // (NaN fails both)
-}
-
-// the pose of the quaternion spline at basis values b: spline_residual's blend and normalisation
-ECAL_HD void spline_pose_quat(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
-    double vq[4] = {0, 0, 0, 0};
-    T[0] = T[1] = T[2] = 0;
-    for (int j = 0; j < 4; j++) {
-        for (int k = 0; k < 4; k++) vq[k] += b[j] * q[j][k];
-        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
-    }
-    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
-    for (int k = 0; k < 4; k++) Q[k] = vq[k] * ivn;
-}
-
-// the pose of the cumulative SO3 spline: spline_residual_so3's product of the three factors
-ECAL_HD void spline_pose_so3(const double b[4], const double (*q)[4], const double (*t)[3], double Q[4], double T[3]) {
-    double beta[3];
-    beta[2] = b[3];
-    beta[1] = beta[2] + b[2];
-    beta[0] = beta[1] + b[1];
-    for (int k = 0; k < 4; k++) Q[k] = q[0][k];
-    T[0] = T[1] = T[2] = 0;
-    for (int j = 1; j <= 3; j++) {
-        const double inv[4] = {-q[j - 1][0], -q[j - 1][1], -q[j - 1][2], q[j - 1][3]};
-        double rel[4], d[3], bd[3], e[4], nq[4];
-        quat_mul(inv, q[j], rel);
-        so3_log(rel, d);
-        for (int k = 0; k < 3; k++) bd[k] = beta[j - 1] * d[k];
-        so3_exp(bd, e);
-        quat_mul(Q, e, nq);
-        for (int k = 0; k < 4; k++) Q[k] = nq[k];
-    }
-    for (int j = 0; j < 4; j++)
-        for (int k = 0; k < 3; k++) T[k] += b[j] * t[j][k];
+    ResidualRay R;
+    residual_ray<FISHEYE>(u, v, intr, ifx_in, ify_in, ux, uy, uz, w, T, R);
+    Xw[0] = T[0] + R.s * R.Y0;
+    Xw[1] = T[1] + R.s * R.Y1;
+    return R.s > 0.0 && R.s <= 1.79769313486231570e308;   // (NaN fails both)
 }
 
 // ---- the residual and its gradient by the event's own pixel (the report in pixels, ecal_report_px.hip) ------------------------
 // r and g = (d r / d u, d r / d v): the lean pair behind the first-order (Sampson) distance r / |g| from the event to the projected
 // rim, in pixels (include/ecal.h, "report in pixels").  d r / d (u, v) is minus d r / d (cx, cy), columns 2 and 3 of the Jacobian
-// row: g = (gx * ifx, gy * ify) = (-J[2], -J[3]), with no robust loss.  The three functions below DUPLICATE the lines of
-// residual_core, spline_residual and spline_residual_so3 that lead to gx, gy, the same operations in the same order, for the reason
-// the board-point functions above do: the residual functions are not rewritten on top of them.  tests/cpp/check_residual_px.cpp
-// holds r and g to the originals bit for bit.
+// row: g = (gx * ifx, gy * ify) = (-J[2], -J[3]), with no robust loss: residual_core without what belongs to the row alone.
 template <bool FISHEYE = false>
 ECAL_HD double residual_core_px(const ResidualInput &in, const double *intr, double ux, double uy, double uz, double w,
                                 const double T[3], double g[2]) {
-    const double cx = intr[2], cy = intr[3];
-    const double ifx = in.ifx != 0.0 ? in.ifx : 1.0 / intr[0], ify = in.ify != 0.0 ? in.ify : 1.0 / intr[1];
-    const double x = (in.u - cx) * ifx, y = (in.v - cy) * ify;
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2, r8 = r6 * r2, r10 = r8 * r2;
-    const double poly = 1.0 + intr[4] * r2 + intr[5] * r4 + intr[6] * r6 + intr[7] * r8 + intr[8] * r10;
-    double c = poly, sec2 = 1.0;
-    if (FISHEYE) {
-        if (r2 > 1e-16) {
-            const double r = sqrt(r2), tn = tan(r * poly);
-            sec2 = 1.0 + tn * tn;
-            c = tn / r;
-        }
-    }
-    const double px = x * c, py = y * c, pz = 1.0;
-    const double cxp0 = uy * pz - uz * py, cxp1 = uz * px - ux * pz, cxp2 = ux * py - uy * px;
-    const double udp = ux * px + uy * py + uz * pz, udu = ux * ux + uy * uy + uz * uz;
-    const double Y0 = px + 2 * w * cxp0 + 2 * (ux * udp - px * udu);
-    const double Y1 = py + 2 * w * cxp1 + 2 * (uy * udp - py * udu);
-    const double Y2 = pz + 2 * w * cxp2 + 2 * (uz * udp - pz * udu);
-    const double iY2 = 1.0 / Y2;
-    const double s = -T[2] * iY2;
-    const double Xw0 = T[0] + s * Y0, Xw1 = T[1] + s * Y1, Xw2 = T[2] + s * Y2;
-    const double d0 = Xw0 - in.lmx, d1 = Xw1 - in.lmy, d2 = Xw2 - in.lmz;
-    const double dd = d0 * d0 + d1 * d1 + d2 * d2;
-    const double idist = res_rsqrt(dd);
-    const double dist = dd * idist;
-    const double res = dist - in.radius;
+    ResidualRay R;
+    residual_ray<FISHEYE>(in.u, in.v, intr, in.ifx, in.ify, ux, uy, uz, w, T, R);
+    const double x = R.x, y = R.y, c = R.c, Y0 = R.Y0, Y1 = R.Y1, Y2 = R.Y2, iY2 = R.iY2, s = R.s;
+    double d[3], idist;
+    const double res = residual_distance(in, R, T, d, &idist);
 
-    const double esc = idist;
-    const double e0 = d0 * esc, e1 = d1 * esc, e2 = d2 * esc;
+    const double e0 = d[0] * idist, e1 = d[1] * idist, e2 = d[2] * idist;
     const double eY = e0 * Y0 + e1 * Y1 + e2 * Y2;
     const double k = s;
     const double gY0 = k * e0, gY1 = k * e1, gY2 = k * e2 - k * eY * iY2;
-    const double udg = ux * gY0 + uy * gY1 + uz * gY2;
-    const double cxg0 = uy * gY2 - uz * gY1, cxg1 = uz * gY0 - ux * gY2;
-    const double gp0 = gY0 - 2 * w * cxg0 + 2 * (ux * udg - gY0 * udu);
-    const double gp1 = gY1 - 2 * w * cxg1 + 2 * (uy * udg - gY1 * udu);
-    double cp = intr[4] + 2 * intr[5] * r2 + 3 * intr[6] * r4 + 4 * intr[7] * r6 + 5 * intr[8] * r8;
-    if (FISHEYE) {
-        cp = r2 > 1e-8 ? (sec2 * (0.5 * poly + r2 * cp) - 0.5 * c) / r2 : cp + poly * poly * poly * (1.0 / 3.0);
-    }
+    double udg, gp0, gp1;
+    residual_ray_back(R, ux, uy, uz, w, gY0, gY1, gY2, &udg, &gp0, &gp1);
+    const double cp = residual_dc_dr2<FISHEYE>(intr, R);
     const double gx = gp0 * (c + 2 * x * x * cp) + gp1 * (2 * x * y * cp);
     const double gy = gp0 * (2 * x * y * cp) + gp1 * (c + 2 * y * y * cp);
-    g[0] = gx * ifx;
-    g[1] = gy * ify;
+    g[0] = gx * R.ifx;
+    g[1] = gy * R.ify;
     return res;
 }
 
 template <bool FISHEYE = false>
 ECAL_HD double spline_residual_px(const ResidualInput &in, const double *intr, const double (*q)[4], const double (*t)[3],
                                   double g[2]) {
-    double vq[4] = {0, 0, 0, 0}, T[3] = {0, 0, 0};
-    for (int j = 0; j < 4; j++) {
-        for (int k = 0; k < 4; k++) vq[k] += in.b[j] * q[j][k];
-        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
-    }
-    const double ivn = res_rsqrt(vq[0] * vq[0] + vq[1] * vq[1] + vq[2] * vq[2] + vq[3] * vq[3]);
-    const double ux = vq[0] * ivn, uy = vq[1] * ivn, uz = vq[2] * ivn, w = vq[3] * ivn;
-    return residual_core_px<FISHEYE>(in, intr, ux, uy, uz, w, T, g);
+    double Q[4], T[3];
+    spline_pose_quat(in.b, q, t, Q, T);
+    return residual_core_px<FISHEYE>(in, intr, Q[0], Q[1], Q[2], Q[3], T, g);
 }
 
 template <bool FISHEYE = false>
 ECAL_HD double spline_residual_px_so3(const ResidualInput &in, const double *intr, const double (*q)[4],
                                       const double (*t)[3], double g[2]) {
-    double beta[3];
-    beta[2] = in.b[3];
-    beta[1] = beta[2] + in.b[2];
-    beta[0] = beta[1] + in.b[1];
-    double d[3][3], bd[3][3], Q[4] = {q[0][0], q[0][1], q[0][2], q[0][3]}, T[3] = {0, 0, 0};
-    for (int j = 1; j <= 3; j++) {
-        const double inv[4] = {-q[j - 1][0], -q[j - 1][1], -q[j - 1][2], q[j - 1][3]};
-        double rel[4], e[4], nq[4];
-        quat_mul(inv, q[j], rel);
-        so3_log(rel, d[j - 1]);
-        for (int k = 0; k < 3; k++) bd[j - 1][k] = beta[j - 1] * d[j - 1][k];
-        so3_exp(bd[j - 1], e);
-        quat_mul(Q, e, nq);
-        for (int k = 0; k < 4; k++) Q[k] = nq[k];
-    }
-    for (int j = 0; j < 4; j++)
-        for (int k = 0; k < 3; k++) T[k] += in.b[j] * t[j][k];
+    double Q[4], T[3];
+    spline_pose_so3(in.b, q, t, Q, T);
     return residual_core_px<FISHEYE>(in, intr, Q[0], Q[1], Q[2], Q[3], T, g);
 }
 

@@ -1,7 +1,7 @@
 // Undistortion of a pixel with the solved camera — one restatement of include/ecal.h, "undistortion", for the kernels
 // (ecal_undistort.hip), the host entry point (ecal_undistort_points_host) and the CPU test (tests/cpp/check_undistort.cpp).
 //
-// The solver's intrinsics are the INVERSE model: pixel -> ideal ray is a closed-form polynomial (spline_residual.hpp:131-132), so a
+// The solver's intrinsics are the INVERSE model: pixel -> ideal ray is a closed-form polynomial (spline_residual.hpp, residual_ray), so a
 // point is ~25 f64 operations and nothing is iterated.  Every operation below is one IEEE f64 operation rounded on its own: the
 // translation units that include this header are built with -ffp-contract=off, a division is a division, and the rounding to a canvas
 // pixel is spelled out (ud_round_half_away) instead of left to a library.  Only tan (FISHEYE) is not correctly rounded.

@@ -1,8 +1,10 @@
 // CPU check (g++): spline_board_point / spline_pose_quat / spline_pose_so3 (eventcalib_amd/csrc/spline_residual.hpp) — the
-// duplicated first half of the residual that the board-frame event image uses — against the residual functions themselves.
-// Both are host builds of one header with one set of flags, so |Xw - lm| - radius must equal spline_residual*'s value BIT FOR
-// BIT, and the function's verdict must be "the depth is finite and positive" exactly.  Test harness only; stand-alone (its own
-// main), so it can also be built with -fsanitize=address,undefined and run as it is.
+// first half of the residual, which the board-frame event image uses on its own — against the residual functions.  They share
+// residual_ray and the pose functions, so this is no longer a copy held to its original: what is checked is that the tail of
+// the residual, reconstructed HERE from the board point (|Xw - lm| - radius on two coordinates), equals spline_residual*'s value
+// BIT FOR BIT (one header, one set of flags), and that the verdict is "the depth is finite and positive" exactly, against a
+// depth computed by another route in long double.  That the shared arithmetic is what it was: residual_frozen.cpp.  Test harness
+// only; stand-alone (its own main), so it can also be built with -fsanitize=address,undefined and run as it is.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>

@@ -1,9 +1,11 @@
 // CPU check (g++): spline_residual_px / spline_residual_px_so3 / residual_px_distance (eventcalib_amd/csrc/spline_residual.hpp) —
 // the residual with its gradient by the event's own pixel, the lean pair behind the report in pixels — against the residual
-// functions themselves.  Both are host builds of one header with one set of flags (-ffp-contract=off), so r must equal
-// spline_residual*'s value and (gu, gv) the negated columns 2 and 3 of the same call's Jacobian row BIT FOR BIT, and the degenerate
-// verdict must be "r or g2 is not finite, or g2 > 0 is false" exactly.  Test harness only; stand-alone (its own main), so it can
-// also be built with -fsanitize=address,undefined and run as it is.
+// functions themselves.  Both are built on the same helpers of one header (residual_ray, residual_distance, residual_ray_back,
+// residual_dc_dr2, the pose functions) with one set of flags (-ffp-contract=off); what each adds — the robust loss and the row in
+// residual_core, the two lines that form gx, gy in both — must leave r equal to spline_residual*'s value and (gu, gv) to the
+// negated columns 2 and 3 of the same call's Jacobian row BIT FOR BIT, and the degenerate verdict must be "r or g2 is not finite,
+// or g2 > 0 is false" exactly.  That the shared arithmetic is what it was: residual_frozen.cpp.  Test harness only; stand-alone
+// (its own main), so it can also be built with -fsanitize=address,undefined and run as it is.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>

@@ -1,8 +1,11 @@
 """CPU: the board-point functions of eventcalib_amd/csrc/spline_residual.hpp (spline_board_point, spline_pose_quat,
-spline_pose_so3: the duplicated first half of the residual behind the board-frame event image) compiled for the host —
-tests/cpp/check_board_point.cpp: 10 000 random cases over pinhole / fisheye and quaternion / SO3 bit-equal to spline_residual*,
-the `false` verdicts exactly the non-finite and non-positive depths — once plainly and once under AddressSanitizer +
-UndefinedBehaviorSanitizer (a stand-alone program with its own main: nothing is preloaded)."""
+spline_pose_so3: the first half of the residual behind the board-frame event image; the residual functions are built on the same
+residual_ray and pose code) compiled for the host — tests/cpp/check_board_point.cpp: 10 000 random cases over pinhole / fisheye
+and quaternion / SO3, the residual's tail reconstructed from the board point bit-equal to spline_residual*, the `false` verdicts
+exactly the non-finite and non-positive depths (against a depth computed by another route) — once plainly and once under
+AddressSanitizer + UndefinedBehaviorSanitizer (a stand-alone program with its own main: nothing is preloaded).  The device code
+of every kernel that uses these functions was compared with the code from before they shared (design/08_solver.md, "One copy of
+the residual's pieces"); that the values are the earlier ones is test_residual_frozen_host.py's part."""
 import os
 import subprocess
 

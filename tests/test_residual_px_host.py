@@ -3,7 +3,11 @@ residual_px_distance: the residual with its gradient by the event's own pixel, b
 host — tests/cpp/check_residual_px.cpp: 10 000 random cases over radial / fisheye and quaternion / SO3, r bit-equal to
 spline_residual*, (gu, gv) bit-equal to (-J[2], -J[3]) of the same call with a Jacobian row, the degenerate verdicts exactly the
 non-finite and non-positive cases (a board point exactly on its landmark among them) — once plainly and once under
-AddressSanitizer + UndefinedBehaviorSanitizer (a stand-alone program with its own main: nothing is preloaded)."""
+AddressSanitizer + UndefinedBehaviorSanitizer (a stand-alone program with its own main: nothing is preloaded).  Both sides are
+built on the same helpers of the header (ray, distance, way back, d c / d r2, pose), so the check is of what each side adds to
+them; the device code was compared with the code from before they shared (design/08_solver.md, "One copy of the residual's
+pieces": moving gx, gy into a helper changes a rounding in the solver), and that the values are the earlier ones is
+test_residual_frozen_host.py's part."""
 import os
 import subprocess
 
