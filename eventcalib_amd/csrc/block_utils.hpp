@@ -5,6 +5,39 @@
 
 namespace ecal {
 
+// the sum of v over the workgroup, for every thread (s_red: T / 64 words, a set of its own per call; one barrier)
+template <int T>
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *s_red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint32_t t = 0;
+    for (int w = 0; w < T / 64; w++) t += s_red[w];
+    return t;
+}
+
+// the exclusive prefix of `mine` over the workgroup in thread order; *total (may be null): the workgroup's sum.  s_wsum: T / 64
+// words, not to be written again before the caller's next barrier (one barrier here, behind the waves' sums)
+template <int T>
+__device__ __forceinline__ uint32_t block_exscan_u32(uint32_t mine, uint32_t *s_wsum, uint32_t *total = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_wsum[wave] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+    for (int x = 0; x < T / 64; x++) {
+        if (x < wave) pre += s_wsum[x];
+        tot += s_wsum[x];
+    }
+    if (total) *total = tot;
+    return pre + inc - mine;
+}
+
 // two independent exclusive scans of one value per thread (packed into 64 bits), totals included.
 // red: >= T/64 unsigned long long of LDS.
 template <int T>

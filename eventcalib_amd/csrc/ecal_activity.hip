@@ -8,10 +8,9 @@
 //                              map does not depend on the order of arrival.
 //   activity_verdict_kernel    one keep / remove byte per event from the u8 mask, the kept events per block, the totals
 //   ecal_scan_blocks           the blocks' first kept index (the association's)
-//   activity_write_kernel      reads the verdicts (16 bytes per thread), ranks the kept events inside the block in event order, packs
-//                              their own 25 bytes into LDS a quarter of the block at a time and copies them out with aligned 16-byte
-//                              stores
-// The scan and the writing pass are ecal_compact_by_verdict (ecal_ctx.hpp): the noise filter (ecal_noise.hip) ends in them too.
+//   activity_write_kernel      compact_write_block (stream_compact.hpp) with the kept events' own 25 bytes
+// The scan and the writing pass are ecal_compact_copy_by_verdict (ecal_ctx.hpp): the noise filter (ecal_noise.hip) ends in them too.
+// This file also holds the host steps every compacting stage shares (ecal_ctx.hpp, "what the compacting stages share").
 // Bytes per event: 25 read + 4 atomic in the activity pass; 17 read (x, y, the mask byte) + 1 written in the verdict pass; 1 read in
 // the writing pass, and per KEPT event 25 read + 25 written.
 // Nothing behind n_events * 25 bytes of the input is loaded and nothing behind the kept records is stored: any caller tensor will do.
@@ -19,6 +18,7 @@
 #include <vector>
 #include "ecal_ctx.hpp"
 #include "pixel_activity.hpp"
+#include "stream_compact.hpp"
 
 namespace ecal {
 
@@ -26,27 +26,8 @@ using namespace ecal_activity;
 
 static_assert(ECAL_ERR_INVALID == PA_INVALID && ECAL_OK == PA_OK, "status codes");
 
-constexpr int PA_T = 256;
-constexpr uint32_t PA_BLOCK = PA_BLOCK_EVENTS;
-constexpr uint32_t PA_PER = PA_BLOCK / PA_T;     // consecutive events per thread where the verdicts are ranked
-constexpr uint32_t PA_CHUNK = 1024;              // records staged in LDS at a time (25 600 bytes)
-constexpr uint32_t PA_GROUPS = PA_CHUNK / PA_PER;   // threads' runs per chunk
-static_assert(PA_PER == 16, "the writing pass reads a thread's verdicts as one 16-byte word, its keep bits as 16 bits");
-static_assert(PA_BLOCK % PA_CHUNK == 0 && PA_CHUNK % PA_T == 0, "whole chunks, whole rounds of the workgroup");
-
-__device__ __forceinline__ uint32_t pa_block_count(uint64_t n_events, uint64_t base) {
-    return (uint32_t) (n_events - base < (uint64_t) PA_BLOCK ? n_events - base : (uint64_t) PA_BLOCK);
-}
-
-// the sum of v over the workgroup, for thread 0 (s_red: PA_T / 64 words; one barrier)
-__device__ __forceinline__ uint32_t pa_block_sum(uint32_t v, uint32_t *s_red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < PA_T / 64; w++) t += s_red[w];
-    return t;
-}
+constexpr int PA_T = SC_T;
+constexpr uint32_t PA_BLOCK = SC_BLOCK;
 
 // counts: [2][height][width], zero before the launch; totals (may be null): n_events, n_on_grid, n_off_grid, zero before the launch
 __global__ __launch_bounds__(PA_T) void pixel_activity_kernel(const uint8_t *__restrict__ rec, uint64_t n_events, uint32_t width,
@@ -55,7 +36,7 @@ __global__ __launch_bounds__(PA_T) void pixel_activity_kernel(const uint8_t *__r
     __shared__ uint32_t s_red[PA_T / 64];
     const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * PA_BLOCK;
-    const uint32_t count = pa_block_count(n_events, base);
+    const uint32_t count = stream_block_count(n_events, base);
     const uint8_t *const blk = rec + base * PA_RECORD_BYTES;
     const size_t plane = (size_t) width * height;
     uint32_t on = 0;
@@ -68,7 +49,7 @@ __global__ __launch_bounds__(PA_T) void pixel_activity_kernel(const uint8_t *__r
         }
     }
     if (!totals) return;
-    on = pa_block_sum(on, s_red);
+    on = block_sum<PA_T>(on, s_red);
     if (tid == 0) atomicAdd(&totals[0], (unsigned long long) count);
     if (tid == 1 && on) atomicAdd(&totals[1], (unsigned long long) on);
     if (tid == 2 && count - on) atomicAdd(&totals[2], (unsigned long long) (count - on));
@@ -83,7 +64,7 @@ __global__ __launch_bounds__(PA_T) void activity_verdict_kernel(const uint8_t *_
     __shared__ uint32_t s_red[2][PA_T / 64];
     const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * PA_BLOCK;
-    const uint32_t count = pa_block_count(n_events, base);
+    const uint32_t count = stream_block_count(n_events, base);
     const uint8_t *const blk = rec + base * PA_RECORD_BYTES;
     uint32_t keep = 0, off = 0;
     for (uint32_t k = (uint32_t) tid; k < count; k += PA_T) {
@@ -93,8 +74,8 @@ __global__ __launch_bounds__(PA_T) void activity_verdict_kernel(const uint8_t *_
         keep += v;
         off += og ? 1u : 0u;
     }
-    keep = pa_block_sum(keep, s_red[0]);
-    off = pa_block_sum(off, s_red[1]);
+    keep = block_sum<PA_T>(keep, s_red[0]);
+    off = block_sum<PA_T>(off, s_red[1]);
     if (tid == 0) block_cnt[blockIdx.x] = keep;
     if (!totals) return;
     if (tid == 0) atomicAdd(&totals[0], (unsigned long long) count);
@@ -107,84 +88,17 @@ __global__ __launch_bounds__(PA_T) void activity_verdict_kernel(const uint8_t *_
 __global__ __launch_bounds__(PA_T) void activity_write_kernel(const uint8_t *__restrict__ rec, uint64_t n_events,
                                                               const uint8_t *__restrict__ verdict, const uint32_t *__restrict__ block_off,
                                                               uint8_t *__restrict__ out) {
-    __shared__ uint32_t s_pre[PA_T];      // the block's kept events in front of every thread's run
-    __shared__ uint32_t s_bits[PA_T];     // the run's keep bits
-    __shared__ uint32_t s_wsum[PA_T / 64];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[PA_CHUNK * PA_RECORD_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t base = (uint64_t) blockIdx.x * PA_BLOCK;
-    const uint32_t count = pa_block_count(n_events, base);
-    const uint32_t k0 = (uint32_t) tid * PA_PER;
-    const uint4 w = *reinterpret_cast<const uint4 *>(verdict + base + k0);   // (16-byte aligned: base and k0 are multiples of 16)
-    const uint32_t words[4] = {w.x, w.y, w.z, w.w};
-    uint32_t bits = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < PA_PER; e++) {
-        const uint32_t v = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
-        bits |= (k0 + e < count && v != 0u) ? 1u << e : 0u;
-    }
-    const uint32_t mine = (uint32_t) __popc(bits);
-    // exclusive scan of `mine` over the block (thread order = event order)
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, ktot = 0;
-    for (int x = 0; x < PA_T / 64; x++) {
-        if (x < wave) pre += s_wsum[x];
-        ktot += s_wsum[x];
-    }
-    s_pre[tid] = pre + inc - mine;
-    s_bits[tid] = bits;
-    __syncthreads();
-    if (!ktot) return;   // (the same for every thread)
-    uint8_t *const dst_blk = out + (uint64_t) block_off[blockIdx.x] * PA_RECORD_BYTES;
-    for (uint32_t q = 0; q * PA_CHUNK < count; q++) {
-        // the kept events in front of chunk q and behind it, in the block
-        const uint32_t r0 = s_pre[q * PA_GROUPS], r1 = (q + 1) * PA_CHUNK < PA_BLOCK ? s_pre[(q + 1) * PA_GROUPS] : ktot;
-        if (r1 == r0) continue;   // (the same for every thread; no barrier is skipped that another thread reaches)
-        // pack: lanes next to each other take events next to each other
-#pragma unroll
-        for (uint32_t i = 0; i < PA_CHUNK / PA_T; i++) {
-            const uint32_t k = q * PA_CHUNK + i * PA_T + (uint32_t) tid, g = k / PA_PER, b = k % PA_PER;
-            const uint32_t m = s_bits[g];
-            if (m >> b & 1u) {   // (kept: k < count)
-                const uint32_t rank = s_pre[g] + (uint32_t) __popc(m & ((1u << b) - 1u)) - r0;   // < PA_CHUNK
-                const uint8_t *r = rec + (base + k) * PA_RECORD_BYTES;
-                uint8_t *d = s_rec + rank * PA_RECORD_BYTES;
-                uint64_t a0, a1, a2;
-                __builtin_memcpy(&a0, r, 8);
-                __builtin_memcpy(&a1, r + 8, 8);
-                __builtin_memcpy(&a2, r + 16, 8);
-                const uint8_t a3 = r[24];
-                __builtin_memcpy(d, &a0, 8);
-                __builtin_memcpy(d + 8, &a1, 8);
-                __builtin_memcpy(d + 16, &a2, 8);
-                d[24] = a3;
-            }
-        }
-        __syncthreads();
-        // copy-out: bytes up to the first 16-byte boundary of the destination, whole 16-byte words, the bytes behind them
-        uint8_t *dst = dst_blk + (size_t) r0 * PA_RECORD_BYTES;
-        const uint32_t nbytes = (r1 - r0) * PA_RECORD_BYTES;
-        uint32_t head = (uint32_t) ((16u - ((uintptr_t) dst & 15u)) & 15u);
-        head = head < nbytes ? head : nbytes;
-        const uint32_t nw = (nbytes - head) / 16u;
-        if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-        for (uint32_t j = (uint32_t) tid; j < nw; j += PA_T) {
-            const uint32_t at = head + 16u * j;
-            uint4 v;
-            __builtin_memcpy(&v, s_rec + at, 16);
-            *reinterpret_cast<uint4 *>(dst + at) = v;
-        }
-        const uint32_t tail0 = head + 16u * nw;
-        if (tail0 + (uint32_t) tid < nbytes) dst[tail0 + tid] = s_rec[tail0 + tid];   // (fewer than 16 bytes)
-        __syncthreads();
-    }
+    compact_write_block(rec, n_events, verdict, block_off, out, [](const uint8_t *r, uint8_t *d) {
+        uint64_t a0, a1, a2;
+        __builtin_memcpy(&a0, r, 8);
+        __builtin_memcpy(&a1, r + 8, 8);
+        __builtin_memcpy(&a2, r + 16, 8);
+        const uint8_t a3 = r[24];
+        __builtin_memcpy(d, &a0, 8);
+        __builtin_memcpy(d + 8, &a1, 8);
+        __builtin_memcpy(d + 16, &a2, 8);
+        d[24] = a3;
+    });
 }
 
 }  // namespace ecal
@@ -236,16 +150,84 @@ extern "C" int ecal_hot_pixel_mask(const uint32_t *counts, const ecal_hot_pixel_
     return ECAL_OK;
 }
 
-static int activity_check(ecal_ctx *ctx, const char *who, uint64_t n_events, uint32_t width, uint32_t height) {
-    if (!pa_size_ok(width, height)) {
-        ctx->last_error = std::string(who) + ": width and height from 1 to 4096";
-        return ECAL_ERR_INVALID;
-    }
+// ---- what the compacting stages share (ecal_ctx.hpp) ----
+static_assert(ECAL_STREAM_BLOCK == SC_BLOCK, "the host's blocks are the kernels'");
+
+int ecal_verdict_tables_ensure(ecal_ctx *ctx, ecal_devbuf &scratch, uint64_t n_events, ecal_verdict_tables *V) {
+    const uint32_t nb = ecal_stream_blocks(n_events);
+    const int rc = ecal_ensure(ctx, scratch, ecal_verdict_tables_bytes(nb));
+    if (rc) return rc;
+    *V = ecal_verdict_tables_at(scratch.as<uint8_t>(), nb);
+    return ECAL_OK;
+}
+
+int ecal_events_range_check(ecal_ctx *ctx, const char *who, uint64_t n_events) {
     if (n_events > 0xFFFFFFFFull) {
         ctx->last_error = std::string(who) + ": more than 2^32-1 events";
         return ECAL_ERR_RANGE;
     }
     return ECAL_OK;
+}
+
+int ecal_compact_begin(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_out, uint32_t *d_count,
+                       void *d_totals, size_t totals_bytes, hipStream_t st) {
+    const size_t bytes = (size_t) n_events * PA_RECORD_BYTES;
+    if (n_events && d_out && d_events < d_out + bytes && d_out < d_events + bytes) {
+        ctx->last_error = std::string(who) + ": the output overlaps the events";
+        return ECAL_ERR_INVALID;
+    }
+    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
+    if (d_totals) ECAL_HIP_TRY(ctx, hipMemsetAsync(d_totals, 0, totals_bytes, st));
+    return ECAL_OK;
+}
+
+int ecal_compact_copy_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const ecal_verdict_tables &V, uint8_t *d_out,
+                                 uint32_t *d_count, ecal_load_timer &tm, hipStream_t st) {
+    return ecal_compact_by_verdict(ctx, V, d_count, &tm, st, [&]() {
+        hipLaunchKernelGGL(activity_write_kernel, dim3(V.nb), dim3(PA_T), 0, st, d_events, n_events, (const uint8_t *) V.verdict,
+                           (const uint32_t *) V.off, d_out);
+    });
+}
+
+int ecal_stream_compacted(ecal_ctx *ctx, const char *who, const ecal_stream *in, void *d_results, void *totals, size_t totals_bytes,
+                          const ecal_stream_dev_fn &run_dev, const ecal_stream_disagree_fn &disagree, ecal_stream **out) {
+    const uint64_t n = ecal_stream_size(in);
+    hipStream_t st = ctx->stream;
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_results) + totals_bytes);
+    uint8_t *d_out = nullptr;
+    int rc = ecal_ingest_alloc_records(ctx, who, n, &d_out);
+    if (rc) {
+        (void) hipStreamSynchronize(st);   // (a caller's upload may still read host memory that goes out of scope with this return)
+        return rc;
+    }
+    uint32_t kept = 0;
+    auto run = [&]() -> int {
+        const int frc = run_dev(d_out, d_count, d_results, st);
+        if (frc) return frc;
+        ECAL_HIP_TRY(ctx, hipMemcpyAsync(totals, d_results, totals_bytes, hipMemcpyDeviceToHost, st));
+        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, st));
+        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
+        return ECAL_OK;
+    };
+    rc = run();
+    if (rc) {
+        (void) hipStreamSynchronize(st);
+        return ecal_ingest_drop_records(&d_out, rc);
+    }
+    if (const char *bad = disagree(kept, n)) {
+        ctx->last_error = std::string(who) + ": " + bad;
+        return ecal_ingest_drop_records(&d_out, ECAL_ERR_HIP);
+    }
+    return ecal_stream_from_events(ctx, who, d_out, kept, out);
+}
+
+static int activity_check(ecal_ctx *ctx, const char *who, uint64_t n_events, uint32_t width, uint32_t height) {
+    if (!pa_size_ok(width, height)) {
+        ctx->last_error = std::string(who) + ": width and height from 1 to 4096";
+        return ECAL_ERR_INVALID;
+    }
+    return ecal_events_range_check(ctx, who, n_events);
 }
 
 extern "C" int ecal_pixel_activity_dev(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, uint32_t width, uint32_t height,
@@ -284,44 +266,19 @@ extern "C" int ecal_filter_events_dev(ecal_ctx *ctx, const uint8_t *d_events, ui
     }
     int rc = activity_check(ctx, "ecal_filter_events", n_events, width, height);
     if (rc) return rc;
-    const size_t bytes = (size_t) n_events * PA_RECORD_BYTES;
-    if (n_events && d_events < d_out + bytes && d_out < d_events + bytes) {
-        ctx->last_error = "ecal_filter_events: the output overlaps the events";
-        return ECAL_ERR_INVALID;
-    }
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t) stream;
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
-    if (d_totals) ECAL_HIP_TRY(ctx, hipMemsetAsync(d_totals, 0, sizeof(ecal_filter_totals), st));
+    if ((rc = ecal_compact_begin(ctx, "ecal_filter_events", d_events, n_events, d_out, d_count, d_totals, sizeof(ecal_filter_totals), st))) return rc;
     if (!n_events) return ECAL_OK;
-    const uint32_t nb = (uint32_t) ((n_events + PA_BLOCK - 1) / PA_BLOCK);
-    // verdicts (whole blocks) | counts [nb] | offsets [nb + 1]
-    const size_t o_cnt = (size_t) nb * PA_BLOCK, o_off = o_cnt + (size_t) nb * 4, total = o_off + ((size_t) nb + 1) * 4;
-    rc = ecal_ensure(ctx, ctx->activity_scratch, total);
-    if (rc) return rc;
-    uint8_t *verdict = ctx->activity_scratch.as<uint8_t>();
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(verdict + o_cnt), *off = reinterpret_cast<uint32_t *>(verdict + o_off);
+    ecal_verdict_tables V;
+    if ((rc = ecal_verdict_tables_ensure(ctx, ctx->activity_scratch, n_events, &V))) return rc;
     ecal_load_timer tm("hot pixel filter", ctx->sw.load_trace, st);
     tm.mark("start");
-    hipLaunchKernelGGL(activity_verdict_kernel, dim3(nb), dim3(PA_T), 0, st, d_events, n_events, d_mask, width, height, verdict, cnt,
+    hipLaunchKernelGGL(activity_verdict_kernel, dim3(V.nb), dim3(PA_T), 0, st, d_events, n_events, d_mask, width, height, V.verdict, V.cnt,
                        (unsigned long long *) d_totals);
     tm.mark("verdict");
-    rc = ecal_compact_by_verdict(ctx, d_events, n_events, verdict, cnt, off, d_out, d_count, tm, st);
+    rc = ecal_compact_copy_by_verdict(ctx, d_events, n_events, V, d_out, d_count, tm, st);
     if (rc) return rc;
     if (tm.on) ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (ECAL_TRACE=load alone: the timer reads its events when it goes out of scope)
-    return ECAL_OK;
-}
-
-int ecal_compact_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_verdict, const uint32_t *d_cnt,
-                            uint32_t *d_off, uint8_t *d_out, uint32_t *d_count, ecal_load_timer &tm, hipStream_t st) {
-    const uint32_t nb = (uint32_t) ((n_events + PA_BLOCK - 1) / PA_BLOCK);
-    const int rc = ecal_scan_blocks(ctx, d_cnt, nb, d_off, st);
-    if (rc) return rc;
-    tm.mark("scan");
-    hipLaunchKernelGGL(activity_write_kernel, dim3(nb), dim3(PA_T), 0, st, d_events, n_events, d_verdict, (const uint32_t *) d_off, d_out);
-    tm.mark("write");
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, d_off + nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    ECAL_HIP_TRY(ctx, hipGetLastError());
     return ECAL_OK;
 }
 
@@ -347,7 +304,7 @@ extern "C" int ecal_stream_remove_hot_pixels(ecal_ctx *ctx, const ecal_stream *i
     int rc = ecal_ensure(ctx, ctx->activity_maps, total);
     if (rc) return rc;
     uint8_t *base = ctx->activity_maps.as<uint8_t>();
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(base), *d_count = reinterpret_cast<uint32_t *>(base + o_cnt);
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(base);   // (the count stands behind the totals: ecal_stream_compacted's results)
     ecal_filter_totals *d_tot = reinterpret_cast<ecal_filter_totals *>(base + o_tot);
     uint8_t *d_mask = base + o_mask;
     // 1. the count map, and the small trip to the host for the rule (one-off ingest work)
@@ -370,39 +327,21 @@ extern "C" int ecal_stream_remove_hot_pixels(ecal_ctx *ctx, const ecal_stream *i
     rc = pa_hot_pixel_mask(counts, o, extra_mask, mask, &I);
     if (rc) return rc;
     ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_mask, mask, plane, hipMemcpyHostToDevice, st));
-    // 2. the filter into records of the new stream's own (every event may stay)
-    uint8_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **) &d_out, (size_t) n * PA_RECORD_BYTES + 16);
-    if (e != hipSuccess) {
-        (void) hipStreamSynchronize(st);   // (the mask's upload reads host memory that may go out of scope here)
-        ctx->last_error = std::string("ecal_stream_remove_hot_pixels: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-    }
+    // 2. the filter into records of the new stream's own (every event may stay); the helper synchronises the stream before it
+    // returns, whatever happens: the mask's upload reads host memory that goes out of scope here
     ecal_filter_totals T;
-    uint32_t kept = 0;
-    auto run = [&]() -> int {
-        const int frc = ecal_filter_events_dev(ctx, d_in, n, d_mask, o.width, o.height, d_out, d_count, d_tot, st);
-        if (frc) return frc;
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&T, d_tot, sizeof(T), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
-    rc = run();
-    if (rc) {
-        (void) hipStreamSynchronize(st);
-        (void) hipFree(d_out);
-        return rc;
-    }
-    I.n_events = T.n_events;
-    I.n_off_grid = T.n_off_grid;
-    I.n_removed = T.n_removed;
-    I.n_kept = T.n_kept;
-    hot_info_out(info, I);
-    if (T.n_kept != kept || T.n_removed + T.n_kept != n) {
-        (void) hipFree(d_out);
-        ctx->last_error = "ecal_stream_remove_hot_pixels: the filter's counters disagree";
-        return ECAL_ERR_HIP;
-    }
-    return ecal_stream_adopt(ctx, d_out, kept, out);
+    return ecal_stream_compacted(
+        ctx, "ecal_stream_remove_hot_pixels", in, d_tot, &T, sizeof(T),
+        [&](uint8_t *d_out, uint32_t *d_cnt, void *d_totals, hipStream_t s) {
+            return ecal_filter_events_dev(ctx, d_in, n, d_mask, o.width, o.height, d_out, d_cnt, (ecal_filter_totals *) d_totals, s);
+        },
+        [&](uint32_t kept, uint64_t n_in) -> const char * {
+            I.n_events = T.n_events;
+            I.n_off_grid = T.n_off_grid;
+            I.n_removed = T.n_removed;
+            I.n_kept = T.n_kept;
+            hot_info_out(info, I);
+            return T.n_kept != kept || T.n_removed + T.n_kept != n_in ? "the filter's counters disagree" : nullptr;
+        },
+        out);
 }

@@ -274,12 +274,57 @@ struct ecal_load_timer {
         for (int i = 0; i < n; i++) (void) hipEventDestroy(ev[i]);
     }
 };
-// The ordered compaction both stream filters end in (ecal_activity.hip): the exclusive scan of the nb = ceil(n_events / 4096) per-block
-// kept counts d_cnt into d_off [nb + 1], activity_write_kernel — the events whose verdict byte is non-zero, their own 25 bytes each, in
-// input order into d_out — and *d_count = the total.  d_verdict: whole blocks of 4096 bytes, 16-byte aligned (the bytes behind
-// n_events are read and masked).  n_events > 0.  Marks "scan" and "write" on tm; does not synchronise.
-int ecal_compact_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_verdict, const uint32_t *d_cnt,
-                            uint32_t *d_off, uint8_t *d_out, uint32_t *d_count, ecal_load_timer &tm, hipStream_t st);
+// ---- what the compacting stages share on the host (ecal_activity.hip): the hot-pixel filter, the noise filter, undistortion and
+// re-association judge every event of a packed stream, count the kept events per block of ECAL_STREAM_BLOCK, scan the counts and
+// write the kept events out in input order (the device side: stream_compact.hpp) ---------------------------------------------------
+constexpr uint32_t ECAL_STREAM_BLOCK = 4096;
+// verdicts (whole blocks, 16-byte aligned) | counts [nb] | offsets [nb + 1]
+struct ecal_verdict_tables {
+    uint8_t *verdict;
+    uint32_t *cnt, *off;
+    uint32_t nb;
+};
+inline uint32_t ecal_stream_blocks(uint64_t n_events) { return (uint32_t) ((n_events + ECAL_STREAM_BLOCK - 1) / ECAL_STREAM_BLOCK); }
+inline size_t ecal_verdict_tables_bytes(uint32_t nb) { return (size_t) nb * ECAL_STREAM_BLOCK + (size_t) nb * 4 + ((size_t) nb + 1) * 4; }
+inline ecal_verdict_tables ecal_verdict_tables_at(uint8_t *base, uint32_t nb) {
+    uint8_t *cnt = base + (size_t) nb * ECAL_STREAM_BLOCK;
+    return ecal_verdict_tables{base, reinterpret_cast<uint32_t *>(cnt), reinterpret_cast<uint32_t *>(cnt + (size_t) nb * 4), nb};
+}
+// ... for n_events events in a scratch buffer of their own
+int ecal_verdict_tables_ensure(ecal_ctx *ctx, ecal_devbuf &scratch, uint64_t n_events, ecal_verdict_tables *V);
+// "<who>: more than 2^32-1 events" (ECAL_ERR_RANGE)
+int ecal_events_range_check(ecal_ctx *ctx, const char *who, uint64_t n_events);
+// A compacting _dev form behind its own null-pointer, option and range tests (their order is each entry point's): "<who>: the output
+// overlaps the events" (d_out null: not asked — re-association writes other arrays), the context's device, and *d_count and the
+// d_totals (may be null) zeroed
+int ecal_compact_begin(ecal_ctx *ctx, const char *who, const uint8_t *d_events, uint64_t n_events, const uint8_t *d_out, uint32_t *d_count,
+                       void *d_totals, size_t totals_bytes, hipStream_t st);
+// The ordered compaction every one of them ends in: the exclusive scan of the per-block kept counts V.cnt into V.off, launch_write()
+// — the stage's writing kernel over V.nb workgroups — and *d_count = the total.  n_events > 0.  Marks "scan" and "write" on tm (may
+// be null); does not synchronise.
+template <class Launch>
+int ecal_compact_by_verdict(ecal_ctx *ctx, const ecal_verdict_tables &V, uint32_t *d_count, ecal_load_timer *tm, hipStream_t st,
+                            Launch launch_write) {
+    const int rc = ecal_scan_blocks(ctx, V.cnt, V.nb, V.off, st);
+    if (rc) return rc;
+    if (tm) tm->mark("scan");
+    launch_write();
+    if (tm) tm->mark("write");
+    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, V.off + V.nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    ECAL_HIP_TRY(ctx, hipGetLastError());
+    return ECAL_OK;
+}
+// ... with activity_write_kernel: the events whose verdict byte is non-zero, their own 25 bytes each, into d_out (both filters)
+int ecal_compact_copy_by_verdict(ecal_ctx *ctx, const uint8_t *d_events, uint64_t n_events, const ecal_verdict_tables &V, uint8_t *d_out,
+                                 uint32_t *d_count, ecal_load_timer &tm, hipStream_t st);
+// The stream form of a compacting stage, on ctx->stream: records of the new stream's own (every event may stay), run_dev — the _dev
+// form into them, d_results = totals (totals_bytes) | count —, the totals into `totals` and the count in ONE synchronisation, then
+// disagree(kept, n): null, or what is wrong with the counters ("<who>: <that>", ECAL_ERR_HIP; it may hand the totals on first).  The
+// records are dropped on every failure; the stream is synchronised before any return.
+typedef std::function<int(uint8_t *d_out, uint32_t *d_count, void *d_totals, hipStream_t st)> ecal_stream_dev_fn;
+typedef std::function<const char *(uint32_t kept, uint64_t n)> ecal_stream_disagree_fn;
+int ecal_stream_compacted(ecal_ctx *ctx, const char *who, const ecal_stream *in, void *d_results, void *totals, size_t totals_bytes,
+                          const ecal_stream_dev_fn &run_dev, const ecal_stream_disagree_fn &disagree, ecal_stream **out);
 // reference element order: the per-pixel bucket table of the hot-path slicer, built on first use (ecal_events.hip)
 int ecal_ensure_bucket_table(ecal_ctx *ctx, hipStream_t st);
 // tail scheduling (see ecal_ctx::tail_seen): slots of the stages' lists, and "may this call run lean?"

@@ -27,6 +27,7 @@
 //   image_remap_kernel      a thread per four canvas pixels and IMG_FRAMES frames: a map word is read once for those frames; u8 straight
 //                           out with aligned 4-byte stores (normalize 0, no min / max asked), else f32 to scratch and image_finish_kernel
 #include "ecal_ctx.hpp"
+#include "block_utils.hpp"
 #include "image_undistort.hpp"
 
 #include <rocprim/rocprim.hpp>   // (behind ecal_ctx.hpp, as in ecal_sort.hip: its headers use the host's string.h)
@@ -50,15 +51,6 @@ constexpr int IMG_T = 256;
 constexpr uint32_t IMG_FRAMES = 4;            // frames per thread of the applying kernels
 constexpr uint32_t IMG_MIN_INIT = 0x7F800000u;   // +inf: above every value
 
-__device__ __forceinline__ uint32_t img_block_sum(uint32_t v, uint32_t *s_red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < IMG_T / 64; w++) t += s_red[w];
-    return t;
-}
-
 // counters: [0] invalid sources
 __global__ __launch_bounds__(IMG_T) void image_position_kernel(const Camera cam, const Options opt, uint32_t W, uint32_t n_src, uint32_t n_cells,
                                                                double *__restrict__ cu, double *__restrict__ cv, uint32_t *__restrict__ key,
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(IMG_T) void image_position_kernel(const Camera cam,
         val[idx] = idx;
         inv = invalid ? 1u : 0u;
     }
-    inv = img_block_sum(inv, s_red);
+    inv = block_sum<IMG_T>(inv, s_red);
     if (threadIdx.x == 0 && inv) atomicAdd(&counters[0], (unsigned long long) inv);
 }
 
@@ -113,8 +105,8 @@ __global__ __launch_bounds__(IMG_T) void image_count_kernel(const Options opt, u
         most = other > most ? other : most;
     }
     if ((threadIdx.x & 63) == 0 && most) atomicMax(&counters[2], (unsigned long long) most);
-    const uint32_t total = img_block_sum(n, s_red[0]);
-    empty = img_block_sum(empty, s_red[1]);
+    const uint32_t total = block_sum<IMG_T>(n, s_red[0]);
+    empty = block_sum<IMG_T>(empty, s_red[1]);
     if (threadIdx.x == 0) {
         block_cnt[blockIdx.x] = total;
         if (empty) atomicAdd(&counters[1], (unsigned long long) empty);
@@ -127,21 +119,11 @@ __global__ __launch_bounds__(IMG_T) void image_fill_kernel(const Options opt, ui
                                                            const double *__restrict__ cv, const uint32_t *__restrict__ block_off,
                                                            uint32_t *__restrict__ cnt_off, uint32_t *__restrict__ t_idx, double *__restrict__ t_w) {
     __shared__ uint32_t s_wsum[IMG_T / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t p = blockIdx.x * IMG_T + threadIdx.x;
     const uint32_t mine = p < np ? cnt_off[p] : 0u;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (int x = 0; x < wave; x++) pre += s_wsum[x];
+    const uint32_t before = block_exscan_u32<IMG_T>(mine, s_wsum);
     if (p >= np) return;
-    const uint32_t first = block_off[blockIdx.x] + pre + inc - mine;
+    const uint32_t first = block_off[blockIdx.x] + before;
     cnt_off[p] = first;
     if (p == np - 1u) cnt_off[np] = first + mine;
     uint32_t at = first;
@@ -368,8 +350,8 @@ __global__ __launch_bounds__(IMG_T) void image_maps_kernel(const Camera cam, con
         inv = flag == IMG_DISTORT_INVALID ? 1u : 0u;
         slow = flag == IMG_DISTORT_NOT_CONVERGED ? 1u : 0u;
     }
-    inv = img_block_sum(inv, s_red[0]);
-    slow = img_block_sum(slow, s_red[1]);
+    inv = block_sum<IMG_T>(inv, s_red[0]);
+    slow = block_sum<IMG_T>(slow, s_red[1]);
     if (threadIdx.x == 0 && inv) atomicAdd(&counters[0], (unsigned long long) inv);
     if (threadIdx.x == 1 && slow) atomicAdd(&counters[1], (unsigned long long) slow);
 }

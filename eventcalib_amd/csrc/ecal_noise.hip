@@ -13,10 +13,11 @@
 //                          same lists.  For each neighbour pixel a binary search of its list for the last entry in front of event i,
 //                          one support test; the verdict byte goes to verdict[i]; the totals are reduced in the block.
 //   noise_count_kernel     the kept events of every block of PA_BLOCK_EVENTS verdict bytes
-//   ecal_compact_by_verdict   the hot-pixel filter's scan and writing pass (ecal_activity.hip)
+//   ecal_compact_copy_by_verdict   the hot-pixel filter's scan and writing pass (ecal_activity.hip)
 // Nothing behind n_events * 25 bytes of the input is loaded and nothing behind the kept records is stored: any caller tensor will do.
 #include "ecal_ctx.hpp"
 #include "noise_filter.hpp"
+#include "stream_compact.hpp"
 
 #include <rocprim/rocprim.hpp>   // (behind ecal_ctx.hpp, as in ecal_sort.hip: its headers use the host's string.h)
 
@@ -25,8 +26,7 @@ namespace ecal {
 using namespace ecal_noise;
 using ecal_activity::PA_BLOCK_EVENTS;
 
-constexpr int NF_T = 256;
-static_assert(PA_BLOCK_EVENTS == NF_T * 16, "the counting pass reads a thread's verdicts as one 16-byte word");
+constexpr int NF_T = SC_T;
 
 __global__ __launch_bounds__(NF_T) void noise_key_kernel(const uint8_t *__restrict__ rec, uint32_t n_events, uint32_t width, uint32_t height,
                                                          uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
@@ -53,16 +53,6 @@ __global__ __launch_bounds__(NF_T) void noise_index_kernel(const uint8_t *__rest
     if (j < (uint64_t) n_events) sts[j] = ecal_activity::pa_load_f64(rec + (size_t) sval[j] * PA_RECORD_BYTES);
 }
 
-// the sum of v over the workgroup, for every thread (s_red: NF_T / 64 words; one barrier)
-__device__ __forceinline__ uint32_t nf_block_sum(uint32_t v, uint32_t *s_red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < NF_T / 64; w++) t += s_red[w];
-    return t;
-}
-
 // verdict [n_events]: one byte per event (1 keep, 0 remove), written at the event's stream index; totals (may be null): n_events,
 // n_off_grid, n_removed, n_kept, zero before the launch
 __global__ __launch_bounds__(NF_T) void noise_support_kernel(uint32_t n_events, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval,
@@ -80,10 +70,9 @@ __global__ __launch_bounds__(NF_T) void noise_support_kernel(uint32_t n_events, 
         off = og ? 1u : 0u;
     }
     if (!totals) return;
-    keep = nf_block_sum(keep, s_red[0]);
-    off = nf_block_sum(off, s_red[1]);
-    const uint64_t base = (uint64_t) blockIdx.x * NF_T;
-    const uint32_t count = (uint32_t) ((uint64_t) n_events - base < (uint64_t) NF_T ? (uint64_t) n_events - base : (uint64_t) NF_T);
+    keep = block_sum<NF_T>(keep, s_red[0]);
+    off = block_sum<NF_T>(off, s_red[1]);
+    const uint32_t count = stream_block_count<NF_T>(n_events, (uint64_t) blockIdx.x * NF_T);
     const int tid = threadIdx.x;
     if (tid == 0) atomicAdd(&totals[0], (unsigned long long) count);
     if (tid == 1 && off) atomicAdd(&totals[1], (unsigned long long) off);
@@ -95,17 +84,8 @@ __global__ __launch_bounds__(NF_T) void noise_support_kernel(uint32_t n_events, 
 __global__ __launch_bounds__(NF_T) void noise_count_kernel(const uint8_t *__restrict__ verdict, uint32_t n_events, uint32_t *__restrict__ block_cnt) {
     __shared__ uint32_t s_red[NF_T / 64];
     const uint64_t base = (uint64_t) blockIdx.x * PA_BLOCK_EVENTS;
-    const uint32_t count = (uint32_t) ((uint64_t) n_events - base < (uint64_t) PA_BLOCK_EVENTS ? (uint64_t) n_events - base : (uint64_t) PA_BLOCK_EVENTS);
-    const uint32_t k0 = (uint32_t) threadIdx.x * 16u;
-    const uint4 w = *reinterpret_cast<const uint4 *>(verdict + base + k0);
-    const uint32_t words[4] = {w.x, w.y, w.z, w.w};
-    uint32_t keep = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < 16u; e++) {
-        const uint32_t v = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
-        keep += (k0 + e < count && v != 0u) ? 1u : 0u;
-    }
-    keep = nf_block_sum(keep, s_red);
+    const uint32_t bits = verdict_keep_bits<0u>(verdict, base, (uint32_t) threadIdx.x * SC_PER, stream_block_count(n_events, base));
+    const uint32_t keep = block_sum<NF_T>((uint32_t) __popc(bits), s_red);
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = keep;
 }
 
@@ -143,18 +123,14 @@ static int noise_check(ecal_ctx *ctx, const char *who, uint64_t n_events, const 
         ctx->last_error = std::string(who) + ": " + bad;
         return ECAL_ERR_INVALID;
     }
-    if (n_events > 0xFFFFFFFFull) {
-        ctx->last_error = std::string(who) + ": more than 2^32-1 events";
-        return ECAL_ERR_RANGE;
-    }
-    return ECAL_OK;
+    return ecal_events_range_check(ctx, who, n_events);
 }
 
 namespace {
 // ctx->noise_scratch for n events on a plane of pixels: keys and indices in and out of the sort, the stamps in sorted order, the
-// start table, verdict bytes in whole blocks, per-block counts / offsets, the sort's workspace
+// start table, the verdict tables (ecal_verdict_tables_at: verdict bytes in whole blocks, per-block counts / offsets), the sort's workspace
 struct noise_layout {
-    size_t o_kin, o_kout, o_vin, o_vout, o_sts, o_start, o_verdict, o_cnt, o_off, o_tmp, total;
+    size_t o_kin, o_kout, o_vin, o_vout, o_sts, o_start, o_verdict, o_tmp, total;
     noise_layout(size_t n, size_t plane, size_t nb, size_t tmp_bytes) {
         auto up = [](size_t v) { return (v + 255) & ~(size_t) 255; };
         size_t at = 0;
@@ -164,9 +140,7 @@ struct noise_layout {
         o_vin = at, at += up(n * 4);
         o_vout = at, at += up(n * 4);
         o_start = at, at += up((plane + 1) * 4);
-        o_verdict = at, at += up(nb * PA_BLOCK_EVENTS);
-        o_cnt = at, at += up(nb * 4);
-        o_off = at, at += up((nb + 1) * 4);
+        o_verdict = at, at += up(ecal_verdict_tables_bytes((uint32_t) nb));
         o_tmp = at, at += tmp_bytes;
         total = at;
     }
@@ -178,7 +152,7 @@ struct noise_layout {
 static int noise_verdicts(ecal_ctx *ctx, const uint8_t *d_events, uint32_t n, const NoiseOptions &o, uint8_t *d_verdict, ecal_filter_totals *d_totals,
                           ecal_load_timer &tm, noise_layout *L_out, hipStream_t st) {
     const uint32_t plane = o.width * o.height, bits = nf_key_bits(plane);
-    const uint32_t nb = (uint32_t) (((uint64_t) n + PA_BLOCK_EVENTS - 1) / PA_BLOCK_EVENTS);
+    const uint32_t nb = ecal_stream_blocks(n);
     size_t tmp_bytes = 0;
     uint32_t *k_in = nullptr, *k_out = nullptr, *v_in = nullptr, *v_out = nullptr;
     ECAL_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (size_t) n, 0, bits, st));
@@ -244,27 +218,17 @@ extern "C" int ecal_denoise_events_dev(ecal_ctx *ctx, const uint8_t *d_events, u
     const NoiseOptions o = noise_options(opt);
     int rc = noise_check(ctx, "ecal_denoise_events", n_events, o);
     if (rc) return rc;
-    const size_t bytes = (size_t) n_events * PA_RECORD_BYTES;
-    if (n_events && d_events < d_out + bytes && d_out < d_events + bytes) {
-        ctx->last_error = "ecal_denoise_events: the output overlaps the events";
-        return ECAL_ERR_INVALID;
-    }
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t) stream;
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
-    if (d_totals) ECAL_HIP_TRY(ctx, hipMemsetAsync(d_totals, 0, sizeof(ecal_filter_totals), st));
+    if ((rc = ecal_compact_begin(ctx, "ecal_denoise_events", d_events, n_events, d_out, d_count, d_totals, sizeof(ecal_filter_totals), st))) return rc;
     if (!n_events) return ECAL_OK;
     ecal_load_timer tm("noise filter", ctx->sw.load_trace, st);
     noise_layout L(0, 0, 0, 0);
     rc = noise_verdicts(ctx, d_events, (uint32_t) n_events, o, nullptr, d_totals, tm, &L, st);
     if (rc) return rc;
-    uint8_t *base = ctx->noise_scratch.as<uint8_t>();
-    const uint8_t *verdict = base + L.o_verdict;
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(base + L.o_cnt), *off = reinterpret_cast<uint32_t *>(base + L.o_off);
-    const uint32_t nb = (uint32_t) ((n_events + PA_BLOCK_EVENTS - 1) / PA_BLOCK_EVENTS);
-    hipLaunchKernelGGL(noise_count_kernel, dim3(nb), dim3(NF_T), 0, st, verdict, (uint32_t) n_events, cnt);
+    const ecal_verdict_tables V = ecal_verdict_tables_at(ctx->noise_scratch.as<uint8_t>() + L.o_verdict, ecal_stream_blocks(n_events));
+    hipLaunchKernelGGL(noise_count_kernel, dim3(V.nb), dim3(NF_T), 0, st, (const uint8_t *) V.verdict, (uint32_t) n_events, V.cnt);
     tm.mark("count");
-    rc = ecal_compact_by_verdict(ctx, d_events, n_events, verdict, cnt, off, d_out, d_count, tm, st);
+    rc = ecal_compact_copy_by_verdict(ctx, d_events, n_events, V, d_out, d_count, tm, st);
     if (rc) return rc;
     if (tm.on) ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (ECAL_TRACE=load alone: the timer reads its events when it goes out of scope)
     return ECAL_OK;
@@ -281,40 +245,18 @@ extern "C" int ecal_stream_remove_noise(ecal_ctx *ctx, const ecal_stream *in, co
     if (rc) return rc;
     const uint8_t *d_in = ecal_stream_data(in);
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     // filter totals | count
     rc = ecal_ensure(ctx, ctx->noise_results, sizeof(ecal_filter_totals) + 8);
     if (rc) return rc;
-    ecal_filter_totals *d_tot = ctx->noise_results.as<ecal_filter_totals>();
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_tot + 1);
-    // the filter into records of the new stream's own (every event may stay)
-    uint8_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **) &d_out, (size_t) n * PA_RECORD_BYTES + 16);
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("ecal_stream_remove_noise: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? ECAL_ERR_NOMEM : ECAL_ERR_HIP;
-    }
     ecal_filter_totals T;
-    uint32_t kept = 0;
-    auto run = [&]() -> int {
-        const int frc = ecal_denoise_events_dev(ctx, d_in, n, opt, d_out, d_count, d_tot, st);
-        if (frc) return frc;
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&T, d_tot, sizeof(T), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
-    rc = run();
-    if (rc) {
-        (void) hipStreamSynchronize(st);
-        (void) hipFree(d_out);
-        return rc;
-    }
-    if (totals) *totals = T;
-    if (T.n_kept != kept || T.n_removed + T.n_kept != n) {
-        (void) hipFree(d_out);
-        ctx->last_error = "ecal_stream_remove_noise: the filter's counters disagree";
-        return ECAL_ERR_HIP;
-    }
-    return ecal_stream_adopt(ctx, d_out, kept, out);
+    return ecal_stream_compacted(
+        ctx, "ecal_stream_remove_noise", in, ctx->noise_results.ptr, &T, sizeof(T),
+        [&](uint8_t *d_out, uint32_t *d_count, void *d_totals, hipStream_t st) {
+            return ecal_denoise_events_dev(ctx, d_in, n, opt, d_out, d_count, (ecal_filter_totals *) d_totals, st);
+        },
+        [&](uint32_t kept, uint64_t n_in) -> const char * {
+            if (totals) *totals = T;
+            return T.n_kept != kept || T.n_removed + T.n_kept != n_in ? "the filter's counters disagree" : nullptr;
+        },
+        out);
 }

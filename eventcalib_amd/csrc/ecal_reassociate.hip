@@ -25,7 +25,7 @@
 #include "spline_residual.hpp"
 #pragma clang fp contract(off)
 #include "ecal_solver_state.hpp"
-#include "block_utils.hpp"
+#include "stream_compact.hpp"
 #include "board_nearest.hpp"
 #include "board_block.hpp"
 
@@ -34,8 +34,7 @@
 namespace ecal {
 
 constexpr uint32_t RA_NTOT = 5;    // words of ecal_reassociate_totals
-constexpr uint32_t RA_PER = BI_BLOCK / BI_T;   // consecutive events per thread in the writing pass
-static_assert(RA_PER == 16, "the writing pass reads a thread's verdicts as one 16-byte word");
+static_assert(BI_BLOCK == SC_BLOCK && BI_T == SC_T, "the writing pass reads its verdicts as the stream filters do (stream_compact.hpp)");
 
 template <bool SO3, bool FISHEYE>
 __global__ __launch_bounds__(BI_T, 2) void reassoc_verdict_kernel(const uint8_t *__restrict__ rec, uint64_t n_events,
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(BI_T, 2) void reassoc_verdict_kernel(const uint8_t 
     __shared__ uint32_t s_red[(BI_T / 64) * RA_NTOT];
     const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * BI_BLOCK;
-    const uint32_t count = (uint32_t) (n_events - base < (uint64_t) BI_BLOCK ? n_events - base : (uint64_t) BI_BLOCK);
+    const uint32_t count = stream_block_count(n_events, base);
     const uint8_t *const blk = rec + base * 25;
     for (uint32_t i = (uint32_t) tid; i < n_lm; i += BI_T) {   // (n_lm <= BI_MAX_LM: the entry point checks)
         s_lm[2 * i] = landmarks[3 * (size_t) i];
@@ -112,43 +111,27 @@ __global__ __launch_bounds__(BI_T) void reassoc_write_kernel(const uint8_t *__re
                                                             uint32_t *__restrict__ lm, uint32_t *__restrict__ seg) {
     __shared__ double s_seg[2 * BI_SEG_LDS];
     __shared__ uint32_t s_wsum[BI_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * BI_BLOCK;
-    const uint32_t count = (uint32_t) (n_events - base < (uint64_t) BI_BLOCK ? n_events - base : (uint64_t) BI_BLOCK);
+    const uint32_t count = stream_block_count(n_events, base);
     const bool seg_lds = n_seg <= BI_SEG_LDS;
     if (seg_lds && (uint32_t) tid < 2 * n_seg) s_seg[tid] = seg_range[tid];
-    const uint32_t k0 = (uint32_t) tid * RA_PER;
-    const uint4 w = *reinterpret_cast<const uint4 *>(verdict + base + k0);   // (16-byte aligned: base and k0 are multiples of 16)
+    const uint32_t k0 = (uint32_t) tid * SC_PER;
+    uint4 w;
+    const uint32_t bits = verdict_keep_bits<BOARD_NOT_KEPT>(verdict, base, k0, count, &w);
     const uint32_t words[4] = {w.x, w.y, w.z, w.w};
-    uint32_t mine = 0;
+    // the kept events in front of this thread's (thread order = event order; the barrier inside also publishes s_seg)
+    uint64_t at = (uint64_t) block_off[blockIdx.x] + block_exscan_u32<BI_T>((uint32_t) __popc(bits), s_wsum);
+    if (!bits) return;
 #pragma unroll
-    for (uint32_t e = 0; e < RA_PER; e++) {
-        const uint32_t v = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
-        mine += (k0 + e < count && v != BOARD_NOT_KEPT) ? 1u : 0u;
-    }
-    // exclusive scan of `mine` over the block (thread order = event order)
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();   // (... and s_seg)
-    uint32_t pre = 0;
-    for (int x = 0; x < wave; x++) pre += s_wsum[x];
-    uint64_t at = (uint64_t) block_off[blockIdx.x] + pre + inc - mine;
-    if (!mine) return;
-#pragma unroll
-    for (uint32_t e = 0; e < RA_PER; e++) {
-        const uint32_t v = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
-        if (k0 + e < count && v != BOARD_NOT_KEPT) {
+    for (uint32_t e = 0; e < SC_PER; e++) {
+        if (bits >> e & 1u) {
             const uint8_t *r = rec + (base + k0 + e) * 25;
             const double et = bi_load_f64(r);
             obs[2 * at] = bi_load_f64(r + 8);
             obs[2 * at + 1] = bi_load_f64(r + 16);
             time[at] = et;
-            lm[at] = v;
+            lm[at] = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
             seg[at] = (uint32_t) bi_segment_of(et, seg_lds ? s_seg : seg_range, n_seg);   // (kept: the time lies in a segment)
             at++;
         }
@@ -185,43 +168,31 @@ extern "C" int ecal_solver_reassociate_dev(ecal_solver *s, const double *d_param
         ctx->last_error = "ecal_solver_reassociate: null pointer (parameters, count, events or outputs)";
         return ECAL_ERR_INVALID;
     }
-    if (n_events > 0xFFFFFFFFull) {
-        ctx->last_error = "ecal_solver_reassociate: more than 2^32-1 events";
-        return ECAL_ERR_RANGE;
-    }
+    int rc = ecal_events_range_check(ctx, "ecal_solver_reassociate", n_events);
+    if (rc) return rc;
     double tol;
-    int rc = reassoc_tol(s, ring_tol, &tol);
-    if (rc) return rc;
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = reassoc_tol(s, ring_tol, &tol))) return rc;
     hipStream_t st = (hipStream_t) stream;
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
-    if (d_totals) ECAL_HIP_TRY(ctx, hipMemsetAsync(d_totals, 0, sizeof(ecal_reassociate_totals), st));
+    if ((rc = ecal_compact_begin(ctx, "ecal_solver_reassociate", d_events, n_events, nullptr, d_count, d_totals, sizeof(ecal_reassociate_totals), st)))
+        return rc;
     if (!n_events) return ECAL_OK;
-    const uint32_t nb = (uint32_t) ((n_events + BI_BLOCK - 1) / BI_BLOCK);
-    // verdicts (whole blocks) | counts [nb] | offsets [nb + 1]
-    const size_t o_cnt = (size_t) nb * BI_BLOCK, o_off = o_cnt + (size_t) nb * 4, total = o_off + ((size_t) nb + 1) * 4;
-    rc = ecal_ensure(ctx, ctx->reassoc_scratch, total);
-    if (rc) return rc;
-    uint8_t *verdict = ctx->reassoc_scratch.as<uint8_t>();
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(verdict + o_cnt), *off = reinterpret_cast<uint32_t *>(verdict + o_off);
+    ecal_verdict_tables V;
+    if ((rc = ecal_verdict_tables_ensure(ctx, ctx->reassoc_scratch, n_events, &V))) return rc;
     unsigned long long *tot = (unsigned long long *) d_totals;
 #define ECAL_RA_LAUNCH(SO3_, FISH_)                                                                                                      \
-    hipLaunchKernelGGL((reassoc_verdict_kernel<SO3_, FISH_>), dim3(nb), dim3(BI_T), 0, st, d_events, n_events,                            \
+    hipLaunchKernelGGL((reassoc_verdict_kernel<SO3_, FISH_>), dim3(V.nb), dim3(BI_T), 0, st, d_events, n_events,                          \
                        (const double *) s->d_knots, (const uint32_t *) s->d_knot_off, (const uint32_t *) s->d_cp_off, d_params,           \
-                       (const double *) s->d_seg_range, s->n_seg, s->n_cp, (const double *) s->d_landmarks, s->n_lm, s->radius, tol, verdict, cnt, tot)
+                       (const double *) s->d_seg_range, s->n_seg, s->n_cp, (const double *) s->d_landmarks, s->n_lm, s->radius, tol, V.verdict, V.cnt, tot)
     if (s->use_so3) {
         if (s->fisheye) ECAL_RA_LAUNCH(true, true); else ECAL_RA_LAUNCH(true, false);
     } else {
         if (s->fisheye) ECAL_RA_LAUNCH(false, true); else ECAL_RA_LAUNCH(false, false);
     }
 #undef ECAL_RA_LAUNCH
-    rc = ecal_scan_blocks(ctx, cnt, nb, off, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(reassoc_write_kernel, dim3(nb), dim3(BI_T), 0, st, d_events, n_events, (const uint8_t *) verdict,
-                       (const uint32_t *) off, (const double *) s->d_seg_range, s->n_seg, d_obs, d_time, d_lm_id, d_seg_id);
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, off + nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    ECAL_HIP_TRY(ctx, hipGetLastError());
-    return ECAL_OK;
+    return ecal_compact_by_verdict(ctx, V, d_count, nullptr, st, [&]() {
+        hipLaunchKernelGGL(reassoc_write_kernel, dim3(V.nb), dim3(BI_T), 0, st, d_events, n_events, (const uint8_t *) V.verdict,
+                           (const uint32_t *) V.off, (const double *) s->d_seg_range, s->n_seg, d_obs, d_time, d_lm_id, d_seg_id);
+    });
 }
 
 namespace {

@@ -7,10 +7,9 @@
 // workgroups:
 //   undistort_verdict_kernel   reads the 16 coordinate bytes of each record: a keep byte per event, the kept events per block, the totals
 //   ecal_scan_blocks           the blocks' first kept index (the association's)
-//   undistort_write_kernel     activity_write_kernel's sibling: ranks the kept events inside the block in event order, stages their
-//                              records in LDS a quarter of the block at a time — x and y RECOMPUTED there (about 25 f64 operations:
-//                              cheaper than carrying 16 more bytes an event through HBM between the passes) — and copies them out with
-//                              aligned 16-byte stores
+//   undistort_write_kernel     compact_write_block (stream_compact.hpp), the writing pass of the filters, with x and y RECOMPUTED
+//                              where a record is staged in LDS (about 25 f64 operations: cheaper than carrying 16 more bytes an event
+//                              through HBM between the passes)
 // Bytes per event: 16 read + 1 written in the verdict pass; 1 read in the writing pass, and per KEPT event 25 read + 25 written.
 // No per-pixel lookup table: the rule must hold for off-grid and sub-pixel inputs too, and the arithmetic is cheaper than the gather.
 //
@@ -21,41 +20,20 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "ecal_ctx.hpp"
-#include "pixel_activity.hpp"
+#include "stream_compact.hpp"
 #include "undistort_point.hpp"
 
 namespace ecal {
 
 using namespace ecal_undistort;
-using ecal_activity::PA_BLOCK_EVENTS;
 
-constexpr int UD_T = 256;
-constexpr uint32_t UD_BLOCK = PA_BLOCK_EVENTS;
-constexpr uint32_t UD_PER = UD_BLOCK / UD_T;       // consecutive events per thread where the verdicts are ranked
-constexpr uint32_t UD_CHUNK = 1024;                // records staged in LDS at a time (25 600 bytes)
-constexpr uint32_t UD_GROUPS = UD_CHUNK / UD_PER;  // threads' runs per chunk
-static_assert(UD_PER == 16, "the writing pass reads a thread's verdicts as one 16-byte word, its keep bits as 16 bits");
-static_assert(UD_BLOCK % UD_CHUNK == 0 && UD_CHUNK % UD_T == 0, "whole chunks, whole rounds of the workgroup");
-static_assert(UD_RECORD_BYTES == ecal_activity::PA_RECORD_BYTES, "one record layout");
+constexpr int UD_T = SC_T;
+constexpr uint32_t UD_BLOCK = SC_BLOCK;
+static_assert(UD_RECORD_BYTES == SC_RECORD, "one record layout");
 
 constexpr uint32_t UF_T = 256;
 constexpr uint32_t UF_LDS_WORDS = 8192;            // 32 KB of presence bits: canvases up to 131 072 pixels (the reference's 415 x 312 = 129 480)
 constexpr uint32_t UF_PIXELS_PER_WORD = 16;
-
-__device__ __forceinline__ uint32_t ud_block_count(uint64_t n_events, uint64_t base) {
-    return (uint32_t) (n_events - base < (uint64_t) UD_BLOCK ? n_events - base : (uint64_t) UD_BLOCK);
-}
-
-// the sum of v over the workgroup, for every thread (s_red: T / 64 words; one barrier)
-template <int T>
-__device__ __forceinline__ uint32_t ud_block_sum(uint32_t v, uint32_t *s_red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < T / 64; w++) t += s_red[w];
-    return t;
-}
 
 // uv [n][2], flag [n]: the rule per record (0, 0 and flag 1 where invalid)
 __global__ __launch_bounds__(UD_T) void undistort_points_kernel(const Camera cam, const uint8_t *__restrict__ rec, uint32_t n_events,
@@ -78,7 +56,7 @@ __global__ __launch_bounds__(UD_T) void undistort_verdict_kernel(const Camera ca
     __shared__ uint32_t s_red[3][UD_T / 64];
     const int tid = threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * UD_BLOCK;
-    const uint32_t count = ud_block_count(n_events, base);
+    const uint32_t count = stream_block_count(n_events, base);
     const uint8_t *const blk = rec + base * UD_RECORD_BYTES;
     uint32_t keep = 0, inv = 0, outside = 0;
     for (uint32_t k = (uint32_t) tid; k < count; k += UD_T) {
@@ -90,9 +68,9 @@ __global__ __launch_bounds__(UD_T) void undistort_verdict_kernel(const Camera ca
         inv += what == UD_INVALID ? 1u : 0u;
         outside += what == UD_OUTSIDE ? 1u : 0u;
     }
-    keep = ud_block_sum<UD_T>(keep, s_red[0]);
-    inv = ud_block_sum<UD_T>(inv, s_red[1]);
-    outside = ud_block_sum<UD_T>(outside, s_red[2]);
+    keep = block_sum<UD_T>(keep, s_red[0]);
+    inv = block_sum<UD_T>(inv, s_red[1]);
+    outside = block_sum<UD_T>(outside, s_red[2]);
     if (tid == 0) block_cnt[blockIdx.x] = keep;
     if (!totals) return;
     if (tid == 0) atomicAdd(&totals[0], (unsigned long long) count);
@@ -105,86 +83,20 @@ __global__ __launch_bounds__(UD_T) void undistort_verdict_kernel(const Camera ca
 __global__ __launch_bounds__(UD_T) void undistort_write_kernel(const Camera cam, const Options opt, const uint8_t *__restrict__ rec,
                                                                uint64_t n_events, const uint8_t *__restrict__ verdict,
                                                                const uint32_t *__restrict__ block_off, uint8_t *__restrict__ out) {
-    __shared__ uint32_t s_pre[UD_T];      // the block's kept events in front of every thread's run
-    __shared__ uint32_t s_bits[UD_T];     // the run's keep bits
-    __shared__ uint32_t s_wsum[UD_T / 64];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[UD_CHUNK * UD_RECORD_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t base = (uint64_t) blockIdx.x * UD_BLOCK;
-    const uint32_t count = ud_block_count(n_events, base);
-    const uint32_t k0 = (uint32_t) tid * UD_PER;
-    const uint4 w = *reinterpret_cast<const uint4 *>(verdict + base + k0);   // (16-byte aligned: base and k0 are multiples of 16)
-    const uint32_t words[4] = {w.x, w.y, w.z, w.w};
-    uint32_t bits = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < UD_PER; e++) {
-        const uint32_t v = (words[e >> 2] >> (8u * (e & 3u))) & 0xFFu;
-        bits |= (k0 + e < count && v != 0u) ? 1u << e : 0u;
-    }
-    const uint32_t mine = (uint32_t) __popc(bits);
-    // exclusive scan of `mine` over the block (thread order = event order)
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    uint32_t pre = 0, ktot = 0;
-    for (int x = 0; x < UD_T / 64; x++) {
-        if (x < wave) pre += s_wsum[x];
-        ktot += s_wsum[x];
-    }
-    s_pre[tid] = pre + inc - mine;
-    s_bits[tid] = bits;
-    __syncthreads();
-    if (!ktot) return;   // (the same for every thread)
-    uint8_t *const dst_blk = out + (uint64_t) block_off[blockIdx.x] * UD_RECORD_BYTES;
-    for (uint32_t q = 0; q * UD_CHUNK < count; q++) {
-        // the kept events in front of chunk q and behind it, in the block
-        const uint32_t r0 = s_pre[q * UD_GROUPS], r1 = (q + 1) * UD_CHUNK < UD_BLOCK ? s_pre[(q + 1) * UD_GROUPS] : ktot;
-        if (r1 == r0) continue;   // (the same for every thread; no barrier is skipped that another thread reaches)
-        // pack: lanes next to each other take events next to each other; x and y are replaced on the way into LDS
-#pragma unroll
-        for (uint32_t i = 0; i < UD_CHUNK / UD_T; i++) {
-            const uint32_t k = q * UD_CHUNK + i * UD_T + (uint32_t) tid, g = k / UD_PER, b = k % UD_PER;
-            const uint32_t m = s_bits[g];
-            if (m >> b & 1u) {   // (kept: k < count)
-                const uint32_t rank = s_pre[g] + (uint32_t) __popc(m & ((1u << b) - 1u)) - r0;   // < UD_CHUNK
-                const uint8_t *r = rec + (base + k) * UD_RECORD_BYTES;
-                uint8_t *d = s_rec + rank * UD_RECORD_BYTES;
-                uint64_t a0;
-                double x, y, ox = 0.0, oy = 0.0;
-                __builtin_memcpy(&a0, r, 8);
-                __builtin_memcpy(&x, r + 8, 8);
-                __builtin_memcpy(&y, r + 16, 8);
-                const uint8_t a3 = r[24];
-                (void) ud_event(cam, opt, x, y, &ox, &oy);   // (UD_KEPT: the verdict pass saw the same bytes)
-                __builtin_memcpy(d, &a0, 8);
-                __builtin_memcpy(d + 8, &ox, 8);
-                __builtin_memcpy(d + 16, &oy, 8);
-                d[24] = a3;
-            }
-        }
-        __syncthreads();
-        // copy-out: bytes up to the first 16-byte boundary of the destination, whole 16-byte words, the bytes behind them
-        uint8_t *dst = dst_blk + (size_t) r0 * UD_RECORD_BYTES;
-        const uint32_t nbytes = (r1 - r0) * UD_RECORD_BYTES;
-        uint32_t head = (uint32_t) ((16u - ((uintptr_t) dst & 15u)) & 15u);
-        head = head < nbytes ? head : nbytes;
-        const uint32_t nw = (nbytes - head) / 16u;
-        if ((uint32_t) tid < head) dst[tid] = s_rec[tid];
-        for (uint32_t j = (uint32_t) tid; j < nw; j += UD_T) {
-            const uint32_t at = head + 16u * j;
-            uint4 v;
-            __builtin_memcpy(&v, s_rec + at, 16);
-            *reinterpret_cast<uint4 *>(dst + at) = v;
-        }
-        const uint32_t tail0 = head + 16u * nw;
-        if (tail0 + (uint32_t) tid < nbytes) dst[tail0 + tid] = s_rec[tail0 + tid];   // (fewer than 16 bytes)
-        __syncthreads();
-    }
+    // x and y are replaced on the way into LDS
+    compact_write_block(rec, n_events, verdict, block_off, out, [&](const uint8_t *r, uint8_t *d) {
+        uint64_t a0;
+        double x, y, ox = 0.0, oy = 0.0;
+        __builtin_memcpy(&a0, r, 8);
+        __builtin_memcpy(&x, r + 8, 8);
+        __builtin_memcpy(&y, r + 16, 8);
+        const uint8_t a3 = r[24];
+        (void) ud_event(cam, opt, x, y, &ox, &oy);   // (UD_KEPT: the verdict pass saw the same bytes)
+        __builtin_memcpy(d, &a0, 8);
+        __builtin_memcpy(d + 8, &ox, 8);
+        __builtin_memcpy(d + 16, &oy, 8);
+        d[24] = a3;
+    });
 }
 
 // Window s = blockIdx.x.  bits: the window's n_words presence words (LDS: the kernel's own, zeroed here; else g_bits + s * n_words,
@@ -232,8 +144,8 @@ __global__ __launch_bounds__(UF_T) void undistorted_frames_kernel(const Camera c
         }
     }
     if (frame_totals) {
-        const uint32_t a = ud_block_sum<UF_T>(painted[0], s_red[0]), b = ud_block_sum<UF_T>(painted[1], s_red[1]);
-        const uint32_t c = ud_block_sum<UF_T>(inv, s_red[2]), d = ud_block_sum<UF_T>(outside, s_red[3]);
+        const uint32_t a = block_sum<UF_T>(painted[0], s_red[0]), b = block_sum<UF_T>(painted[1], s_red[1]);
+        const uint32_t c = block_sum<UF_T>(inv, s_red[2]), d = block_sum<UF_T>(outside, s_red[3]);
         if (tid == 0) frame_totals[s] = FrameTotals{a, b, c, d};
     }
     __syncthreads();   // (the atomics of this workgroup: LDS, or device memory no other workgroup touches)
@@ -331,11 +243,7 @@ static int undistort_check(ecal_ctx *ctx, const char *who, const ecal_undistort_
             ctx->last_error = std::string(who) + ": " + bad;
             return ECAL_ERR_INVALID;
         }
-    if (n_events > 0xFFFFFFFFull) {
-        ctx->last_error = std::string(who) + ": more than 2^32-1 events";
-        return ECAL_ERR_RANGE;
-    }
-    return ECAL_OK;
+    return ecal_events_range_check(ctx, who, n_events);
 }
 
 extern "C" int ecal_undistort_points_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, const uint8_t *d_events, uint64_t n_events, double *d_uv,
@@ -369,36 +277,22 @@ extern "C" int ecal_undistort_events_dev(ecal_ctx *ctx, const ecal_undistort_cam
     const Options o = ud_options(opt);
     int rc = undistort_check(ctx, "ecal_undistort_events", cam, &o, n_events);
     if (rc) return rc;
-    const size_t bytes = (size_t) n_events * UD_RECORD_BYTES;
-    if (n_events && d_events < d_out + bytes && d_out < d_events + bytes) {
-        ctx->last_error = "ecal_undistort_events: the output overlaps the events";
-        return ECAL_ERR_INVALID;
-    }
-    ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t) stream;
-    ECAL_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
-    if (d_totals) ECAL_HIP_TRY(ctx, hipMemsetAsync(d_totals, 0, sizeof(ecal_undistort_totals), st));
+    if ((rc = ecal_compact_begin(ctx, "ecal_undistort_events", d_events, n_events, d_out, d_count, d_totals, sizeof(ecal_undistort_totals), st))) return rc;
     if (!n_events) return ECAL_OK;
-    const uint32_t nb = (uint32_t) ((n_events + UD_BLOCK - 1) / UD_BLOCK);
-    // verdicts (whole blocks) | counts [nb] | offsets [nb + 1]
-    const size_t o_cnt = (size_t) nb * UD_BLOCK, o_off = o_cnt + (size_t) nb * 4, total = o_off + ((size_t) nb + 1) * 4;
-    rc = ecal_ensure(ctx, ctx->undistort_scratch, total);
-    if (rc) return rc;
-    uint8_t *verdict = ctx->undistort_scratch.as<uint8_t>();
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(verdict + o_cnt), *off = reinterpret_cast<uint32_t *>(verdict + o_off);
+    ecal_verdict_tables V;
+    if ((rc = ecal_verdict_tables_ensure(ctx, ctx->undistort_scratch, n_events, &V))) return rc;
     const Camera c = ud_camera(cam);
     ecal_load_timer tm("undistort", ctx->sw.load_trace, st);
     tm.mark("start");
-    hipLaunchKernelGGL(undistort_verdict_kernel, dim3(nb), dim3(UD_T), 0, st, c, o, d_events, n_events, verdict, cnt, (unsigned long long *) d_totals);
+    hipLaunchKernelGGL(undistort_verdict_kernel, dim3(V.nb), dim3(UD_T), 0, st, c, o, d_events, n_events, V.verdict, V.cnt,
+                       (unsigned long long *) d_totals);
     tm.mark("verdict");
-    rc = ecal_scan_blocks(ctx, cnt, nb, off, st);
+    rc = ecal_compact_by_verdict(ctx, V, d_count, &tm, st, [&]() {
+        hipLaunchKernelGGL(undistort_write_kernel, dim3(V.nb), dim3(UD_T), 0, st, c, o, d_events, n_events, (const uint8_t *) V.verdict,
+                           (const uint32_t *) V.off, d_out);
+    });
     if (rc) return rc;
-    tm.mark("scan");
-    hipLaunchKernelGGL(undistort_write_kernel, dim3(nb), dim3(UD_T), 0, st, c, o, d_events, n_events, (const uint8_t *) verdict, (const uint32_t *) off,
-                       d_out);
-    tm.mark("write");
-    ECAL_HIP_TRY(ctx, hipMemcpyAsync(d_count, off + nb, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    ECAL_HIP_TRY(ctx, hipGetLastError());
     if (tm.on) ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));   // (ECAL_TRACE=load alone: the timer reads its events when it goes out of scope)
     return ECAL_OK;
 }
@@ -414,37 +308,20 @@ extern "C" int ecal_stream_undistort(ecal_ctx *ctx, const ecal_stream *in, const
     if (rc) return rc;
     const uint8_t *d_in = ecal_stream_data(in);
     ECAL_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     // totals | count
     rc = ecal_ensure(ctx, ctx->undistort_results, sizeof(ecal_undistort_totals) + 8);
     if (rc) return rc;
-    ecal_undistort_totals *d_tot = ctx->undistort_results.as<ecal_undistort_totals>();
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_tot + 1);
-    // the records of the new stream's own (every event may stay)
-    uint8_t *d_out = nullptr;
-    rc = ecal_ingest_alloc_records(ctx, "ecal_stream_undistort", n, &d_out);
-    if (rc) return rc;
     ecal_undistort_totals T;
-    uint32_t kept = 0;
-    auto run = [&]() -> int {
-        const int frc = ecal_undistort_events_dev(ctx, cam, opt, d_in, n, d_out, d_count, d_tot, st);
-        if (frc) return frc;
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&T, d_tot, sizeof(T), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&kept, d_count, sizeof(kept), hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        return ECAL_OK;
-    };
-    rc = run();
-    if (rc) {
-        (void) hipStreamSynchronize(st);
-        return ecal_ingest_drop_records(&d_out, rc);
-    }
-    if (totals) *totals = T;
-    if (T.n_kept != kept || T.n_invalid + T.n_outside + T.n_kept != n) {
-        ctx->last_error = "ecal_stream_undistort: the counters disagree";
-        return ecal_ingest_drop_records(&d_out, ECAL_ERR_HIP);
-    }
-    return ecal_stream_from_events(ctx, "ecal_stream_undistort", d_out, kept, out);
+    return ecal_stream_compacted(
+        ctx, "ecal_stream_undistort", in, ctx->undistort_results.ptr, &T, sizeof(T),
+        [&](uint8_t *d_out, uint32_t *d_count, void *d_totals, hipStream_t st) {
+            return ecal_undistort_events_dev(ctx, cam, opt, d_in, n, d_out, d_count, (ecal_undistort_totals *) d_totals, st);
+        },
+        [&](uint32_t kept, uint64_t n_in) -> const char * {
+            if (totals) *totals = T;
+            return T.n_kept != kept || T.n_invalid + T.n_outside + T.n_kept != n_in ? "the counters disagree" : nullptr;
+        },
+        out);
 }
 
 extern "C" int ecal_undistorted_frames_dev(ecal_ctx *ctx, const ecal_undistort_camera *cam, const ecal_undistort_options *opt, const double *d_xy,
