@@ -5,5 +5,6 @@ ctypes binding used by the tests and ``bench.py``.  There is no CPU fallback: im
 ``eventcalib_amd.capi`` and calling into it without the built library raises.
 """
 from .capi import Context, EcalError, lib_path, load_library  # noqa: F401
+from . import uncertainty  # noqa: F401  (attaches Solver.uncertainty / chunk_scores / chunk_table; sets no prototype until used)
 
 __all__ = ["Context", "EcalError", "lib_path", "load_library"]

@@ -286,7 +286,7 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
                      flags=None, aspect_ratio=1.0, use_so3=False, max_num_iterations=50, eps=4.0, minpts=2,
                      gate_mode=capi.GATE_SHARED_MAP, fisheye=False, tables=False, report=False, board_image=False,
                      refine_rounds=0, refine_ring_tol=None, hot_pixels=None, noise_filter=None, undistort=None, undistort_maps=None,
-                     report_px=False):
+                     report_px=False, uncertainty=False):
     """events: uint8 CUDA tensor of packed 25-byte records.  Returns a dict with the initial calibration, the refined
     intrinsics [fx fy cx cy k1..k5 (inverse radial polynomial)] and the keyframe trajectory.
     width, height: the sensor's size.  It goes to the init calibration, to rectify and to the report, and the circle radius threshold
@@ -310,6 +310,9 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
     report_px (opt-in, default False: nothing changes): the same report in PIXELS (capi.Solver.report_px: per residual the
     first-order distance from the event to the projected rim; `rms_px`, `px_per_unit`, `n_degenerate` beside the families) into
     out["report_px"] — a stage of its own, `report_px` (design/23_report_px.md).
+    uncertainty (opt-in, default False: nothing changes; True or dict(cluster_spans=n)): the formal and the cluster-robust
+    covariance of the nine intrinsics at the solution (uncertainty.solver_uncertainty: sigma, sigma_robust, corr, inflation and
+    the validity flags) into out["uncertainty"] — a stage of its own, `uncertainty` (design/24_uncertainty.md).
     board_image: also carry EVERY event of the stream through the solution onto the board (capi.Solver.board_image: the
     motion-compensated image per polarity and the ring profile of every circle) into out["board_image"] — a stage of its own,
     `board_image`.
@@ -562,6 +565,12 @@ def calibrate_stream(ctx, events, t_first, t_last, *, motion_time_step=5e-4, fra
         mark("lm_solve")
         out["report_px"] = solver.report_px(x, kf["time"][kf_idx], width=int(width), height=int(height))
         mark("report_px")
+    if uncertainty:
+        mark("lm_solve")
+        from . import uncertainty as _uncertainty
+        spans = int(uncertainty.get("cluster_spans", 1)) if isinstance(uncertainty, dict) else 1
+        out["uncertainty"] = _uncertainty.solver_uncertainty(solver, x, cluster_spans=spans)
+        mark("uncertainty")
     if board_image:
         mark("lm_solve")
         out["board_image"] = solver.board_image(x, events)

@@ -33,26 +33,7 @@ struct ReportPxArgs {
     double *cell_sum_r2;
 };
 
-// the chunk's constants of both kernels: intrinsics, span inverses, the four control points
-struct ChunkPose {
-    double q[4][4], t[4][3], pin[9], binv[6], ifx, ify;
-    const double *kn;
-    __device__ __forceinline__ void load(const Chunk &ch, const double *knots, const uint32_t *knot_off, const uint32_t *cp_off,
-                                         const double *params, uint32_t n_cp_total) {
-        kn = knots + knot_off[ch.seg];
-        const uint32_t c0 = cp_off[ch.seg] + ch.span - 3;
-        const double *qall = params + 9;
-        const double *tall = params + 9 + 4 * (size_t) n_cp_total;
-        for (int i = 0; i < 9; i++) pin[i] = params[i];
-        spline_span_inverses(kn, ch.span, binv);
-        ifx = 1.0 / pin[0];
-        ify = 1.0 / pin[1];
-        for (int j = 0; j < 4; j++) {
-            for (int k = 0; k < 4; k++) q[j][k] = qall[4 * (size_t) (c0 + j) + k];
-            for (int k = 0; k < 3; k++) t[j][k] = tall[3 * (size_t) (c0 + j) + k];
-        }
-    }
-};
+// (the chunk's constants of both kernels, ChunkPose: ecal_solver_state.hpp)
 
 // r and g = d r / d (u, v) of one record
 template <bool SO3, bool FISHEYE>

@@ -1227,3 +1227,37 @@ extern "C" int ecal_debug_arrow_solve(ecal_solver *s, const double *accum, const
     return ecal_debug_arrow_solve_host(s->n_cp, accum, scale, radius, min_diag, max_diag, delta_out, fail_out, mode, 0);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Uncertainty of the intrinsics (include/ecal_uncertainty.h): one evaluation with Jacobian and the per-chunk score sums
+// (ecal_uncertainty.hip) on the device, the covariance from the banded-arrow system on the host (arrow_covariance.hpp).
+// Only the accumulation buffer, the chunk table and the chunk scores cross to the host.
+// ------------------------------------------------------------------------------------------------
+#include "../../include/ecal_uncertainty.h"
+namespace {
+#include "arrow_covariance.hpp"
+}
+
+extern "C" int ecal_solver_uncertainty(ecal_solver *s, const double *params, const ecal_uncertainty_options *opt_in,
+                                       ecal_uncertainty_result *out) {
+    if (!s || !params || !out) return ECAL_ERR_INVALID;
+    ecal_ctx *ctx = s->ctx;
+    ecal_uncertainty_options opt;
+    if (opt_in) opt = *opt_in; else ecal_uncertainty_default_options(&opt);
+    if (opt.cluster_spans < 1 || opt.reserved != 0) {
+        ctx->last_error = "ecal_solver_uncertainty: cluster_spans at least 1, reserved 0";
+        return ECAL_ERR_INVALID;
+    }
+    std::vector<double> accum(s->n_accum()), score((size_t) s->n_chunks * RES_NJ);
+    std::vector<uint32_t> table(4 * (size_t) s->n_chunks);
+    int rc = ecal_solver_evaluate(s, params, 1, accum.data());
+    if (rc) return rc;
+    rc = ecal_solver_chunk_scores(s, params, score.data(), nullptr);
+    if (rc) return rc;
+    rc = ecal_solver_chunk_table(s, table.data());
+    if (rc) return rc;
+    static_assert(sizeof(ScoreChunk) == 4 * sizeof(uint32_t), "the chunk table's rows");
+    arrow_uncertainty(accum.data(), s->n_cp, s->n_res, reinterpret_cast<const ScoreChunk *>(table.data()), score.data(), s->n_chunks,
+                      opt.cluster_spans, out);
+    return ECAL_OK;
+}

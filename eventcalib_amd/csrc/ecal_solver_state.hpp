@@ -103,5 +103,27 @@ __device__ __forceinline__ void residual_input_fill(ResidualInput &in, const Res
     in.ify = ify;
     spline_basis_inv(kn, span, binv, e.t, in.b);
 }
+
+// the chunk's constants: intrinsics, span inverses, the four control points.  The kernels of ecal_report_px.hip and
+// ecal_uncertainty.hip load them through this; the solver's own kernels write the same lines out (ecal_solver.hip says why).
+struct ChunkPose {
+    double q[4][4], t[4][3], pin[9], binv[6], ifx, ify;
+    const double *kn;
+    __device__ __forceinline__ void load(const Chunk &ch, const double *knots, const uint32_t *knot_off, const uint32_t *cp_off,
+                                         const double *params, uint32_t n_cp_total) {
+        kn = knots + knot_off[ch.seg];
+        const uint32_t c0 = cp_off[ch.seg] + ch.span - 3;
+        const double *qall = params + 9;
+        const double *tall = params + 9 + 4 * (size_t) n_cp_total;
+        for (int i = 0; i < 9; i++) pin[i] = params[i];
+        spline_span_inverses(kn, ch.span, binv);
+        ifx = 1.0 / pin[0];
+        ify = 1.0 / pin[1];
+        for (int j = 0; j < 4; j++) {
+            for (int k = 0; k < 4; k++) q[j][k] = qall[4 * (size_t) (c0 + j) + k];
+            for (int k = 0; k < 3; k++) t[j][k] = tall[3 * (size_t) (c0 + j) + k];
+        }
+    }
+};
 }  // namespace ecal
 #endif

@@ -14,6 +14,7 @@
 #include <iomanip>
 
 #include "event_calib_ini.hpp"
+#include "../../../include/ecal_uncertainty.h"
 
 namespace opengv2 {
 
@@ -71,6 +72,16 @@ public:
             for (uint64_t n : cell_n) empty += n == 0;
             return cell_n.empty() ? 0.0 : (double) empty / (double) cell_n.size();
         }
+    };
+
+    // The uncertainty of the nine intrinsics (ecal_solver_uncertainty, include/ecal_uncertainty.h) at the solution, on the records the
+    // solve ran on: the formal covariance s2 (H^-1)_intr and the cluster-robust one (clusters of clusterSpans knot spans), sigmas,
+    // correlations and the ratio of the two sigmas.  Filled when the constructor is given uncertaintyClusterSpans >= 1; valid = false
+    // otherwise.  The flags of `result` say which of its parts hold numbers.
+    struct Uncertainty {
+        bool valid = false;
+        uint32_t clusterSpans = 0;
+        ecal_uncertainty_result result{};
     };
 
     // The board-frame event image (ecal_solver_board_image) at the solution: every event of the stream carried through the
@@ -150,11 +161,12 @@ public:
                      bool fisheye = false, const ecal_report_options *reportOptions = nullptr, bool wantBoardImage = false,
                      int refineRounds = 0, double refineRingTol = 0.0 /* board units; <= 0: the Huber width */,
                      bool keepEvents = false /* the container's device stream outlives the solve (the caller undistorts it) */,
-                     const ecal_report_options *reportPxOptions = nullptr)
+                     const ecal_report_options *reportPxOptions = nullptr, int uncertaintyClusterSpans = 0 /* >= 1: uncertainty() is filled */)
         : frames_(std::move(frames)), eventContainer_(std::move(eventContainer)), pattern_(std::move(pattern)), useSO3_(useSO3),
           fisheye_(fisheye), motionTimeStep_(motionTimeStep), circleRadius_(pattern_->circleRadius), maxIterations_(maxIterations),
           wantBoardImage_(wantBoardImage), refineRounds_(refineRounds > 0 ? refineRounds : 0), refineRingTol_(refineRingTol),
           keepEvents_(keepEvents) {
+        uncertainty_.clusterSpans = uncertaintyClusterSpans > 0 ? (uint32_t) uncertaintyClusterSpans : 0u;
         if (reportOptions) {
             report_.options = *reportOptions;
             wantReport_ = true;
@@ -217,6 +229,7 @@ public:
     const Summary &summary() const { return summary_; }
     const Report &report() const { return report_; }
     const ReportPx &reportPx() const { return reportPx_; }
+    const Uncertainty &uncertainty() const { return uncertainty_; }
     const BoardImage &boardImage() const { return boardImage_; }
     const std::vector<RefineRound> &refine() const { return refine_; }
     size_t splineNum() const { return segments_.size(); }
@@ -389,6 +402,18 @@ private:
                 throw std::runtime_error(std::string("ecal_solver_report_px: ") + ecal_last_error(ctx));
             }
         }
+        if (rc == ECAL_OK && uncertainty_.clusterSpans) {   // the same records: how well they determine the intrinsics
+            ecal_uncertainty_options uo;
+            ecal_uncertainty_default_options(&uo);
+            uo.cluster_spans = uncertainty_.clusterSpans;
+            rc = ecal_solver_uncertainty(solver, x.data(), &uo, &uncertainty_.result);
+            uncertainty_.valid = rc == ECAL_OK;
+            if (rc != ECAL_OK) {
+                ecal_solver_destroy(solver);
+                if (keepStream) eventContainer_->release();
+                throw std::runtime_error(std::string("ecal_solver_uncertainty: ") + ecal_last_error(ctx));
+            }
+        }
         if (rc == ECAL_OK && wantBoardImage_) {   // every event of the stream through the solution
             BoardImage &b = boardImage_;
             (void) ecal_board_image_default_options(solver, &b.options);
@@ -448,6 +473,7 @@ private:
     bool wantReport_ = false;
     ReportPx reportPx_;
     bool wantReportPx_ = false;
+    Uncertainty uncertainty_;
     BoardImage boardImage_;
     bool wantBoardImage_ = false;
     int refineRounds_ = 0;

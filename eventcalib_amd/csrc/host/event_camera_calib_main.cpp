@@ -394,6 +394,15 @@ int main(int argc, char **argv) {
     ecal_report_px_default_options(&reportPxOptions);
     reportPxOptions.width = (uint32_t) width;
     reportPxOptions.height = (uint32_t) height;
+    // CalibrationUncertainty / CalibrationUncertainty_ClusterSpans (keys of this build, optional): 1 = the formal and the cluster-robust
+    // covariance of the nine intrinsics at the solution (ecal_solver_uncertainty, include/ecal_uncertainty.h; clusters of
+    // CalibrationUncertainty_ClusterSpans knot spans, absent or < 1: 1) written to saveDir/CalibrationUncertainty.txt, and the per-pixel
+    // sigma of the bearing under the robust covariance (the formal one where the robust one is not valid) to
+    // saveDir/uncertainty_sigma_px.npy (f32 (height, width), 0 where the model is invalid); absent or 0: nothing changes
+    int wantUncertainty = 0, uncertaintyClusterSpans = 1;
+    fsSettings["CalibrationUncertainty"] >> wantUncertainty;
+    fsSettings["CalibrationUncertainty_ClusterSpans"] >> uncertaintyClusterSpans;
+    if (uncertaintyClusterSpans < 1) uncertaintyClusterSpans = 1;
     // BoardImage (a key of this build, optional): 1 = every event of the stream carried through the solution onto the board
     // (ecal_solver_board_image), written to saveDir/board_image.png and saveDir/BoardImage.txt; absent or 0: nothing changes
     int wantBoardImage = 0;
@@ -425,7 +434,8 @@ int main(int argc, char **argv) {
     fsSettings["UndistortMaps"] >> wantUndistortMaps;
     fsSettings["UndistortMaps_Reference"] >> wantUndistortMapsReference;
     EventCalibSpline spline(frames, container, pattern, useSO3, step, res.K, dist5, 50, cs->useFisheye, wantReport ? &reportOptions : nullptr,
-                            wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort, wantReportPx ? &reportPxOptions : nullptr);
+                            wantBoardImage != 0, refineRounds, refineRingTol, wantUndistort, wantReportPx ? &reportPxOptions : nullptr,
+                            wantUncertainty ? uncertaintyClusterSpans : 0);
     const double *x = spline.intrinsics();
     std::printf("refined %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g residuals %zu iterations %d splines %zu\n", x[0], x[1], x[2], x[3],
                 x[4], x[5], x[6], x[7], x[8], spline.summary().residuals, spline.summary().iterations, spline.splineNum());
@@ -642,6 +652,62 @@ int main(int argc, char **argv) {
         std::fclose(f);
         std::printf("report_px rms_px %.9g px_per_unit %.9g outliers %.6f degenerate %llu\n", rp.rmsPx(), rp.pxPerUnit(), rp.outlierFraction(),
                     (unsigned long long) rp.totals.n_degenerate);
+    }
+    if (wantUncertainty && spline.uncertainty().valid) {
+        const ecal_uncertainty_result &u = spline.uncertainty().result;
+        static const char *const names[9] = {"fx", "fy", "cx", "cy", "k1", "k2", "k3", "k4", "k5"};
+        std::FILE *f = std::fopen((std::string(argv[3]) + "/CalibrationUncertainty.txt").c_str(), "w");
+        if (!f) {
+            std::fprintf(stderr, "cannot write %s/CalibrationUncertainty.txt\n", argv[3]);
+            return 3;
+        }
+        std::fprintf(f, "# sigma: formal, s2 (H^-1)_intr, assumes independent residuals; sigma_robust: clusters of %u knot span(s); inflation = sigma_robust / sigma\n",
+                     spline.uncertainty().clusterSpans);
+        std::fprintf(f, "counts n_res %llu n_unknowns %u n_cp %u n_chunks %u n_clusters %u cluster_spans %u\n", (unsigned long long) u.n_res, u.n_unknowns,
+                     u.n_cp, u.n_chunks, u.n_clusters, spline.uncertainty().clusterSpans);
+        std::fprintf(f, "flags positive_definite %u formal_valid %u robust_valid %u\n", u.positive_definite, u.formal_valid, u.robust_valid);
+        std::fprintf(f, "cost %.17g s2 %.17g\n", u.cost, u.s2);
+        for (int i = 0; i < 9; i++)
+            std::fprintf(f, "intrinsic %s value %.17g sigma %.17g sigma_robust %.17g inflation %.9g\n", names[i], x[i], u.sigma[i], u.sigma_robust[i],
+                         u.inflation[i]);
+        std::fprintf(f, "correlation 9\n");
+        for (int i = 0; i < 9; i++) {
+            for (int j = 0; j < 9; j++) std::fprintf(f, j ? " %.17g" : "%.17g", u.corr[9 * i + j]);
+            std::fprintf(f, "\n");
+        }
+        if (!u.positive_definite)
+            std::fprintf(f, "# the normal matrix is not positive definite (a control point without residuals?): nothing below is a number\n");
+        else if (!u.formal_valid || !u.robust_valid)
+            std::fprintf(f, "# nan below: %s%s\n", u.formal_valid ? "" : "no formal figures (n_res <= n_unknowns) ",
+                         u.robust_valid ? "" : "no robust figures (fewer than two clusters)");
+        std::fprintf(f, "correlation_robust 9\n");   // cov_robust[i][j] / (sigma_robust[i] sigma_robust[j])
+        for (int i = 0; i < 9; i++) {
+            for (int j = 0; j < 9; j++) std::fprintf(f, j ? " %.17g" : "%.17g", u.cov_robust[9 * i + j] / (u.sigma_robust[i] * u.sigma_robust[j]));
+            std::fprintf(f, "\n");
+        }
+        std::fclose(f);
+        const bool robust = u.robust_valid != 0;
+        double worst = 0.0;
+        if (u.positive_definite && (robust || u.formal_valid)) {
+            std::vector<double> sig((size_t) width * (size_t) height);
+            std::vector<uint8_t> flag(sig.size());
+            const int rc = ecal_uncertainty_map_host(cs->useFisheye ? ECAL_CAMERA_FISHEYE : ECAL_CAMERA_RADIAL, x, robust ? u.cov_robust : u.cov,
+                                                     (uint32_t) width, (uint32_t) height, sig.data(), flag.data(), nullptr);
+            if (rc != ECAL_OK) {
+                std::fprintf(stderr, "ecal_uncertainty_map_host: %s\n", ecal_strerror(rc));
+                return 3;
+            }
+            std::vector<float> sig32(sig.begin(), sig.end());
+            for (double v : sig) worst = std::max(worst, v);
+            if (!ecal_host::write_npy_f32(std::string(argv[3]) + "/uncertainty_sigma_px.npy", (size_t) height, (size_t) width, sig32.data())) {
+                std::fprintf(stderr, "cannot write %s/uncertainty_sigma_px.npy\n", argv[3]);
+                return 3;
+            }
+        }
+        double maxInflation = std::nan("");   // (NaN unless both covariances hold numbers)
+        if (u.formal_valid && u.robust_valid) maxInflation = *std::max_element(u.inflation, u.inflation + 9);
+        std::printf("uncertainty clusters %u sigma_fx %.9g sigma_robust_fx %.9g max_inflation %.9g max_sigma_px %.9g\n", u.n_clusters, u.sigma[0],
+                    u.sigma_robust[0], maxInflation, worst);
     }
     if (wantBoardImage && spline.boardImage().valid) {
         const EventCalibSpline::BoardImage &bi = spline.boardImage();
