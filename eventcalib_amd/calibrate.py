@@ -135,6 +135,16 @@ def load_events_bag(ctx, path, **options):
     return events, t_first, t_last
 
 
+def load_events_mcap(ctx, path, **options):
+    """A ROS 2 .mcap recording of event messages (dvs_msgs / prophesee_event_msgs EventArray, event_camera_msgs EventPacket with mono
+    or evt3 packets) -> (events, t_first, t_last) as calibrate_stream takes them: uploaded and decoded on the device
+    (mcap.stream_from_mcap_file), in time order.  options: mcap.mcap_options' (topic, time_base, width, height, flip_x, flip_y,
+    start_time, end_time).  Times count from the first event's whole second (evt3: the camera's clock) unless time_base is given."""
+    from . import mcap
+    events, _info, t_first, t_last = mcap.stream_from_mcap_file(ctx, path, **options)
+    return events, t_first, t_last
+
+
 def load_events_arrays(ctx, t, x, y, p, **options):
     """Events held as four columns of one length (numpy arrays of any of the array ingest's types, any strides — a structured array's
     fields are taken where they lie) -> (events, t_first, t_last) as calibrate_stream takes them: the columns uploaded as they are

@@ -23,6 +23,8 @@
 #include "../aedat_events.hpp"
 #include "../aedat4_events.hpp"
 #include "../bag_events.hpp"
+#include "../mcap_events.hpp"
+#include "../../../include/ecal_mcap.h"
 #include "../fields_events.hpp"
 #include "dbscan.h"
 
@@ -306,6 +308,57 @@ public:
         if (info) *info = I;
         return (long long) I.n_events;
     }
+    // A ROS 2 .mcap recording of event messages (include/ecal_mcap.h) -> .bin beside it, on one host thread: the plain sequential
+    // decoder of mcap_events.hpp, the records in file order.  The baseline of mcap2binDevice, and its check: both write the same bytes.
+    // opt null: the defaults (every chosen channel, the automatic time base, no bounds, no flips).
+    static long long mcap2bin(const std::string &mcapFilePath, const ecal_mcap_options *opt = nullptr, ecal_mcap_info *info = nullptr) {
+        std::ifstream is(mcapFilePath, std::ifstream::binary);
+        if (!is.is_open()) throw std::invalid_argument("No such file: " + mcapFilePath);
+        is.seekg(0, std::ifstream::end);
+        std::vector<uint8_t> bytes((size_t) is.tellg());
+        is.seekg(0);
+        is.read((char *) bytes.data(), (std::streamsize) bytes.size());
+        if ((size_t) is.gcount() != bytes.size()) throw std::runtime_error("mcap2bin: cannot read " + mcapFilePath);
+        ecal_mcap_options o;
+        if (opt) o = *opt; else ecal_mcap_default_options(&o);
+        if ((o.flip_x && !o.width) || (o.flip_y && !o.height)) throw std::invalid_argument("mcap2bin: flip_x / flip_y need width / height");
+        const ecal_bag::BagFilter f{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+        ecal_mcap::McapCounts c;
+        std::vector<uint8_t> out;
+        auto put = [&](const uint8_t *rec) { out.insert(out.end(), rec, rec + Event::kRecordBytes); };
+        std::string err;
+        int64_t base = 0;
+        if (ecal_mcap::mcap_decode_sequential(bytes.data(), bytes.size(), o.topic ? o.topic : "", o.auto_time_base, f, c, put, &base, &err))
+            throw std::invalid_argument("mcap2bin: " + err + " (" + mcapFilePath + ")");
+        const auto dot = mcapFilePath.find_last_of('.');
+        std::ofstream os(mcapFilePath.substr(0, dot) + ".bin", std::ofstream::binary | std::ofstream::trunc);
+        os.write((const char *) out.data(), (std::streamsize) out.size());
+        if (info) {
+            ecal_mcap_info I;
+            std::memset(&I, 0, sizeof(I));
+            I.n_raw_events = c.n_raw_events; I.n_events = c.n_events; I.n_outside = c.n_outside; I.n_negative = c.n_negative;
+            I.n_before_start = c.n_before_start; I.n_after_end = c.n_after_end; I.n_messages = c.n_messages;
+            I.n_other_messages = c.n_other_messages; I.n_chunks = c.n_chunks; I.n_schemas = c.n_schemas; I.n_channels = c.n_channels;
+            I.n_trailing_bytes = c.n_trailing_bytes; I.first_stamp_ns = c.first_stamp_ns; I.time_base = base; I.msg_width = c.msg_width;
+            I.msg_height = c.msg_height; I.n_payload_bytes = c.n_payload_bytes; I.n_no_state = c.n_no_state;
+            I.n_other_words = c.n_other_words; I.n_time_wraps = c.n_time_wraps;
+            std::memcpy(&I.layout, &c.layout, sizeof(I.layout));
+            *info = I;
+        }
+        return (long long) c.n_events;
+    }
+    // mcap2bin on the device (ecal_mcap_to_bin_file: the messages indexed on the host, the file uploaded and decoded in HBM): the same
+    // arguments, the same output file name, the same bytes in it, the same returned count
+    static long long mcap2binDevice(const std::string &mcapFilePath, const ecal_mcap_options *opt = nullptr, ecal_mcap_info *info = nullptr) {
+        const auto dot = mcapFilePath.find_last_of('.');
+        ecal_mcap_info I;
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_mcap_to_bin_file(ctx, mcapFilePath.c_str(), (mcapFilePath.substr(0, dot) + ".bin").c_str(), opt, &I);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("mcap2binDevice: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK) throw std::runtime_error(std::string("ecal_mcap_to_bin_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (info) *info = I;
+        return (long long) I.n_events;
+    }
     // A .npy file of events (a 1-D structured array or an (N, 4) array; include/ecal.h, "array ingest") -> .bin beside it, on one host
     // thread: the header parser and the plain walk of fields_events.hpp, the records in file order.  The baseline of npy2binDevice,
     // and its check: both write the same bytes.  opt null: the defaults (1e-6 s a tick, base 0, no bounds, no flips).
@@ -490,6 +543,19 @@ struct EventContainer {
         fromFile_ = true;
     }
     ecal_bag_info bagInfo{};     // what the last loadBagFile saw (messages, chunks, drops, the time base in force)
+    // The same from a ROS 2 .mcap recording of event messages (ecal_stream_create_from_mcap_file, include/ecal_mcap.h).
+    void loadMcapFile(const std::string &mcapFilePath, const ecal_mcap_options *opt = nullptr) {
+        release();
+        records.clear();
+        ecal_ctx *ctx = ecal_host::thread_ctx();
+        const int rc = ecal_stream_create_from_mcap_file(ctx, mcapFilePath.c_str(), opt, &stream_, &mcapInfo);
+        if (rc == ECAL_ERR_INVALID) throw std::invalid_argument(std::string("loadMcapFile: ") + ecal_last_error(ctx));
+        if (rc != ECAL_OK)
+            throw std::runtime_error(std::string("ecal_stream_create_from_mcap_file: ") + ecal_strerror(rc) + " — " + ecal_last_error(ctx));
+        if (ecal_stream_times(stream_, &devFirst_, &devLast_) != ECAL_OK) throw std::runtime_error("ecal_stream_times");
+        fromFile_ = true;
+    }
+    ecal_mcap_info mcapInfo{};   // what the last loadMcapFile saw (messages, chunks, drops, the kind, the layout and the time base in force)
     // The same from events held as four columns in host memory (ecal_stream_create_from_fields: f[4] = t, x, y, p, element i at
     // ptr + i * stride, any of the nine ECAL_FIELD_* types): uploaded as they lie and packed on the device.  opt null: the defaults.
     void loadArrays(const ecal_field f[4], uint64_t n, const ecal_fields_options *opt = nullptr) {

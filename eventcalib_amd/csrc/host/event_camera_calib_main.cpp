@@ -4,7 +4,7 @@
 // eventcalib_amd/unit_test_eventCameraCalib next to libecal.so; run by tests/test_gpu_shims.py and bench.py's end_to_end leg.
 //   usage: unit_test_eventCameraCalib settings.yaml events.bin saveDir [batch]     (the reference's argv, eventCameraCalib.cpp:105-110;
 //   with batch, an events path ending in .txt is a text file of "stamp x y polarity" lines, converted on the device; one ending in
-//   .raw, .aedat, .aedat4 or .bag a camera's or recorder's own file, .npy events as numpy saves them, decoded on the device)
+//   .raw, .aedat, .aedat4, .bag or .mcap a camera's or recorder's own file, .npy events as numpy saves them, decoded on the device)
 // "batch": rectifyFeatures of all keyframes in one device pass (ecal_rectify_keyframes) instead of one CirclesEventFrame per
 // keyframe, the file read in one piece, and a "stage <name> <seconds>" line per stage of the chain (bench.py's end_to_end leg).
 #include <chrono>
@@ -157,6 +157,34 @@ int main(int argc, char **argv) {
                 return 4;
             }
             std::printf("bag_time_base %lld\n", (long long) container->bagInfo.time_base);   // nanoseconds: t = 0 of this run
+        } else if (eventsPath.size() >= 5 && eventsPath.compare(eventsPath.size() - 5, 5, ".mcap") == 0) {
+            // a ROS 2 MCAP recording of event messages (dvs_msgs / prophesee_event_msgs EventArray, event_camera_msgs EventPacket with
+            // mono or evt3 packets) decoded on the device.  Keys of this build, all optional: Mcap_Topic (absent: the one topic of
+            // events), Mcap_TimeBase (nanoseconds of epoch time, evt3: microseconds of the camera's clock; absent: the first event's
+            // whole second, evt3: 0), Mcap_FlipX / Mcap_FlipY (0; not for evt3).  Events outside Camera.width x Camera.height are dropped.
+            ecal_mcap_options opt;
+            ecal_mcap_default_options(&opt);
+            std::string mcapTopic;
+            if (!fsSettings["Mcap_Topic"].isNone()) mcapTopic = (std::string) fsSettings["Mcap_Topic"];
+            opt.topic = mcapTopic.c_str();
+            if (!fsSettings["Mcap_TimeBase"].isNone()) {
+                opt.auto_time_base = 0;
+                opt.time_base = std::strtoll(((std::string) fsSettings["Mcap_TimeBase"]).c_str(), nullptr, 10);
+            }
+            if (!fsSettings["Mcap_FlipX"].isNone()) opt.flip_x = (int) fsSettings["Mcap_FlipX"] ? 1 : 0;
+            if (!fsSettings["Mcap_FlipY"].isNone()) opt.flip_y = (int) fsSettings["Mcap_FlipY"] ? 1 : 0;
+            opt.width = (uint32_t) width;
+            opt.height = (uint32_t) height;
+            opt.start_time = startTime;
+            opt.has_end_time = customEnd ? 1 : 0;
+            opt.end_time = endTimeSetting;
+            try {
+                container->loadMcapFile(eventsPath, &opt);
+            } catch (const std::exception &e) {   // (compressed chunks, a stereo file, another message layout or codec: said plainly, no abort)
+                std::fprintf(stderr, "%s\n", e.what());
+                return 4;
+            }
+            std::printf("mcap_time_base %lld\n", (long long) container->mcapInfo.time_base);   // t = 0 of this run
         } else if (eventsPath.size() >= 4 && eventsPath.compare(eventsPath.size() - 4, 4, ".npy") == 0) {
             // events as numpy saves them — a 1-D structured array with fields t|ts|time|timestamp, x, y, p|pol|polarity, or an (N, 4)
             // array — decoded on the device.  Keys of this build, all optional: Npy_TimeMagnitude (seconds per tick, 1e-6; 1 for
