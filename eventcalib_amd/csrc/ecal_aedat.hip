@@ -19,18 +19,18 @@
 //                                     are packed into LDS and copied out with aligned 32-bit stores; the totals
 // "The stream ends here" is the test `slot < first offender` in pass 5, as in the raw ingest.  The host sees the counters once,
 // behind pass 5 (the file forms of 2.0 once more behind pass 1: the record buffer's size is a count).
-// The table scan, the bisection, the clipped load and the tails of passes 3 and 5 are ingest_blocks.hpp's, shared with the other
-// ingests; the record's bytes are event_record.hpp's.
+// The bodies of passes 3 and 5 are slot_kernels.hpp's (AedatFormat<FMT> below is this format's policy), the table scan, the table
+// check, the bisection, the clipped load and the tails of passes 3 and 5 ingest_blocks.hpp's, the host drivers ingest_driver.hpp's (3.1:
+// ecal_ingest_message_table, the bag ingest's whole path with packets for messages; 2.0: ecal_ingest_verdict_write behind its own
+// front), all shared with the other table ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
 #include <math.h>
-#include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 #include "ecal_ctx.hpp"
-#include "block_utils.hpp"
-#include "ingest_blocks.hpp"
+#include "slot_kernels.hpp"
+#include "ingest_driver.hpp"
 #include "aedat_events.hpp"
 
 namespace ecal {
@@ -154,6 +154,31 @@ template <int FMT> struct AeSlots {
     }
 };
 
+// the format of slot_kernels.hpp's bodies
+template <int FMT> struct AedatFormat {
+    typedef AedatSource Source;
+    typedef AedatFilter Filter;
+    typedef AedatWords Words;
+    typedef AeSlots<FMT> Slots;
+    static constexpr int T = AE_T, N_DROPS = 4;
+    static constexpr uint32_t PER = AE_PER, BLOCK = AE_BLOCK;
+    static constexpr uint8_t KEEP = AEDAT_CLASS_KEEP, STOP = AEDAT_CLASS_STOP;
+    static __device__ __forceinline__ Slots slots(const Source &src, unsigned long long *s_scan) { return Slots(src, s_scan, true); }
+    static __device__ __forceinline__ bool is_event(const Slots &s, uint32_t j) { return s.is_event(j); }
+    static __device__ __forceinline__ uint8_t classify(const Slots &s, uint32_t j, const Filter &flt, double *t, uint32_t *x, uint32_t *y) {
+        return aedat_classify(s.event(j), flt, t, x, y);
+    }
+    static __device__ __forceinline__ uint8_t polarity(const Slots &s, uint32_t j) {
+        return (uint8_t) (FMT == AEDAT_FORMAT_31 ? (s.a[j] >> 1) & 1u : (s.a[j] >> 11) & 1u);
+    }
+    static __device__ __forceinline__ constexpr uint8_t drop_class(int i) {
+        return i == 0 ? AEDAT_CLASS_INVALID : i == 1 ? AEDAT_CLASS_OUTSIDE : i == 2 ? AEDAT_CLASS_NEGATIVE : AEDAT_CLASS_BEFORE_START;
+    }
+    static __device__ __forceinline__ unsigned long long *drop_counter(Words *w, int i) {
+        return i == 0 ? &w->n_invalid : i == 1 ? &w->n_outside : i == 2 ? &w->n_negative : &w->n_before_start;
+    }
+};
+
 // first[p] = n_events of the packets before p, first[n] = all of them (table_exscan_1024); the table checked against n_bytes.
 // One workgroup.
 __global__ __launch_bounds__(1024) void aedat_packet_scan_kernel(const AedatPacket *__restrict__ packets, uint32_t n, uint64_t n_bytes,
@@ -161,11 +186,8 @@ __global__ __launch_bounds__(1024) void aedat_packet_scan_kernel(const AedatPack
     const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) packets[p].n_events; }, first);
     if (threadIdx.x == 0) w->n_slots = tot;
     // (a pass of its own, strided: the table is read once more than the scan needs; the scan's value_of runs twice an entry)
-    unsigned long long bad = 0;
-    for (uint64_t p = threadIdx.x; p < n; p += 1024u) {
-        const uint64_t off = packets[p].offset, len = (uint64_t) packets[p].n_events * 8u;
-        if (off > n_bytes || len > n_bytes - off) bad++;
-    }
+    const unsigned long long bad = table_count_outside(n, n_bytes, threadIdx.x, 1024u, [&](uint64_t p) { return packets[p].offset; },
+                                                       [&](uint64_t p) { return (uint64_t) packets[p].n_events * 8u; });
     if (bad) atomicAdd(&w->bad_table, bad);
 }
 
@@ -209,77 +231,14 @@ __global__ __launch_bounds__(AE_T) void aedat20_count_kernel(AedatSource src, ui
 template <int FMT>
 __global__ __launch_bounds__(AE_T) void aedat_verdict_kernel(AedatSource src, AedatFilter flt, uint32_t *__restrict__ blk_keep,
                                                              AedatWords *__restrict__ w) {
-    __shared__ unsigned long long s_scan[AE_T / 64];
-    const int tid = threadIdx.x;
-    const AeSlots<FMT> mine(src, s_scan, true);
-    uint32_t keep = 0, stop = 0xFFFFFFFFu;   // (stop: a slot within the block)
-#pragma unroll
-    for (uint32_t j = 0; j < AE_PER; j++) {
-        if (j < mine.n && mine.is_event(j)) {
-            double t;
-            uint32_t x, y;
-            const uint8_t c = aedat_classify(mine.event(j), flt, &t, &x, &y);
-            keep += c == AEDAT_CLASS_KEEP ? 1u : 0u;
-            const uint32_t at = (uint32_t) tid * AE_PER + j;
-            if (c == AEDAT_CLASS_STOP && at < stop) stop = at;
-        }
-    }
-    block_keep_and_stop<AE_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * AE_BLOCK; });
+    slot_verdict_body<AedatFormat<FMT>>(src, flt, blk_keep, w);
 }
 
 // the kept events below the first offender, packed in LDS and copied out; the totals
 template <int FMT>
 __global__ __launch_bounds__(AE_T) void aedat_write_kernel(AedatSource src, const uint32_t *__restrict__ blk_koff, AedatFilter flt,
                                                            uint8_t *__restrict__ events, uint64_t capacity, AedatWords *__restrict__ w) {
-    __shared__ unsigned long long s_scan[AE_T / 64];
-    __shared__ uint32_t s_cnt[4];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[AE_BLOCK * 25];
-    const int tid = threadIdx.x;
-    const unsigned long long X = w->first_stop;
-    const uint64_t slot0 = (uint64_t) blockIdx.x * AE_BLOCK;
-    if (slot0 >= X) return;   // (the whole block lies behind the offender; the same for every thread)
-    const AeSlots<FMT> mine(src, s_scan, true);
-    // slots of this block below the offender: in-block slot < lim
-    const uint32_t lim = X - slot0 < (unsigned long long) AE_BLOCK ? (uint32_t) (X - slot0) : AE_BLOCK;
-    if (tid < 4) s_cnt[tid] = 0;
-    uint32_t keep = 0, kept_mask = 0, drop[4] = {0u, 0u, 0u, 0u};
-    double kt[AE_PER];
-    uint32_t kx[AE_PER], ky[AE_PER];
-#pragma unroll
-    for (uint32_t j = 0; j < AE_PER; j++) {
-        kt[j] = 0.0;
-        kx[j] = ky[j] = 0u;
-        if (j < mine.n && mine.is_event(j) && (uint32_t) tid * AE_PER + j < lim) {
-            const uint8_t c = aedat_classify(mine.event(j), flt, &kt[j], &kx[j], &ky[j]);
-            if (c == AEDAT_CLASS_KEEP) {
-                keep++;
-                kept_mask |= 1u << j;
-            }
-            drop[0] += c == AEDAT_CLASS_INVALID ? 1u : 0u;
-            drop[1] += c == AEDAT_CLASS_OUTSIDE ? 1u : 0u;
-            drop[2] += c == AEDAT_CLASS_NEGATIVE ? 1u : 0u;
-            drop[3] += c == AEDAT_CLASS_BEFORE_START ? 1u : 0u;
-        }
-    }
-    uint32_t kex, eb, ktot, tb;
-    block_exscan_pair<AE_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    block_add_drops<4>(drop, s_cnt);
-    // at most AE_BLOCK kept events: one chunk of LDS holds them all
-    uint32_t k = kex;
-#pragma unroll
-    for (uint32_t j = 0; j < AE_PER; j++) {
-        if (kept_mask >> j & 1u) {
-            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j],
-                        (uint8_t) (FMT == AEDAT_FORMAT_31 ? (mine.a[j] >> 1) & 1u : (mine.a[j] >> 11) & 1u));
-            k++;
-        }
-    }
-    __syncthreads();
-    if (tid < 4 && s_cnt[tid])
-        atomicAdd(tid == 0 ? &w->n_invalid : tid == 1 ? &w->n_outside : tid == 2 ? &w->n_negative : &w->n_before_start,
-                  (unsigned long long) s_cnt[tid]);
-    if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    block_copy_out<AE_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
+    slot_write_body<AedatFormat<FMT>>(src, blk_koff, flt, events, capacity, w);
 }
 
 }  // namespace ecal
@@ -325,148 +284,98 @@ int aedat_check_options(ecal_ctx *ctx, const ecal_aedat_options &o) {
     return ECAL_OK;
 }
 
-// n_slots_host: 3.1, the sum of the table's n_events when the caller knows it (the file forms), else AE_NONE.
-// own_events != null: the records go into a buffer allocated here for the count (the caller's to hipFree, null when there is
-// nothing to free); else into d_events / capacity
-template <int FMT>
-int aedat_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const AedatPacket *d_packets, uint64_t n_packets,
-                 uint64_t n_slots_host, const ecal_aedat_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events,
-                 ecal_aedat_info &I, hipStream_t st) {
-    constexpr bool V31 = FMT == AEDAT_FORMAT_31;
-    I.format = FMT;
+const ecal_ingest_nouns AEDAT_NOUNS{"aedat ingest", "aedat", "packet", "payload", "packet scan"};
+
+AedatFilter aedat_filter(const ecal_aedat_options &o) {
+    return AedatFilter{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+}
+
+// 3.1: the message-table path, packets for messages.  n_slots_host, own_events: ecal_ingest_message_table's
+int aedat31_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const AedatPacket *d_packets, uint64_t n_packets,
+                   uint64_t n_slots_host, const ecal_aedat_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events,
+                   ecal_aedat_info &I, hipStream_t st) {
+    I.format = AEDAT_FORMAT_31;
+    I.n_packets = n_packets;
+    return ecal_ingest_message_table<AedatWords>(
+        ctx, AEDAT_NOUNS, AedatSource{d_payload, n_bytes, 0, d_packets, nullptr, (uint32_t) n_packets, nullptr}, aedat_filter(o), n_bytes, n_packets, 8u,
+        n_slots_host, AE_BLOCK, d_events, capacity, own_events, I, st,
+        [&](unsigned long long *first, AedatWords *d_w) {
+            hipLaunchKernelGGL(aedat_packet_scan_kernel, dim3(1), dim3(1024), 0, st, d_packets, (uint32_t) n_packets, n_bytes, first, d_w);
+        },
+        [&](const AedatSource &src, const AedatFilter &f, uint32_t nb, uint32_t *keep, AedatWords *d_w) {
+            hipLaunchKernelGGL(aedat_verdict_kernel<AEDAT_FORMAT_31>, dim3(nb), dim3(AE_T), 0, st, src, f, keep, d_w);
+        },
+        [&](const AedatSource &src, const AedatFilter &f, uint32_t nb, const uint32_t *koff, uint8_t *events, uint64_t cap, AedatWords *d_w) {
+            hipLaunchKernelGGL(aedat_write_kernel<AEDAT_FORMAT_31>, dim3(nb), dim3(AE_T), 0, st, src, koff, f, events, cap, d_w);
+        },
+        [&](const AedatWords &W, uint64_t *n_more) {
+            I.n_invalid = *n_more = W.n_invalid;
+            return ECAL_OK;
+        });
+}
+
+// 2.0: the wrap count and its scan in front of the shared back half.  own_events != null: the records go into a buffer allocated here
+// for the count (the caller's to hipFree, null when there is nothing to free); else into d_events / capacity
+int aedat20_ingest(ecal_ctx *ctx, const uint8_t *d_payload, uint64_t n_bytes, const ecal_aedat_options &o, uint8_t *d_events, uint64_t capacity,
+                   uint8_t **own_events, ecal_aedat_info &I, hipStream_t st) {
+    I.format = AEDAT_FORMAT_20;
     if (own_events) *own_events = nullptr;
-    uint64_t bound;   // no fewer than the slots: sizes the per-block arrays
-    if (V31) {
-        I.n_packets = n_packets;
-        if (!n_packets || n_slots_host == 0) return ECAL_OK;
-        bound = n_slots_host != AE_NONE ? n_slots_host : std::min<uint64_t>(n_bytes / 8u, 0xFFFFFFFFull);
-    } else {
-        I.n_records = n_bytes / 8u;
-        I.n_trailing_bytes = n_bytes % 8u;
-        bound = I.n_records;
-        if (!bound) return ECAL_OK;
-    }
-    if (bound > 0xFFFFFFFFull) {
-        I.n_events = bound;
+    I.n_records = n_bytes / 8u;
+    I.n_trailing_bytes = n_bytes % 8u;
+    if (!I.n_records) return ECAL_OK;
+    if (I.n_records > 0xFFFFFFFFull) {
+        I.n_events = I.n_records;
         ctx->last_error = "aedat ingest: more than 2^32-1 events";
         return ECAL_ERR_RANGE;
     }
-    const uint32_t nb_max = (uint32_t) ((bound + AE_BLOCK - 1) / AE_BLOCK);
+    const uint32_t nb = (uint32_t) ((I.n_records + AE_BLOCK - 1) / AE_BLOCK);
     ecal_load_timer tm("aedat", ctx->sw.load_trace, st);
-    const size_t o_first = 0, o_wr = o_first + up16((size_t) (V31 ? n_packets + 1 : 0) * 8), o_win = o_wr + up16((size_t) nb_max * 4),
-                 o_keep = o_win + up16(((size_t) nb_max + 1) * 4), o_koff = o_keep + up16((size_t) nb_max * 4),
-                 o_words = o_koff + up16(((size_t) nb_max + 1) * 4), total = o_words + sizeof(AedatWords);
+    const size_t o_wr = 0, o_win = o_wr + up16((size_t) nb * 4), o_keep = o_win + up16(((size_t) nb + 1) * 4), o_koff = o_keep + up16((size_t) nb * 4),
+                 o_words = o_koff + up16(((size_t) nb + 1) * 4), total = o_words + sizeof(AedatWords);
     ecal_devbuf scratch;
     int rc;
     if ((rc = ecal_ensure(ctx, scratch, total))) return rc;
     uint8_t *base = scratch.as<uint8_t>();
-    unsigned long long *first = (unsigned long long *) (base + o_first);
     uint32_t *wr = (uint32_t *) (base + o_wr), *win = (uint32_t *) (base + o_win), *keep = (uint32_t *) (base + o_keep),
              *koff = (uint32_t *) (base + o_koff);
     AedatWords *d_w = (AedatWords *) (base + o_words);
-    const AedatFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+    const AedatFilter flt = aedat_filter(o);
     if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(AedatWords), &d_w->first_stop, st))) return rc;
     tm.mark("start");
-    AedatSource src{d_payload, n_bytes, bound, d_packets, first, (uint32_t) n_packets, win};
-    AedatWords W;
-    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
-    uint32_t nb = nb_max;
-    if (V31) {
-        hipLaunchKernelGGL(aedat_packet_scan_kernel, dim3(1), dim3(1024), 0, st, d_packets, (uint32_t) n_packets, n_bytes, first, d_w);
-        ECAL_HIP_TRY(ctx, hipGetLastError());
-        tm.mark("packet scan");
-        if (n_slots_host == AE_NONE) {   // the grid is a count of the table: one look at it
-            if ((rc = fetch())) return rc;
-            if (W.bad_table) {
-                ctx->last_error = "aedat ingest: " + std::to_string(W.bad_table) + " packets of the table do not lie within the payload";
-                return ECAL_ERR_INVALID;
-            }
-            if (W.n_slots > 0xFFFFFFFFull) {
-                I.n_events = W.n_slots;
-                ctx->last_error = "aedat ingest: more than 2^32-1 events";
-                return ECAL_ERR_RANGE;
-            }
-            if (W.n_slots > bound) {   // (packets that overlap: more events than the payload has room for)
-                ctx->last_error = "aedat ingest: the packet table names more events than the payload holds";
-                return ECAL_ERR_INVALID;
-            }
-            src.n_slots = W.n_slots;
-            nb = (uint32_t) ((W.n_slots + AE_BLOCK - 1) / AE_BLOCK);
-        }
-        I.n_raw_events = src.n_slots;
-        if (!src.n_slots) return ECAL_OK;
-        if (own_events) capacity = src.n_slots;
-    } else {
-        hipLaunchKernelGGL(aedat20_count_kernel, dim3(nb), dim3(AE_T), 0, st, src, wr, d_w);
-        ECAL_HIP_TRY(ctx, hipGetLastError());
-        tm.mark("wrap count");
-        if ((rc = ecal_scan_blocks(ctx, wr, nb, win, st))) return rc;
-        tm.mark("wrap scan");
-        if (own_events) {   // the one count a size needs
-            if ((rc = fetch())) return rc;
-            capacity = W.n_dvs;
-        }
-    }
-    if (own_events) {
+    const AedatSource src{d_payload, n_bytes, I.n_records, nullptr, nullptr, 0u, win};
+    hipLaunchKernelGGL(aedat20_count_kernel, dim3(nb), dim3(AE_T), 0, st, src, wr, d_w);
+    ECAL_HIP_TRY(ctx, hipGetLastError());
+    tm.mark("wrap count");
+    if ((rc = ecal_scan_blocks(ctx, wr, nb, win, st))) return rc;
+    tm.mark("wrap scan");
+    if (own_events) {   // the one count a size needs
+        AedatWords W;
+        if ((rc = ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st))) return rc;
+        capacity = W.n_dvs;
         if ((rc = ecal_ingest_alloc_records(ctx, "aedat ingest", capacity, own_events))) return rc;
         d_events = *own_events;
     }
-    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
-    auto launched = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipGetLastError());
-        return ECAL_OK;
-    };
-    hipLaunchKernelGGL(aedat_verdict_kernel<FMT>, dim3(nb), dim3(AE_T), 0, st, src, flt, keep, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("verdict");
-    if ((rc = ecal_scan_blocks(ctx, keep, nb, koff, st))) return fail(rc);
-    hipLaunchKernelGGL(aedat_write_kernel<FMT>, dim3(nb), dim3(AE_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("scan, write");
-    if ((rc = fetch())) return fail(rc);
-    if (V31) {
-        if (W.bad_table || W.n_slots != src.n_slots) {
-            ctx->last_error = "aedat ingest: the packet table does not fit the payload (" + std::to_string(W.bad_table) +
-                              " packets outside it, " + std::to_string(W.n_slots) + " events)";
-            return fail(ECAL_ERR_INVALID);
-        }
-    } else {
-        I.n_other_records = W.n_other;
-        I.n_raw_events = W.n_dvs;
-        uint32_t wraps = 0;   // (the scan's total stands behind the blocks' offsets)
-        ECAL_HIP_TRY(ctx, hipMemcpyAsync(&wraps, win + nb, 4, hipMemcpyDeviceToHost, st));
-        ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
-        I.n_time_wraps = wraps;
-    }
-    I.n_events = W.n_events;
-    I.n_invalid = W.n_invalid;
-    I.n_outside = W.n_outside;
-    I.n_negative = W.n_negative;
-    I.n_before_start = W.n_before_start;
-    // every event in front of the offender has one of the five classes
-    I.n_after_end = W.first_stop == AE_NONE ? 0 : I.n_raw_events - (W.n_events + W.n_invalid + W.n_outside + W.n_negative + W.n_before_start);
-    if (I.n_events > capacity) {
-        ctx->last_error = "aedat ingest: " + std::to_string(I.n_events) + " records, more than the capacity";
-        return fail(ECAL_ERR_RANGE);
-    }
-    return ECAL_OK;
+    return ecal_ingest_verdict_write(
+        ctx, "aedat ingest", tm, nb, keep, koff, (const AedatWords *) d_w, capacity, own_events, I, st,
+        [&] { hipLaunchKernelGGL(aedat_verdict_kernel<AEDAT_FORMAT_20>, dim3(nb), dim3(AE_T), 0, st, src, flt, keep, d_w); },
+        [&] { hipLaunchKernelGGL(aedat_write_kernel<AEDAT_FORMAT_20>, dim3(nb), dim3(AE_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w); },
+        [&](const AedatWords &W, uint64_t *n_more) -> int {
+            I.n_other_records = W.n_other;
+            I.n_raw_events = W.n_dvs;
+            uint32_t wraps = 0;   // (the scan's total stands behind the blocks' offsets)
+            ECAL_HIP_TRY(ctx, hipMemcpyAsync(&wraps, win + nb, 4, hipMemcpyDeviceToHost, st));
+            ECAL_HIP_TRY(ctx, hipStreamSynchronize(st));
+            I.n_time_wraps = wraps;
+            I.n_invalid = *n_more = W.n_invalid;
+            return ECAL_OK;
+        });
 }
 
 int aedat_ingest_any(ecal_ctx *ctx, int format, const uint8_t *d_payload, uint64_t n_bytes, const AedatPacket *d_packets, uint64_t n_packets,
                      uint64_t n_slots_host, const ecal_aedat_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events,
                      ecal_aedat_info &I, hipStream_t st) {
-    return format == ECAL_AEDAT_3_1
-               ? aedat_ingest<AEDAT_FORMAT_31>(ctx, d_payload, n_bytes, d_packets, n_packets, n_slots_host, o, d_events, capacity, own_events, I, st)
-               : aedat_ingest<AEDAT_FORMAT_20>(ctx, d_payload, n_bytes, nullptr, 0, AE_NONE, o, d_events, capacity, own_events, I, st);
-}
-
-bool aedat_pread(int fd, void *dst, size_t n, uint64_t at) {
-    for (size_t got = 0; got < n;) {
-        const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
-        if (rd <= 0) return false;
-        got += (size_t) rd;
-    }
-    return true;
+    return format == ECAL_AEDAT_3_1 ? aedat31_ingest(ctx, d_payload, n_bytes, d_packets, n_packets, n_slots_host, o, d_events, capacity, own_events, I, st)
+                                    : aedat20_ingest(ctx, d_payload, n_bytes, o, d_events, capacity, own_events, I, st);
 }
 
 // The packet table of a 3.1 file: the headers alone are read, one pread of 28 bytes a packet at the place the one before names (a
@@ -480,7 +389,7 @@ int aedat_index_file(int fd, uint64_t header_bytes, uint64_t file_bytes, int sou
     if (file_bytes <= header_bytes) return ECAL_OK;
     std::string err;
     const int rc = aedat31_walk_headers(
-        [&](uint64_t pos, uint8_t *raw) { return aedat_pread(fd, raw, AEDAT31_HEADER_BYTES, header_bytes + pos); }, file_bytes - header_bytes,
+        [&](uint64_t pos, uint8_t *raw) { return ecal_ingest_pread_all(fd, raw, AEDAT31_HEADER_BYTES, header_bytes + pos); }, file_bytes - header_bytes,
         source, c, [&](const AedatPacket &p) { table.push_back(p); }, &err);
     if (rc) *error = "aedat ingest: " + err + " (" + path + ")";
     return rc;
@@ -498,27 +407,14 @@ int aedat_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat_optio
     }
     int rc = aedat_check_options(ctx, o);
     if (rc) return rc;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) {
-        ctx->last_error = std::string("aedat ingest: cannot open ") + path;
-        return ECAL_ERR_INVALID;
-    }
-    struct stat sb;
+    int fd;
+    uint64_t file_bytes;
     std::vector<uint8_t> head;
-    bool ok = fstat(fd, &sb) == 0;
-    if (ok) {
-        head.resize((size_t) std::min<uint64_t>((uint64_t) sb.st_size, 1u << 20));
-        ok = aedat_pread(fd, head.data(), head.size(), 0);
-    }
-    if (!ok) {
-        close(fd);
-        ctx->last_error = std::string("aedat ingest: cannot read ") + path;
-        return ECAL_ERR_INVALID;
-    }
+    if ((rc = ecal_ingest_open_head(ctx, "aedat ingest", path, 1u << 20, nullptr, &fd, &file_bytes, &head))) return rc;
     int format = ECAL_AEDAT_AUTO;
     uint64_t header_bytes = 0;
     std::string err;
-    if (aedat_parse_header(head.data(), head.size(), head.size() == (uint64_t) sb.st_size, o.format, &format, &header_bytes, &err)) {
+    if (aedat_parse_header(head.data(), head.size(), head.size() == file_bytes, o.format, &format, &header_bytes, &err)) {
         close(fd);
         ctx->last_error = "aedat ingest: " + err + " (" + path + ")";
         return ECAL_ERR_INVALID;
@@ -531,7 +427,7 @@ int aedat_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat_optio
     ecal_ingest_index_fn index;   // (2.0 has no packets to index)
     if (format == ECAL_AEDAT_3_1)
         index = [&](std::string *error, const void **tab, size_t *tab_bytes) {
-            const int index_rc = aedat_index_file(fd, header_bytes, (uint64_t) sb.st_size, o.source, table, c, path, error);
+            const int index_rc = aedat_index_file(fd, header_bytes, file_bytes, o.source, table, c, path, error);
             *tab = table.data();
             *tab_bytes = table.size() * sizeof(AedatPacket);
             return index_rc;

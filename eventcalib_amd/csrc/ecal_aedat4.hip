@@ -18,18 +18,17 @@
 //        7. ecal_scan_blocks            the blocks' first kept index
 //        8. aedat4_write_kernel         classed again; the kept events below the first offender packed into LDS and copied out
 // Compression NONE skips 1 - 3 and locates in the file itself.
-// The table scans, the bisection, the clipped load and the tails of passes 6 and 8 are ingest_blocks.hpp's, shared with the other
-// ingests; the record's bytes are event_record.hpp's.
+// The bodies of passes 6 and 8 are slot_kernels.hpp's (A4Format below is this format's policy), the table scans, the bisection, the
+// clipped load and the tails of passes 6 and 8 ingest_blocks.hpp's, the host side of passes 6 - 8 ingest_driver.hpp's
+// (ecal_ingest_verdict_write), all shared with the other table ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
 #include <math.h>
-#include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 #include "ecal_ctx.hpp"
-#include "block_utils.hpp"
-#include "ingest_blocks.hpp"
+#include "slot_kernels.hpp"
+#include "ingest_driver.hpp"
 #include "aedat4_events.hpp"
 
 namespace ecal {
@@ -275,74 +274,32 @@ struct A4Slots {
     __device__ __forceinline__ A4Event event(uint32_t j) const { return a4_event(w[j][0], w[j][1], w[j][2], w[j][3]); }
 };
 
-__global__ __launch_bounds__(A4_T) void aedat4_verdict_kernel(A4Source src, A4Filter flt, uint32_t *__restrict__ blk_keep, A4Words *__restrict__ w) {
-    const int tid = threadIdx.x;
-    const A4Slots mine(src);
-    uint32_t keep = 0, stop = 0xFFFFFFFFu;
-#pragma unroll
-    for (uint32_t j = 0; j < A4_PER; j++) {
-        if (j < mine.n) {
-            double t;
-            uint32_t x, y;
-            const uint8_t c = a4_classify(mine.event(j), flt, &t, &x, &y);
-            keep += c == A4_CLASS_KEEP ? 1u : 0u;
-            const uint32_t at = (uint32_t) tid * A4_PER + j;
-            if (c == A4_CLASS_STOP && at < stop) stop = at;
-        }
+// the format of slot_kernels.hpp's bodies
+struct A4Format {
+    typedef A4Source Source;
+    typedef A4Filter Filter;
+    typedef A4Words Words;
+    typedef A4Slots Slots;
+    static constexpr int T = A4_T, N_DROPS = 3;
+    static constexpr uint32_t PER = A4_PER, BLOCK = A4_BLOCK;
+    static constexpr uint8_t KEEP = A4_CLASS_KEEP, STOP = A4_CLASS_STOP;
+    static __device__ __forceinline__ Slots slots(const Source &src, unsigned long long *) { return Slots(src); }
+    static __device__ __forceinline__ bool is_event(const Slots &, uint32_t) { return true; }
+    static __device__ __forceinline__ uint8_t classify(const Slots &s, uint32_t j, const Filter &flt, double *t, uint32_t *x, uint32_t *y) {
+        return a4_classify(s.event(j), flt, t, x, y);
     }
-    block_keep_and_stop<A4_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * A4_BLOCK; });
+    static __device__ __forceinline__ uint8_t polarity(const Slots &s, uint32_t j) { return s.event(j).on; }
+    static __device__ __forceinline__ constexpr uint8_t drop_class(int i) { return i == 0 ? A4_CLASS_OUTSIDE : i == 1 ? A4_CLASS_NEGATIVE : A4_CLASS_BEFORE_START; }
+    static __device__ __forceinline__ unsigned long long *drop_counter(Words *w, int i) { return i == 0 ? &w->n_outside : i == 1 ? &w->n_negative : &w->n_before_start; }
+};
+
+__global__ __launch_bounds__(A4_T) void aedat4_verdict_kernel(A4Source src, A4Filter flt, uint32_t *__restrict__ blk_keep, A4Words *__restrict__ w) {
+    slot_verdict_body<A4Format>(src, flt, blk_keep, w);
 }
 
 __global__ __launch_bounds__(A4_T) void aedat4_write_kernel(A4Source src, const uint32_t *__restrict__ blk_koff, A4Filter flt,
                                                             uint8_t *__restrict__ events, uint64_t capacity, A4Words *__restrict__ w) {
-    __shared__ unsigned long long s_scan[A4_T / 64];
-    __shared__ uint32_t s_cnt[3];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[A4_BLOCK * 25];
-    const int tid = threadIdx.x;
-    const unsigned long long X = w->first_stop;
-    const uint64_t slot0 = (uint64_t) blockIdx.x * A4_BLOCK;
-    if (slot0 >= X) return;   // (the whole block lies behind the offender; the same for every thread)
-    const A4Slots mine(src);
-    const uint32_t lim = X - slot0 < (unsigned long long) A4_BLOCK ? (uint32_t) (X - slot0) : A4_BLOCK;
-    if (tid < 3) s_cnt[tid] = 0;
-    uint32_t keep = 0, kept_mask = 0, drop[3] = {0u, 0u, 0u};
-    double kt[A4_PER];
-    uint32_t kx[A4_PER], ky[A4_PER];
-    uint8_t kp[A4_PER];
-#pragma unroll
-    for (uint32_t j = 0; j < A4_PER; j++) {
-        kt[j] = 0.0;
-        kx[j] = ky[j] = 0u;
-        kp[j] = 0;
-        if (j < mine.n && (uint32_t) tid * A4_PER + j < lim) {
-            const A4Event e = mine.event(j);
-            const uint8_t c = a4_classify(e, flt, &kt[j], &kx[j], &ky[j]);
-            kp[j] = e.on;
-            if (c == A4_CLASS_KEEP) {
-                keep++;
-                kept_mask |= 1u << j;
-            }
-            drop[0] += c == A4_CLASS_OUTSIDE ? 1u : 0u;
-            drop[1] += c == A4_CLASS_NEGATIVE ? 1u : 0u;
-            drop[2] += c == A4_CLASS_BEFORE_START ? 1u : 0u;
-        }
-    }
-    uint32_t kex, eb, ktot, tb;
-    block_exscan_pair<A4_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    block_add_drops<3>(drop, s_cnt);
-    uint32_t k = kex;
-#pragma unroll
-    for (uint32_t j = 0; j < A4_PER; j++) {
-        if (kept_mask >> j & 1u) {
-            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j], kp[j]);
-            k++;
-        }
-    }
-    __syncthreads();
-    if (tid < 3 && s_cnt[tid])
-        atomicAdd(tid == 0 ? &w->n_outside : tid == 1 ? &w->n_negative : &w->n_before_start, (unsigned long long) s_cnt[tid]);
-    if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    block_copy_out<A4_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
+    slot_write_body<A4Format>(src, blk_koff, flt, events, capacity, w);
 }
 
 }  // namespace ecal
@@ -491,36 +448,13 @@ int a4_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const A4Pa
         if ((rc = ecal_ingest_alloc_records(ctx, "AEDAT 4 ingest", capacity, own_events))) return rc;
         d_events = *own_events;
     }
-    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
     const A4Filter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
     const A4Source src{lz4 ? scratch : d_file, lz4 ? scratch_bytes : n_bytes, W.n_slots, located, first, n};
-    hipLaunchKernelGGL(aedat4_verdict_kernel, dim3(nb), dim3(A4_T), 0, st, src, flt, keep, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("verdict");
-    if ((rc = ecal_scan_blocks(ctx, keep, nb, koff, st))) return fail(rc);
-    hipLaunchKernelGGL(aedat4_write_kernel, dim3(nb), dim3(A4_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("scan, write");
-    if ((rc = fetch())) return fail(rc);
-    I.n_events = W.n_events;
-    I.n_outside = W.n_outside;
-    I.n_negative = W.n_negative;
-    I.n_before_start = W.n_before_start;
-    I.n_after_end = W.first_stop == A4_NONE ? 0 : I.n_raw_events - (W.n_events + W.n_outside + W.n_negative + W.n_before_start);
-    if (I.n_events > capacity) {
-        ctx->last_error = "AEDAT 4 ingest: " + std::to_string(I.n_events) + " records, more than the capacity";
-        return fail(ECAL_ERR_RANGE);
-    }
-    return ECAL_OK;
-}
-
-bool a4_pread(int fd, void *dst, size_t n, uint64_t at) {
-    for (size_t got = 0; got < n;) {
-        const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
-        if (rd <= 0) return false;
-        got += (size_t) rd;
-    }
-    return true;
+    return ecal_ingest_verdict_write(
+        ctx, "AEDAT 4 ingest", tm, nb, keep, koff, (const A4Words *) d_w, capacity, own_events, I, st,
+        [&] { hipLaunchKernelGGL(aedat4_verdict_kernel, dim3(nb), dim3(A4_T), 0, st, src, flt, keep, d_w); },
+        [&] { hipLaunchKernelGGL(aedat4_write_kernel, dim3(nb), dim3(A4_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w); },
+        [](const A4Words &, uint64_t *) { return ECAL_OK; });
 }
 
 // file -> header on the host -> (the packet headers read and the stream chosen on a host thread, beside the upload) -> the file in HBM
@@ -531,24 +465,10 @@ int a4_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat4_options
     if (opt) o = *opt; else ecal_aedat4_default_options(&o);
     int rc = a4_check_options(ctx, o);
     if (rc) return rc;
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) {
-        ctx->last_error = std::string("AEDAT 4 ingest: cannot open ") + path;
-        return ECAL_ERR_INVALID;
-    }
-    struct stat sb;
+    int fd;
+    uint64_t file_bytes;
     std::vector<uint8_t> head;
-    bool ok = fstat(fd, &sb) == 0;
-    if (ok) {
-        head.resize((size_t) std::min<uint64_t>((uint64_t) sb.st_size, A4_HEADER_LIMIT));
-        ok = head.empty() || a4_pread(fd, head.data(), head.size(), 0);
-    }
-    if (!ok) {
-        close(fd);
-        ctx->last_error = std::string("AEDAT 4 ingest: cannot read ") + path;
-        return ECAL_ERR_INVALID;
-    }
-    const uint64_t file_bytes = (uint64_t) sb.st_size;
+    if ((rc = ecal_ingest_open_head(ctx, "AEDAT 4 ingest", path, A4_HEADER_LIMIT, nullptr, &fd, &file_bytes, &head))) return rc;
     A4Header h;
     std::string err;
     uint64_t end = 0;
@@ -566,12 +486,12 @@ int a4_file_to_events(ecal_ctx *ctx, const char *path, const ecal_aedat4_options
     ecal_ingest_upload up;
     rc = ecal_ingest_upload_indexed(ctx, "aedat4", "AEDAT 4 ingest", "host packet index", path, fd, 0, ECAL_INGEST_ANY_SIZE, [&](std::string *error, const void **tab, size_t *tab_bytes) {
         std::vector<A4ChainPacket> chain;
-        int index_rc = a4_walk_chain([&](uint64_t pos, uint8_t *raw) { return a4_pread(fd, raw, 8, pos); }, h.packets_begin, end,
+        int index_rc = a4_walk_chain([&](uint64_t pos, uint8_t *raw) { return ecal_ingest_pread_all(fd, raw, 8, pos); }, h.packets_begin, end,
                                      [&](const A4ChainPacket &p) { chain.push_back(p); }, &c.n_trailing_bytes, error);
         if (!index_rc)
             index_rc = a4_choose_stream(chain, h.compression, o.stream_id, [&](uint64_t off, uint32_t nb, std::vector<uint8_t> &out) {
                 out.resize(nb);
-                return nb == 0 || a4_pread(fd, out.data(), nb, off);
+                return nb == 0 || ecal_ingest_pread_all(fd, out.data(), nb, off);
             }, table, c, error);
         if (index_rc) *error += std::string(" (") + path + ")";
         *tab = table.data();

@@ -16,18 +16,17 @@
 //                               packed into LDS and copied out with aligned 32-bit stores; the totals
 // "The stream ends here" is the test `slot < first offender` in pass 4, as in the raw and AEDAT ingests.  The host sees the counters
 // once, behind pass 4 (ecal_events_from_bag_dev once more behind pass 1: the grid is a count of the table).
-// The table scan, the bisection, the clipped load and the tails of passes 2 and 4 are ingest_blocks.hpp's, shared with the other
-// ingests; the record's bytes are event_record.hpp's.
+// The bodies of passes 2 and 4 are slot_kernels.hpp's (BagFormat below is this format's policy), the table scan, the table check, the
+// bisection, the clipped load and the tails of passes 2 and 4 ingest_blocks.hpp's, the host driver ingest_driver.hpp's
+// (ecal_ingest_message_table), all shared with the other table ingests; the record's bytes are event_record.hpp's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
 #include <math.h>
-#include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 #include "ecal_ctx.hpp"
-#include "block_utils.hpp"
-#include "ingest_blocks.hpp"
+#include "slot_kernels.hpp"
+#include "ingest_driver.hpp"
 #include "bag_events.hpp"
 
 namespace ecal {
@@ -42,13 +41,7 @@ constexpr uint32_t BG_PER = BAG_THREAD_EVENTS;
 constexpr uint32_t BG_BLOCK = BAG_BLOCK_EVENTS;   // slots per block, and records staged in LDS (25 600 bytes: six workgroups a CU)
 constexpr unsigned long long BG_NONE = ~0ull;
 
-// the counters of one ingest (device)
-struct BagWords {
-    unsigned long long n_slots;      // slots of the table
-    unsigned long long first_stop;   // the first slot that reaches end_time (BG_NONE: none)
-    unsigned long long n_events, n_outside, n_negative, n_before_start;
-    unsigned long long bad_table;    // messages of the table that do not lie within n_bytes
-};
+typedef MessageWords BagWords;   // the counters of one ingest (device)
 
 // what a block kernel is given of the file
 struct BagSource {
@@ -111,6 +104,25 @@ struct BgSlots {
     __device__ __forceinline__ BagEvent event(uint32_t j) const { return bag_event(xy[j], secs[j], nsecs[j], pol[j]); }
 };
 
+// the format of slot_kernels.hpp's bodies
+struct BagFormat {
+    typedef BagSource Source;
+    typedef BagFilter Filter;
+    typedef BagWords Words;
+    typedef BgSlots Slots;
+    static constexpr int T = BG_T, N_DROPS = 3;
+    static constexpr uint32_t PER = BG_PER, BLOCK = BG_BLOCK;
+    static constexpr uint8_t KEEP = BAG_CLASS_KEEP, STOP = BAG_CLASS_STOP;
+    static __device__ __forceinline__ Slots slots(const Source &src, unsigned long long *) { return Slots(src); }
+    static __device__ __forceinline__ bool is_event(const Slots &, uint32_t) { return true; }
+    static __device__ __forceinline__ uint8_t classify(const Slots &s, uint32_t j, const Filter &flt, double *t, uint32_t *x, uint32_t *y) {
+        return bag_classify(s.event(j), flt, t, x, y);
+    }
+    static __device__ __forceinline__ uint8_t polarity(const Slots &s, uint32_t j) { return (uint8_t) (s.pol[j] != 0u ? 1u : 0u); }
+    static __device__ __forceinline__ constexpr uint8_t drop_class(int i) { return i == 0 ? BAG_CLASS_OUTSIDE : i == 1 ? BAG_CLASS_NEGATIVE : BAG_CLASS_BEFORE_START; }
+    static __device__ __forceinline__ unsigned long long *drop_counter(Words *w, int i) { return i == 0 ? &w->n_outside : i == 1 ? &w->n_negative : &w->n_before_start; }
+};
+
 // first[m] = n_events of the messages before m, first[n] = all of them (table_exscan_1024); the table checked against n_bytes.
 // One workgroup.
 __global__ __launch_bounds__(1024) void bag_message_scan_kernel(const BagMessage *__restrict__ messages, uint32_t n, uint64_t n_bytes,
@@ -118,82 +130,20 @@ __global__ __launch_bounds__(1024) void bag_message_scan_kernel(const BagMessage
     const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) messages[p].n_events; }, first);
     if (threadIdx.x == 0) w->n_slots = tot;
     // (a pass of its own, strided: the table is read once more than the scan needs; the scan's value_of runs twice an entry)
-    unsigned long long bad = 0;
-    for (uint64_t p = threadIdx.x; p < n; p += 1024u) {
-        const uint64_t off = messages[p].offset, len = (uint64_t) messages[p].n_events * BAG_EVENT_BYTES;
-        if (off > n_bytes || len > n_bytes - off) bad++;
-    }
+    const unsigned long long bad = table_count_outside(n, n_bytes, threadIdx.x, 1024u, [&](uint64_t p) { return messages[p].offset; },
+                                                       [&](uint64_t p) { return (uint64_t) messages[p].n_events * BAG_EVENT_BYTES; });
     if (bad) atomicAdd(&w->bad_table, bad);
 }
 
 // the class of every slot, the kept events per block, the first slot that reaches end_time
 __global__ __launch_bounds__(BG_T) void bag_verdict_kernel(BagSource src, BagFilter flt, uint32_t *__restrict__ blk_keep, BagWords *__restrict__ w) {
-    const int tid = threadIdx.x;
-    const BgSlots mine(src);
-    uint32_t keep = 0, stop = 0xFFFFFFFFu;   // (stop: a slot within the block)
-#pragma unroll
-    for (uint32_t j = 0; j < BG_PER; j++) {
-        if (j < mine.n) {
-            double t;
-            uint32_t x, y;
-            const uint8_t c = bag_classify(mine.event(j), flt, &t, &x, &y);
-            keep += c == BAG_CLASS_KEEP ? 1u : 0u;
-            const uint32_t at = (uint32_t) tid * BG_PER + j;
-            if (c == BAG_CLASS_STOP && at < stop) stop = at;
-        }
-    }
-    block_keep_and_stop<BG_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * BG_BLOCK; });
+    slot_verdict_body<BagFormat>(src, flt, blk_keep, w);
 }
 
 // the kept events below the first offender, packed in LDS and copied out; the totals
 __global__ __launch_bounds__(BG_T) void bag_write_kernel(BagSource src, const uint32_t *__restrict__ blk_koff, BagFilter flt,
                                                          uint8_t *__restrict__ events, uint64_t capacity, BagWords *__restrict__ w) {
-    __shared__ unsigned long long s_scan[BG_T / 64];
-    __shared__ uint32_t s_cnt[3];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[BG_BLOCK * 25];
-    const int tid = threadIdx.x;
-    const unsigned long long X = w->first_stop;
-    const uint64_t slot0 = (uint64_t) blockIdx.x * BG_BLOCK;
-    if (slot0 >= X) return;   // (the whole block lies behind the offender; the same for every thread)
-    const BgSlots mine(src);
-    // slots of this block below the offender: in-block slot < lim
-    const uint32_t lim = X - slot0 < (unsigned long long) BG_BLOCK ? (uint32_t) (X - slot0) : BG_BLOCK;
-    if (tid < 3) s_cnt[tid] = 0;
-    uint32_t keep = 0, kept_mask = 0, drop[3] = {0u, 0u, 0u};
-    double kt[BG_PER];
-    uint32_t kx[BG_PER], ky[BG_PER];
-#pragma unroll
-    for (uint32_t j = 0; j < BG_PER; j++) {
-        kt[j] = 0.0;
-        kx[j] = ky[j] = 0u;
-        if (j < mine.n && (uint32_t) tid * BG_PER + j < lim) {
-            const uint8_t c = bag_classify(mine.event(j), flt, &kt[j], &kx[j], &ky[j]);
-            if (c == BAG_CLASS_KEEP) {
-                keep++;
-                kept_mask |= 1u << j;
-            }
-            drop[0] += c == BAG_CLASS_OUTSIDE ? 1u : 0u;
-            drop[1] += c == BAG_CLASS_NEGATIVE ? 1u : 0u;
-            drop[2] += c == BAG_CLASS_BEFORE_START ? 1u : 0u;
-        }
-    }
-    uint32_t kex, eb, ktot, tb;
-    block_exscan_pair<BG_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    block_add_drops<3>(drop, s_cnt);
-    // at most BG_BLOCK kept events: one chunk of LDS holds them all
-    uint32_t k = kex;
-#pragma unroll
-    for (uint32_t j = 0; j < BG_PER; j++) {
-        if (kept_mask >> j & 1u) {
-            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j], (uint8_t) (mine.pol[j] != 0u ? 1u : 0u));
-            k++;
-        }
-    }
-    __syncthreads();
-    if (tid < 3 && s_cnt[tid])
-        atomicAdd(tid == 0 ? &w->n_outside : tid == 1 ? &w->n_negative : &w->n_before_start, (unsigned long long) s_cnt[tid]);
-    if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    block_copy_out<BG_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
+    slot_write_body<BagFormat>(src, blk_koff, flt, events, capacity, w);
 }
 
 }  // namespace ecal
@@ -243,131 +193,30 @@ int bag_check_options(ecal_ctx *ctx, const ecal_bag_options &o) {
     return ECAL_OK;
 }
 
-// o.time_base: the base in force (the caller has resolved auto_time_base).
-// n_slots_host: the sum of the table's n_events when the caller knows it (the file forms), else BG_NONE.
-// own_events != null: the records go into a buffer allocated here for the count (the caller's to hipFree, null when there is
-// nothing to free); else into d_events / capacity
-int bag_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const BagMessage *d_messages, uint64_t n_messages, uint64_t n_slots_host,
-               const ecal_bag_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events, ecal_bag_info &I, hipStream_t st) {
-    if (own_events) *own_events = nullptr;
-    I.n_messages = n_messages;
-    I.time_base = o.time_base;
-    if (!n_messages || n_slots_host == 0) return ECAL_OK;
-    // no fewer than the slots: sizes the per-block arrays
-    const uint64_t bound = n_slots_host != BG_NONE ? n_slots_host : std::min<uint64_t>(n_bytes / BAG_EVENT_BYTES, 0xFFFFFFFFull);
-    if (bound > 0xFFFFFFFFull) {
-        I.n_events = bound;
-        ctx->last_error = "bag ingest: more than 2^32-1 events";
-        return ECAL_ERR_RANGE;
-    }
-    const uint32_t nb_max = (uint32_t) ((bound + BG_BLOCK - 1) / BG_BLOCK);
-    ecal_load_timer tm("bag", ctx->sw.load_trace, st);
-    const size_t o_first = 0, o_keep = o_first + up16((size_t) (n_messages + 1) * 8), o_koff = o_keep + up16(((size_t) nb_max + 1) * 4),
-                 o_words = o_koff + up16(((size_t) nb_max + 1) * 4), total = o_words + sizeof(BagWords);
-    ecal_devbuf scratch;
-    int rc;
-    if ((rc = ecal_ensure(ctx, scratch, total))) return rc;
-    uint8_t *base = scratch.as<uint8_t>();
-    unsigned long long *first = (unsigned long long *) (base + o_first);
-    uint32_t *keep = (uint32_t *) (base + o_keep), *koff = (uint32_t *) (base + o_koff);
-    BagWords *d_w = (BagWords *) (base + o_words);
-    const BagFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
-    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(BagWords), &d_w->first_stop, st))) return rc;
-    tm.mark("start");
-    BagSource src{d_file, n_bytes, bound, d_messages, first, (uint32_t) n_messages};
-    BagWords W;
-    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
-    uint32_t nb = nb_max;
+const ecal_ingest_nouns BAG_NOUNS{"bag ingest", "bag", "message", "file", "message scan"};
+
+void bag_launch_scan(const BagMessage *d_messages, uint64_t n_messages, uint64_t n_bytes, unsigned long long *first, BagWords *d_w, hipStream_t st) {
     hipLaunchKernelGGL(bag_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, first, d_w);
-    ECAL_HIP_TRY(ctx, hipGetLastError());
-    tm.mark("message scan");
-    if (n_slots_host == BG_NONE) {   // the grid is a count of the table: one look at it
-        if ((rc = fetch())) return rc;
-        if (W.bad_table) {
-            ctx->last_error = "bag ingest: " + std::to_string(W.bad_table) + " messages of the table do not lie within the file";
-            return ECAL_ERR_INVALID;
-        }
-        if (W.n_slots > 0xFFFFFFFFull) {
-            I.n_events = W.n_slots;
-            ctx->last_error = "bag ingest: more than 2^32-1 events";
-            return ECAL_ERR_RANGE;
-        }
-        if (W.n_slots > bound) {   // (messages that overlap: more events than the file has room for)
-            ctx->last_error = "bag ingest: the message table names more events than the file holds";
-            return ECAL_ERR_INVALID;
-        }
-        src.n_slots = W.n_slots;
-        nb = (uint32_t) ((W.n_slots + BG_BLOCK - 1) / BG_BLOCK);
-    }
-    I.n_raw_events = src.n_slots;
-    if (!src.n_slots) return ECAL_OK;
-    if (own_events) {
-        capacity = src.n_slots;
-        if ((rc = ecal_ingest_alloc_records(ctx, "bag ingest", capacity, own_events))) return rc;
-        d_events = *own_events;
-    }
-    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
-    auto launched = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipGetLastError());
-        return ECAL_OK;
-    };
-    hipLaunchKernelGGL(bag_verdict_kernel, dim3(nb), dim3(BG_T), 0, st, src, flt, keep, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("verdict");
-    if ((rc = ecal_scan_blocks(ctx, keep, nb, koff, st))) return fail(rc);
-    hipLaunchKernelGGL(bag_write_kernel, dim3(nb), dim3(BG_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("scan, write");
-    if ((rc = fetch())) return fail(rc);
-    if (W.bad_table || W.n_slots != src.n_slots) {
-        ctx->last_error = "bag ingest: the message table does not fit the file (" + std::to_string(W.bad_table) + " messages outside it, " +
-                          std::to_string(W.n_slots) + " events)";
-        return fail(ECAL_ERR_INVALID);
-    }
-    I.n_events = W.n_events;
-    I.n_outside = W.n_outside;
-    I.n_negative = W.n_negative;
-    I.n_before_start = W.n_before_start;
-    // every event in front of the offender has one of the four classes
-    I.n_after_end = W.first_stop == BG_NONE ? 0 : I.n_raw_events - (W.n_events + W.n_outside + W.n_negative + W.n_before_start);
-    if (I.n_events > capacity) {
-        ctx->last_error = "bag ingest: " + std::to_string(I.n_events) + " records, more than the capacity";
-        return fail(ECAL_ERR_RANGE);
-    }
-    return ECAL_OK;
 }
 
-// Bytes of a file through a small read-ahead window: the walk asks for a record's header length, its header, the front of a message
-// — a few dozen bytes at places 10 – 100 KB apart — and one pread of a window serves them all.
-struct BagFileReader {
-    int fd;
-    uint64_t file_bytes;
-    std::vector<uint8_t> win;
-    uint64_t win_at = 0, win_n = 0;
-    static constexpr size_t WINDOW = 512;
-    bool pread_all(void *dst, size_t n, uint64_t at) const {
-        for (size_t got = 0; got < n;) {
-            const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
-            if (rd <= 0) return false;
-            got += (size_t) rd;
-        }
-        return true;
-    }
-    bool operator()(uint64_t pos, uint8_t *dst, size_t n) {
-        if (pos >= win_at && pos + n <= win_at + win_n) {
-            memcpy(dst, win.data() + (pos - win_at), n);
-            return true;
-        }
-        if (n >= WINDOW) return pread_all(dst, n, pos);
-        const size_t want = (size_t) std::min<uint64_t>(WINDOW, file_bytes - pos);
-        win.resize(WINDOW);
-        if (!pread_all(win.data(), want, pos)) return false;
-        win_at = pos;
-        win_n = want;
-        memcpy(dst, win.data(), n);
-        return true;
-    }
-};
+// o.time_base: the base in force (the caller has resolved auto_time_base).  n_slots_host, own_events: ecal_ingest_message_table's
+int bag_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const BagMessage *d_messages, uint64_t n_messages, uint64_t n_slots_host,
+               const ecal_bag_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events, ecal_bag_info &I, hipStream_t st) {
+    I.n_messages = n_messages;
+    I.time_base = o.time_base;
+    const BagFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
+    return ecal_ingest_message_table<BagWords>(
+        ctx, BAG_NOUNS, BagSource{d_file, n_bytes, 0, d_messages, nullptr, (uint32_t) n_messages}, flt, n_bytes, n_messages, BAG_EVENT_BYTES, n_slots_host,
+        BG_BLOCK, d_events, capacity, own_events, I, st,
+        [&](unsigned long long *first, BagWords *d_w) { bag_launch_scan(d_messages, n_messages, n_bytes, first, d_w, st); },
+        [&](const BagSource &src, const BagFilter &f, uint32_t nb, uint32_t *keep, BagWords *d_w) {
+            hipLaunchKernelGGL(bag_verdict_kernel, dim3(nb), dim3(BG_T), 0, st, src, f, keep, d_w);
+        },
+        [&](const BagSource &src, const BagFilter &f, uint32_t nb, const uint32_t *koff, uint8_t *events, uint64_t cap, BagWords *d_w) {
+            hipLaunchKernelGGL(bag_write_kernel, dim3(nb), dim3(BG_T), 0, st, src, koff, f, events, cap, d_w);
+        },
+        [](const BagWords &, uint64_t *) { return ECAL_OK; });
+}
 
 // file -> (message table on the host, from record headers, beside the upload) -> file in HBM -> records in a device buffer of their
 // own (null for none), the file's bytes freed
@@ -378,23 +227,13 @@ int bag_file_to_events(ecal_ctx *ctx, const char *path, const ecal_bag_options *
     int rc = bag_check_options(ctx, o);
     if (rc) return rc;
     const BagChoice choice = bag_choice(&o);
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) {
-        ctx->last_error = std::string("bag ingest: cannot open ") + path;
-        return ECAL_ERR_INVALID;
-    }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) {
-        close(fd);
-        ctx->last_error = std::string("bag ingest: cannot read ") + path;
-        return ECAL_ERR_INVALID;
-    }
+    int fd;
+    uint64_t file_bytes;
     {   // the first line in front of everything: a file of another kind is not uploaded
-        uint8_t head[32];
-        BagFileReader rd{fd, (uint64_t) sb.st_size};
-        const size_t hn = (size_t) std::min<uint64_t>((uint64_t) sb.st_size, sizeof(head));
-        std::string err = "cannot be read";
-        if ((hn && !rd.pread_all(head, hn, 0)) || bag_check_magic(head, hn, &err)) {
+        std::vector<uint8_t> head;
+        if ((rc = ecal_ingest_open_head(ctx, "bag ingest", path, 32, "cannot be read", &fd, &file_bytes, &head))) return rc;
+        std::string err;
+        if (bag_check_magic(head.data(), head.size(), &err)) {
             close(fd);
             ctx->last_error = "bag ingest: " + err + " (" + path + ")";
             return ECAL_ERR_INVALID;
@@ -404,10 +243,10 @@ int bag_file_to_events(ecal_ctx *ctx, const char *path, const ecal_bag_options *
     BagCounts c;
     memset(&c, 0, sizeof(c));
     ecal_ingest_upload up;
-    rc = ecal_ingest_upload_indexed(ctx, "bag", "bag ingest", "host message index", path, fd, 0, (uint64_t) sb.st_size, [&](std::string *error, const void **tab, size_t *tab_bytes) {
-        BagFileReader rd{fd, (uint64_t) sb.st_size};
+    rc = ecal_ingest_upload_indexed(ctx, "bag", "bag ingest", "host message index", path, fd, 0, file_bytes, [&](std::string *error, const void **tab, size_t *tab_bytes) {
+        ecal_ingest_file_reader rd{fd, file_bytes};
         std::string err;
-        const int index_rc = bag_walk(rd, (uint64_t) sb.st_size, choice, c, [&](const BagMessage &m) { table.push_back(m); }, &err);
+        const int index_rc = bag_walk(rd, file_bytes, choice, c, [&](const BagMessage &m) { table.push_back(m); }, &err);
         if (index_rc) *error = "bag ingest: " + err + " (" + path + ")";
         *tab = table.data();
         *tab_bytes = table.size() * sizeof(BagMessage);
@@ -452,19 +291,11 @@ extern "C" int ecal_bag_count_events_dev(ecal_ctx *ctx, const uint8_t *d_file, u
     hipStream_t st = (hipStream_t) stream;
     if (!n_messages) return ECAL_OK;
     ecal_devbuf buf;
-    const size_t o_words = up16((size_t) (n_messages + 1) * 8);
-    if ((rc = ecal_ensure(ctx, buf, o_words + sizeof(BagWords)))) return rc;
-    BagWords *d_w = (BagWords *) (buf.as<uint8_t>() + o_words);
-    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(BagWords), &d_w->first_stop, st))) return rc;
-    hipLaunchKernelGGL(bag_message_scan_kernel, dim3(1), dim3(1024), 0, st, reinterpret_cast<const BagMessage *>(d_messages), (uint32_t) n_messages,
-                       n_bytes, buf.as<unsigned long long>(), d_w);
-    ECAL_HIP_TRY(ctx, hipGetLastError());
     BagWords W;
-    if ((rc = ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st))) return rc;
-    if (W.bad_table) {
-        ctx->last_error = "bag ingest: " + std::to_string(W.bad_table) + " messages of the table do not lie within the file";
-        return ECAL_ERR_INVALID;
-    }
+    if ((rc = ecal_ingest_scan_table(ctx, BAG_NOUNS, n_messages, buf, W, "", st, [&](unsigned long long *first, BagWords *d_w) {
+            bag_launch_scan(reinterpret_cast<const BagMessage *>(d_messages), n_messages, n_bytes, first, d_w, st);
+        })))
+        return rc;
     *n_events = W.n_slots;
     return ECAL_OK;
 }

@@ -245,6 +245,23 @@ constexpr uint64_t ECAL_INGEST_ANY_SIZE = ~0ull;
 int ecal_ingest_upload_indexed(ecal_ctx *ctx, const char *tag, const char *who, const char *index_label, const char *path, int fd,
                                uint64_t file_offset, uint64_t expect_bytes, const ecal_ingest_index_fn &index, ecal_ingest_upload *up);
 void ecal_ingest_free_upload(ecal_ctx *ctx, ecal_ingest_upload *up);
+// n bytes of fd from `at` on into dst, in as many reads as it takes; false when the file ends first or a read fails
+bool ecal_ingest_pread_all(int fd, void *dst, size_t n, uint64_t at);
+// Bytes of a file through a small read-ahead window: a host index walk asks for a record's header, a schema, the front of a message —
+// a few dozen bytes at places 10 – 100 KB apart — and one pread of a window serves the neighbours.
+struct ecal_ingest_file_reader {
+    int fd;
+    uint64_t file_bytes;
+    std::vector<uint8_t> win;
+    uint64_t win_at = 0, win_n = 0;
+    static constexpr size_t WINDOW = 512;
+    bool operator()(uint64_t pos, uint8_t *dst, size_t n);
+};
+// The front of a file form: path opened (*fd), *file_bytes = its size, *head = its first min(size, head_max) bytes.  "<who>: cannot open
+// <path>"; "<who>: cannot read <path>" for a size that cannot be asked and for a head that cannot be read — the latter as "<who>:
+// <unread> (<path>)" where `unread` is given.  ECAL_ERR_INVALID with the file closed again.
+int ecal_ingest_open_head(ecal_ctx *ctx, const char *who, const char *path, size_t head_max, const char *unread, int *fd, uint64_t *file_bytes,
+                          std::vector<uint8_t> *head);
 // a file form's records as a stream (d_events null: no events, a stream of none), or written to bin_path and freed
 int ecal_stream_from_events(ecal_ctx *ctx, const char *who, uint8_t *d_events, uint64_t n_events, ecal_stream **out);
 int ecal_ingest_records_to_bin(ecal_ctx *ctx, const char *who, uint8_t *d_events, uint64_t n_events, const char *bin_path);

@@ -360,15 +360,6 @@ NpyChoice npy_choice(const ecal_npy_options *o) {
     return ch;
 }
 
-bool fd_pread_all(int fd, void *dst, size_t n, uint64_t at) {
-    for (size_t got = 0; got < n;) {
-        const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
-        if (rd <= 0) return false;
-        got += (size_t) rd;
-    }
-    return true;
-}
-
 // file -> (header on the host) -> payload in HBM -> records in a device buffer of their own (null for none), the payload freed
 int npy_file_to_events(ecal_ctx *ctx, const char *path, const ecal_npy_options *opt, uint8_t **d_events, ecal_fields_info &I) {
     *d_events = nullptr;
@@ -385,10 +376,10 @@ int npy_file_to_events(ecal_ctx *ctx, const char *path, const ecal_npy_options *
     std::vector<uint8_t> head((size_t) std::min<uint64_t>((uint64_t) sb.st_size, 1u << 20));
     NpyLayout L;
     std::string err = "the file cannot be read";
-    int rc = (head.empty() || fd_pread_all(fd, head.data(), head.size(), 0)) ? npy_parse_header(head.data(), head.size(), (uint64_t) sb.st_size, npy_choice(&o), L, &err)
+    int rc = (head.empty() || ecal_ingest_pread_all(fd, head.data(), head.size(), 0)) ? npy_parse_header(head.data(), head.size(), (uint64_t) sb.st_size, npy_choice(&o), L, &err)
                                                                               : ECAL_ERR_INVALID;
     uint64_t first_stamp = 0;
-    if (!rc && L.n_events && !fd_pread_all(fd, &first_stamp, fd_type_size(L.field[FD_T].type), L.data_offset + L.field[FD_T].offset)) {
+    if (!rc && L.n_events && !ecal_ingest_pread_all(fd, &first_stamp, fd_type_size(L.field[FD_T].type), L.data_offset + L.field[FD_T].offset)) {
         rc = ECAL_ERR_INVALID;
         err = "the file cannot be read";
     }

@@ -1,9 +1,13 @@
 // What the host sides of the ingests share (ecal_ctx.hpp declares it): the refusals of a device form's arguments, the counters'
-// wipe and fetch, the record buffer an ingest allocates for its caller, the middle of the file forms that index a file beside its
-// upload (bag, AEDAT 3.1, AEDAT 4), and the two ends of every file form (a stream, a .bin file).
+// wipe and fetch, the record buffer an ingest allocates for its caller, the full read, the windowed reader and the front of the file
+// forms, their middle that indexes a file beside its upload (bag, MCAP, AEDAT 3.1, AEDAT 4), and the two ends of every file form (a
+// stream, a .bin file).  The drivers that are templates over a format's kernels are ingest_driver.hpp's.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <chrono>
 #include <thread>
+#include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 
@@ -52,6 +56,52 @@ int ecal_ingest_drop_records(uint8_t **own, int code) {
         *own = nullptr;
     }
     return code;
+}
+
+bool ecal_ingest_pread_all(int fd, void *dst, size_t n, uint64_t at) {
+    for (size_t got = 0; got < n;) {
+        const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
+        if (rd <= 0) return false;
+        got += (size_t) rd;
+    }
+    return true;
+}
+
+bool ecal_ingest_file_reader::operator()(uint64_t pos, uint8_t *dst, size_t n) {
+    if (pos >= win_at && pos + n <= win_at + win_n) {
+        memcpy(dst, win.data() + (pos - win_at), n);
+        return true;
+    }
+    if (n >= WINDOW) return ecal_ingest_pread_all(fd, dst, n, pos);
+    const size_t want = (size_t) std::min<uint64_t>(WINDOW, file_bytes - pos);
+    win.resize(WINDOW);
+    if (!ecal_ingest_pread_all(fd, win.data(), want, pos)) return false;
+    win_at = pos;
+    win_n = want;
+    memcpy(dst, win.data(), n);
+    return true;
+}
+
+int ecal_ingest_open_head(ecal_ctx *ctx, const char *who, const char *path, size_t head_max, const char *unread, int *fd, uint64_t *file_bytes,
+                          std::vector<uint8_t> *head) {
+    *fd = open(path, O_RDONLY);
+    if (*fd < 0) {
+        ctx->last_error = std::string(who) + ": cannot open " + path;
+        return ECAL_ERR_INVALID;
+    }
+    struct stat sb;
+    const bool sized = fstat(*fd, &sb) == 0;
+    if (sized) {
+        *file_bytes = (uint64_t) sb.st_size;
+        head->resize((size_t) std::min<uint64_t>(*file_bytes, head_max));
+    }
+    if (!sized || !ecal_ingest_pread_all(*fd, head->data(), head->size(), 0)) {
+        close(*fd);
+        *fd = -1;
+        ctx->last_error = sized && unread ? std::string(who) + ": " + unread + " (" + path + ")" : std::string(who) + ": cannot read " + path;
+        return ECAL_ERR_INVALID;
+    }
+    return ECAL_OK;
 }
 
 int ecal_ingest_upload_indexed(ecal_ctx *ctx, const char *tag, const char *who, const char *index_label, const char *path, int fd,

@@ -11,6 +11,9 @@
 //   3. ecal_scan_blocks          the blocks' first kept index
 //   4. mcap_write_kernel         classed again; the kept events below the first offender get their index, are packed into LDS and
 //                                copied out with aligned stores; the totals
+// The bodies of passes 2 and 4 are slot_kernels.hpp's (McapFormat<KIND> below is this format's policy), the table scan, the table check,
+// the bisection, the clipped load and the tails ingest_blocks.hpp's, the host driver and the table scan's host side ingest_driver.hpp's
+// (ecal_ingest_message_table, ecal_ingest_scan_table), all shared with the other table ingests.
 // An event is fetched from the aligned load32_clipped words that cover it and its fields are shifted out of them (mcap_fetch_event):
 // event 0 of a message and the later ones have their own offsets, and nothing in the file is aligned.
 // EVT3: the same scan over the table's byte counts, then mcap_gather_kernel copies the messages' byte arrays, in file order, into one
@@ -20,13 +23,11 @@
 #include <algorithm>
 #include <vector>
 #include <math.h>
-#include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 #include "ecal_ctx.hpp"
 #include "../../include/ecal_mcap.h"
-#include "block_utils.hpp"
-#include "ingest_blocks.hpp"
+#include "slot_kernels.hpp"
+#include "ingest_driver.hpp"
 #include "mcap_events.hpp"
 
 namespace ecal {
@@ -49,13 +50,7 @@ constexpr uint32_t MC_PER = MCAP_THREAD_EVENTS;
 constexpr uint32_t MC_BLOCK = MCAP_BLOCK_EVENTS;   // slots per block, and records staged in LDS (25 600 bytes: six workgroups a CU)
 constexpr unsigned long long MC_NONE = ~0ull;
 
-// the counters of one ingest (device)
-struct McapWords {
-    unsigned long long n_slots;      // slots of the table (EVT3: payload bytes)
-    unsigned long long first_stop;   // the first slot that reaches end_time (MC_NONE: none)
-    unsigned long long n_events, n_outside, n_negative, n_before_start;
-    unsigned long long bad_table;    // messages of the table that do not lie within n_bytes
-};
+typedef MessageWords McapWords;   // the counters of one ingest (device; EVT3: n_slots = payload bytes)
 
 // what a block kernel is given of the file
 struct McapSource {
@@ -107,6 +102,26 @@ template <uint32_t KIND> struct McSlots {
             }
         }
     }
+    __device__ __forceinline__ const BagEvent &event(uint32_t j) const { return ev[j]; }
+};
+
+// the format of slot_kernels.hpp's bodies: the bag ingest's filter and classes
+template <uint32_t KIND> struct McapFormat {
+    typedef McapSource Source;
+    typedef BagFilter Filter;
+    typedef McapWords Words;
+    typedef McSlots<KIND> Slots;
+    static constexpr int T = MC_T, N_DROPS = 3;
+    static constexpr uint32_t PER = MC_PER, BLOCK = MC_BLOCK;
+    static constexpr uint8_t KEEP = BAG_CLASS_KEEP, STOP = BAG_CLASS_STOP;
+    static __device__ __forceinline__ Slots slots(const Source &src, unsigned long long *) { return Slots(src); }
+    static __device__ __forceinline__ bool is_event(const Slots &, uint32_t) { return true; }
+    static __device__ __forceinline__ uint8_t classify(const Slots &s, uint32_t j, const Filter &flt, double *t, uint32_t *x, uint32_t *y) {
+        return bag_classify(s.event(j), flt, t, x, y);
+    }
+    static __device__ __forceinline__ uint8_t polarity(const Slots &s, uint32_t j) { return s.event(j).pol; }
+    static __device__ __forceinline__ constexpr uint8_t drop_class(int i) { return i == 0 ? BAG_CLASS_OUTSIDE : i == 1 ? BAG_CLASS_NEGATIVE : BAG_CLASS_BEFORE_START; }
+    static __device__ __forceinline__ unsigned long long *drop_counter(Words *w, int i) { return i == 0 ? &w->n_outside : i == 1 ? &w->n_negative : &w->n_before_start; }
 };
 
 // first[m] = n of the messages before m, first[n] = all of them (table_exscan_1024); the table checked against n_bytes.  One workgroup.
@@ -114,85 +129,26 @@ __global__ __launch_bounds__(1024) void mcap_message_scan_kernel(const McapMessa
                                                                  unsigned long long *__restrict__ first, McapWords *__restrict__ w) {
     const unsigned long long tot = table_exscan_1024(n, [&](uint64_t p) { return (unsigned long long) messages[p].n; }, first);
     if (threadIdx.x == 0) w->n_slots = tot;
-    unsigned long long bad = 0;
-    for (uint64_t p = threadIdx.x; p < n; p += 1024u) {
-        const uint64_t off = messages[p].offset, len = mcap_message_bytes(layout, messages[p].n);
-        if (off > n_bytes || len > n_bytes - off) bad++;
-        if (layout.kind == MCAP_EVT3 && (messages[p].n & 1u)) bad++;   // (an odd byte count: the gather moves whole 16-bit words)
-    }
+    unsigned long long bad = table_count_outside(n, n_bytes, threadIdx.x, 1024u, [&](uint64_t p) { return messages[p].offset; },
+                                                 [&](uint64_t p) { return mcap_message_bytes(layout, messages[p].n); });
+    // EVT3: an odd byte count is a bad entry too (the gather moves whole 16-bit words).  A second walk over the table on purpose: the
+    // shared check stays free of the format's own rule, and one workgroup over the table once more is nothing beside the gather
+    if (layout.kind == MCAP_EVT3)
+        for (uint64_t p = threadIdx.x; p < n; p += 1024u) bad += messages[p].n & 1u;
     if (bad) atomicAdd(&w->bad_table, bad);
 }
 
 // the class of every slot, the kept events per block, the first slot that reaches end_time
 template <uint32_t KIND>
 __global__ __launch_bounds__(MC_T) void mcap_verdict_kernel(McapSource src, BagFilter flt, uint32_t *__restrict__ blk_keep, McapWords *__restrict__ w) {
-    const int tid = threadIdx.x;
-    const McSlots<KIND> mine(src);
-    uint32_t keep = 0, stop = 0xFFFFFFFFu;   // (stop: a slot within the block)
-#pragma unroll
-    for (uint32_t j = 0; j < MC_PER; j++) {
-        if (j < mine.n) {
-            double t;
-            uint32_t x, y;
-            const uint8_t c = bag_classify(mine.ev[j], flt, &t, &x, &y);
-            keep += c == BAG_CLASS_KEEP ? 1u : 0u;
-            const uint32_t at = (uint32_t) tid * MC_PER + j;
-            if (c == BAG_CLASS_STOP && at < stop) stop = at;
-        }
-    }
-    block_keep_and_stop<MC_T>(keep, stop, blk_keep, &w->first_stop, [] { return (unsigned long long) blockIdx.x * MC_BLOCK; });
+    slot_verdict_body<McapFormat<KIND>>(src, flt, blk_keep, w);
 }
 
 // the kept events below the first offender, packed in LDS and copied out; the totals
 template <uint32_t KIND>
 __global__ __launch_bounds__(MC_T) void mcap_write_kernel(McapSource src, const uint32_t *__restrict__ blk_koff, BagFilter flt, uint8_t *__restrict__ events,
                                                           uint64_t capacity, McapWords *__restrict__ w) {
-    __shared__ unsigned long long s_scan[MC_T / 64];
-    __shared__ uint32_t s_cnt[3];
-    __shared__ __attribute__((aligned(16))) uint8_t s_rec[MC_BLOCK * 25];
-    const int tid = threadIdx.x;
-    const unsigned long long X = w->first_stop;
-    const uint64_t slot0 = (uint64_t) blockIdx.x * MC_BLOCK;
-    if (slot0 >= X) return;   // (the whole block lies behind the offender; the same for every thread)
-    const McSlots<KIND> mine(src);
-    // slots of this block below the offender: in-block slot < lim
-    const uint32_t lim = X - slot0 < (unsigned long long) MC_BLOCK ? (uint32_t) (X - slot0) : MC_BLOCK;
-    if (tid < 3) s_cnt[tid] = 0;
-    uint32_t keep = 0, kept_mask = 0, drop[3] = {0u, 0u, 0u};
-    double kt[MC_PER];
-    uint32_t kx[MC_PER], ky[MC_PER];
-#pragma unroll
-    for (uint32_t j = 0; j < MC_PER; j++) {
-        kt[j] = 0.0;
-        kx[j] = ky[j] = 0u;
-        if (j < mine.n && (uint32_t) tid * MC_PER + j < lim) {
-            const uint8_t c = bag_classify(mine.ev[j], flt, &kt[j], &kx[j], &ky[j]);
-            if (c == BAG_CLASS_KEEP) {
-                keep++;
-                kept_mask |= 1u << j;
-            }
-            drop[0] += c == BAG_CLASS_OUTSIDE ? 1u : 0u;
-            drop[1] += c == BAG_CLASS_NEGATIVE ? 1u : 0u;
-            drop[2] += c == BAG_CLASS_BEFORE_START ? 1u : 0u;
-        }
-    }
-    uint32_t kex, eb, ktot, tb;
-    block_exscan_pair<MC_T>(keep, 0u, s_scan, &kex, &eb, &ktot, &tb);   // (its barriers order the zeroing of s_cnt too)
-    block_add_drops<3>(drop, s_cnt);
-    // at most MC_BLOCK kept events: one chunk of LDS holds them all
-    uint32_t k = kex;
-#pragma unroll
-    for (uint32_t j = 0; j < MC_PER; j++) {
-        if (kept_mask >> j & 1u) {
-            pack_record(s_rec + k * 25u, kt[j], (double) kx[j], (double) ky[j], mine.ev[j].pol);
-            k++;
-        }
-    }
-    __syncthreads();
-    if (tid < 3 && s_cnt[tid])
-        atomicAdd(tid == 0 ? &w->n_outside : tid == 1 ? &w->n_negative : &w->n_before_start, (unsigned long long) s_cnt[tid]);
-    if (tid == 0 && ktot) atomicAdd(&w->n_events, (unsigned long long) ktot);
-    block_copy_out<MC_T>(s_rec, ktot, events, blk_koff[blockIdx.x], capacity);
+    slot_write_body<McapFormat<KIND>>(src, blk_koff, flt, events, capacity, w);
 }
 
 // EVT3: bytes [16 q, 16 q + 16) of the payload, q = the thread's index in the grid, from the message(s) that hold them.  src.n_slots =
@@ -261,6 +217,7 @@ extern "C" uint32_t ecal_mcap_block_events(void) { return MC_BLOCK; }
 namespace {
 
 const char WHO[] = "mcap ingest";
+const ecal_ingest_nouns MCAP_NOUNS{WHO, "mcap", "message", "file", "message scan"};
 
 McapLayout mcap_layout_of(const ecal_mcap_layout &l) {
     McapLayout L;
@@ -311,20 +268,10 @@ int mcap_check_options(ecal_ctx *ctx, const ecal_mcap_options &o) {
 // in `scratch` for the gather
 int mcap_scan_table(ecal_ctx *ctx, const McapMessage *d_messages, uint64_t n_messages, uint64_t n_bytes, const McapLayout &L, ecal_devbuf &scratch,
                     McapWords &W, hipStream_t st) {
-    const size_t o_words = up16((size_t) (n_messages + 1) * 8);
-    int rc;
-    if ((rc = ecal_ensure(ctx, scratch, o_words + sizeof(McapWords)))) return rc;
-    McapWords *d_w = (McapWords *) (scratch.as<uint8_t>() + o_words);
-    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(McapWords), &d_w->first_stop, st))) return rc;
-    hipLaunchKernelGGL(mcap_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, L, scratch.as<unsigned long long>(), d_w);
-    ECAL_HIP_TRY(ctx, hipGetLastError());
-    if ((rc = ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st))) return rc;
-    if (W.bad_table) {
-        ctx->last_error = std::string(WHO) + ": " + std::to_string(W.bad_table) + " messages of the table do not lie within the file" +
-                          (L.kind == MCAP_EVT3 ? " or have an odd byte count" : "");
-        return ECAL_ERR_INVALID;
-    }
-    return ECAL_OK;
+    return ecal_ingest_scan_table(ctx, MCAP_NOUNS, n_messages, scratch, W, L.kind == MCAP_EVT3 ? " or have an odd byte count" : "", st,
+                                  [&](unsigned long long *first, McapWords *d_w) {
+                                      hipLaunchKernelGGL(mcap_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, L, first, d_w);
+                                  });
 }
 
 // EVT3: the table's byte arrays into one payload of its own (*payload, hipMalloc; null for no bytes), *total its bytes
@@ -418,97 +365,25 @@ int mcap_ingest_evt3(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, con
     return rc ? ecal_ingest_drop_records(own_events, rc) : rc;
 }
 
-// STRUCT and MONO: the bag ingest's device path.  o.time_base: the base in force.  n_slots_host: the sum of the table's n when the caller
-// knows it (the file forms), else MC_NONE.  own_events != null: the records go into a buffer allocated here for the count
+// STRUCT and MONO: the bag ingest's device path.  o.time_base: the base in force.  n_slots_host, own_events: ecal_ingest_message_table's
 template <uint32_t KIND>
 int mcap_ingest(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, const McapMessage *d_messages, uint64_t n_messages, uint64_t n_slots_host,
                 const McapLayout &L, const ecal_mcap_options &o, uint8_t *d_events, uint64_t capacity, uint8_t **own_events, ecal_mcap_info &I,
                 hipStream_t st) {
-    if (own_events) *own_events = nullptr;
-    if (n_slots_host == 0) return ECAL_OK;
-    const uint64_t least = std::min(L.span[0], L.span[1]);
-    // no fewer than the slots: sizes the per-block arrays
-    const uint64_t bound = n_slots_host != MC_NONE ? n_slots_host : std::min<uint64_t>(n_bytes / least, 0xFFFFFFFFull);
-    if (bound > 0xFFFFFFFFull) {
-        I.n_events = bound;
-        ctx->last_error = std::string(WHO) + ": more than 2^32-1 events";
-        return ECAL_ERR_RANGE;
-    }
-    const uint32_t nb_max = (uint32_t) ((bound + MC_BLOCK - 1) / MC_BLOCK);
-    ecal_load_timer tm("mcap", ctx->sw.load_trace, st);
-    const size_t o_first = 0, o_keep = o_first + up16((size_t) (n_messages + 1) * 8), o_koff = o_keep + up16(((size_t) nb_max + 1) * 4),
-                 o_words = o_koff + up16(((size_t) nb_max + 1) * 4), total = o_words + sizeof(McapWords);
-    ecal_devbuf scratch;
-    int rc;
-    if ((rc = ecal_ensure(ctx, scratch, total))) return rc;
-    uint8_t *base = scratch.as<uint8_t>();
-    unsigned long long *first = (unsigned long long *) (base + o_first);
-    uint32_t *keep = (uint32_t *) (base + o_keep), *koff = (uint32_t *) (base + o_koff);
-    McapWords *d_w = (McapWords *) (base + o_words);
     const BagFilter flt{o.time_base, o.width, o.height, o.start_time, o.has_end_time, o.end_time, o.flip_x, o.flip_y};
-    if ((rc = ecal_ingest_wipe_words(ctx, d_w, sizeof(McapWords), &d_w->first_stop, st))) return rc;
-    tm.mark("start");
-    McapSource src{d_file, n_bytes, bound, d_messages, first, (uint32_t) n_messages, L};
-    McapWords W;
-    auto fetch = [&]() { return ecal_ingest_fetch_words(ctx, &W, d_w, sizeof(W), st); };
-    uint32_t nb = nb_max;
-    hipLaunchKernelGGL(mcap_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, L, first, d_w);
-    ECAL_HIP_TRY(ctx, hipGetLastError());
-    tm.mark("message scan");
-    if (n_slots_host == MC_NONE) {   // the grid is a count of the table: one look at it
-        if ((rc = fetch())) return rc;
-        if (W.bad_table) {
-            ctx->last_error = std::string(WHO) + ": " + std::to_string(W.bad_table) + " messages of the table do not lie within the file";
-            return ECAL_ERR_INVALID;
-        }
-        if (W.n_slots > 0xFFFFFFFFull) {
-            I.n_events = W.n_slots;
-            ctx->last_error = std::string(WHO) + ": more than 2^32-1 events";
-            return ECAL_ERR_RANGE;
-        }
-        if (W.n_slots > bound) {   // (messages that overlap: more events than the file has room for)
-            ctx->last_error = std::string(WHO) + ": the message table names more events than the file holds";
-            return ECAL_ERR_INVALID;
-        }
-        src.n_slots = W.n_slots;
-        nb = (uint32_t) ((W.n_slots + MC_BLOCK - 1) / MC_BLOCK);
-    }
-    I.n_raw_events = src.n_slots;
-    if (!src.n_slots) return ECAL_OK;
-    if (own_events) {
-        capacity = src.n_slots;
-        if ((rc = ecal_ingest_alloc_records(ctx, WHO, capacity, own_events))) return rc;
-        d_events = *own_events;
-    }
-    auto fail = [&](int code) { return ecal_ingest_drop_records(own_events, code); };
-    auto launched = [&]() -> int {
-        ECAL_HIP_TRY(ctx, hipGetLastError());
-        return ECAL_OK;
-    };
-    hipLaunchKernelGGL(mcap_verdict_kernel<KIND>, dim3(nb), dim3(MC_T), 0, st, src, flt, keep, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("verdict");
-    if ((rc = ecal_scan_blocks(ctx, keep, nb, koff, st))) return fail(rc);
-    hipLaunchKernelGGL(mcap_write_kernel<KIND>, dim3(nb), dim3(MC_T), 0, st, src, (const uint32_t *) koff, flt, d_events, capacity, d_w);
-    if ((rc = launched())) return fail(rc);
-    tm.mark("scan, write");
-    if ((rc = fetch())) return fail(rc);
-    if (W.bad_table || W.n_slots != src.n_slots) {
-        ctx->last_error = std::string(WHO) + ": the message table does not fit the file (" + std::to_string(W.bad_table) + " messages outside it, " +
-                          std::to_string(W.n_slots) + " events)";
-        return fail(ECAL_ERR_INVALID);
-    }
-    I.n_events = W.n_events;
-    I.n_outside = W.n_outside;
-    I.n_negative = W.n_negative;
-    I.n_before_start = W.n_before_start;
-    // every event in front of the offender has one of the four classes
-    I.n_after_end = W.first_stop == MC_NONE ? 0 : I.n_raw_events - (W.n_events + W.n_outside + W.n_negative + W.n_before_start);
-    if (I.n_events > capacity) {
-        ctx->last_error = std::string(WHO) + ": " + std::to_string(I.n_events) + " records, more than the capacity";
-        return fail(ECAL_ERR_RANGE);
-    }
-    return ECAL_OK;
+    return ecal_ingest_message_table<McapWords>(
+        ctx, MCAP_NOUNS, McapSource{d_file, n_bytes, 0, d_messages, nullptr, (uint32_t) n_messages, L}, flt, n_bytes, n_messages,
+        std::min(L.span[0], L.span[1]), n_slots_host, MC_BLOCK, d_events, capacity, own_events, I, st,
+        [&](unsigned long long *first, McapWords *d_w) {
+            hipLaunchKernelGGL(mcap_message_scan_kernel, dim3(1), dim3(1024), 0, st, d_messages, (uint32_t) n_messages, n_bytes, L, first, d_w);
+        },
+        [&](const McapSource &src, const BagFilter &f, uint32_t nb, uint32_t *keep, McapWords *d_w) {
+            hipLaunchKernelGGL(mcap_verdict_kernel<KIND>, dim3(nb), dim3(MC_T), 0, st, src, f, keep, d_w);
+        },
+        [&](const McapSource &src, const BagFilter &f, uint32_t nb, const uint32_t *koff, uint8_t *events, uint64_t cap, McapWords *d_w) {
+            hipLaunchKernelGGL(mcap_write_kernel<KIND>, dim3(nb), dim3(MC_T), 0, st, src, koff, f, events, cap, d_w);
+        },
+        [](const McapWords &, uint64_t *) { return ECAL_OK; });
 }
 
 // by kind; I.n_messages, I.time_base and I.layout are set here
@@ -526,38 +401,6 @@ int mcap_ingest_any(ecal_ctx *ctx, const uint8_t *d_file, uint64_t n_bytes, cons
                : mcap_ingest<MCAP_STRUCT>(ctx, d_file, n_bytes, d_messages, n_messages, n_slots_host, L, o, d_events, capacity, own_events, I, st);
 }
 
-// Bytes of a file through a small read-ahead window: the walk asks for a record's 9 header bytes, a schema, the fields in front of a
-// message's events — a few dozen bytes at places far apart — and one pread of a window serves the neighbours.
-struct McapFileReader {
-    int fd;
-    uint64_t file_bytes;
-    std::vector<uint8_t> win;
-    uint64_t win_at = 0, win_n = 0;
-    static constexpr size_t WINDOW = 512;
-    bool pread_all(void *dst, size_t n, uint64_t at) const {
-        for (size_t got = 0; got < n;) {
-            const ssize_t rd = pread(fd, (uint8_t *) dst + got, n - got, (off_t) (at + got));
-            if (rd <= 0) return false;
-            got += (size_t) rd;
-        }
-        return true;
-    }
-    bool operator()(uint64_t pos, uint8_t *dst, size_t n) {
-        if (pos >= win_at && pos + n <= win_at + win_n) {
-            memcpy(dst, win.data() + (pos - win_at), n);
-            return true;
-        }
-        if (n >= WINDOW) return pread_all(dst, n, pos);
-        const size_t want = (size_t) std::min<uint64_t>(WINDOW, file_bytes - pos);
-        win.resize(WINDOW);
-        if (!pread_all(win.data(), want, pos)) return false;
-        win_at = pos;
-        win_n = want;
-        memcpy(dst, win.data(), n);
-        return true;
-    }
-};
-
 // file -> (message table on the host, beside the upload) -> file in HBM -> records in a device buffer of their own (null for none), the
 // file's bytes freed
 int mcap_file_to_events(ecal_ctx *ctx, const char *path, const ecal_mcap_options *opt, uint8_t **d_events, ecal_mcap_info &I) {
@@ -567,23 +410,13 @@ int mcap_file_to_events(ecal_ctx *ctx, const char *path, const ecal_mcap_options
     int rc = mcap_check_options(ctx, o);
     if (rc) return rc;
     const std::string topic = o.topic ? o.topic : "";
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) {
-        ctx->last_error = std::string(WHO) + ": cannot open " + path;
-        return ECAL_ERR_INVALID;
-    }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) {
-        close(fd);
-        ctx->last_error = std::string(WHO) + ": cannot read " + path;
-        return ECAL_ERR_INVALID;
-    }
+    int fd;
+    uint64_t file_bytes;
     {   // the magic in front of everything: a file of another kind is not uploaded
-        uint8_t head[16];
-        McapFileReader rd{fd, (uint64_t) sb.st_size};
-        const size_t hn = (size_t) std::min<uint64_t>((uint64_t) sb.st_size, sizeof(head));
-        std::string err = "cannot be read";
-        if ((hn && !rd.pread_all(head, hn, 0)) || mcap_check_magic(head, hn, &err)) {
+        std::vector<uint8_t> head;
+        if ((rc = ecal_ingest_open_head(ctx, WHO, path, 16, "cannot be read", &fd, &file_bytes, &head))) return rc;
+        std::string err;
+        if (mcap_check_magic(head.data(), head.size(), &err)) {
             close(fd);
             ctx->last_error = std::string(WHO) + ": " + err + " (" + path + ")";
             return ECAL_ERR_INVALID;
@@ -593,10 +426,10 @@ int mcap_file_to_events(ecal_ctx *ctx, const char *path, const ecal_mcap_options
     McapCounts c;
     memset(&c, 0, sizeof(c));
     ecal_ingest_upload up;
-    rc = ecal_ingest_upload_indexed(ctx, "mcap", WHO, "host message index", path, fd, 0, (uint64_t) sb.st_size, [&](std::string *error, const void **tab, size_t *tab_bytes) {
-        McapFileReader rd{fd, (uint64_t) sb.st_size};
+    rc = ecal_ingest_upload_indexed(ctx, "mcap", WHO, "host message index", path, fd, 0, file_bytes, [&](std::string *error, const void **tab, size_t *tab_bytes) {
+        ecal_ingest_file_reader rd{fd, file_bytes};
         std::string err;
-        const int index_rc = mcap_walk(rd, (uint64_t) sb.st_size, topic, c, [&](const McapMessage &m) { table.push_back(m); }, &err);
+        const int index_rc = mcap_walk(rd, file_bytes, topic, c, [&](const McapMessage &m) { table.push_back(m); }, &err);
         if (index_rc) *error = std::string(WHO) + ": " + err + " (" + path + ")";
         *tab = table.data();
         *tab_bytes = table.size() * sizeof(McapMessage);

@@ -1,6 +1,7 @@
-// What the ingest decoders share (ecal_text.hip, ecal_raw.hip, ecal_aedat.hip, ecal_aedat4.hip, ecal_bag.hip), beside
-// block_utils.hpp: the clipped load and the bisection of a table's slot space, the one-workgroup scan of a table, and the tails of
-// the verdict and write kernels.  The load and the bisection compile for the host too
+// What the ingest decoders share (ecal_text.hip, ecal_raw.hip, ecal_aedat.hip, ecal_aedat4.hip, ecal_bag.hip, ecal_mcap.hip), beside
+// block_utils.hpp: the clipped load and the bisection of a table's slot space, the check of a table against the file's bytes, the
+// counters of a message-table ingest, the one-workgroup scan of a table, and the tails of the verdict and write kernels (their bodies:
+// slot_kernels.hpp; the host driver: ingest_driver.hpp).  The load, the bisection and the table check compile for the host too
 // (tests/cpp/check_ingest_blocks.cpp runs them under the sanitizers); the rest is device code (wave64; T = threads per workgroup).
 #pragma once
 #include <stdint.h>
@@ -35,6 +36,26 @@ ECAL_INGEST_HD uint32_t table_find(const unsigned long long *__restrict__ first,
     }
     return lo;
 }
+
+// the entries p = start, start + step, ... of a table of n that do not lie wholly within n_bytes: [offset_of(p), offset_of(p) +
+// bytes_of(p)), without wrapping
+template <class OffsetOf, class BytesOf>
+ECAL_INGEST_HD unsigned long long table_count_outside(uint64_t n, uint64_t n_bytes, uint64_t start, uint64_t step, OffsetOf offset_of, BytesOf bytes_of) {
+    unsigned long long bad = 0;
+    for (uint64_t p = start; p < n; p += step) {
+        const uint64_t off = offset_of(p), len = bytes_of(p);
+        if (off > n_bytes || len > n_bytes - off) bad++;
+    }
+    return bad;
+}
+
+// the counters of one message-table ingest (device; bag and MCAP)
+struct MessageWords {
+    unsigned long long n_slots;      // slots of the table (MCAP EVT3: payload bytes)
+    unsigned long long first_stop;   // the first slot that reaches end_time (all ones: none)
+    unsigned long long n_events, n_outside, n_negative, n_before_start;
+    unsigned long long bad_table;    // messages of the table that do not lie within n_bytes
+};
 
 #if defined(__HIPCC__)
 

@@ -5,6 +5,8 @@
 //                   1 - 3 bytes behind it, wholly behind it), against a bytewise reference
 //   table_find      fixed tables (empty entries in front, in the middle, at the end; one entry; an entry over several blocks) and
 //                   seeded random ones, random ranges [lo, hi] around the entry of a random slot, against a linear search
+//   table_count_outside  entries that end at, one byte behind and far behind n_bytes, offsets behind it, lengths and sums that wrap 64
+//                   bits, every start and step of a strided walk, against 128-bit arithmetic
 //   pack_record     against the bytes of '<dddB', printed for the Python side too
 #include <stdint.h>
 #include <stdio.h>
@@ -64,6 +66,27 @@ static void check_table(const std::vector<uint32_t> &counts, uint64_t *cases, ui
     }
 }
 
+// entries around the end of the file and around 2^64, counted by strided walks that together visit every entry once
+static void check_outside(uint64_t *cases, uint64_t *wrong) {
+    struct Entry { uint64_t off, len; };
+    const uint64_t top = ~0ull;
+    for (uint64_t n_bytes : std::vector<uint64_t>{0u, 1u, 13u, 4096u, top - 1u, top}) {
+        std::vector<Entry> tab;
+        for (uint64_t off : std::vector<uint64_t>{0u, 1u, n_bytes / 2u, n_bytes - 1u, n_bytes, n_bytes + 1u, top - 7u, top})
+            for (uint64_t len : std::vector<uint64_t>{0u, 1u, 8u, n_bytes - off, n_bytes - off + 1u, n_bytes, top - off, top - off + 1u, top}) tab.push_back(Entry{off, len});
+        for (int k = 0; k < 64; k++) tab.push_back(Entry{rnd() >> (rnd() % 64), rnd() >> (rnd() % 64)});
+        unsigned long long want = 0;
+        for (const Entry &e : tab) want += (unsigned __int128) e.off + e.len > (unsigned __int128) n_bytes ? 1u : 0u;
+        for (uint64_t step : std::vector<uint64_t>{1u, 3u, 64u, 1024u}) {
+            unsigned long long got = 0;
+            for (uint64_t start = 0; start < step; start++)
+                got += ecal::table_count_outside(tab.size(), n_bytes, start, step, [&](uint64_t p) { return tab[p].off; }, [&](uint64_t p) { return tab[p].len; });
+            (*cases)++;
+            if (got != want && !(*wrong)++) printf("table_count_outside: n_bytes %llu, step %llu differs\n", (unsigned long long) n_bytes, (unsigned long long) step);
+        }
+    }
+}
+
 int main() {
     uint64_t cases = 0, wrong = 0;
     check_loads(&cases, &wrong);
@@ -91,6 +114,11 @@ int main() {
         check_table(counts, &cases, &wrong);
     }
     printf("tables: %llu cases, %llu wrong\n", (unsigned long long) cases, (unsigned long long) wrong);
+    failures += wrong;
+
+    cases = wrong = 0;
+    check_outside(&cases, &wrong);
+    printf("outside: %llu cases, %llu wrong\n", (unsigned long long) cases, (unsigned long long) wrong);
     failures += wrong;
 
     // '<dddB' of (1.0, 2.0, -0.5, 1), by hand; then what the Python side packs itself
